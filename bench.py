@@ -9,9 +9,16 @@ images (the path is embarrassingly parallel over the batch; no data-path collect
 scaling is weak.
 
   python bench.py --gpus 1 --steps 20 --warmup 5
+  python bench.py --gpus 1 --steps 20 --warmup 5 --full
+  python bench.py --gpus 1 --steps 20 --warmup 5 --dump-outputs DIR
   python -m torch.distributed.run --nproc-per-node N ... bench.py --gpus N --steps K --warmup W
 
-Rank 0 prints ONE JSON line.  `roofline` describes the dominant kernel group — the controller
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the K steps and prints the
+headline (`value`, `ms_per_step`); `--dump-outputs DIR` also writes what the last timed step
+computed (DIR/y_out_sample.npy, DIR/y_out_image0.npy, DIR/s_out.npy; float32, inputs seeded).
+Everything else below — the lone-batch and steady-state figures, the `train` / `train_bf16`
+objects, the roofline objects, the Hungarian timings and the CPU baseline — is measured with
+`--full` only.  `roofline` describes the dominant kernel group — the controller
 CNN's conv3x3 f32-MFMA launches (1.585 GFLOP per image-timestep at cfg2) —
 timed with HIP events on the launch stream; `roofline_attn` the HBM-bound attention resample
 (extract + paste, 7.0 MiB algorithmic per image-timestep); `cpu_baseline` the PyTorch-CPU
@@ -456,6 +463,32 @@ def ops_group(eng):
   return ra_ops.ctrl_batch_group(eng.desc, eng.subs[0]['img'].shape[0])
 
 
+DUMP_SAMPLE = 1 << 22  # y_out elements in y_out_sample.npy (16 MiB of float32)
+
+
+def dump_outputs(out_dir, model, pipe, ticket):
+  """--dump-outputs: what a caller of the timed path receives for the LAST timed step (pipe.collect() of that batch: y_out
+  [B, T, H, W], s_out [B, T]), read from the slot buffers after the drain.  Written as float32: s_out whole, y_out of the
+  first image whole (y_out_image0) and a fixed sample of y_out (y_out_sample: DUMP_SAMPLE flat indices drawn by
+  RandomState(0), sorted; all of y_out when it is smaller), so two builds can be compared output for output."""
+  rec = ticket['launch']
+  cols = []
+  for k, plo, phi in zip(rec['used'], rec['bounds'][:-1], rec['bounds'][1:]):
+    lo, hi = max(ticket['lo'], plo) - plo, min(ticket['hi'], phi) - plo
+    if hi > lo:
+      eng = pipe.slots[k][0]
+      cols.append([model._fetch(n, eng)[lo:hi] for n in ticket['names']])
+  y, s = [torch.cat(c, dim=0) for c in zip(*cols)]
+  n = y.numel()
+  if n <= DUMP_SAMPLE:
+    idx = torch.arange(n, device=y.device)
+  else:
+    idx = torch.as_tensor(np.sort(np.random.RandomState(0).randint(0, n, DUMP_SAMPLE)), device=y.device)
+  os.makedirs(out_dir, exist_ok=True)
+  for name, a in (('y_out_sample', y.reshape(-1)[idx]), ('y_out_image0', y[0]), ('s_out', s)):
+    np.save(os.path.join(out_dir, name + '.npy'), a.detach().float().cpu().numpy())
+
+
 def train_steps(rank, world, B, T, S, steps, warmup, sync_bn=False, dtype='f32'):
   """`steps` timed optimisation steps at BASELINE.json configs[3]'s per-GPU shapes (every rank takes part: the
   gradient all-reduce is inside the step).  Returns (elapsed seconds (max over ranks), last loss, model)."""
@@ -592,6 +625,12 @@ def main():
   ap.add_argument('--batch', type=int, default=8, help='images per GPU')
   ap.add_argument('--size', type=int, default=512)
   ap.add_argument('--timespan', type=int, default=16)
+  ap.add_argument('--full', action='store_true',
+                  help='cfg2: besides the headline, measure the lone-batch and steady-state figures, the `train` objects, the '
+                       'roofline objects, the Hungarian timings and the CPU baseline (a plain run times the steps only)')
+  ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                  help='cfg2: after the timed steps, write y_out / s_out of the last timed step to DIR/<name>.npy (float32; '
+                       'y_out as a fixed, seeded sample)')
   ap.add_argument('--no-cpu-baseline', action='store_true')
   ap.add_argument('--no-graph', action='store_true')
   ap.add_argument('--part-images', type=int, default=0, help='--config cfg3|cfg5: cut each batch into parts of this many images')
@@ -625,11 +664,13 @@ def main():
                        'configurations of BASELINE.json as their own JSON lines')
   ap.add_argument('--sync_bn', action='store_true', help='--train: BatchNorm moments over the whole data-parallel batch')
   ap.add_argument('--dtype', default='f32', choices=['f32', 'bf16'], help="--train: the conv layers' operand type (model_opt['compute_dtype'])")
-  ap.add_argument('--no-train-object', action='store_true', help='skip the `train` object (3 timed training steps) of the default line')
+  ap.add_argument('--no-train-object', action='store_true', help='skip the `train` object (3 timed training steps) of the --full line')
   ap.add_argument('--train', action='store_true',
                   help='time the TRAINING step instead (BASELINE.json configs[3] shapes: B images per GPU, '
                        'data-parallel, one RCCL all-reduce of the gradient bucket per step); prints its own JSON line')
   args = ap.parse_args()
+  if args.dump_outputs and (args.config != 'cfg2' or args.train or args.pmc_group):
+    raise SystemExit('--dump-outputs: the cfg2 decode pipeline only (not with --config, --train or --pmc-group)')
   if args.in_flight <= 0:
     args.in_flight = {'cfg2': 8, 'cfg3': 8, 'cfg5': 8}[args.config]  # eight submitted batches decoding, as at cfg2
   if args.coalesce <= 0 and args.config != 'cfg2':
@@ -642,6 +683,7 @@ def main():
     raise SystemExit('launch with torch.distributed.run --nproc-per-node %d' % args.gpus)
   torch.cuda.set_device(int(os.environ.get('LOCAL_RANK', '0')))
   rank, world, local_rank = ra_dist.init('nccl')  # 'nccl' is RCCL on ROCm
+  torch.manual_seed(1234)  # the weight initialisers draw from torch's default generator: the same weights in every run and rank
 
   if args.config != 'cfg2':
     return bench_other(args, rank, world, args.config)
@@ -693,18 +735,22 @@ def main():
     print(json.dumps({'pmc_group': args.pmc_group, 'images': int(sb['img'].shape[0]), 'size': S}))
     return
 
-  # one batch alone, launch to completion (the latency a lone model.run sees; SURVEY.md §8d's literal protocol: median
-  # of >= 20 forwards, each bracketed by a device synchronize, after >= 5 warm-ups)
+  # warm-up of the lone engine, in every run: the pipeline below has only ever been timed after these forwards, and
+  # without them its steps measure ~4 % slower (55k instead of 57k instance-timesteps/s at cfg2)
   for _ in range(max(args.warmup, 5)):
     eng.forward(feed['x'])
   torch.cuda.synchronize()
-  lone = []
-  for _ in range(21):
-    t0 = time.perf_counter()
-    eng.forward(feed['x'])
-    torch.cuda.synchronize()
-    lone.append(1e3 * (time.perf_counter() - t0))
-  lone_ms = float(np.median(lone))
+  lone_ms = None
+  if args.full:
+    # one batch alone, launch to completion (the latency a lone model.run sees; SURVEY.md §8d's literal protocol: median
+    # of >= 20 forwards, each bracketed by a device synchronize, after the >= 5 warm-ups above)
+    lone = []
+    for _ in range(21):
+      t0 = time.perf_counter()
+      eng.forward(feed['x'])
+      torch.cuda.synchronize()
+      lone.append(1e3 * (time.perf_counter() - t0))
+    lone_ms = float(np.median(lone))
 
   # the timed region: K steps = K batches through the evaluator's decode pipeline
   # (full_model.DecodePipeline: up to --in-flight batches decode concurrently, each a whole
@@ -724,28 +770,35 @@ def main():
   t0 = time.perf_counter()
   for _ in range(args.steps):
     step()
+  last = pipe.pending[-1] if pipe.pending else None  # the last timed step's batch
   pipe.drain()
   barrier()
   elapsed = ra_dist.max_over_ranks(time.perf_counter() - t0)
   value = world * B * T * args.steps / elapsed
-  # SURVEY 8(d)'s protocol beside the contract's mean: the MEDIAN time per batch in the steady state, fill and drain of the
-  # pipeline excluded — the host clock at every completion (retire() returns when the oldest batch has finished); a
-  # window of `streams` consecutive completions is one batch per stream, so (t[i + w] - t[i]) / w is a per-batch time
-  n_steady = max(24, 3 * pipe.depth * coalesce)
-  done = []
-  for _ in range(pipe.depth * coalesce):
-    pipe.submit(['y_out', 's_out'], feed, to_host=args.host_output)
-  for _ in range(n_steady):
-    while pipe.full():
-      pipe.retire()
-      done.append(time.perf_counter())
-    pipe.submit(['y_out', 's_out'], feed, to_host=args.host_output)
-  pipe.drain()
-  wdw = max(1, int(pipe.streams)) * coalesce  # one launch per stream: that many batches complete per round of the streams
-  gaps = [(done[i + wdw] - done[i]) / wdw for i in range(wdw, len(done) - wdw)]
-  steady_ms = 1e3 * ra_dist.max_over_ranks(float(np.median(gaps)))
   for eng_k, _ in pipe.slots:  # a controller workgroup that timed out on its peers would have produced garbage: fail loudly
     eng_k.check_status(recover=False)
+  if args.dump_outputs and rank == 0:
+    dump_outputs(args.dump_outputs, model, pipe, last)
+  wdw = max(1, int(pipe.streams)) * coalesce  # one launch per stream: that many batches complete per round of the streams
+  n_steady = max(24, 3 * pipe.depth * coalesce)
+  steady_ms = None
+  if args.full:
+    # SURVEY 8(d)'s protocol beside the contract's mean: the MEDIAN time per batch in the steady state, fill and drain of the
+    # pipeline excluded — the host clock at every completion (retire() returns when the oldest batch has finished); a
+    # window of `streams` consecutive completions is one batch per stream, so (t[i + w] - t[i]) / w is a per-batch time
+    done = []
+    for _ in range(pipe.depth * coalesce):
+      pipe.submit(['y_out', 's_out'], feed, to_host=args.host_output)
+    for _ in range(n_steady):
+      while pipe.full():
+        pipe.retire()
+        done.append(time.perf_counter())
+      pipe.submit(['y_out', 's_out'], feed, to_host=args.host_output)
+    pipe.drain()
+    gaps = [(done[i + wdw] - done[i]) / wdw for i in range(wdw, len(done) - wdw)]
+    steady_ms = 1e3 * ra_dist.max_over_ranks(float(np.median(gaps)))
+    for eng_k, _ in pipe.slots:
+      eng_k.check_status(recover=False)
 
   out = {
       'metric': 'instance-timesteps/sec, full_model forward 512x512 T=16 (whole job; pipelined throughput: %d batches in flight '
@@ -764,19 +817,22 @@ def main():
                  'pipeline_note': ('each of the %d pipeline slots decodes %d consecutively submitted batches of %d images as ONE forward '
                                    '(DecodePipeline(coalesce=%d): eval-mode images are independent, every batch is collected on its own); '
                                    '--coalesce 1 = one batch per slot, the protocol of rounds 2-4' % (pipe.depth, coalesce, B, coalesce)),
-                 'steady_ms_per_step_median': steady_ms, 'steady_value_median': world * B * T / (steady_ms * 1e-3),
-                 'steady_protocol': 'median over %d completions of the time per batch in the steady state of the pipeline '
-                                    '(fill and drain excluded; windows of %d consecutive completions)' % (n_steady, wdw),
-                 'lone_batch_ms': lone_ms, 'lone_batch_value': B * T / (lone_ms * 1e-3),
-                 'lone_batch_protocol': 'median of 21 forwards, each bracketed by a device synchronize', 'input': 'host (PCIe inclusive)' if args.host_input else 'resident in HBM',
+                 'input': 'host (PCIe inclusive)' if args.host_input else 'resident in HBM',
                  'output': 'y_out + s_out copied to pinned host memory (PCIe inclusive)' if args.host_output else 'left in HBM'},
   }
+  if args.full:
+    out['config'].update({
+        'steady_ms_per_step_median': steady_ms, 'steady_value_median': world * B * T / (steady_ms * 1e-3),
+        'steady_protocol': 'median over %d completions of the time per batch in the steady state of the pipeline '
+                           '(fill and drain excluded; windows of %d consecutive completions)' % (n_steady, wdw),
+        'lone_batch_ms': lone_ms, 'lone_batch_value': B * T / (lone_ms * 1e-3),
+        'lone_batch_protocol': 'median of 21 forwards, each bracketed by a device synchronize'})
 
   train_obj = train_bf16 = None
-  if not args.no_train_object:
+  if args.full and not args.no_train_object:
     train_obj = train_object(rank, world, B, T, S)  # every rank: the step holds the gradient all-reduce
     train_bf16 = train_object(rank, world, B, T, S, dtype='bf16')
-  if rank == 0:
+  if rank == 0 and args.full:
     if train_obj is not None:
       out['train'] = train_obj
       out['train_bf16'] = train_bf16
@@ -1108,6 +1164,7 @@ def main():
     out['config']['sub_batches'] = len(eng.subs)
     if world == 1 and not args.no_cpu_baseline:
       out['cpu_baseline'] = cpu_baseline(opt, 1234)
+  if rank == 0:
     print(json.dumps(out))
   if world > 1:
     ra_dist.barrier()

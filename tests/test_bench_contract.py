@@ -1,5 +1,5 @@
-"""bench.py's output contract (one JSON line with the driver's fields, the roofline object and the
-CPU baseline), checked on the GPU with a short run; the argument parser on the CPU."""
+"""bench.py's output contract (one JSON line with the driver's fields; with --full also the roofline objects, the training
+objects and the CPU baseline; --dump-outputs), checked on the GPU with short runs; the argument parser on the CPU."""
 import json
 import os
 import subprocess
@@ -13,14 +13,14 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 def test_bench_flags_parse_without_a_gpu():
   out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--help'], capture_output=True, text=True)
   assert out.returncode == 0
-  for flag in ('--gpus', '--steps', '--warmup', '--no-cpu-baseline', '--host-input', '--pmc-group'):
+  for flag in ('--gpus', '--steps', '--warmup', '--full', '--dump-outputs', '--no-cpu-baseline', '--host-input', '--pmc-group'):
     assert flag in out.stdout
 
 
 @pytest.mark.gpu
 def test_bench_json_line(cuda):
   env = dict(os.environ)
-  out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1',
+  out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', '2', '--warmup', '1', '--full',
                         '--no-cpu-baseline'], capture_output=True, text=True, env=env, timeout=600)
   assert out.returncode == 0, out.stderr[-2000:]
   line = [l for l in out.stdout.strip().splitlines() if l.startswith('{')][-1]
@@ -51,6 +51,33 @@ def test_bench_json_line(cuda):
     rf = t['roofline']
     assert rf['bound'] == 'hbm' and rf['unit'] == 'GB/s' and abs(rf['frac'] - rf['achieved'] / rf['peak']) < 1e-9
     assert abs(rf['achieved'] - rf['bytes_per_step'] / (t['ms_per_step'] * 1e-3) / 1e9) < 1e-6 * rf['achieved']
+
+
+@pytest.mark.gpu
+def test_bench_plain_line_and_dumped_outputs(cuda, tmp_path):
+  """A plain run times exactly --steps steps and measures nothing else; --dump-outputs writes the last timed step's y_out /
+  s_out as float32 (y_out as a fixed sample, 64 MB at most in all), and they are the masks and scores of a real decode."""
+  import numpy as np
+  dump = tmp_path / 'out'
+  out = subprocess.run([sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '1', '--steps', '3', '--warmup', '1',
+                        '--dump-outputs', str(dump)], capture_output=True, text=True, env=dict(os.environ), timeout=600)
+  assert out.returncode == 0, out.stderr[-2000:]
+  line = [l for l in out.stdout.strip().splitlines() if l.startswith('{')][-1]
+  d = json.loads(line)
+  for k in ('metric', 'value', 'unit', 'n_gpus', 'steps', 'warmup', 'ms_per_step', 'higher_is_better', 'dtype', 'config'):
+    assert k in d, k
+  assert d['steps'] == 3 and d['warmup'] == 1 and d['dtype'] == 'f32' and d['higher_is_better'] is True
+  assert d['unit'] == 'instance-timesteps/s' and abs(d['value'] - 8 * 16 * 1000.0 / d['ms_per_step']) < 1e-6 * d['value']
+  for k in ('roofline', 'roofline_attn', 'train', 'train_bf16', 'cpu_baseline', 'tail_us', 'controller_us', 'hungarian_cfg4_step'):
+    assert k not in d, k
+  assert 'lone_batch_ms' not in d['config'] and 'steady_ms_per_step_median' not in d['config']
+  files = {f.name: np.load(f) for f in dump.iterdir()}
+  assert set(files) == {'y_out_sample.npy', 'y_out_image0.npy', 's_out.npy'}
+  assert sum(f.stat().st_size for f in dump.iterdir()) <= 64 * 2 ** 20
+  for a in files.values():
+    assert a.dtype == np.float32 and np.isfinite(a).all() and 0.0 <= a.min() and a.max() <= 1.0
+  assert files['s_out.npy'].shape == (8, 16) and files['y_out_image0.npy'].shape == (16, 512, 512)
+  assert files['y_out_sample.npy'].shape == (1 << 22,) and files['y_out_sample.npy'].std() > 0
 
 
 def test_train_layer_bytes_formula():

@@ -181,8 +181,9 @@ def _state_worker(rank, world, port, q):
   xs = xall[lo:hi].reshape(-1, 4)
   mean, var = xs.mean(dim=0), xs.var(dim=0, unbiased=False)
   ntot = ra_train.sync_moments(mean, var, xs.shape[0])
-  q.put((r, n, before.numpy(), bucket.param.numpy().copy(), bucket.m.numpy().copy(), bucket.global_step,
-         float(model['global_step']), mean.numpy(), var.numpy(), ntot, model['ctrl_cnn_w_0'].numpy().copy()))
+  # (.cpu(): where a GPU exists the model's tensors live on it)
+  q.put((r, n, before.cpu().numpy(), bucket.param.cpu().numpy().copy(), bucket.m.cpu().numpy().copy(), bucket.global_step,
+         float(model['global_step']), mean.cpu().numpy(), var.cpu().numpy(), ntot, model['ctrl_cnn_w_0'].cpu().numpy().copy()))
   ra_dist.barrier()
   torch.distributed.destroy_process_group()
 

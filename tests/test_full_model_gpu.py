@@ -527,11 +527,19 @@ def test_xcd_local_controller_with_part_of_its_xcd_taken(cuda):
   for longer than the controller's spin limit.  Image 0's team then cannot be resident together: whether the dispatcher holds
   its other workgroups back (the residents time out on their peers) or deals them to other XCDs (tickets beyond an XCD's share
   wrap onto roles that exist; XCD 0's team stays short), the launch must flag its status word, model.run must decode the batch
-  again on the one-workgroup controller, and the masks must be the oracle's."""
+  again on the one-workgroup controller, and the masks must be the oracle's.
+  The parked kernel runs in a child process: the HIP runtime multiplexes a process's streams onto a few hardware queues
+  (GPU_MAX_HW_QUEUES), so a side stream of this process can share a queue with the stream that polls the parked count or
+  with the run's own streams, and everything queued behind the park then starts only after it has ended.  A second process
+  has hardware queues of its own; in it, the park goes on a high-priority stream (its own queue pool) and the poll on the
+  null stream."""
+  import os
+  import select
+  import subprocess
+  import sys
   import time
   import warnings
   import full_model
-  import ra_ops as ops
   opt = ora.make_opt('cvppp', 128, 128, 2)
   P = ora.random_params(opt, 47)
   x = np.random.RandomState(12).rand(2, 128, 128, 3).astype(np.float32)
@@ -544,23 +552,49 @@ def test_xcd_local_controller_with_part_of_its_xcd_taken(cuda):
   if 'ctrl_ws' not in sb or sb.get('ctrl_batch'):
     pytest.skip('the per-image split controller is not what this engine runs')
   assert np.abs(good[0] - ref['y_out']).max() < MASK_TOL
-  resident = torch.zeros(1, dtype=torch.int32, device=cuda)
-  side = torch.cuda.Stream()
   torch.cuda.synchronize()
-  ops.park_xcd(0, 24, lds_bytes=100 * 1024, millis=12000, resident=resident, stream=side)
-  t0 = time.time()
-  while int(resident.item()) < 24 and time.time() - t0 < 5.0:  # (.item() runs on the default stream: it does not wait for `side`)
-    time.sleep(0.01)
-  n_parked = int(resident.item())
-  assert n_parked == 24, 'parked workgroups resident on XCD 0: %d' % n_parked
-  with warnings.catch_warnings(record=True) as w:
-    warnings.simplefilter('always')
+  park = ('import sys, time\n'
+          'sys.path.insert(0, %r)\n'
+          'import torch\n'
+          'import ra_ops as ops\n'
+          'resident = torch.zeros(1, dtype=torch.int32, device="cuda")\n'
+          'side = torch.cuda.Stream(priority=-1)\n'
+          'torch.cuda.synchronize()\n'
+          'ops.park_xcd(0, 24, lds_bytes=100 * 1024, millis=12000, resident=resident, stream=side)\n'
+          't0 = time.time()\n'
+          'while int(resident.item()) < 24 and time.time() - t0 < 5.0:\n'
+          '  time.sleep(0.01)\n'
+          'print("parked %%d %%.3f" %% (int(resident.item()), time.time() - t0), flush=True)\n'
+          'torch.cuda.synchronize()\n' % os.path.dirname(os.path.abspath(full_model.__file__)))
+  child = subprocess.Popen([sys.executable, '-c', park], stdout=subprocess.PIPE, text=True)
+  try:
+    line = ''
     t0 = time.time()
-    y, s = m.run(['y_out', 's_out'], feed, as_numpy=True)
-    dt = time.time() - t0
-  torch.cuda.synchronize()
+    while not line.startswith('parked') and time.time() - t0 < 120.0:
+      if select.select([child.stdout], [], [], 120.0 - (time.time() - t0))[0]:
+        line = child.stdout.readline()
+        if not line:
+          break  # the child ended without reporting
+    assert line.startswith('parked'), 'the parking process did not report (exit status %s)' % child.poll()
+    n_parked, t_park = int(line.split()[1]), float(line.split()[2])
+    assert n_parked == 24 and t_park < 5.0, 'parked workgroups resident on XCD 0: %d after %.2f s' % (n_parked, t_park)
+    with warnings.catch_warnings(record=True) as w:
+      warnings.simplefilter('always')
+      t0 = time.time()
+      y, s = m.run(['y_out', 's_out'], feed, as_numpy=True)
+      dt = time.time() - t0
+    torch.cuda.synchronize()
+    still_parked = child.poll() is None
+  finally:
+    try:
+      child.wait(timeout=60)
+    except subprocess.TimeoutExpired:
+      child.kill()
+      child.wait()
+  assert child.returncode == 0, 'parking process exit status %d' % child.returncode
   timed_out = any('one-workgroup controller' in str(x_.message) for x_ in w)
-  print('run with 24 CUs of XCD 0 parked: %.2f s, timed out and re-decoded: %s' % (dt, timed_out))
+  print('run with 24 CUs of XCD 0 parked: %.2f s (park still running at its end: %s), timed out and re-decoded: %s'
+        % (dt, still_parked, timed_out))
   # 8 free CUs on XCD 0 < 16 workgroups: the team could not have been resident together
   assert timed_out and eng.ctrl_split is False and 'ctrl_ws' not in eng.subs[0]
   assert np.abs(y - ref['y_out']).max() < MASK_TOL and np.abs(s - ref['s_out']).max() < MASK_TOL

@@ -11,7 +11,7 @@ mkdir -p $OUT
 export TMPDIR=/tmp
 ROOT=$PWD
 R="timeout 900 rocprofv3 --output-format csv"
-B="--no-cpu-baseline --no-train-object"
+B="--full --no-cpu-baseline --no-train-object"
 # kernel durations that can be compared with the bench line's roofline: one batch in flight (with 4 in
 # flight the kernels of different batches share the chip and every duration is inflated by the overlap);
 # the second trace is the default run, for the record
@@ -34,7 +34,7 @@ cp $(find $OUT/trace4 -name '*kernel_stats.csv' | head -1) $OUT/${R3}_bench_kern
 rm -rf $OUT/trace $OUT/trace4 $OUT/pmc_*_f $OUT/pmc_*_w $OUT/pmc_sq
 # the traffic files must be in profiles/ for the bench line to pick them up
 cp $OUT/${R3}_pmc_encoder_traffic.json $OUT/${R3}_pmc_attn_traffic.json $OUT/${R3}_pmc_sq_mfma_per_kernel.csv profiles/ 2>/dev/null  # (roofline.traffic / mfma_busy / executed read them)
-timeout 900 python bench.py > $OUT/${R3}_bench_n1.json 2> $OUT/bench.err
+timeout 900 python bench.py --full > $OUT/${R3}_bench_n1.json 2> $OUT/bench.err
 for DT in f32 bf16; do
   SUF=""; [ $DT = bf16 ] && SUF="_bf16"
   timeout 900 python bench.py --train --dtype $DT --steps 4 --warmup 3 > $OUT/${R3}_train${SUF}_n1.json 2>> $OUT/bench.err

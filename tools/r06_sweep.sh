@@ -11,7 +11,7 @@ cat $OUT/tests.txt
 for v in "$@"; do
   name=${v%%:*}; envs=${v#*:}
   for c in ${CFGS:-cfg3 cfg5 cfg2}; do
-    extra="--config $c"; [ $c = cfg2 ] && extra="--no-train-object"
+    extra="--config $c"; [ $c = cfg2 ] && extra="--full --no-train-object"
     env $(echo $envs | tr ',' ' ') timeout 600 python bench.py $extra --no-cpu-baseline > $OUT/bench_${c}_$name.json 2>> $OUT/bench.err
   done
 done
