@@ -105,6 +105,15 @@ size_t ra_conv_packed_floats(int Cin, int Cout);
  * with Cin_w == Cin.  out: host buffer of ra_conv_packed_floats(Cin, Cout) floats. */
 int ra_conv_pack_weights(const float *w, int Cin_w, int Cout, int Cin, const int *chan_map,
                          int flags, float *out);
+/* Other filter sizes (nnlib.cnn / nnlib.dcnn take one per layer: nnlib.py:131-257, :260-404): KF in {1, 3, 5, 7}.
+ * ra_conv_packed_floats_k: floats of the packed buffer for a [KF,KF,Cin,Cout] filter (0 for another KF or shape).
+ * ra_conv_pack_weights_k: as ra_conv_pack_weights for a [KF,KF,Cin_w,Cout] (or, RA_CONV_TRANSPOSED, [KF,KF,Cout,Cin_w]:
+ * flipped taps, swapped in/out) filter; packed order [chunk][tap = ky*KF+kx][cg][ksub][CoutP], channel
+ * chunk*CK + 4*cg + ksub, CK = 16 / 8 / 4 (the largest dividing Cin) for KF <= 3, 8 or 4 for KF = 5, 4 for KF = 7.
+ * KF = 3 is exactly ra_conv_packed_floats / ra_conv_pack_weights. */
+size_t ra_conv_packed_floats_k(int KF, int Cin, int Cout);
+int ra_conv_pack_weights_k(const float *w, int KF, int Cin_w, int Cout, int Cin, const int *chan_map, int flags,
+                           float *out);
 /* Host-side fold of bias + BN(eval) into scale/shift [CoutP] (nnlib.py:119: eps = 1e-3).
  * beta/gamma/mean/var nullable together (no BN: scale = 1, shift = bias). */
 int ra_conv_fold_bn(const float *bias, const float *beta, const float *gamma, const float *mean,
@@ -116,6 +125,14 @@ int ra_conv3x3_f32(const float *src0, int C0, const float *src1, int C1, int B, 
                    int upsample, const float *wpacked, const float *scale, const float *shift,
                    int Cout, int relu, int pool, const float *plane, int plane_chan, float *y,
                    void *stream);
+
+/* ra_conv3x3_f32 for a KF x KF filter packed by ra_conv_pack_weights_k(KF) (nnlib.py:131-257, :260-404): SAME conv,
+ * centred window; with upsample == 1 the stride-2 SAME conv2d_transpose, whose window on U is TF's asymmetric one for
+ * KF = 5, 7.  Float32 operands and accumulation, same epilogue, sources and canvas plane.  KF = 3 is ra_conv3x3_f32;
+ * another KF (even, or not 1 / 5 / 7) returns RA_E_SHAPE, as does a shape ra_conv3x3_f32 refuses, without a launch. */
+int ra_convkxk_f32(const float *src0, int C0, const float *src1, int C1, int B, int Hs, int Ws, int upsample,
+                   const float *wpacked, int KF, const float *scale, const float *shift, int Cout, int relu, int pool,
+                   const float *plane, int plane_chan, float *y, void *stream);
 
 /* Mixed precision for the training step (model_opt['compute_dtype'] = 'bf16'; the reference trains in float32 —
  * this is an extension behind its option dictionary): the same layer with bf16 OPERANDS — pixels and weights are

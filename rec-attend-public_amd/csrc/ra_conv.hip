@@ -20,9 +20,10 @@
 
 #include "ra_common.h"
 
-// This file is compiled three times (Makefile): RA_K1_PART 0 = the decode loop's float32 kernels + every host entry
-// point, 1 = the bf16-operand variants, 2 = float32 with batch moments in the epilogue (the training forward).  The
-// three sets of template instantiations build in parallel; part 0's entry forwards to the other parts' dispatchers.
+// This file is compiled four times (Makefile): RA_K1_PART 0 = the decode loop's float32 kernels + every host entry
+// point, 1 = the bf16-operand variants, 2 = float32 with batch moments in the epilogue (the training forward), 3 = the
+// decode loop's float32 kernels for filter sizes 1, 5 and 7 (ra_convkxk_f32).  The sets of template instantiations build
+// in parallel; part 0's entry forwards to the other parts' dispatchers.
 #ifndef RA_K1_PART
 #define RA_K1_PART 0
 #endif
@@ -66,7 +67,10 @@ struct Args {
   float *mom_part;              // MOM kernels: per-(workgroup, wave row) channel sums of the pre-activation output
   int *nparts_out;              // host: the number of partial records the launch writes (grid * WM)
   int prio;                     // wave priority (s_setprio) of a patch-sized launch: the decode loop's latency-bound tail (ra_common.h)
+  int org;                      // KF != 3 only: conv row / col of LDS row / col 0 is the tile origin minus org (the window origin;
+                                // the 3 x 3 kernels use their constant 1).  Fills the struct's tail padding: sizeof stays 168
 };
+static_assert(sizeof(Args) == 168, "the 3 x 3 kernels' argument offsets (tiles_x ...) stay where they were");
 
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 constexpr int kOOB = 0x7fffffff;  // a buffer offset past every tensor: loads return 0, stores drop
@@ -78,21 +82,22 @@ __device__ inline __amdgpu_buffer_rsrc_t make_rsrc(const void *p, int bytes) {
   return __builtin_amdgcn_make_buffer_rsrc(const_cast<void *>(p), 0, bytes, 0x00020000);
 }
 
-template <int CK, int NC, int WN, int GX, int GY>
+template <int CK, int NC, int WN, int GX, int GY, int KF = 3>
 struct Geo {
   static constexpr int WM = 4 / WN;            // waves along pixel rows
   static constexpr int PM = GX * GY;           // pixel groups per wave
   static constexpr int TW = 8 * GX;            // tile cols
   static constexpr int WR = 2 * GY;            // rows per wave
   static constexpr int TH = WR * WM;           // tile rows
-  static constexpr int LW = TW + 2;            // LDS cols (halo)
-  static constexpr int LH = TH + 2;            // LDS rows
+  static constexpr int LW = TW + KF - 1;       // LDS cols (halo)
+  static constexpr int LH = TH + KF - 1;       // LDS rows
   static constexpr int NCG = CK / 4;           // channel groups per chunk
   // LDS record of one pixel: [ksub 0..3][cg 0..NCG-1] (channel = 4*cg + ksub), so ONE wide
   // ds_read (b128 for CK=16, b64 for CK=8) fetches a lane's A operands of all NCG k-steps of a
   // tap.
   static constexpr int PIX = CK;  // unpadded: modelled b128/b64 conflicts are lowest at 16 / 8
-  static constexpr int KS = 9 * NCG;           // MFMA k-steps per chunk
+  static constexpr int KK = KF * KF;           // taps
+  static constexpr int KS = KK * NCG;          // MFMA k-steps per chunk
   static constexpr int LDS_FLOATS = LH * LW * PIX;
 };
 
@@ -148,12 +153,17 @@ __device__ inline bf16x4 pack_bf16(float v0, float v1, float v2, float v3) {
 // Tile origins are even, so for such a pixel only the taps with ky = py and kx = px (mod 2) meet stuffed data — 4, 2, 2 and 1
 // taps for the four classes, 9 per 64 pixels instead of 36: a quarter of the MFMAs and of the A-operand reads, same results
 // (the skipped products are exact zeros).
-template <int CK, int NC, int WN, int GX, int GY, bool SWAP, bool BF16 = false, bool MOM = false, bool UPS = false>
+// KF (RA_K1_PART 3): a KF x KF filter, KF in {1, 5, 7} — KF * KF taps, a halo of KF - 1 rows and columns, and the window origin
+// a.org passed by the host (centred for stride 1; TF's asymmetric SAME origin for the stride-2 transposed conv).  Those kernels
+// are the plain float32 zero-stuffed form only; KF = 3 is every other instantiation, its origin the constant 1.
+template <int CK, int NC, int WN, int GX, int GY, bool SWAP, bool BF16 = false, bool MOM = false, bool UPS = false, int KF = 3>
 __global__ __launch_bounds__(256, (GX * GY * NC > 8) ? 1 : 2) void conv3x3_mfma(const Args a, int tiles_x, int tiles_y, int ntiles) {
   static_assert(!MOM || SWAP, "batch moments ride on the channel-vector epilogue");
   static_assert(!UPS || (SWAP && GX == 2 && GY == 2 && !BF16 && !MOM), "sub-pixel form: float32 SWAP layers on the (2, 2) geometry");
+  static_assert(KF == 3 || (KF & 1 && KF <= 7 && !UPS && !BF16 && !MOM), "KF != 3: odd sizes up to 7, float32 zero-stuffed form only");
   raise_prio(a.prio);
-  using G = Geo<CK, NC, WN, GX, GY>;
+  using G = Geo<CK, NC, WN, GX, GY, KF>;
+  const int org = KF == 3 ? 1 : a.org;
   extern __shared__ __attribute__((aligned(16))) float tile[];  // 2 * G::LDS_FLOATS
   constexpr int NPIX = G::LH * G::LW;        // pixel records of one staged chunk
   constexpr int NST = (NPIX + 255) / 256;    // pixels per thread
@@ -272,8 +282,8 @@ __global__ __launch_bounds__(256, (GX * GY * NC > 8) ? 1 : 2) void conv3x3_mfma(
 #pragma unroll
   for (int i = 0; i < NST; ++i) {
     const int e = tid + 256 * i;
-    rel_r[i] = e / G::LW - 1;
-    rel_c[i] = e % G::LW - 1;
+    rel_r[i] = e / G::LW - org;
+    rel_c[i] = e % G::LW - org;
     const int ys = a.ups ? (rel_r[i] >> 1) : rel_r[i];
     const int xs = a.ups ? (rel_c[i] >> 1) : rel_c[i];
     off0[i] = (ys * a.Ws + xs) * a.C0;
@@ -375,7 +385,7 @@ __global__ __launch_bounds__(256, (GX * GY * NC > 8) ? 1 : 2) void conv3x3_mfma(
       }
     }
   };
-  auto compute = [&](int buf) {  // MFMA main loop: 9 taps, one wide A read per (tap, group)
+  auto compute = [&](int buf) {  // MFMA main loop: KF * KF taps, one wide A read per (tap, group)
     const float *tb = tile + buf * G::LDS_FLOATS;
     if constexpr (BF16) {
       constexpr int TPF = 4 / G::NCG;  // taps per bf16 quad (4 k-steps of this lane's ksub)
@@ -385,8 +395,8 @@ __global__ __launch_bounds__(256, (GX * GY * NC > 8) ? 1 : 2) void conv3x3_mfma(
         float v4[4];
 #pragma unroll
         for (int tp = 0; tp < TPF; ++tp) {
-          const int tap = (f * TPF + tp < 9) ? f * TPF + tp : 8;  // beyond the 9 taps: any staged pixel (zero weights)
-          const int ky = tap / 3, kx = tap % 3;
+          const int tap = (f * TPF + tp < G::KK) ? f * TPF + tp : G::KK - 1;  // beyond the taps: any staged pixel (zero weights)
+          const int ky = tap / KF, kx = tap % KF;
           const avec av = *reinterpret_cast<const avec *>(&tb[a_base + ((2 * gy + ky) * G::LW + 8 * gx + kx) * G::PIX]);
 #pragma unroll
           for (int cg = 0; cg < G::NCG; ++cg) v4[tp * G::NCG + cg] = av[cg];
@@ -416,8 +426,8 @@ __global__ __launch_bounds__(256, (GX * GY * NC > 8) ? 1 : 2) void conv3x3_mfma(
       return;
     }
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap) {
-      const int ky = tap / 3, kx = tap % 3;
+    for (int tap = 0; tap < G::KK; ++tap) {
+      const int ky = tap / KF, kx = tap % KF;
       avec av[G::PM];
 #pragma unroll
       for (int g = 0; g < G::PM; ++g) {
@@ -607,10 +617,10 @@ __global__ __launch_bounds__(256, (GX * GY * NC > 8) ? 1 : 2) void conv3x3_mfma(
   }
 }
 
-template <int CK, int NC, int WN, int GX, int GY, bool SWAP, bool BF16 = false, bool MOM = false, bool UPS = false>
+template <int CK, int NC, int WN, int GX, int GY, bool SWAP, bool BF16 = false, bool MOM = false, bool UPS = false, int KF = 3>
 int launch_s(const Args &a, int B, hipStream_t st) {
-  using G = Geo<CK, NC, WN, GX, GY>;
-  auto kern = conv3x3_mfma<CK, NC, WN, GX, GY, SWAP, BF16, MOM, UPS>;
+  using G = Geo<CK, NC, WN, GX, GY, KF>;
+  auto kern = conv3x3_mfma<CK, NC, WN, GX, GY, SWAP, BF16, MOM, UPS, KF>;
   constexpr size_t lds = 2 * G::LDS_FLOATS * sizeof(float);
   static int wgs_per_cu = 0;  // idempotent lazy init
   if (!wgs_per_cu) {
@@ -626,9 +636,16 @@ int launch_s(const Args &a, int B, hipStream_t st) {
   const int grid = ntiles < cap ? ntiles : cap;
   if (a.nparts_out) *a.nparts_out = grid * G::WM;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, tiles_x, tiles_y, ntiles);
-  return launch_status("ra_conv3x3_f32");
+  return launch_status(KF == 3 ? "ra_conv3x3_f32" : "ra_convkxk_f32");
 }
 
+// the filter's input channels per staged chunk: 3 x 3 (and 1 x 1) as large as Cin allows (16 / 8 / 4); larger filters shrink it
+// so that the chunk's B operand (KF * KF * CK / 4 k-steps of 16 couts per cout group, held in VGPRs) stays near the 3 x 3
+// kernel's 36: 5 x 5 takes 8 (50 k-steps), 7 x 7 takes 4 (49)
+inline int chunk_of(int Cin) { return (Cin % 16 == 0) ? 16 : (Cin % 8 == 0) ? 8 : 4; }
+inline int chunk_of_k(int KF, int Cin) { return KF <= 3 ? chunk_of(Cin) : (KF == 5 && Cin % 8 == 0) ? 8 : 4; }
+
+#if RA_K1_PART != 3
 namespace {  // the dispatch chain differs between the parts of this file (RA_K1_PART): internal linkage, one per part
 inline bool ups_subpixel() {  // RA_CONV_UPS_SUBPIXEL=0: the zero-stuffed form of rounds 1-5 (A/B aid)
   static int on = -1;
@@ -730,7 +747,6 @@ int dispatch_cout(const Args &a, int B, hipStream_t st) {
 }
 
 }  // namespace
-inline int chunk_of(int Cin) { return (Cin % 16 == 0) ? 16 : (Cin % 8 == 0) ? 8 : 4; }
 
 // this part's dispatcher (the chain of template choices above); parts 1 and 2 export theirs to part 0's entry
 #if RA_K1_PART == 1
@@ -741,6 +757,7 @@ inline int chunk_of(int Cin) { return (Cin % 16 == 0) ? 16 : (Cin % 8 == 0) ? 8 
 #define RA_K1_DISPATCH k1_dispatch_plain
 int k1_dispatch_bf16(const Args &a, int B, hipStream_t st);
 int k1_dispatch_moments(const Args &a, int B, hipStream_t st);
+int k1_dispatch_kxk(const Args &a, int KF, int B, hipStream_t st);
 #endif
 int RA_K1_DISPATCH(const Args &a, int B, hipStream_t st) {
   switch (chunk_of(a.C0 + a.C1)) {
@@ -749,6 +766,43 @@ int RA_K1_DISPATCH(const Args &a, int B, hipStream_t st) {
     default: return dispatch_cout<4>(a, B, st);
   }
 }
+
+#else  // RA_K1_PART == 3: K1 with a KF x KF filter, KF in {1, 5, 7} (nnlib.cnn / nnlib.dcnn layers of another filter size)
+namespace {
+// The plain form only: pixels as the A operand (every pool / Cout), the zero-stuffed stride-2 transposed conv, and three tile
+// geometries — the 32 x 16 tile where it still yields ~2 workgroups per CU, else 16-col tiles, else one pixel group per wave.
+template <int KF, int CK, int NC, int WN>
+int kxk_geo(const Args &a, int B, hipStream_t st) {
+  constexpr int WM = 4 / WN;
+  auto wgs = [&](int gx, int gy) { return (long)ceil_div(a.W, 8 * gx) * ceil_div(a.H, 2 * gy * WM) * B; };
+  const bool narrow = (a.W % 32 != 0) && (a.W % 32 <= 16);
+  if (!narrow && wgs(4, 2) >= 512) return launch_s<CK, NC, WN, 4, 2, false, false, false, false, KF>(a, B, st);
+  if (wgs(2, 1) >= 200) return launch_s<CK, NC, WN, 2, 1, false, false, false, false, KF>(a, B, st);
+  return launch_s<CK, NC, WN, 1, 1, false, false, false, false, KF>(a, B, st);
+}
+template <int KF, int CK>
+int kxk_cout(const Args &a, int B, hipStream_t st) {
+  const bool small = (long)ceil_div(a.W, 16) * ceil_div(a.H, 8) * B < 256;  // as dispatch_cout
+  switch (a.CoutP) {
+    case 16: return kxk_geo<KF, CK, 1, 1>(a, B, st);
+    case 32: return small ? kxk_geo<KF, CK, 1, 2>(a, B, st) : kxk_geo<KF, CK, 2, 1>(a, B, st);
+    case 64: return small ? kxk_geo<KF, CK, 1, 4>(a, B, st) : kxk_geo<KF, CK, 2, 2>(a, B, st);
+    case 128: return kxk_geo<KF, CK, 2, 4>(a, B, st);
+    default: return fail(RA_E_SHAPE, "ra_convkxk_f32: CoutP %d unsupported", a.CoutP);
+  }
+}
+}  // namespace
+
+int k1_dispatch_kxk(const Args &a, int KF, int B, hipStream_t st) {
+  const int ck = chunk_of_k(KF, a.C0 + a.C1);
+  switch (KF) {
+    case 1: return ck == 16 ? kxk_cout<1, 16>(a, B, st) : ck == 8 ? kxk_cout<1, 8>(a, B, st) : kxk_cout<1, 4>(a, B, st);
+    case 5: return ck == 8 ? kxk_cout<5, 8>(a, B, st) : kxk_cout<5, 4>(a, B, st);
+    case 7: return kxk_cout<7, 4>(a, B, st);
+    default: return fail(RA_E_SHAPE, "ra_convkxk_f32: filter size %d not built (1, 3, 5, 7)", KF);
+  }
+}
+#endif  // RA_K1_PART
 
 }  // namespace conv
 }  // namespace ra
@@ -764,42 +818,52 @@ extern "C" int ra_conv_cout_padded(int Cout) {
   return 0;
 }
 
-extern "C" size_t ra_conv_packed_floats(int Cin, int Cout) {
+static bool kf_built(int KF) { return KF == 1 || KF == 3 || KF == 5 || KF == 7; }
+
+extern "C" size_t ra_conv_packed_floats_k(int KF, int Cin, int Cout) {
   const int cp = ra_conv_cout_padded(Cout);
-  if (Cin <= 0 || Cin % 4 || !cp) return 0;
-  return (size_t)9 * Cin * cp;
+  if (!kf_built(KF) || Cin <= 0 || Cin % 4 || !cp) return 0;
+  return (size_t)KF * KF * Cin * cp;
 }
 
-// Packed order: [chunk][tap = ky*3+kx][cg][ksub][CoutP]; channel = chunk*CK + cg*4 + ksub.
-extern "C" int ra_conv_pack_weights(const float *w, int Cin_w, int Cout, int Cin, const int *chan_map,
-                                    int flags, float *out) {
+extern "C" size_t ra_conv_packed_floats(int Cin, int Cout) { return ra_conv_packed_floats_k(3, Cin, Cout); }
+
+// Packed order: [chunk][tap = ky*KF+kx][cg][ksub][CoutP]; channel = chunk*CK + cg*4 + ksub, CK = chunk_of_k(KF, Cin).
+extern "C" int ra_conv_pack_weights_k(const float *w, int KF, int Cin_w, int Cout, int Cin, const int *chan_map, int flags,
+                                      float *out) {
   const int cp = ra_conv_cout_padded(Cout);
   if (!w || !out || Cin_w <= 0 || Cin <= 0) return ra::fail(RA_E_INVALID, "ra_conv_pack_weights: bad argument");
+  if (!kf_built(KF)) return ra::fail(RA_E_SHAPE, "ra_conv_pack_weights_k: filter size %d not built (1, 3, 5, 7)", KF);
   if (Cin % 4 || !cp) return ra::fail(RA_E_SHAPE, "ra_conv_pack_weights: Cin %d %% 4 or Cout %d", Cin, Cout);
   if (!chan_map && Cin_w != Cin) return ra::fail(RA_E_SHAPE, "ra_conv_pack_weights: Cin_w != Cin without map");
-  const int CK = ra::conv::chunk_of(Cin), NCG = CK / 4;
+  const int CK = ra::conv::chunk_of_k(KF, Cin), NCG = CK / 4, KK = KF * KF;
   const bool tr = flags & RA_CONV_TRANSPOSED;
   for (int c = 0; c < Cin; ++c) {
     const int src_c = chan_map ? chan_map[c] : c;
     if (src_c >= Cin_w) return ra::fail(RA_E_SHAPE, "ra_conv_pack_weights: chan_map[%d] = %d", c, src_c);
     const int chunk = c / CK, cg = (c % CK) / 4, ksub = c % 4;
-    for (int ky = 0; ky < 3; ++ky)
-      for (int kx = 0; kx < 3; ++kx) {
-        const int tap = ky * 3 + kx;
-        float *dst = out + ((((size_t)chunk * 9 + tap) * NCG + cg) * 4 + ksub) * cp;
+    for (int ky = 0; ky < KF; ++ky)
+      for (int kx = 0; kx < KF; ++kx) {
+        const int tap = ky * KF + kx;
+        float *dst = out + ((((size_t)chunk * KK + tap) * NCG + cg) * 4 + ksub) * cp;
         for (int co = 0; co < cp; ++co) {
           float v = 0.f;
           if (co < Cout && src_c >= 0) {
             if (!tr)
-              v = w[(((size_t)ky * 3 + kx) * Cin_w + src_c) * Cout + co];
-            else  // conv2d_transpose filter [3,3,Cout,Cin_w]: flip taps, swap in/out
-              v = w[(((size_t)(2 - ky) * 3 + (2 - kx)) * Cout + co) * Cin_w + src_c];
+              v = w[(((size_t)ky * KF + kx) * Cin_w + src_c) * Cout + co];
+            else  // conv2d_transpose filter [KF,KF,Cout,Cin_w]: flip taps, swap in/out
+              v = w[(((size_t)(KF - 1 - ky) * KF + (KF - 1 - kx)) * Cout + co) * Cin_w + src_c];
           }
           dst[co] = v;
         }
       }
   }
   return 0;
+}
+
+extern "C" int ra_conv_pack_weights(const float *w, int Cin_w, int Cout, int Cin, const int *chan_map,
+                                    int flags, float *out) {
+  return ra_conv_pack_weights_k(w, 3, Cin_w, Cout, Cin, chan_map, flags, out);
 }
 
 extern "C" int ra_conv_fold_bn(const float *bias, const float *beta, const float *gamma,
@@ -840,12 +904,16 @@ int run(const void *x, int Cin, int in_bf16, int B, int H, int W, const float *w
 static int conv3x3_entry(const float *src0, int C0, const float *src1, int C1, int B, int Hs, int Ws, int upsample,
                          const float *wpacked, const float *scale, const float *shift, int Cout, int relu, int pool,
                          const float *plane, int plane_chan, float *y, void *stream, int bf16, float *mom_part = nullptr,
-                         int *nparts = nullptr, int store_flags = 0) {
+                         int *nparts = nullptr, int store_flags = 0, int KF = 3) {
   if (!src0 || !wpacked || !scale || !shift || !y || B <= 0 || Hs <= 0 || Ws <= 0 || C0 <= 0 ||
       C1 < 0 || (C1 > 0 && !src1))
     return ra::fail(RA_E_INVALID, "ra_conv3x3_f32: bad argument");
+  if (!kf_built(KF)) return ra::fail(RA_E_SHAPE, "ra_convkxk_f32: filter size %d not built (1, 3, 5, 7)", KF);
+  if (KF != 3 && (bf16 || mom_part || store_flags))
+    return ra::fail(RA_E_INVALID, "ra_convkxk_f32: filter size %d: float32 operands, no batch moments", KF);
   if (C0 % 4 || C1 % 4) return ra::fail(RA_E_SHAPE, "ra_conv3x3_f32: C0=%d C1=%d must be %% 4", C0, C1);
   ra::conv::Args a;
+  a.org = 1;
   // patch-sized launches (the attention CNN / decoder on 48 x 48 and below: <= 32 K conv pixels) are links of the decode
   // loop's serial tail, a few us each, and run beside other batches' controller CNNs in the pipeline
   a.prio = ((size_t)B * Hs * Ws * (upsample ? 4 : 1) <= 32768) ? ra::tail_prio(2) : 0;
@@ -894,6 +962,13 @@ static int conv3x3_entry(const float *src0, int C0, const float *src1, int C1, i
   // a chunk may not straddle the src0/src1 boundary at finer than 4 channels (always true) but
   // the chunk index arithmetic needs C0 % 4 == 0 only: chunks are resolved per channel group.
   hipStream_t st = ra::as_stream(stream);
+  if (KF != 3) {
+    // window origin (oracle conv2d / conv2d_transpose, TF SAME): stride 1, plain or transposed, is centred; the stride-2
+    // transposed conv reads z[o + j - (KF - 1 - pad_lo)], pad_lo = max(KF - 2, 0) / 2, of z[2i] = x[i] — on the staged
+    // U[2i + 1] = x[i] (U[m] = z[m - 1]) that is origin KF - 2 - pad_lo: -1, 2, 3 for KF = 1, 5, 7
+    a.org = a.ups ? KF - 2 - (KF > 2 ? KF - 2 : 0) / 2 : KF / 2;
+    return ra::conv::k1_dispatch_kxk(a, KF, B, st);
+  }
   // bf16 mode, eight output channels at full resolution: the bf16-LDS kernel (ra_conv8.hip)
   if (a.bf16 && !C1 && !a.ups && pool == 1 && !plane && ra::conv8::takes(C0, Cout, a.in_bf16, B, a.H, a.W))
     return ra::conv8::run(src0, C0, a.in_bf16, B, a.H, a.W, wpacked, scale, shift, relu, y, a.out_bf16, mom_part, nparts,
@@ -914,6 +989,15 @@ extern "C" int ra_conv3x3_f32(const float *src0, int C0, const float *src1, int 
                               int plane_chan, float *y, void *stream) {
   return conv3x3_entry(src0, C0, src1, C1, B, Hs, Ws, upsample, wpacked, scale, shift, Cout, relu, pool, plane,
                        plane_chan, y, stream, 0);
+}
+
+// nnlib.cnn / nnlib.dcnn layers of filter size KF in {1, 3, 5, 7} (nnlib.py:131-257, :260-404); wpacked from
+// ra_conv_pack_weights_k(KF).  KF = 3 is ra_conv3x3_f32 itself.
+extern "C" int ra_convkxk_f32(const float *src0, int C0, const float *src1, int C1, int B, int Hs, int Ws, int upsample,
+                              const float *wpacked, int KF, const float *scale, const float *shift, int Cout, int relu, int pool,
+                              const float *plane, int plane_chan, float *y, void *stream) {
+  return conv3x3_entry(src0, C0, src1, C1, B, Hs, Ws, upsample, wpacked, scale, shift, Cout, relu, pool, plane, plane_chan, y,
+                       stream, 0, nullptr, nullptr, 0, KF);
 }
 
 extern "C" size_t ra_conv3x3_moments_part_floats(int Cout) {

@@ -168,20 +168,32 @@ def _dev(a, like):
   return torch.from_numpy(np.ascontiguousarray(a)).to(like.device)
 
 
+def _check_filter_sizes(f, what):
+  for fi in f:
+    if fi not in ops.FILTER_SIZES:
+      raise RecAttendError('%s: filter size %r not built (sizes %s)' % (what, fi, ops.FILTER_SIZES))
+
+
+def _check_train_filter_sizes(f, what):
+  """Training (the backward kernels) is built for 3x3 filters only: refuse before any kernel runs."""
+  if any(fi != 3 for fi in f):
+    raise RecAttendError('%s: training with filter sizes %s is not built (3x3 only; eval decodes any of %s)' %
+                         (what, list(f), ops.FILTER_SIZES))
+
+
 def cnn(f, ch, pool, act, use_bn, phase_train=None, wd=None, scope='cnn', model=None,
         init_weights=None, frozen=None, shared_weights=None):
   """nnlib.py:131-257.  Returns run_cnn(x) -> list of the N layer outputs.
 
-  Each layer is ONE fused kernel: conv3x3 + bias + BN(copy) + ReLU + max-pool.  `act[i]`
-  must be relu (or None); `f[i]` must be 3.  BN parameters are separate per call ("copy"),
+  Each layer is ONE fused kernel: conv f x f + bias + BN(copy) + ReLU + max-pool.  `act[i]`
+  must be relu (or None); `f[i]` in ops.FILTER_SIZES (training: 3).  BN parameters are separate per call ("copy"),
   like the reference's copy counter (nnlib.py:212,254); run_cnn.reset_copy() rewinds it for
   the next forward pass, run_cnn(x, copy=t) addresses a copy explicitly."""
   nlayers = len(f)
   w = [None] * nlayers
   b = [None] * nlayers
+  _check_filter_sizes(f, 'cnn')
   for ii in range(nlayers):
-    if f[ii] != 3:
-      raise RecAttendError('cnn: filter size %d not built (path uses 3x3 only)' % f[ii])
     iw = init_weights[ii] if init_weights is not None and init_weights[ii] is not None else None
     trainable = not (frozen is not None and frozen[ii])
     if shared_weights:
@@ -234,6 +246,7 @@ def cnn(f, ch, pool, act, use_bn, phase_train=None, wd=None, scope='cnn', model=
     """phase_train = True: per layer conv + b -> BN on the batch moments -> ReLU -> max-pool as one autograd node on the
     training step's kernels; the copy's EMA shadows move (nnlib.py:229-253 with :98-112)."""
     import ra_train as rt
+    _check_train_filter_sizes(f, 'cnn')
     h = [None] * nlayers
     prev = x
     stats = run_cnn.batch_stats = {}
@@ -269,8 +282,8 @@ def cnn(f, ch, pool, act, use_bn, phase_train=None, wd=None, scope='cnn', model=
       if cin % 4:
         prev = torch.nn.functional.pad(prev, (0, 4 - cin % 4))
       wp, sc, sh = layer_params(ii, cp, prev, cin_kernel=prev.shape[3])
-      h[ii] = ops.conv3x3(prev.contiguous(), wp, sc, sh, ch[ii + 1], relu=act[ii] is not None,
-                          pool=pool[ii] if pool[ii] > 1 else 1)
+      h[ii] = ops.conv2d_fused(prev.contiguous(), wp, sc, sh, ch[ii + 1], f[ii], relu=act[ii] is not None,
+                               pool=pool[ii] if pool[ii] > 1 else 1)
       if pool[ii] > 2:
         raise RecAttendError('cnn: pool ratio %d not fused (path uses 1 or 2)' % pool[ii])
       prev = h[ii]
@@ -298,9 +311,8 @@ def dcnn(f, ch, pool, act, use_bn, skip_ch=None, phase_train=None, wd=None, scop
   b = [None] * nlayers
   in_chs = [None] * nlayers
   in_ch = ch[0]
+  _check_filter_sizes(f, 'dcnn')
   for ii in range(nlayers):
-    if f[ii] != 3:
-      raise RecAttendError('dcnn: filter size %d not built' % f[ii])
     out_ch = ch[ii + 1]
     if skip_ch is not None and skip_ch[ii] is not None:
       in_ch += skip_ch[ii]
@@ -353,6 +365,7 @@ def dcnn(f, ch, pool, act, use_bn, skip_ch=None, phase_train=None, wd=None, scop
     node per layer on the training step's kernels (nnlib.py:362-400 with :98-112).  The concat is ONE packed kernel
     input whose chan_map sends every packed channel to its row of the [3,3,out,in] filter."""
     import ra_train as rt
+    _check_train_filter_sizes(f, 'dcnn')
     h = [None] * nlayers
     prev = x
     stats = run_dcnn.batch_stats = {}
@@ -397,9 +410,9 @@ def dcnn(f, ch, pool, act, use_bn, skip_ch=None, phase_train=None, wd=None, scop
       if pool[ii] not in (1, 2):
         raise RecAttendError('dcnn: unpool ratio %d not built' % pool[ii])
       wp, sc, sh = layer_params(ii, cp, prev, prev.shape[3], 0 if sk is None else sk.shape[3])
-      h[ii] = ops.conv3x3(prev.contiguous(), wp, sc, sh, ch[ii + 1], relu=act[ii] is not None,
-                          pool=1, src1=None if sk is None else sk.contiguous(),
-                          upsample=(pool[ii] == 2))
+      h[ii] = ops.conv2d_fused(prev.contiguous(), wp, sc, sh, ch[ii + 1], f[ii], relu=act[ii] is not None,
+                               pool=1, src1=None if sk is None else sk.contiguous(),
+                               upsample=(pool[ii] == 2))
       prev = h[ii]
     if copy_idx is None:
       copy[0] += 1

@@ -133,12 +133,18 @@ class DecodeEngine(object):
       return _dev(np.stack(sc), device), _dev(np.stack(sh), device)
 
     W = {}
+    # filter size per layer (nnlib.cnn / dcnn take one each): a layer of another size than 3 packs with its own and always runs
+    # on ra_convkxk_f32 — none of the 3x3 forms (Winograd, K1s, fused pairs, the first layer's image cache, extract + conv0)
+    ks = self.ksize = {'ccnn': list(d['ccnn_filters'])}
+    if not self.box:
+      ks['acnn'], ks['adcnn'] = list(d['acnn_filters']), list(d['adcnn_filters'])
     cmap_c, n_c = self._chan_map(d['ctrl_in'])
     assert n_c == d['ccnn_channels'][0]
     W['ccnn'], W['ccnn_wino'], W['ccnn_split'] = [], [], []
     hh, ww = d['H'], d['W']
     for i in range(d['ccnn_nlayers']):
       cin, cout = d['ccnn_channels'][i], d['ccnn_channels'][i + 1]
+      k3 = ks['ccnn'][i] == 3
       if i == 0:
         wp = ops.pack_conv_weights(M['ctrl_cnn_w_0'], cin_kernel=d['C0p'], chan_map=cmap_c)
       else:
@@ -146,16 +152,17 @@ class DecodeEngine(object):
       sc, sh = fold_all('ctrl_cnn', i, cout)
       W['ccnn'].append((_dev(wp, device), sc, sh, cout, d['ccnn_pool'][i]))
       # mid-resolution layers also as Winograd F(2x2,3x3) filters (K1w: 2.25x fewer MFMAs), where the shape allows
-      wino = i > 0 and self.use_wino and ops.conv_wino_supported(cin, cout, d['ccnn_pool'][i], hh, ww)
+      wino = i > 0 and k3 and self.use_wino and ops.conv_wino_supported(cin, cout, d['ccnn_pool'][i], hh, ww)
       W['ccnn_wino'].append(_dev(ops.pack_wino_weights(M['ctrl_cnn_w_%d' % i]), device) if wino else None)
       # ... and as the exact three-piece bf16 split of the filter, for the direct form on the bf16 matrix pipe (K1s, round 5)
       # Cin >= 32: always.  Cin = 16: where Winograd does not take the layer; and, round 6, where the layer has 16 output channels —
       # K1s then runs two workgroups per CU (Geo::OCC) with two windows in flight and beats K1w (KITTI's L1, 16 -> 16 pool 2:
       # 12.4 -> 10.1 us at cfg3, 8.1 -> 6.8 at cfg5); 16 -> 32 stays with K1w (cfg2's L4 12.3 vs 12.9 us, cfg5's L2 6.0 vs 7.1:
       # profiles/r06_k1s_sweep.txt)
-      split = (i > 0 and self.use_split and (cin >= int(os.environ.get('RA_SPLIT_MIN_CIN', '32')) or not wino or cout == 16) and
+      split = (i > 0 and k3 and self.use_split and (cin >= int(os.environ.get('RA_SPLIT_MIN_CIN', '32')) or not wino or cout == 16) and
                ops.conv_split_supported(_r4(cin), cout, d['ccnn_pool'][i], hh, ww))
-      if i == 0 and self.use_split and self.split_first and d['C0p'] != 4 and ops.conv_split_supported(d['C0p'], cout, d['ccnn_pool'][0], hh, ww):
+      if (i == 0 and k3 and self.use_split and self.split_first and d['C0p'] != 4 and
+          ops.conv_split_supported(d['C0p'], cout, d['ccnn_pool'][0], hh, ww)):
         W['ccnn_split'].append(torch.from_numpy(ops.pack_split_weights(M['ctrl_cnn_w_0'], cin_kernel=d['C0p'], chan_map=cmap_c)).to(device))
       else:
         W['ccnn_split'].append(torch.from_numpy(ops.pack_split_weights(M['ctrl_cnn_w_%d' % i])).to(device) if split else None)
@@ -190,14 +197,15 @@ class DecodeEngine(object):
         sc, sh = fold_all('attn_cnn', i, cout)
         W['acnn'].append((_dev(wp, device), sc, sh, cout, d['acnn_pool'][i]))
         ck = d['C0p'] if i == 0 else _r4(cin)
+        k3 = ks['acnn'][i] == 3
         sp = None
-        if self.use_split and self.split_patch != '0' and ops.conv_split_supported(ck, cout, d['acnn_pool'][i], ph, pw):
+        if k3 and self.use_split and self.split_patch != '0' and ops.conv_split_supported(ck, cout, d['acnn_pool'][i], ph, pw):
           mf = 2e-6 * 9 * cin * cout * ph * pw  # MFLOP per image
           if self.split_patch == '1' or mf >= float(os.environ.get('RA_SPLIT_PATCH_MIN_MF', '4')):
             sp = torch.from_numpy(ops.pack_split_weights(M['attn_cnn_w_%d' % i], cin_kernel=ck, chan_map=cmap_a if i == 0 else None)).to(device)
         W['acnn_split'].append(sp)
         ph, pw = ph // d['acnn_pool'][i], pw // d['acnn_pool'][i]
-        if i == 0 and ops.extract_conv0_supported(d['C0p'], d['Fh'], d['Fw'], cout, d['acnn_pool'][0]):
+        if i == 0 and k3 and ops.extract_conv0_supported(d['C0p'], d['Fh'], d['Fw'], cout, d['acnn_pool'][0]):
           # the layer's filter in the PACKED input's channel order, for the launch that fuses it into the extract
           w0 = M['attn_cnn_w_0'].detach().cpu().numpy().astype(np.float32)
           plain = np.zeros((3, 3, d['C0p'], cout), np.float32)
@@ -246,12 +254,12 @@ class DecodeEngine(object):
     d = self.d
     plan = {}
 
-    def pair_up(n, cin, cout, a_ok, b_ok, unfuse=lambda i: False):
+    def pair_up(n, cin, cout, a_ok, b_ok, unfuse=lambda i: False, ks=None):
       steps, i = [], 0
       while i < n:
         # measured on MI355X: fusion pays while the intermediate has <= 16 channels (LDS tile
-        # small enough for a 16x32 tile); wider pairs recompute too much halo
-        if (self.fuse_pairs and i + 1 < n and a_ok(i) and b_ok(i + 1) and cout(i) <= 16 and
+        # small enough for a 16x32 tile); wider pairs recompute too much halo.  3x3 layers only
+        if (self.fuse_pairs and i + 1 < n and ks[i] == 3 and ks[i + 1] == 3 and a_ok(i) and b_ok(i + 1) and cout(i) <= 16 and
             ops.conv_pair_supported(cin(i), cout(i), cout(i + 1)) and not unfuse(i + 1)):
           steps.append(('pair', i, i + 1))
           i += 2
@@ -264,7 +272,7 @@ class DecodeEngine(object):
     # a layer that can run as Winograd (K1w) is worth more alone than as the second half of a fused pair
     wino_alone = lambda i: self.use_wino and self.wino_unfuse and W['ccnn_wino'][i] is not None
     plan['ccnn'] = pair_up(d['ccnn_nlayers'], lambda i: d['C0p'] if i == 0 else _r4(cc[i]),
-                           lambda i: cc[i + 1], lambda i: d['ccnn_pool'][i] == 1, lambda i: True, wino_alone)
+                           lambda i: cc[i + 1], lambda i: d['ccnn_pool'][i] == 1, lambda i: True, wino_alone, ks=self.ksize['ccnn'])
     if not self.box:
       ac = d['acnn_channels']
       L = d['acnn_nlayers']
@@ -273,12 +281,12 @@ class DecodeEngine(object):
       fuse_patch = self.fuse_patch_pairs
       plan['acnn'] = pair_up(L, lambda i: d['C0p'] if i == 0 else _r4(ac[i]), lambda i: ac[i + 1],
                              lambda i: fuse_patch and d['acnn_pool'][i] == 1 and i not in skip_used,
-                             lambda i: True)
+                             lambda i: True, ks=self.ksize['acnn'])
       dc = d['adcnn_channels']
       lay = W['adcnn']
       plan['adcnn'] = pair_up(d['adcnn_nlayers'], lambda i: _r4(dc[i]), lambda i: dc[i + 1],
                               lambda i: fuse_patch and lay[i][5] is None,
-                              lambda i: lay[i][5] is None and lay[i][4] == 1)
+                              lambda i: lay[i][5] is None and lay[i][4] == 1, ks=self.ksize['adcnn'])
     return plan
 
   # ------------------------------------------------------------------ buffers
@@ -338,7 +346,7 @@ class DecodeEngine(object):
       b['gmaps'] = f(T, Bs, d['iters'], d['G'])
       b['attn'] = f(T, Bs, rn.RA_ATTN_STRIDE)
       st0 = self.plan['ccnn'][0]
-      if self.cache_first and st0[0] == 'pair' and d['C0p'] == 4 and \
+      if self.cache_first and st0[0] == 'pair' and d['C0p'] == 4 and self.ksize['ccnn'][:2] == [3, 3] and \
           ops.first_cache_supported(4, d['ccnn_channels'][1], d['ccnn_channels'][2], d['ccnn_pool'][1], H, W):
         b['l0cache'] = ops.first_cache_alloc(Bs, H, W, device)
       # the 16 workgroups of an image exchange through spin-waits, so ALL workgroups of every launch that
@@ -557,8 +565,12 @@ class DecodeEngine(object):
         i = step[1]
         wp, sc, sh, cout, unpool, sidx = Wt['adcnn'][i]
         out = b['y_out_patch'][tt] if b['adcnn'][i] is None else b['adcnn'][i]
-        ops.conv3x3(src, wp, sc[tt], sh[tt], cout, relu=True, pool=1,
-                    src1=None if sidx is None else skips[sidx], upsample=(unpool == 2), out=out)
+        if self.ksize['adcnn'][i] != 3:
+          ops.conv2d_fused(src, wp, sc[tt], sh[tt], cout, self.ksize['adcnn'][i], relu=True, pool=1,
+                           src1=None if sidx is None else skips[sidx], upsample=(unpool == 2), out=out)
+        else:
+          ops.conv3x3(src, wp, sc[tt], sh[tt], cout, relu=True, pool=1,
+                      src1=None if sidx is None else skips[sidx], upsample=(unpool == 2), out=out)
       src = out
     self._mark('attn_dcnn')
     fused_score = self.fuse_score and self.timing is None
@@ -583,6 +595,7 @@ class DecodeEngine(object):
     """plane: the canvas plane standing in for channel D of the FIRST layer's packed input;
     cache: the first layer's timestep-invariant image part (ops.first_cache)."""
     pc = self.d['D'] if plane is not None else -1
+    ks = self.ksize['acnn'] if layers is self.W.get('acnn') else self.ksize['ccnn']  # the layers' filter sizes
     for step in steps:
       pl = plane if step[1] == 0 else None
       if step[0] == 'pair':
@@ -611,7 +624,10 @@ class DecodeEngine(object):
           split = self.W['ccnn_split'][i]
         elif self.use_split and layers is self.W.get('acnn'):
           split = self.W['acnn_split'][i]
-        if split is not None:
+        if ks[i] != 3:
+          ops.conv2d_fused(src, wp, sc[tt], sh[tt], cout, ks[i], relu=True, pool=pool, out=bufs[i], plane=pl,
+                           plane_chan=pc if pl is not None else -1)
+        elif split is not None:
           ops.conv_split(src, split, sc[tt], sh[tt], cout, relu=True, pool=pool, out=bufs[i], plane=pl, plane_chan=pc if pl is not None else -1)
         elif wino is not None:
           ops.conv_wino(src, wino, sc[tt], sh[tt], cout, relu=True, pool=pool, out=bufs[i])

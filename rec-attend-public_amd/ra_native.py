@@ -62,6 +62,10 @@ SIGNATURES = {
     'ra_conv_pack_weights': (_I, [_P, _I, _I, _I, _P, _I, _P]),
     'ra_conv_fold_bn': (_I, [_P, _P, _P, _P, _P, _I, _F, _P, _P]),
     'ra_conv3x3_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    # nnlib.cnn / nnlib.dcnn layers of filter size 1, 5 or 7 (nnlib.py:131-257, :260-404)
+    'ra_conv_packed_floats_k': (_Z, [_I, _I, _I]),
+    'ra_conv_pack_weights_k': (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),
+    'ra_convkxk_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
     'ra_conv3x3_moments_part_floats': (_Z, [_I]),
     'ra_conv3x3_moments_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _Z, _P, _P]),
     'ra_bn_moments_from_partials_f32': (_I, [_P, _I, _I, _P, _P, _P]),

@@ -38,17 +38,22 @@ def cout_padded(cout):
   return rn.lib().ra_conv_cout_padded(int(cout))
 
 
+FILTER_SIZES = (1, 3, 5, 7)  # the K1 filter sizes built (ra_convkxk_f32)
+
+
 def pack_conv_weights(w, cin_kernel=None, chan_map=None, transposed=False):
-  """TF-layout filter -> packed B-operand order (numpy, host).  w [3,3,Ci,Co] or, when
-  transposed, the conv2d_transpose filter [3,3,Co,Ci]."""
+  """TF-layout filter -> packed B-operand order (numpy, host).  w [f,f,Ci,Co] or, when
+  transposed, the conv2d_transpose filter [f,f,Co,Ci]; f in FILTER_SIZES (3: ra_conv_pack_weights,
+  else ra_conv_pack_weights_k — the input of conv2d_fused(..., ksize=f))."""
   w = _np32(w)
-  if w.shape[0] != 3 or w.shape[1] != 3:
-    raise rn.RecAttendError('only 3x3 filters are supported, got %r' % (w.shape,))
+  f = w.shape[0]
+  if w.ndim != 4 or w.shape[1] != f or f not in FILTER_SIZES:
+    raise rn.RecAttendError('filter of shape %r: square filters of size %s are built' % (w.shape, FILTER_SIZES))
   cin_w, cout = (w.shape[3], w.shape[2]) if transposed else (w.shape[2], w.shape[3])
   cin = cin_w if cin_kernel is None else int(cin_kernel)
   if chan_map is None and cin != cin_w:
     chan_map = list(range(cin_w)) + [-1] * (cin - cin_w)
-  n = rn.lib().ra_conv_packed_floats(cin, cout)
+  n = rn.lib().ra_conv_packed_floats(cin, cout) if f == 3 else rn.lib().ra_conv_packed_floats_k(f, cin, cout)
   if n == 0:
     raise rn.RecAttendError('unsupported conv shape Cin=%d Cout=%d' % (cin, cout))
   out = np.empty(n, dtype=np.float32)
@@ -56,9 +61,11 @@ def pack_conv_weights(w, cin_kernel=None, chan_map=None, transposed=False):
   if chan_map is not None:
     cm = np.ascontiguousarray(chan_map, dtype=np.int32)
     assert cm.shape[0] == cin
-  check(rn.lib().ra_conv_pack_weights(ptr(w), cin_w, cout, cin, ptr(cm),
-                                      rn.RA_CONV_TRANSPOSED if transposed else 0, ptr(out)),
-        'ra_conv_pack_weights')
+  flags = rn.RA_CONV_TRANSPOSED if transposed else 0
+  if f == 3:
+    check(rn.lib().ra_conv_pack_weights(ptr(w), cin_w, cout, cin, ptr(cm), flags, ptr(out)), 'ra_conv_pack_weights')
+  else:
+    check(rn.lib().ra_conv_pack_weights_k(ptr(w), f, cin_w, cout, cin, ptr(cm), flags, ptr(out)), 'ra_conv_pack_weights_k')
   return out
 
 
@@ -193,6 +200,26 @@ def conv3x3(src0, wp, scale, shift, cout, relu=True, pool=1, src1=None, upsample
   check(fn(ptr(src0), C0, ptr(src1), C1, B, Hs, Ws, int(upsample), ptr(wp), ptr(scale), ptr(shift), int(cout),
            int(relu), int(pool), ptr(plane), int(plane_chan), ptr(out), rn.stream_ptr()),
         'ra_conv3x3_bf16ops_f32' if bf16 else 'ra_conv3x3_f32')
+  return out
+
+
+def conv2d_fused(src0, wp, scale, shift, cout, ksize, relu=True, pool=1, src1=None, upsample=False, out=None, plane=None,
+                 plane_chan=-1):
+  """conv3x3 for a ksize x ksize filter, ksize in FILTER_SIZES; wp = pack_conv_weights of that filter.  ksize = 3 IS
+  conv3x3; other sizes run ra_convkxk_f32 (float32 operands only)."""
+  if ksize == 3:
+    return conv3x3(src0, wp, scale, shift, cout, relu=relu, pool=pool, src1=src1, upsample=upsample, out=out, plane=plane,
+                   plane_chan=plane_chan)
+  _need_cuda(src0, src1, wp, scale, shift, out)
+  B, Hs, Ws, C0 = src0.shape
+  C1 = 0 if src1 is None else src1.shape[3]
+  up = 2 if upsample else 1
+  Ho, Wo = Hs * up // pool, Ws * up // pool
+  if out is None:
+    out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=src0.device)
+  check(rn.lib().ra_convkxk_f32(ptr(src0), C0, ptr(src1), C1, B, Hs, Ws, int(upsample), ptr(wp), int(ksize), ptr(scale),
+                                ptr(shift), int(cout), int(relu), int(pool), ptr(plane), int(plane_chan), ptr(out),
+                                rn.stream_ptr()), 'ra_convkxk_f32')
   return out
 
 

@@ -1473,6 +1473,14 @@ def _flat_bn_statistics(trainer):
     eng._stamp = None
 
 
+def _check_3x3(d, keys):
+  """The training step's kernels (data / weight gradients, batch moments, bf16) are built for 3x3 filters only: a model with
+  another filter size decodes (ra_convkxk_f32) but refuses to train, before any kernel runs."""
+  bad = ['%s %s' % (k, d[k]) for k in keys if k in d and any(f != 3 for f in d[k])]
+  if bad:
+    raise rn.RecAttendError('training is built for 3x3 filters only; this model has filter sizes %s' % ', '.join(bad))
+
+
 class TrainStep(object):
   """model.run(['loss', 'train_step'], feed) of the reference's trainer (full_model_train.py:107)."""
 
@@ -1480,6 +1488,7 @@ class TrainStep(object):
     import full_model  # noqa: F401  (the Model class)
     self.model, self.opt, self.d = model, model.opt, model.dims
     d = self.d
+    _check_3x3(d, ('ccnn_filters', 'acnn_filters', 'adcnn_filters'))
     if not torch.cuda.is_available():
       raise rn.RecAttendError('the training step needs an MI355X (HIP device); there is no CPU fallback')
     if self.opt.get('box_loss_fn', 'iou') not in ('iou', 'mse', 'huber') or \
@@ -2469,6 +2478,7 @@ class BoxTrainStep(TrainStep):
 
   def __init__(self, model, world=1):
     self.model, self.opt, self.d = model, model.opt, model.dims
+    _check_3x3(self.d, ('ccnn_filters',))
     if not torch.cuda.is_available():
       raise rn.RecAttendError('the training step needs an MI355X (HIP device); there is no CPU fallback')
     if self.opt.get('box_loss_fn', 'iou') not in ('iou', 'mse', 'huber'):
