@@ -134,6 +134,30 @@ int ra_convkxk_f32(const float *src0, int C0, const float *src1, int C1, int B, 
                    const float *wpacked, int KF, const float *scale, const float *shift, int Cout, int relu, int pool,
                    const float *plane, int plane_chan, float *y, void *stream);
 
+/* K1-wide: the same fused layer for the channel widths K1 refuses — Cout 129 .. 512 (a multiple of 16), C0 + C1 <= 1024, each
+ * a multiple of 4 (ra_conv_wide_supported(C0 + C1, Cout)).  These are the inner layers of fg_model, the fully
+ * convolutional pre-stage that produces y_in / d_in (fg_model.py:112-160: nnlib.cnn run_cnn nnlib.py:229-253 and nnlib.dcnn
+ * run_dcnn nnlib.py:362-400 with 192 .. 512 channels and skip concats of up to 1024).  Exact float32 on the f32 MFMA, both
+ * operands staged through LDS, the Cout range split over workgroups in slices of 64 (csrc/ra_conv_wide.hip); no canvas
+ * plane.  wpacked: ra_conv_wide_packed_floats() floats from ra_conv_wide_pack_weights (arguments as ra_conv_pack_weights;
+ * packed order [co / 64][c / 16][tap][ksub][co % 64][cg], channel c = 16 chunk + 4 cg + ksub, zero past Cin and Cout).
+ * scale / shift: Cout floats.  A shape outside the range returns RA_E_SHAPE without a launch. */
+int ra_conv_wide_supported(int Cin, int Cout);
+size_t ra_conv_wide_packed_floats(int Cin, int Cout);
+int ra_conv_wide_pack_weights(const float *w, int Cin_w, int Cout, int Cin, const int *chan_map, int flags, float *out);
+int ra_conv3x3_wide_f32(const float *src0, int C0, const float *src1, int C1, int B, int Hs, int Ws, int upsample,
+                        const float *wpacked, const float *scale, const float *shift, int Cout, int relu, int pool,
+                        float *y, void *stream);
+
+/* The head of fg_model (fg_model.py:179-194): logits [npix, nsc + no] -> y_out [npix, nsc] = sigmoid (nsc == 1) or softmax
+ * over the nsc semantic classes, d_out [npix, no] = softmax over the no orientation classes (nsc 1 .. 16; no 0 | 8, d_out
+ * NULL when 0).  quantise != 0 stores floor(v * 255) / 255: the 8-bit round trip of the pack step (fg_model_pack.py:41-48
+ * writes PNGs, data_api/ins_seg_dataset.py:273-292 reads them back as uint8 / 255).  packed (nullable): also writes the
+ * decode loop's packed input image [npix, Cp] = [x (D) | canvas = 0 | d_out | y_out | 0 ...] — ra_pack_input_plane_f32's
+ * pixel, from x [npix, D] — and zeroes canvas_plane [npix] (nullable), so a chained run needs no pack launch. */
+int ra_fg_head_f32(const float *logits, size_t npix, int nsc, int no, int quantise, float *y_out, float *d_out,
+                   const float *x, int D, float *packed, int Cp, float *canvas_plane, void *stream);
+
 /* Mixed precision for the training step (model_opt['compute_dtype'] = 'bf16'; the reference trains in float32 —
  * this is an extension behind its option dictionary): the same layer with bf16 OPERANDS — pixels and weights are
  * rounded to bf16 (round-to-nearest-even) on their way from LDS / registers into v_mfma_f32_16x16x16_bf16 — and

@@ -6,7 +6,8 @@ Restores results/<model_id>/{model_opt.yaml, weights.npz}, forces `use_knob=Fals
 ['y_out', 's_out'] (full_model_eval.py:35; runner.py:91-105) batch by batch on the MI355X
 kernels, sharding the images over the ranks when launched with torch.distributed.run.  Inputs
 come from --input (an .npz with x [N,H,W,3] and optionally d_in / y_in / y_gt / s_gt / fg) or are
-synthetic; the reference's HDF5 datasets are out of scope.  The raw outputs are
+synthetic; with --fg_model_id (not a reference flag) d_in / y_in come from that fg_model's prestage() on the device, batch by
+batch, as the 8-bit values fg_model_pack.py would store; the reference's HDF5 datasets are out of scope.  The raw outputs are
 written to <output>/output_<split>/pred_rank<r>.npz.  With y_gt and s_gt in the input the
 reference's write_log chain (full_model_eval.py:97-139) runs on the device for every threshold of
 --threshold_list (default 0.3, the reference CLI's default, :193-194): apply_confidence, apply_one_label,
@@ -38,6 +39,9 @@ def build_parser():
   p.add_argument('--fused_postprocess', action='store_true',
                  help='not a reference flag: skip upsample\'s bilateral filter when the labels have the network\'s size (one fused '
                       'post-processing pass; results near the threshold differ from the reference chain)')
+  p.add_argument('--fg_model_id', default=None,
+                 help='not a reference flag: run this fg_model (results/<id>/{model_opt.yaml, weights.npz}) in front of the decode '
+                      'loop; d_in / y_in then come from its prestage() on the device, not from --input')
   p.add_argument('--in_flight', type=int, default=8, help='batches submitted to one GPU at a time (four decode concurrently, the rest queue behind them)')
   return p
 
@@ -66,6 +70,12 @@ def main(argv=None):
       data['d_in'] = np.eye(8, dtype=np.float32)[rng.randint(0, 8, (n, H, W))]
       lg = rng.randn(n, H, W, model.dims['nsc']).astype(np.float32)
       data['y_in'] = np.exp(lg) / np.exp(lg).sum(-1, keepdims=True)
+  fg = None
+  if args.fg_model_id:
+    import fg_model_pack
+    fg = fg_model_pack.restore_model(args.results, args.fg_model_id)
+    for k in ('d_in', 'y_in'):
+      data.pop(k, None)
   lo, hi = ra_dist.shard_range(rank, world, data['x'].shape[0])
   # the reference CLI defaults to [0.3] (MyEvalArgsParser.make_opt, full_model_eval.py:193-198); the
   # 0.0 .. 0.9 sweep of :39-40 is only EvalRunner's fallback for a caller that hands it None
@@ -79,12 +89,12 @@ def main(argv=None):
   acc = {th: {n: [] for n in names} for th in thresholds}
   ys, ss, t0 = [], [], time.time()
   try:
-    _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0)
+    _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0, fg=fg)
   finally:
     ra_dist.barrier()  # always reached: a rank that fails must not leave the others hanging
 
 
-def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0):
+def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0, fg=None):
   import torch
   def consume(b0, b1, y_dev, s_dev):
     if analyze:
@@ -136,6 +146,8 @@ def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, anal
     b1 = min(hi, b0 + args.batch_size)
     feed = {k: v[b0:b1] for k, v in data.items() if k in ('x', 'd_in', 'y_in')}
     feed['phase_train'] = False
+    if fg is not None:  # the pre-stage: the 8-bit values the pack step would store, as device tensors
+      feed['y_in'], feed['d_in'] = fg.prestage(feed['x'], quantise=True)
     left = -(-(hi - b1) // args.batch_size)  # batches still to come: the last few go out one per slot (DecodePipeline._ends_soon)
     while pipe.full(b1 - b0, remaining=left):
       consume(*(spans.pop(0) + tuple(pipe.collect())))

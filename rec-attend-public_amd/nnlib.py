@@ -181,18 +181,39 @@ def _check_train_filter_sizes(f, what):
                          (what, list(f), ops.FILTER_SIZES))
 
 
+WIDE_COUT = 128  # K1 serves up to 128 output channels; wider 3x3 layers run the wide kernel (ops.conv_wide), eval only
+
+
+def _check_wide_layers(f, ch, what):
+  """Layers of more than 128 output channels (fg_model's inner layers) are built for 3x3 filters only."""
+  for ii, fi in enumerate(f):
+    if ch[ii + 1] > WIDE_COUT and fi != 3:
+      raise RecAttendError('%s: layer %d has %d output channels and filter size %d: wide layers (more than %d channels) '
+                           'are built for 3x3 filters only' % (what, ii, ch[ii + 1], fi, WIDE_COUT))
+
+
+def _check_train_wide(ch, what):
+  """Training (the backward kernels) is built for layers of up to 128 output channels: refuse before any kernel runs."""
+  wide = [c for c in ch[1:] if c > WIDE_COUT]
+  if wide:
+    raise RecAttendError('%s: training with layers of %s output channels is not built (up to %d; eval decodes 3x3 layers '
+                         'of up to 512)' % (what, wide, WIDE_COUT))
+
+
 def cnn(f, ch, pool, act, use_bn, phase_train=None, wd=None, scope='cnn', model=None,
         init_weights=None, frozen=None, shared_weights=None):
   """nnlib.py:131-257.  Returns run_cnn(x) -> list of the N layer outputs.
 
   Each layer is ONE fused kernel: conv f x f + bias + BN(copy) + ReLU + max-pool.  `act[i]`
-  must be relu (or None); `f[i]` in ops.FILTER_SIZES (training: 3).  BN parameters are separate per call ("copy"),
+  must be relu (or None); `f[i]` in ops.FILTER_SIZES (training: 3).  A 3x3 layer of more than 128 output channels (up to 512;
+  fg_model's inner layers) runs the wide kernel (ops.conv_wide) at eval; training refuses it.  BN parameters are separate per call ("copy"),
   like the reference's copy counter (nnlib.py:212,254); run_cnn.reset_copy() rewinds it for
   the next forward pass, run_cnn(x, copy=t) addresses a copy explicitly."""
   nlayers = len(f)
   w = [None] * nlayers
   b = [None] * nlayers
   _check_filter_sizes(f, 'cnn')
+  _check_wide_layers(f, ch, 'cnn')
   for ii in range(nlayers):
     iw = init_weights[ii] if init_weights is not None and init_weights[ii] is not None else None
     trainable = not (frozen is not None and frozen[ii])
@@ -247,6 +268,7 @@ def cnn(f, ch, pool, act, use_bn, phase_train=None, wd=None, scope='cnn', model=
     training step's kernels; the copy's EMA shadows move (nnlib.py:229-253 with :98-112)."""
     import ra_train as rt
     _check_train_filter_sizes(f, 'cnn')
+    _check_train_wide(ch, 'cnn')
     h = [None] * nlayers
     prev = x
     stats = run_cnn.batch_stats = {}
@@ -305,13 +327,14 @@ def dcnn(f, ch, pool, act, use_bn, skip_ch=None, phase_train=None, wd=None, scop
 
   Layer = [concat(prev, skip[i])] -> conv2d_transpose(w[f,f,out,in], stride pool[i], SAME) + b
   -> BN(copy) -> ReLU, as ONE fused kernel (the concat is two source pointers, the stride-2
-  transpose is a conv over the zero-stuffed input with flipped taps)."""
+  transpose is a conv over the zero-stuffed input with flipped taps).  Wide layers (more than 128 output channels) as in cnn."""
   nlayers = len(f)
   w = [None] * nlayers
   b = [None] * nlayers
   in_chs = [None] * nlayers
   in_ch = ch[0]
   _check_filter_sizes(f, 'dcnn')
+  _check_wide_layers(f, ch, 'dcnn')
   for ii in range(nlayers):
     out_ch = ch[ii + 1]
     if skip_ch is not None and skip_ch[ii] is not None:
@@ -366,6 +389,7 @@ def dcnn(f, ch, pool, act, use_bn, skip_ch=None, phase_train=None, wd=None, scop
     input whose chan_map sends every packed channel to its row of the [3,3,out,in] filter."""
     import ra_train as rt
     _check_train_filter_sizes(f, 'dcnn')
+    _check_train_wide(ch, 'dcnn')
     h = [None] * nlayers
     prev = x
     stats = run_dcnn.batch_stats = {}

@@ -500,8 +500,11 @@ class DecodeEngine(object):
             ops.fill_rider_ok(b['y_out']))
 
   def _launch_pack(self, b):
-    ops.pack_input(b['x'], b.get('d_in'), b.get('y_in'), self.d['C0p'], b['img'],
-                   canvas_plane=b['canvas'])  # canvas = 0 (full_model.py:239) in the same pass
+    if self._prepacked:  # fg_model's head wrote b['img'] (forward(prepacked=True)); the canvas starts at zero in every forward
+      b['canvas'].zero_()
+    else:
+      ops.pack_input(b['x'], b.get('d_in'), b.get('y_in'), self.d['C0p'], b['img'],
+                     canvas_plane=b['canvas'])  # canvas = 0 (full_model.py:239) in the same pass
     if not self.box and not self.d['disable_overwrite']:
       # every pixel outside an attention window is sigmoid(0 - 5) (full_model.py:813-818): fill
       # once per forward, the per-timestep paste then writes windows only.  Nothing reads y_out before
@@ -662,9 +665,26 @@ class DecodeEngine(object):
     self._mark('box_step')
 
   # ------------------------------------------------------------------ public
-  def forward(self, x, d_in=None, y_in=None, y_gt=None, noise=None, want_box=False):
+  _prepacked = False
+
+  def prestage_slots(self, B):
+    """The buffers a pre-stage (fg_model.prestage(into=...)) writes for a batch of B: one dict per sub-batch with its packed
+    input 'img' and its slices of the shared 'x' / 'd_in' / 'y_in'.  forward(x, prepacked=True) then decodes
+    from them."""
     if not torch.cuda.is_available():
       raise rn.RecAttendError('the decode loop needs an MI355X (HIP device); no CPU fallback')
+    device = torch.device('cuda')
+    if self._stamp is None:
+      self.prepare(device)
+    self.alloc(B, device)
+    return self.subs
+
+  def forward(self, x, d_in=None, y_in=None, y_gt=None, noise=None, want_box=False, prepacked=False):
+    """prepacked: the packed input image and the d_in / y_in buffers of prestage_slots(B) already hold this
+    batch (written on the current stream); d_in / y_in are not read and the pack launch is left out."""
+    if not torch.cuda.is_available():
+      raise rn.RecAttendError('the decode loop needs an MI355X (HIP device); no CPU fallback')
+    self._prepacked = bool(prepacked)
     device = torch.device('cuda')
     as_t = lambda a: (a if isinstance(a, torch.Tensor) else torch.from_numpy(
         np.ascontiguousarray(a, dtype=np.float32))).to(device=device, dtype=torch.float32)
@@ -680,9 +700,9 @@ class DecodeEngine(object):
     self.alloc(B, device)
     b = self.glob
     b['x'].copy_(x)
-    if 'd_in' in b:
+    if 'd_in' in b and not prepacked:
       b['d_in'].copy_(as_t(d_in))
-    if 'y_in' in b:
+    if 'y_in' in b and not prepacked:
       b['y_in'].copy_(as_t(y_in))
     if self.box:
       b['y_gt'].copy_(as_t(y_gt))
@@ -706,7 +726,7 @@ class DecodeEngine(object):
     if not graphable:
       self._launch_all(want_box)
       return self
-    key = bool(want_box)
+    key = (bool(want_box), True) if self._prepacked else bool(want_box)  # without a pack launch: a graph of its own
     if self.box:  # the GT boxes are a fresh tensor per forward: the graph reads a fixed buffer
       for sb in self.subs:
         if 'box_gt_buf' not in sb:

@@ -66,6 +66,12 @@ SIGNATURES = {
     'ra_conv_packed_floats_k': (_Z, [_I, _I, _I]),
     'ra_conv_pack_weights_k': (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),
     'ra_convkxk_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    # the wide 3x3 layer and the head of fg_model (fg_model.py:112-194)
+    'ra_conv_wide_supported': (_I, [_I, _I]),
+    'ra_conv_wide_packed_floats': (_Z, [_I, _I]),
+    'ra_conv_wide_pack_weights': (_I, [_P, _I, _I, _I, _P, _I, _P]),
+    'ra_conv3x3_wide_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
+    'ra_fg_head_f32': (_I, [_P, _Z, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
     'ra_conv3x3_moments_part_floats': (_Z, [_I]),
     'ra_conv3x3_moments_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _Z, _P, _P]),
     'ra_bn_moments_from_partials_f32': (_I, [_P, _I, _I, _P, _P, _P]),

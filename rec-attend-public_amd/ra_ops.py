@@ -53,6 +53,10 @@ def pack_conv_weights(w, cin_kernel=None, chan_map=None, transposed=False):
   cin = cin_w if cin_kernel is None else int(cin_kernel)
   if chan_map is None and cin != cin_w:
     chan_map = list(range(cin_w)) + [-1] * (cin - cin_w)
+  if cout > 128 and f == 3 and conv_wide_supported(cin, cout):  # the wide layer's own order (conv_wide / conv2d_fused run it)
+    return pack_wide_weights(w, cin_kernel=cin, chan_map=chan_map, transposed=transposed)
+  if cout > 128 and f != 3 and conv_wide_supported(cin, cout):
+    raise rn.RecAttendError('wide layers (Cout = %d > 128) are built for 3x3 filters only, not %dx%d' % (cout, f, f))
   n = rn.lib().ra_conv_packed_floats(cin, cout) if f == 3 else rn.lib().ra_conv_packed_floats_k(f, cin, cout)
   if n == 0:
     raise rn.RecAttendError('unsupported conv shape Cin=%d Cout=%d' % (cin, cout))
@@ -72,6 +76,13 @@ def pack_conv_weights(w, cin_kernel=None, chan_map=None, transposed=False):
 def fold_bn(bias, cout, bn=None):
   """(scale, shift) [CoutP] numpy.  bn = (beta, gamma, ema_mean, ema_var) or None."""
   cp = cout_padded(cout)
+  if cp == 0 and 128 < cout <= 512:  # a wide layer (conv_wide): Cout floats each, the same float32 fold as ra_conv_fold_bn
+    b = np.zeros(cout, np.float32) if bias is None else _np32(bias)
+    if bn is None:
+      return np.ones(cout, np.float32), b.copy()
+    beta, gamma, mean, var = (_np32(a) for a in bn)
+    sc = (gamma / np.sqrt(var + np.float32(BN_EPS))).astype(np.float32)
+    return sc, ((b - mean) * sc + beta).astype(np.float32)
   scale = np.empty(cp, dtype=np.float32)
   shift = np.empty(cp, dtype=np.float32)
   b = None if bias is None else _np32(bias)
@@ -207,6 +218,10 @@ def conv2d_fused(src0, wp, scale, shift, cout, ksize, relu=True, pool=1, src1=No
                  plane_chan=-1):
   """conv3x3 for a ksize x ksize filter, ksize in FILTER_SIZES; wp = pack_conv_weights of that filter.  ksize = 3 IS
   conv3x3; other sizes run ra_convkxk_f32 (float32 operands only)."""
+  if cout > 128:  # K1 stops at 128 output channels: the wide layer (3x3 only, no canvas plane)
+    if ksize != 3 or plane is not None:
+      raise rn.RecAttendError('wide layers (Cout = %d > 128) are built for 3x3 filters without a canvas plane' % cout)
+    return conv_wide(src0, wp, scale, shift, cout, relu=relu, pool=pool, src1=src1, upsample=upsample, out=out)
   if ksize == 3:
     return conv3x3(src0, wp, scale, shift, cout, relu=relu, pool=pool, src1=src1, upsample=upsample, out=out, plane=plane,
                    plane_chan=plane_chan)
@@ -221,6 +236,85 @@ def conv2d_fused(src0, wp, scale, shift, cout, ksize, relu=True, pool=1, src1=No
                                 ptr(shift), int(cout), int(relu), int(pool), ptr(plane), int(plane_chan), ptr(out),
                                 rn.stream_ptr()), 'ra_convkxk_f32')
   return out
+
+
+def conv_wide_supported(cin, cout):
+  """The wide 3x3 layer takes Cout 129 .. 512 (a multiple of 16) and cin = C0 + C1 <= 1024 (a multiple of 4)."""
+  return bool(rn.lib().ra_conv_wide_supported(int(cin), int(cout)))
+
+
+def pack_wide_weights(w, cin_kernel=None, chan_map=None, transposed=False):
+  """pack_conv_weights for the wide layer: w [3,3,Ci,Co] (transposed: [3,3,Co,Ci]) -> ra_conv_wide_pack_weights' order
+  [co / 64][c / 16][tap][ksub][co % 64][cg], channel c = 16 chunk + 4 cg + ksub (numpy, host)."""
+  w = _np32(w)
+  if w.ndim != 4 or tuple(w.shape[:2]) != (3, 3):
+    raise rn.RecAttendError('filter of shape %r: wide layers are built for 3x3 filters only' % (w.shape,))
+  cin_w, cout = (w.shape[3], w.shape[2]) if transposed else (w.shape[2], w.shape[3])
+  cin = cin_w if cin_kernel is None else int(cin_kernel)
+  if chan_map is None and cin != cin_w:
+    chan_map = list(range(cin_w)) + [-1] * (cin - cin_w)
+  n = rn.lib().ra_conv_wide_packed_floats(cin, cout)
+  if n == 0:
+    raise rn.RecAttendError('unsupported wide conv shape Cin=%d Cout=%d (Cin %% 4, <= 1024; Cout 129 .. 512, %% 16)' % (cin, cout))
+  out = np.empty(n, dtype=np.float32)
+  cm = None
+  if chan_map is not None:
+    cm = np.ascontiguousarray(chan_map, dtype=np.int32)
+    assert cm.shape[0] == cin
+  check(rn.lib().ra_conv_wide_pack_weights(ptr(w), cin_w, cout, cin, ptr(cm), rn.RA_CONV_TRANSPOSED if transposed else 0,
+                                           ptr(out)), 'ra_conv_wide_pack_weights')
+  return out
+
+
+def conv_wide(src0, wp, scale, shift, cout, relu=True, pool=1, src1=None, upsample=False, out=None):
+  """conv3x3 for Cout 129 .. 512: src0 [B,Hs,Ws,C0] (+ src1 [B,Hs,Ws,C1]) -> [B,Ho,Wo,cout]; wp = pack_wide_weights,
+  scale / shift of cout floats (fold_bn)."""
+  _need_cuda(src0, src1, wp, scale, shift, out)
+  B, Hs, Ws, C0 = src0.shape
+  C1 = 0 if src1 is None else src1.shape[3]
+  if src1 is not None and tuple(src1.shape[:3]) != (B, Hs, Ws):
+    raise rn.RecAttendError('conv_wide: sources of %r and %r' % (tuple(src0.shape), tuple(src1.shape)))
+  n = rn.lib().ra_conv_wide_packed_floats(C0 + C1, int(cout))
+  if n == 0 or wp.numel() != n or scale.numel() < cout or shift.numel() < cout:
+    raise rn.RecAttendError('conv_wide: unsupported shape Cin=%d Cout=%d, or weights not packed for it' % (C0 + C1, cout))
+  up = 2 if upsample else 1
+  Ho, Wo = Hs * up // pool, Ws * up // pool
+  if out is None:
+    out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=src0.device)
+  elif tuple(out.shape) != (B, Ho, Wo, cout):
+    raise rn.RecAttendError('conv_wide: out of shape %r, expected %r' % (tuple(out.shape), (B, Ho, Wo, cout)))
+  check(rn.lib().ra_conv3x3_wide_f32(ptr(src0), C0, ptr(src1), C1, B, Hs, Ws, int(upsample), ptr(wp), ptr(scale), ptr(shift),
+                                     int(cout), int(relu), int(pool), ptr(out), rn.stream_ptr()), 'ra_conv3x3_wide_f32')
+  return out
+
+
+def fg_head(logits, nsc, no, quantise=False, y_out=None, d_out=None, x=None, packed=None, canvas_plane=None):
+  """The head of fg_model: logits [B,H,W,nsc+no] -> (y_out [B,H,W,nsc], d_out [B,H,W,no] or None); quantise: the 8-bit
+  round trip floor(v * 255) / 255.  packed [B,H,W,Cp] (with x [B,H,W,D]): the decode engine's packed input image is
+  written in the same pass, canvas_plane [B,H,W] zeroed."""
+  _need_cuda(logits, y_out, d_out, x, packed, canvas_plane)
+  B, H, W, C = logits.shape
+  if C != nsc + no:
+    raise rn.RecAttendError('fg_head: %d channels for nsc %d + no %d' % (C, nsc, no))
+  npix = B * H * W
+  f = lambda c: torch.empty((B, H, W, c), dtype=torch.float32, device=logits.device)
+  if y_out is None:
+    y_out = f(nsc)
+  if d_out is None and no:
+    d_out = f(no)
+  if y_out.numel() != npix * nsc or (no and d_out.numel() != npix * no):
+    raise rn.RecAttendError('fg_head: destination sizes')
+  D = Cp = 0
+  if packed is not None:
+    if x is None or x.numel() % npix or packed.numel() % npix:
+      raise rn.RecAttendError('fg_head: the packed destination needs x [B,H,W,D]')
+    D, Cp = x.numel() // npix, packed.numel() // npix
+    if canvas_plane is not None and canvas_plane.numel() != npix:
+      raise rn.RecAttendError('fg_head: canvas plane size')
+  check(rn.lib().ra_fg_head_f32(ptr(logits), npix, int(nsc), int(no), int(bool(quantise)), ptr(y_out), ptr(d_out if no else None),
+                                ptr(x if packed is not None else None), D, ptr(packed), Cp,
+                                ptr(canvas_plane if packed is not None else None), rn.stream_ptr()), 'ra_fg_head_f32')
+  return y_out, (d_out if no else None)
 
 
 def conv_wino_supported(cin, cout, pool, H, W):
