@@ -689,6 +689,36 @@ int ra_weighted_sum_f32(const float *w, const float *y, int B, int T, int HW, fl
                         void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The Cityscapes output stage behind the decode loop (csrc/ra_instance_class.hip): the foreground mask of the
+ * pre-stage's semantic map and a semantic class for every decoded instance.  sem is the semantic map at network size,
+ * [B,Hs,Ws,C] channel-last (channel 0 = background); H x W is the labels' size.  "Resized" below is
+ * cv2.resize(plane, (W, H)) with its default INTER_LINEAR in float32 (the arithmetic of ra_resize_linear_f32 with the
+ * source coordinate (d + 0.5) * (src / dst) - 0.5 evaluated in double as cv2 does); no full-size map is ever written.
+ *
+ * ra_sem_foreground_f32 — cityscapes_eval.py:166-176: fg[b,r,c] = C == 1 ? resized(sem) > thresh
+ *   : resized(sem[..., 0]) <= 1 - thresh  (FG_THRESHOLD = 0.3 there); fg [B,H,W] of 0 / 1.  1 <= C <= 16.
+ * ra_instance_class_vote_f32 — analysis.py:235-237: vote[b,t,c] = mean over the H * W pixels of
+ *   y[b,t,r,c'] * resized(sem[b,...,c])[r,c'] for any float y [B,T,H,W] (soft values, several instances on a pixel).  y is
+ *   read once, with 16-byte loads when H * W % 4 == 0 and y is 16-byte aligned (element loads otherwise).  Every workgroup
+ *   leaves its partial sums in ws (ra_instance_class_vote_workspace_floats(B, T, H, W, C) floats) and a second launch adds
+ *   them in a fixed order: no float atomics, the same bits on every run.  With conf [B,T] != NULL that launch also does
+ *   ra_instance_class_pick_f32's work (class_idx / label_id nullable).  1 <= T <= 32, 2 <= C <= 16, else RA_E_SHAPE and
+ *   nothing is launched.
+ * ra_instance_class_pick_f32 — analysis.py:232,251-261: an instance is written when conf > 0.5 and vote[0] <= 0.7, with
+ *   class_idx = argmax(vote[1:]) (first maximum) and label_id = (24, 25, 26, 27, 28, 31, 32, 33)[class_idx] (person,
+ *   rider, car, truck, bus, train, motorcycle, bicycle, analysis.py:203-210; -1 beyond the table); otherwise both are -1.
+ *   vote[0] is a mean over the whole image, so the gate almost never closes: the reference's rule, kept.
+ * ---------------------------------------------------------------------------------- */
+int ra_sem_foreground_f32(const float *sem, int B, int Hs, int Ws, int C, int H, int W, float thresh, float *fg,
+                          void *stream);
+size_t ra_instance_class_vote_workspace_floats(int B, int T, int H, int W, int C);
+int ra_instance_class_vote_f32(const float *y, const float *sem, int B, int T, int H, int W, int Hs, int Ws, int C,
+                               const float *conf, float *ws, size_t ws_floats, float *vote, int *class_idx,
+                               int *label_id, void *stream);
+int ra_instance_class_pick_f32(const float *vote, const float *conf, int B, int T, int C, int *class_idx, int *label_id,
+                               void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Training step (full_model.py:1039-1057).
  * ra_adam_step_f32 — gradient clip + Adam on one flat float32 bucket of n parameters:
  *   g = clip(grads * grad_scale + wd_coef * params, -clip, clip)   (wd_coef nullable; the

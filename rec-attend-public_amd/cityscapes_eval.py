@@ -1,0 +1,199 @@
+#!/usr/bin/env python
+"""Entry point with the flag surface of the reference's cityscapes_eval.py (:260-272 + EvalArgsParser): the stage BEHIND the
+decode loop, which turns decoded instance masks and the pre-stage's semantic map into the Cityscapes instance-level output —
+one mask, one class id and one score per instance.
+
+Like the reference it does not run the model.  --input is an .npz with
+  y_out_ins [N,T,h,w]   the decoded masks at network size (full_model_eval.py's pred_rank<r>.npz: y_out),
+  s_out     [N,T]       their scores ([N,T,K]: channel 0, as full_model_eval.py reads multi-class scores),
+  y_out     [N,h,w,C]   the pre-stage's semantic map (fg_model_pack.py's y_out / full_model's y_in; channel 0 = background),
+and optionally y_gt_full [N,T,H,W] + s_gt [N,T] (ground truth at the labels' size: the --analyzers then run per threshold),
+names (N file names, default 'image_<i>') and full_size (H, W; default: y_gt_full's size, else 1024 x 2048 for
+--dataset cityscapes and the network size otherwise).
+
+Per image (write_log, :148-205), all on the device, batch by batch:
+  1. + 2. the foreground mask of the semantic map at full size, FG_THRESHOLD = 0.3 (ops.sem_foreground);
+  3. pp.upsample -> pp.apply_confidence -> pp.apply_one_label, then for every threshold of --threshold_list (default
+     0.0 ... 0.9) pp.apply_threshold -> pp.mask_foreground -> pp.remove_tiny(--remove_tiny, default 400).  Two things differ
+     from full_model_eval.py's chain and are followed as they stand in the reference: upsample comes BEFORE
+     apply_confidence, and `conf` is re-assigned inside the threshold loop (:188-189), so an instance that remove_tiny zeroes
+     at one threshold keeps conf = 0 at every later threshold;
+  4. the class vote and the pick (analysis.f_instance_class);
+  5. <output>/output_<split>/cityscapes/<run>/<name>.txt + one 8-bit PNG per written instance
+     (analysis.RenderCityScapesOutputAnalyzer); every threshold writes into the same folder, as in the reference, so the last
+     threshold of the list is what remains on disk.
+The per-threshold means of the analyzers go to <output>/output_<split>/metrics.yaml.  Two names of the reference's default
+--analyzers list (and of its --test list), fg_iou_all and bg_iou_all, accumulate over the whole dataset (analysis.py:834-900)
+and are not built: the default lists run without them and say so on standard output; naming one explicitly is an error.
+
+--lrr_seg, --foreground_folder and --render_gt are accepted and refused: they read files of the authors' machines (LRR .mat
+files, a foreground folder, the HDF5 dataset); --lrr_filename is accepted and unused (its default there is a path of that
+cluster).  --split_id / --num_split select images [split_id * num_split, (split_id + 1) * num_split) (:41-46).  There is no
+CPU path: without a GPU the stage raises RecAttendError."""
+import argparse
+import os
+
+import numpy as np
+import yaml
+
+import cmd_args_parser as cap
+from ra_native import RecAttendError
+
+FG_THRESHOLD = 0.3  # :171
+DEFAULT_ANALYZERS = ['sbd', 'wt_cov', 'unwt_cov', 'fg_dice', 'fg_iou', 'fg_iou_all', 'bg_iou_all', 'avg_fp', 'avg_fn', 'avg_pr',
+                     'avg_re', 'obj_pr', 'obj_re', 'count_acc', 'count_mse', 'dic', 'dic_abs']  # :294-298
+TEST_ANALYZERS = ['fg_iou', 'fg_iou_all', 'bg_iou_all']  # :292
+# whole-dataset foreground / background IoU (analysis.py:834-900): accumulating analyzers, not per-image functions; not built
+NOT_BUILT = ('fg_iou_all', 'bg_iou_all')
+MAX_BATCH_ELEMS = 1 << 29  # floats of one [B,T,H,W] tensor of the chain (2 GiB); several are alive at a time
+
+REFUSED = {
+    'lrr_seg': '--lrr_seg reads the LRR segmentation .mat files of the authors\' cluster (cityscapes_eval.py:207-230); give the '
+               'semantic map as y_out in --input instead',
+    'foreground_folder': '--foreground_folder reads a folder of foreground images of the authors\' cluster; give the semantic '
+                         'map as y_out in --input instead',
+    'render_gt': '--render_gt renders the ground truth from the HDF5 dataset, which is out of scope here',
+}
+
+
+def build_parser():
+  p = argparse.ArgumentParser(description='Eval ris pp output')
+  for table in (cap.CITYSCAPES_EVAL_FLAGS, cap.DATA_FLAGS):
+    cap.add_flags(p, table)
+  p.add_argument('--input', default=None, help='.npz with y_out_ins [N,T,h,w], s_out [N,T], y_out [N,h,w,C] '
+                                               '(+ y_gt_full, s_gt, names, full_size)')
+  return p
+
+
+def make_opt(args):
+  """CityscapesEvalArgsParser.make_opt (:274-306)."""
+  for flag, why in REFUSED.items():
+    if getattr(args, flag):
+      raise RecAttendError(why)
+  opt = {k: getattr(args, k) for k in ('split_id', 'num_split', 'remove_tiny', 'no_iou', 'output', 'results', 'model_id',
+                                        'batch_size', 'dataset')}
+  opt['split'] = args.split.split(',')
+  opt['threshold_list'] = ([i * 0.1 for i in range(10)] if args.threshold_list is None
+                           else [float(t) for t in args.threshold_list.split(',')])
+  if args.analyzers is None:
+    opt['analyzers'] = [n for n in (TEST_ANALYZERS if args.test else DEFAULT_ANALYZERS) if n not in NOT_BUILT]
+    print('analyzers: the default list without %s (whole-dataset accumulators, not built)' % ', '.join(NOT_BUILT))
+  else:
+    opt['analyzers'] = [n for n in args.analyzers.split(',') if n]
+    for n in opt['analyzers']:
+      if n in NOT_BUILT:
+        raise RecAttendError('analyzer %s accumulates over the whole dataset (analysis.py:834-900) and is not built' % n)
+  return opt
+
+
+def _need_device():
+  import torch
+  if not torch.cuda.is_available():
+    raise RecAttendError('the Cityscapes output stage runs on the GPU; no device is available and there is no CPU fallback')
+  return torch
+
+
+def iter_label_instances(y_ins, s_out, sem, size, thresholds, remove_tiny=400):
+  """Steps 1-4 of the module docstring on device tensors: y_ins [B,T,h,w], s_out [B,T] (or [B,T,K]: channel 0), sem
+  [B,h',w',C], size = (H, W).  Yields one dict per threshold, in order: 'threshold', 'y_out' [B,T,H,W] binary, 's_out'
+  (s_out > 0.5), 'conf' [B,T] (s_out with the instances remove_tiny dropped at this or an EARLIER threshold zeroed),
+  'y_in' (sem), 'fg' [B,H,W], 'class_idx', 'label_id' int32 [B,T] (-1 = not written), 'vote' [B,T,C]."""
+  torch = _need_device()
+  import ra_ops as ops
+  from utils import postprocess as pp
+  for t in (y_ins, s_out, sem):
+    if not t.is_cuda:
+      raise RecAttendError('the Cityscapes output stage needs device tensors; there is no CPU fallback')
+  H, W = int(size[0]), int(size[1])
+  if s_out.dim() == 3:
+    s_out = s_out[:, :, 0]
+  s_out = s_out.contiguous().to(torch.float32)
+  sem = sem.contiguous()
+  fg = ops.sem_foreground(sem, H, W, FG_THRESHOLD)            # :166-176
+  y = pp.upsample(y_ins.contiguous(), (H, W))                 # :179
+  y, conf_hard = pp.apply_confidence(y, s_out)                # :180
+  one = pp.apply_one_label(y)                                 # :181
+  del y
+  conf = s_out.clone()
+  for th in thresholds:
+    y_bin = pp.mask_foreground(pp.apply_threshold(one, float(th)), fg)                # :184-185
+    y_bin, conf = pp.remove_tiny(y_bin, conf, threshold=remove_tiny)                  # :188-189: conf carries over
+    vote, idx, lab = ops.instance_class_vote(y_bin, sem, conf)                        # analysis.py:232-261
+    yield {'threshold': float(th), 'y_out': y_bin, 's_out': conf_hard, 'conf': conf, 'y_in': sem, 'fg': fg,
+           'class_idx': idx, 'label_id': lab, 'vote': vote, '_instance_class': (idx, lab, vote)}
+
+
+def label_instances(y_ins, s_out, sem, size, thresholds, remove_tiny=400):
+  """list(iter_label_instances(...)): every threshold's tensors at once ([B,T,H,W] floats each — mind the size)."""
+  return list(iter_label_instances(y_ins, s_out, sem, size, thresholds, remove_tiny))
+
+
+def _full_size(data, dataset):
+  if 'full_size' in data:
+    return int(data['full_size'][0]), int(data['full_size'][1])
+  if 'y_gt_full' in data:
+    return tuple(int(v) for v in data['y_gt_full'].shape[-2:])
+  if dataset == 'cityscapes':
+    return 1024, 2048
+  return tuple(int(v) for v in data['y_out_ins'].shape[-2:])
+
+
+def main(argv=None):
+  args = build_parser().parse_args(argv)
+  opt = make_opt(args)
+  if args.input is None:
+    raise RecAttendError('--input is required: an .npz with y_out_ins, s_out and y_out (the stage does not run the model)')
+  if opt['output'] is None:
+    if args.model_id is None:
+      raise Exception('You must provide model ID')  # cmd_args_parser.py:154-155 (needed for the default output folder)
+    opt['output'] = os.path.join(args.results, args.model_id)  # CityscapesEvalExperiment.get_runner :236-239
+  torch = _need_device()
+  import analysis
+  data = dict(np.load(args.input, allow_pickle=False))
+  for k in ('y_out_ins', 's_out', 'y_out'):
+    if k not in data:
+      raise RecAttendError('--input lacks %s' % k)
+  N, T = data['y_out_ins'].shape[:2]
+  H, W = _full_size(data, args.dataset)
+  names = [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(N)]
+  lo, hi = (0, N) if opt['split_id'] == -1 else (min(N, opt['split_id'] * opt['num_split']),
+                                                min(N, (opt['split_id'] + 1) * opt['num_split']))  # :41-46
+  have_gt = 'y_gt_full' in data and 's_gt' in data
+  an_names = opt['analyzers'] if have_gt else []
+  out_dir = os.path.join(opt['output'], 'output_' + opt['split'][0])
+  os.makedirs(out_dir, exist_ok=True)
+  thresholds = opt['threshold_list']
+  renders = [analysis.RenderCityScapesOutputAnalyzer(os.path.join(out_dir, 'cityscapes'), names) for _ in thresholds]
+  acc = [{n: [] for n in an_names} for _ in thresholds]
+  bs = max(1, min(opt['batch_size'], MAX_BATCH_ELEMS // max(1, T * H * W)))
+  dev = torch.device('cuda', torch.cuda.current_device())
+  up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+  for b0 in range(lo, hi, bs):
+    b1 = min(hi, b0 + bs)
+    gt = up(data['y_gt_full'][b0:b1]) if have_gt else None
+    sg = up(data['s_gt'][b0:b1]) if have_gt else None
+    chain = iter_label_instances(up(data['y_out_ins'][b0:b1]), up(data['s_out'][b0:b1]), up(data['y_out'][b0:b1]), (H, W),
+                                 thresholds, opt['remove_tiny'])
+    for tt, res in enumerate(chain):
+      res['indices'] = list(range(b0, b1))
+      if have_gt:
+        res['y_gt'], res['s_gt'] = gt, sg
+        if not opt['no_iou']:
+          res['iou_pairwise'] = analysis.f_iou_pairwise(res['y_out'], gt)  # :199-202
+        for n in an_names:
+          acc[tt][n].append(analysis.create_analyzer(n)(res).cpu().numpy())
+      renders[tt].stage(res)
+  for r in renders:
+    r.finalize()
+  summary = {}
+  for tt, th in enumerate(thresholds):
+    vals = {n: np.concatenate(v) if v else np.zeros(0) for n, v in acc[tt].items()}
+    summary['%.2f' % th] = {n: {'mean': float(v.mean()) if v.size else 0.0, 'count': int(v.size)} for n, v in vals.items()}
+  with open(os.path.join(out_dir, 'metrics.yaml'), 'w') as f:
+    yaml.safe_dump(summary, f)
+  print('images [%d, %d) -> %s' % (lo, hi, os.path.join(out_dir, 'cityscapes')))
+  return renders
+
+
+if __name__ == '__main__':
+  main()

@@ -69,6 +69,13 @@ EVAL_FLAGS = [  # EvalArgsParser + MyEvalArgsParser, cmd_args_parser.py:143-151,
     ('test', _B, False), ('no_morph', _B, False), ('remove_tiny', _I, 0),
 ]
 DATA_FLAGS = [('dataset', _S, 'cvppp'), ('dataset_folder', _S, None)]  # DataArgsParser :168-171
+CITYSCAPES_EVAL_FLAGS = [  # EvalArgsParser + CityscapesEvalArgsParser, cmd_args_parser.py:143-151, cityscapes_eval.py:260-272
+    ('model_id', _S, None), ('batch_size', _I, 32), ('results', _S, './results'), ('output', _S, None),
+    ('split', _S, 'valid'), ('prefetch', _B, False), ('queue_size', _I, 50), ('num_worker', _I, 4),
+    ('threshold_list', _S, None), ('analyzers', _S, None), ('test', _B, False), ('split_id', _I, -1),
+    ('num_split', _I, 100), ('remove_tiny', _I, 400), ('foreground_folder', _S, None), ('no_iou', _B, False),
+    ('render_gt', _B, False), ('lrr_seg', _B, False), ('lrr_filename', _S, None),
+]
 
 
 def add_flags(parser, table):

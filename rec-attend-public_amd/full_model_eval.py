@@ -17,7 +17,13 @@ the per-threshold means go to <output>/output_<split>/metrics_rank<r>.yaml.  The
 to the labels' size, then bilateralFilter(5, 10, 10), which on [0, 1] maps is close to a radius-2 blur — ALWAYS runs, also when
 the labels already have the network's size (full_model_eval.py:114), and the dilation runs when a foreground mask is given and
 --no_morph is not.  --fused_postprocess (not a reference flag) skips the bilateral step when no resize is needed: the chain
-then collapses into one fused device pass; masks and metrics near the threshold differ from the reference's in that mode."""
+then collapses into one fused device pass; masks and metrics near the threshold differ from the reference's in that mode.
+--cityscapes_output DIR (not a reference flag; needs --fg_model_id with a 9-class pre-stage) puts the reference's THIRD stage
+behind the loop: every decoded batch and the pre-stage's y_in go through cityscapes_eval.label_instances on the device — its
+chain, not the one above: upsample before apply_confidence, the semantic map's own foreground mask, conf carried across the
+thresholds — at --threshold_list / --remove_tiny, and DIR/<run>/<name>.txt + one PNG per written instance come out
+(analysis.RenderCityScapesOutputAnalyzer; the labels' size is y_gt's or full_size's of --input, else the network's; file
+names from `names` of --input, else image_<index>).  pred_rank<r>.npz is the same with and without the flag."""
 import argparse
 import os
 import time
@@ -42,6 +48,9 @@ def build_parser():
   p.add_argument('--fg_model_id', default=None,
                  help='not a reference flag: run this fg_model (results/<id>/{model_opt.yaml, weights.npz}) in front of the decode '
                       'loop; d_in / y_in then come from its prestage() on the device, not from --input')
+  p.add_argument('--cityscapes_output', default=None,
+                 help='not a reference flag: write the Cityscapes instance-level output (a mask, a class id and a score per instance) '
+                      'of every decoded image into this folder; needs --fg_model_id with 9 semantic classes')
   p.add_argument('--in_flight', type=int, default=8, help='batches submitted to one GPU at a time (four decode concurrently, the rest queue behind them)')
   return p
 
@@ -51,6 +60,9 @@ def main(argv=None):
   args = build_parser().parse_args(argv)
   if args.model_id is None:
     raise Exception('You must provide model ID')  # cmd_args_parser.py:154-155
+  if args.cityscapes_output and not args.fg_model_id:
+    from ra_native import RecAttendError
+    raise RecAttendError('--cityscapes_output needs --fg_model_id: the instance classes are voted on the pre-stage\'s semantic map')
   restore = os.path.join(args.results, args.model_id)
   with open(os.path.join(restore, 'model_opt.yaml')) as f:
     model_opt = yaml.safe_load(f)
@@ -76,6 +88,10 @@ def main(argv=None):
     fg = fg_model_pack.restore_model(args.results, args.fg_model_id)
     for k in ('d_in', 'y_in'):
       data.pop(k, None)
+    if args.cityscapes_output and fg.dims['nsc'] != 9:
+      from ra_native import RecAttendError
+      raise RecAttendError('--cityscapes_output needs a pre-stage with 9 semantic classes (background + the 8 Cityscapes instance '
+                           'classes); fg_model %s has %d' % (args.fg_model_id, fg.dims['nsc']))
   lo, hi = ra_dist.shard_range(rank, world, data['x'].shape[0])
   # the reference CLI defaults to [0.3] (MyEvalArgsParser.make_opt, full_model_eval.py:193-198); the
   # 0.0 .. 0.9 sweep of :39-40 is only EvalRunner's fallback for a caller that hands it None
@@ -96,7 +112,23 @@ def main(argv=None):
 
 def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0, fg=None):
   import torch
+  cs_dir, sems, render = getattr(args, 'cityscapes_output', None), {}, None
+  if cs_dir:
+    import analysis
+    import cityscapes_eval
+    n_all = data['x'].shape[0]
+    render = analysis.RenderCityScapesOutputAnalyzer(
+        cs_dir, [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(n_all)])
+    if 'full_size' in data:
+      cs_size = (int(data['full_size'][0]), int(data['full_size'][1]))
+    else:
+      cs_size = tuple(int(v) for v in data['y_gt'].shape[-2:]) if 'y_gt' in data else (model.dims['H'], model.dims['W'])
+
   def consume(b0, b1, y_dev, s_dev):
+    if cs_dir:  # the stage behind the loop, on the device: one staging per threshold, as cityscapes_eval.py does
+      for res in cityscapes_eval.iter_label_instances(y_dev, s_dev, sems.pop(b0), cs_size, thresholds, args.remove_tiny):
+        res['indices'] = list(range(b0, b1))
+        render.stage(res)
     if analyze:
       import analysis
       from utils import postprocess as pp
@@ -148,10 +180,12 @@ def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, anal
     feed['phase_train'] = False
     if fg is not None:  # the pre-stage: the 8-bit values the pack step would store, as device tensors
       feed['y_in'], feed['d_in'] = fg.prestage(feed['x'], quantise=True)
+      if cs_dir:
+        sems[b0] = feed['y_in']
     left = -(-(hi - b1) // args.batch_size)  # batches still to come: the last few go out one per slot (DecodePipeline._ends_soon)
     while pipe.full(b1 - b0, remaining=left):
       consume(*(spans.pop(0) + tuple(pipe.collect())))
-    pipe.submit(['y_out', 's_out'], feed, to_host=not analyze, remaining=left)
+    pipe.submit(['y_out', 's_out'], feed, to_host=not (analyze or cs_dir), remaining=left)
     spans.append((b0, b1))
   while len(pipe):
     consume(*(spans.pop(0) + tuple(pipe.collect())))

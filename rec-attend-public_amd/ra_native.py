@@ -135,6 +135,10 @@ SIGNATURES = {
     'ra_eval_metrics_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     'ra_random_transform_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
     'ra_weighted_sum_f32': (_I, [_P, _P, _I, _I, _I, _P, _P]),
+    'ra_sem_foreground_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
+    'ra_instance_class_vote_workspace_floats': (_Z, [_I, _I, _I, _I, _I]),
+    'ra_instance_class_vote_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P, _P, _P, _P]),
+    'ra_instance_class_pick_f32': (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
     'ra_fill_f32': (_I, [_P, _Z, _F, _P]),
     'ra_tile_tickets_bind': (_I, [_P, _I]),
     'ra_tile_tickets_slot_bytes': (_I, []),

@@ -1024,3 +1024,53 @@ def weighted_sum(w, y, out):
   B, T, H, W = y.shape
   check(rn.lib().ra_weighted_sum_f32(ptr(w), ptr(y), B, T, H * W, ptr(out), rn.stream_ptr()),
         'ra_weighted_sum_f32')
+
+
+# ---------------------------------------------------------------------------- Cityscapes output stage
+
+
+def sem_foreground(sem, H, W, thresh=0.3):
+  """cityscapes_eval.py:166-176: the foreground mask [B,H,W] of a semantic map sem [B,Hs,Ws,C] (channel-last) at the labels'
+  size — one channel: resized > thresh; several: resized channel 0 (background) <= 1 - thresh (ra_sem_foreground_f32)."""
+  sem = sem.contiguous()
+  _need_cuda(sem)
+  B, Hs, Ws, Cc = sem.shape
+  fg = torch.empty((B, int(H), int(W)), dtype=torch.float32, device=sem.device)
+  check(rn.lib().ra_sem_foreground_f32(ptr(sem), B, Hs, Ws, Cc, int(H), int(W), C.c_float(thresh), ptr(fg), rn.stream_ptr()),
+        'ra_sem_foreground_f32')
+  return fg
+
+
+def instance_class_vote(y, sem, conf=None):
+  """analysis.py:235-261 for y [B,T,H,W] and the semantic map sem [B,Hs,Ws,C] at network size: vote [B,T,C] = the mean over
+  the image of y * resized(sem); with conf [B,T] also (class_idx, label_id) int32 [B,T] from the same finishing launch
+  (ra_instance_class_vote_f32).  Returns vote, or (vote, class_idx, label_id)."""
+  y, sem = y.contiguous(), sem.contiguous()
+  conf = None if conf is None else conf.contiguous()
+  _need_cuda(y, sem, conf)
+  B, T, H, W = y.shape
+  Bs, Hs, Ws, Cc = sem.shape
+  if Bs != B or (conf is not None and tuple(conf.shape) != (B, T)):
+    raise rn.RecAttendError('instance_class_vote: y %s, sem %s, conf %s do not belong together' % (
+        tuple(y.shape), tuple(sem.shape), None if conf is None else tuple(conf.shape)))
+  dev = y.device
+  n = rn.lib().ra_instance_class_vote_workspace_floats(B, T, H, W, Cc)
+  ws = torch.empty((max(n, 1),), dtype=torch.float32, device=dev)
+  vote = torch.empty((B, T, Cc), dtype=torch.float32, device=dev)
+  idx = torch.empty((B, T), dtype=torch.int32, device=dev) if conf is not None else None
+  lab = torch.empty((B, T), dtype=torch.int32, device=dev) if conf is not None else None
+  check(rn.lib().ra_instance_class_vote_f32(ptr(y), ptr(sem), B, T, H, W, Hs, Ws, Cc, ptr(conf), ptr(ws), n, ptr(vote), ptr(idx),
+                                            ptr(lab), rn.stream_ptr()), 'ra_instance_class_vote_f32')
+  return vote if conf is None else (vote, idx, lab)
+
+
+def instance_class_pick(vote, conf):
+  """analysis.py:232,251-261 on vote [B,T,C], conf [B,T]: (class_idx, label_id) int32 [B,T]; -1 = not written."""
+  vote, conf = vote.contiguous(), conf.contiguous()
+  _need_cuda(vote, conf)
+  B, T, Cc = vote.shape
+  idx = torch.empty((B, T), dtype=torch.int32, device=vote.device)
+  lab = torch.empty((B, T), dtype=torch.int32, device=vote.device)
+  check(rn.lib().ra_instance_class_pick_f32(ptr(vote), ptr(conf), B, T, Cc, ptr(idx), ptr(lab), rn.stream_ptr()),
+        'ra_instance_class_pick_f32')
+  return idx, lab
