@@ -817,11 +817,7 @@ extern "C" int ra_extract_conv0_f32(const float *img, int Ci, int chan0, const f
     return fail(RA_E_SHAPE, "ra_extract_conv0_f32: Ci=%d chan0=%d Fh=%d Fw=%d Cout=%d", Ci, chan0, Fh, Fw, Cout);
   if ((size_t)H * W * Ci * 4 >= 0x7fffffffu) return fail(RA_E_SHAPE, "ra_extract_conv0_f32: one image exceeds 2 GiB");
   const int n_items = Fh * B, chunk = ceil_div(n_items, 8);
-  static int kr = 0;  // RA_EXC0_KR=4: tuning aid (rows per wave and load round; 5 covers cfg2's 38-row union in two rounds)
-  if (!kr) {
-    const char *e = getenv("RA_EXC0_KR");
-    kr = (e && atoi(e) == 4) ? 4 : 5;
-  }
+  static const int kr = env_int("RA_EXC0_KR", 5) == 4 ? 4 : 5;  // =4: tuning aid (rows per wave and load round; 5 covers cfg2's 38-row union in two rounds)
   if (kr == 4)
     hipLaunchKernelGGL((attnd::extract_conv0_kernel<4>), dim3(8 * chunk), dim3(256), 0, as_stream(stream), img, Ci, chan0, canvas,
                        canvas_chan, attn_rec, H, W, Fh, Fw, use_gamma, patch, w0, scale, shift, Cout, relu, y0, n_items, chunk);

@@ -4,6 +4,7 @@
 
 #include <cstdarg>
 #include <cstdio>
+#include <cstdlib>
 
 #include "recattend.h"
 
@@ -34,6 +35,22 @@ inline int fail(int code, const char *fmt, ...) {
 }
 
 constexpr int kWave = 64;  // CDNA wavefront
+
+// A tuning variable, read NOW: atoi of its value, or dflt when it is unset.  A site that wants it read once keeps the result
+// in a static (`static const int x = env_int(..)`); the few that tests and probes flip between launches call this every time.
+inline int env_int(const char *name, int dflt) {
+  const char *e = getenv(name);
+  return e ? atoi(e) : dflt;
+}
+
+// Raises a kernel's dynamic-LDS limit above the default 64 KB.  Declared `static` where the kernel is launched, so the call is
+// made once per kernel, at its first launch: the engine warms every kernel up before it captures a graph.
+struct [[maybe_unused]] MaxDynamicLds {
+  template <typename K>
+  MaxDynamicLds(K kern, size_t bytes) {
+    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+  }
+};
 
 // Wave priority of the decode loop's LATENCY-bound kernels (controller, patch-sized convs, extract, paste, score).  In the
 // decode pipeline they share every SIMD with another batch's MFMA-bound controller-CNN waves, and the arbiter deals issue

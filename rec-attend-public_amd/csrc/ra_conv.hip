@@ -624,8 +624,7 @@ int launch_s(const Args &a, int B, hipStream_t st) {
   constexpr size_t lds = 2 * G::LDS_FLOATS * sizeof(float);
   static int wgs_per_cu = 0;  // idempotent lazy init
   if (!wgs_per_cu) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    MaxDynamicLds{kern, lds};
     int n = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256, lds) != hipSuccess || n < 1) n = 1;
     wgs_per_cu = n > 4 ? 4 : n;
@@ -648,12 +647,8 @@ inline int chunk_of_k(int KF, int Cin) { return KF <= 3 ? chunk_of(Cin) : (KF ==
 #if RA_K1_PART != 3
 namespace {  // the dispatch chain differs between the parts of this file (RA_K1_PART): internal linkage, one per part
 inline bool ups_subpixel() {  // RA_CONV_UPS_SUBPIXEL=0: the zero-stuffed form of rounds 1-5 (A/B aid)
-  static int on = -1;
-  if (on < 0) {
-    const char *e = getenv("RA_CONV_UPS_SUBPIXEL");
-    on = (e && atoi(e) == 0) ? 0 : 1;
-  }
-  return on == 1;
+  static const bool on = env_int("RA_CONV_UPS_SUBPIXEL", 1) != 0;
+  return on;
 }
 template <int CK, int NC, int WN, int GX, int GY>
 int launch(const Args &a, int B, hipStream_t st) {
@@ -690,20 +685,12 @@ int dispatch_geo(const Args &a, int B, hipStream_t st) {
   };
   const bool narrow = (a.W % 32 != 0) && (a.W % 32 <= 16);
   const long want = 512;
-  static int force = -1;  // RA_CONV_GEO=<gx><gy> (e.g. 41) forces a geometry: tuning aid only
-  if (force < 0) {
-    const char *e = getenv("RA_CONV_GEO");
-    force = e ? atoi(e) : 0;
-  }
+  static const int force = env_int("RA_CONV_GEO", 0);  // =<gx><gy> (e.g. 41) forces a geometry: tuning aid only
 #if RA_K1_PART == 0
   // a stride-2 transposed conv without pooling runs its sub-pixel form (UPS), which lives on the (2, 2) geometry
   // ... where that geometry still yields enough workgroups: with few (a lone batch of 8 CVPPP patches: 16-72) the zero-stuffed
   // form on one-group tiles has 4 x the workgroups at the same chain length per wave and wins (RA_CONV_UPS_MIN_WGS, profiles/r06_k1s_sweep.txt)
-  static int ups_min = -1;
-  if (ups_min < 0) {
-    const char *e = getenv("RA_CONV_UPS_MIN_WGS");
-    ups_min = e ? atoi(e) : 96;
-  }
+  static const int ups_min = env_int("RA_CONV_UPS_MIN_WGS", 96);
   if (!force && a.ups && a.pool == 1 && (a.Cout & 3) == 0 && !a.mom_part && ups_subpixel() && wgs(2, 2) >= ups_min)
     return launch<CK, NC, WN, 2, 2>(a, B, st);
 #endif
@@ -721,11 +708,7 @@ int dispatch_geo(const Args &a, int B, hipStream_t st) {
   // without a workgroup — the patch-sized layers with many channels (KITTI's attention DCNN: 128 -> 64 at 12 x 12 is 288
   // dependent k-steps per pixel group; two groups per wave and 96 workgroups made it 16.5 us whatever the batch).  RA_CONV_TINY_WGS:
   // the workgroup count of the (2, 1) geometry below which the (1, 1) form is taken (0 = never).
-  static int tiny = -1;
-  if (tiny < 0) {
-    const char *e = getenv("RA_CONV_TINY_WGS");
-    tiny = e ? atoi(e) : 200;
-  }
+  static const int tiny = env_int("RA_CONV_TINY_WGS", 200);
   if (force == 11 || (!force && wgs(2, 1) < tiny)) return launch<CK, NC, WN, 1, 1>(a, B, st);
 #endif
   return launch<CK, NC, WN, 2, 1>(a, B, st);

@@ -1110,26 +1110,14 @@ int launch8(const PArgs &a_in, int B, hipStream_t st) {
   a.bytes_y = (int)((size_t)B * a.Ho * a.Wo * a.CoutB * sizeof(float));
   auto kern = conv_pair8_mfma<CINA, CACHED, SPLIT>;
   constexpr size_t lds = (size_t)(((G::LH * G::LW * (CACHED ? 1 : CINA) + 3) & ~3) + (SPLIT ? 3 * G::AHS * G::AW * 4 : G::MID_FLOATS)) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
+  static const MaxDynamicLds lds_limit(kern, lds);
   const int tiles_x = ceil_div(a.W, G::TW), tiles_y = ceil_div(a.H, G::TH);
   const int ntiles = tiles_x * tiles_y * B;
-  static int wgs = -1;  // RA_PAIR8_WGS: tuning aid, persistent workgroups (default 3 per CU)
-  if (wgs < 0) {
-    const char *e = getenv("RA_PAIR8_WGS");
-    // the cached form (122 VGPRs) could run 4 workgroups per CU and is 0.3 us faster alone that way, but 3 leave
-    // room for the kernels of the other decode graphs: 50.4k vs 49.7k instance-timesteps/s with four batches in flight
-    wgs = e ? atoi(e) : 768;
-  }
-  static int xcd = -1;  // RA_PAIR8_XCD=0: tuning aid, the interleaved tile walk (51.7k vs 52.1k instance-timesteps/s pipelined)
-  if (xcd < 0) {
-    const char *e = getenv("RA_PAIR8_XCD");
-    xcd = e ? atoi(e) : 1;
-  }
+  // RA_PAIR8_WGS: tuning aid, persistent workgroups (default 3 per CU).  The cached form (122 VGPRs) could run 4 workgroups
+  // per CU and is 0.3 us faster alone that way, but 3 leave room for the kernels of the other decode graphs: 50.4k vs 49.7k
+  // instance-timesteps/s with four batches in flight
+  static const int wgs = env_int("RA_PAIR8_WGS", 768);
+  static const int xcd = env_int("RA_PAIR8_XCD", 1);  // =0: tuning aid, the interleaved tile walk (51.7k vs 52.1k instance-timesteps/s pipelined)
   PArgs a2 = a;
   const int grid = ntiles < wgs ? ntiles : wgs;
   a2.xcd_map = (xcd && grid % 8 == 0 && grid >= 8) ? 1 : 0;
@@ -1202,12 +1190,7 @@ int launch(const PArgs &a, int B, hipStream_t st) {
   auto kern = conv_pair_mfma<CINA, CMID, NCB, GX, GYB>;
   constexpr size_t lds = (size_t)(G::IN_FLOATS + G::MID_FLOATS) * sizeof(float);
   static_assert(lds <= 160 * 1024, "pair tile does not fit LDS");
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr = true;
-  }
+  static const MaxDynamicLds lds_limit(kern, lds);
   const int tiles_x = ceil_div(a.W, G::TWB), tiles_y = ceil_div(a.H, G::THB);
   const int ntiles = tiles_x * tiles_y * B;
   if constexpr (G::NCHA == 1 && G::NCHB == 1) {
@@ -1215,10 +1198,9 @@ int launch(const PArgs &a, int B, hipStream_t st) {
     // loaded once, the next tile's input prefetched into registers behind the MFMA phases
     static int pers = -1, cap = 0;
     if (pers < 0) {
-      const char *e = getenv("RA_PAIR_PERSIST");
-      pers = e ? atoi(e) : 1;
+      pers = env_int("RA_PAIR_PERSIST", 1);
       auto kp = conv_pair_persist_mfma<CINA, CMID, NCB, GX, GYB>;
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+      MaxDynamicLds{kp, lds};
       int nb = 0;
       if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kp, 256, lds) != hipSuccess || nb < 1) nb = 1;
       hipDeviceProp_t prop;
@@ -1242,11 +1224,7 @@ int dispatch_geo(const PArgs &a, int B, hipStream_t st) {
   constexpr bool big_fits = (size_t)(Big::IN_FLOATS + Big::MID_FLOATS) * 4 <= 80 * 1024;
   const bool narrow = (a.W % 32 != 0) && (a.W % 32 <= 16);
   auto wgs = [&](int gx, int gyb) { return (long)ceil_div(a.W, 8 * gx) * ceil_div(a.H, 8 * gyb) * B; };
-  static int force = -1;  // RA_PAIR_GEO=<gx><gyb>: tuning aid
-  if (force < 0) {
-    const char *e = getenv("RA_PAIR_GEO");
-    force = e ? atoi(e) : 0;
-  }
+  static const int force = env_int("RA_PAIR_GEO", 0);  // =<gx><gyb>: tuning aid
   // single-chunk plain pairs run the persistent kernel, which measures fastest with the 8-row tile
   // (cfg2 L2+L3: 41.8 us at 32x8 against 47.4 at 32x16 and 45.3 one-shot; profiles/r02)
   constexpr bool single_chunk = Big::NCHA == 1 && Big::NCHB == 1;
@@ -1288,17 +1266,12 @@ extern "C" int ra_conv_pair_supported(int Cin, int CoutA, int CoutB) {
   return cin_ok && mid_ok && CoutB >= 1 && CoutB <= 32;
 }
 
-extern "C" int ra_conv_pair_f32(const float *src, int Cin, int B, int Hs, int Ws, int upsampleA,
-                                const float *wpA, const float *scaleA, const float *shiftA, int CoutA,
-                                int reluA, const float *wpB, const float *scaleB, const float *shiftB,
-                                int CoutB, int reluB, int poolB, const float *plane, int plane_chan,
-                                float *y, void *stream) {
-  if (!src || !wpA || !scaleA || !shiftA || !wpB || !scaleB || !shiftB || !y || B <= 0 || Hs <= 0 ||
-      Ws <= 0)
-    return fail(RA_E_INVALID, "ra_conv_pair_f32: bad argument");
-  if (!ra_conv_pair_supported(Cin, CoutA, CoutB))
-    return fail(RA_E_SHAPE, "ra_conv_pair_f32: Cin=%d CoutA=%d CoutB=%d", Cin, CoutA, CoutB);
-  if (poolB != 1 && poolB != 2) return fail(RA_E_SHAPE, "ra_conv_pair_f32: pool %d", poolB);
+namespace {
+// The launch arguments every pair entry point fills alike: layer A over src [B,Hs,Ws,Cin] (the stride-2 transposed conv with
+// upsampleA), layer B with pool poolB.  bytes0, the cache and the rider stay zero: each entry point sets what its form reads.
+cpair::PArgs pair_args(const float *src, int Cin, int B, int Hs, int Ws, int upsampleA, const float *wpA, const float *scaleA,
+                       const float *shiftA, int CoutA, int reluA, const float *wpB, const float *scaleB, const float *shiftB,
+                       int CoutB, int reluB, int poolB, const float *plane, int plane_chan, float *y) {
   cpair::PArgs a{};
   a.src = src;
   a.y = y;
@@ -1314,7 +1287,6 @@ extern "C" int ra_conv_pair_f32(const float *src, int Cin, int B, int Hs, int Ws
   a.ups = upsampleA ? 1 : 0;
   a.H = Hs * (1 + a.ups);
   a.W = Ws * (1 + a.ups);
-  if (poolB == 2 && ((a.H | a.W) & 1)) return fail(RA_E_SHAPE, "ra_conv_pair_f32: odd size with pool 2");
   a.CoutAP = ra_conv_cout_padded(CoutA);
   a.CoutB = CoutB;
   a.CoutBP = ra_conv_cout_padded(CoutB);
@@ -1325,13 +1297,39 @@ extern "C" int ra_conv_pair_f32(const float *src, int Cin, int B, int Hs, int Ws
   a.reluB = reluB;
   a.plane = plane;
   a.plane_chan = plane_chan;
+  a.bytes_p = (int)((size_t)B * Hs * Ws * 4);
+  return a;
+}
+
+// ... and layer A's cached partial sums, for the two forms of the first pair that write / read them.  0, or `what`'s error.
+int pair_args_cache(cpair::PArgs &a, const float *cache, int B, const char *what) {
+  a.cache = cache;
+  cpair::cache_dims(a.H, a.W, a.cache_rows, a.cache_gx);
+  const size_t cb = (size_t)B * a.cache_rows * a.cache_gx * 64 * sizeof(float);
+  if (cb >= (1ull << 31)) return fail(RA_E_SHAPE, "%s: cache exceeds 2 GiB", what);
+  a.bytes_c = (int)cb;
+  return 0;
+}
+}  // namespace
+
+extern "C" int ra_conv_pair_f32(const float *src, int Cin, int B, int Hs, int Ws, int upsampleA,
+                                const float *wpA, const float *scaleA, const float *shiftA, int CoutA,
+                                int reluA, const float *wpB, const float *scaleB, const float *shiftB,
+                                int CoutB, int reluB, int poolB, const float *plane, int plane_chan,
+                                float *y, void *stream) {
+  if (!src || !wpA || !scaleA || !shiftA || !wpB || !scaleB || !shiftB || !y || B <= 0 || Hs <= 0 ||
+      Ws <= 0)
+    return fail(RA_E_INVALID, "ra_conv_pair_f32: bad argument");
+  if (!ra_conv_pair_supported(Cin, CoutA, CoutB))
+    return fail(RA_E_SHAPE, "ra_conv_pair_f32: Cin=%d CoutA=%d CoutB=%d", Cin, CoutA, CoutB);
+  if (poolB != 1 && poolB != 2) return fail(RA_E_SHAPE, "ra_conv_pair_f32: pool %d", poolB);
+  cpair::PArgs a = pair_args(src, Cin, B, Hs, Ws, upsampleA, wpA, scaleA, shiftA, CoutA, reluA, wpB, scaleB, shiftB, CoutB, reluB,
+                             poolB, plane, plane_chan, y);
+  if (poolB == 2 && ((a.H | a.W) & 1)) return fail(RA_E_SHAPE, "ra_conv_pair_f32: odd size with pool 2");
   if (plane && (plane_chan < 0 || plane_chan >= Cin)) return fail(RA_E_INVALID, "ra_conv_pair_f32: plane channel");
   hipStream_t st = as_stream(stream);
   const size_t bytes0 = (size_t)B * Hs * Ws * Cin * 4;
   a.bytes0 = (int)bytes0;
-  a.bytes_p = (int)((size_t)B * Hs * Ws * 4);
-  a.cache = nullptr;
-  a.cache_rows = a.cache_gx = a.bytes_c = 0;
   static int no8 = -1;  // RA_PAIR_NO8=1: tuning aid, disables the N-packed kernel
   if (no8 < 0) no8 = getenv("RA_PAIR_NO8") ? 1 : 0;
   if (!no8 && CoutA == 8 && CoutB <= 8 && poolB == 2 && !a.ups && bytes0 < (1u << 31) && a.W > 16) {
@@ -1393,38 +1391,11 @@ extern "C" int ra_conv_pair_fill_cache_rider_f32(const float *src, const float *
     return fail(RA_E_SHAPE, "ra_conv_pair_fill_cache_rider_f32: the fill must be 16-byte aligned, a multiple of 4 floats, < 2 GiB");
   if (!ra_conv_first_cache_supported(4, 8, CoutB, 2, H, W) || plane_chan < 0 || plane_chan > 3)
     return fail(RA_E_SHAPE, "ra_conv_pair_fill_cache_f32: unsupported shape");
-  cpair::PArgs a{};
-  a.src = src;
-  a.y = y;
-  a.wpA = wpA;
-  a.scA = scaleA;
-  a.shA = shiftA;
-  a.wpB = wpB;
-  a.scB = scaleB;
-  a.shB = shiftB;
-  a.C0 = 4;
-  a.Hs = a.H = H;
-  a.Ws = a.W = W;
-  a.ups = 0;
-  a.CoutAP = ra_conv_cout_padded(8);
-  a.CoutB = CoutB;
-  a.CoutBP = ra_conv_cout_padded(CoutB);
-  a.poolB = 2;
-  a.Ho = H / 2;
-  a.Wo = W / 2;
-  a.reluA = reluA;
-  a.reluB = reluB;
-  a.plane = plane;
-  a.plane_chan = plane_chan;
+  cpair::PArgs a = pair_args(src, 4, B, H, W, 0, wpA, scaleA, shiftA, 8, reluA, wpB, scaleB, shiftB, CoutB, reluB, 2, plane, plane_chan, y);
   const size_t b0 = (size_t)B * H * W * 4 * sizeof(float);
   if (b0 >= (1ull << 31)) return fail(RA_E_SHAPE, "ra_conv_pair_fill_cache_f32: input exceeds 2 GiB");
   a.bytes0 = (int)b0;
-  a.bytes_p = (int)((size_t)B * H * W * 4);
-  a.cache = cache;
-  cpair::cache_dims(H, W, a.cache_rows, a.cache_gx);
-  const size_t cb = (size_t)B * a.cache_rows * a.cache_gx * 64 * sizeof(float);
-  if (cb >= (1ull << 31)) return fail(RA_E_SHAPE, "ra_conv_pair_fill_cache_f32: cache exceeds 2 GiB");
-  a.bytes_c = (int)cb;
+  if (int rc = pair_args_cache(a, cache, B, "ra_conv_pair_fill_cache_f32")) return rc;
   a.rider_dst = fill_floats ? fill_dst : nullptr;
   a.rider_quads = (int)(fill_floats / 4);
   a.rider_val = fill_value;
@@ -1439,41 +1410,10 @@ extern "C" int ra_conv_pair_cached_f32(const float *cache, const float *plane, i
     return fail(RA_E_INVALID, "ra_conv_pair_cached_f32: bad argument");
   if (!ra_conv_first_cache_supported(4, 8, CoutB, 2, H, W) || plane_chan < 0 || plane_chan > 3)
     return fail(RA_E_SHAPE, "ra_conv_pair_cached_f32: unsupported shape");
-  cpair::PArgs a{};
-  a.src = plane;  // unused by the cached form (only the canvas plane is staged)
-  a.y = y;
-  a.wpA = wpA;
-  a.scA = scaleA;
-  a.shA = shiftA;
-  a.wpB = wpB;
-  a.scB = scaleB;
-  a.shB = shiftB;
-  a.C0 = 4;
-  a.Hs = a.H = H;
-  a.Ws = a.W = W;
-  a.ups = 0;
-  a.CoutAP = ra_conv_cout_padded(8);
-  a.CoutB = CoutB;
-  a.CoutBP = ra_conv_cout_padded(CoutB);
-  a.poolB = 2;
-  a.Ho = H / 2;
-  a.Wo = W / 2;
-  a.reluA = reluA;
-  a.reluB = reluB;
-  a.plane = plane;
-  a.plane_chan = plane_chan;
-  a.bytes0 = 0;
-  a.bytes_p = (int)((size_t)B * H * W * 4);
-  a.cache = cache;
-  cpair::cache_dims(H, W, a.cache_rows, a.cache_gx);
-  const size_t cb = (size_t)B * a.cache_rows * a.cache_gx * 64 * sizeof(float);
-  if (cb >= (1ull << 31)) return fail(RA_E_SHAPE, "ra_conv_pair_cached_f32: cache exceeds 2 GiB");
-  a.bytes_c = (int)cb;
-  static int split = -1;  // RA_PAIR8_SPLIT=0: layer B on the float32 MFMA (rounds 2-4) instead of the split-precision bf16 form
-  if (split < 0) {
-    const char *e = getenv("RA_PAIR8_SPLIT");
-    split = e ? atoi(e) : 1;
-  }
+  // src: unused by the cached form (only the canvas plane is staged), and bytes0 stays 0
+  cpair::PArgs a = pair_args(plane, 4, B, H, W, 0, wpA, scaleA, shiftA, 8, reluA, wpB, scaleB, shiftB, CoutB, reluB, 2, plane, plane_chan, y);
+  if (int rc = pair_args_cache(a, cache, B, "ra_conv_pair_cached_f32")) return rc;
+  static const int split = env_int("RA_PAIR8_SPLIT", 1);  // =0: layer B on the float32 MFMA (rounds 2-4) instead of the split-precision bf16 form
   if (split) return cpair::launch8<4, true, true>(a, B, as_stream(stream));
   return cpair::launch8<4, true>(a, B, as_stream(stream));
 }

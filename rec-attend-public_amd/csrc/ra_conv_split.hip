@@ -361,11 +361,7 @@ template <int CIN, int POOL, int NB, bool PL = false>
 int launch(const SArgs &a, hipStream_t st) {
   auto kern = conv_split_kernel<CIN, POOL, NB, PL>;
   constexpr int lds = Geo<CIN, NB>::LDS;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    attr = true;
-  }
+  static const MaxDynamicLds lds_limit(kern, lds);
   const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + Geo<CIN, NB>::TH - 1) / Geo<CIN, NB>::TH, ntiles = tiles_x * tiles_y * a.B, slices = a.Cout / (16 * NB);
   int gx = Geo<CIN, NB>::OCC * cu_count() / slices;  // one workgroup per CU (141 KB of LDS at Cin = 32), two where their LDS fits (Geo::OCC)
   if (gx < 1) gx = 1;

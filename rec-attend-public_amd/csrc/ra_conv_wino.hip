@@ -257,7 +257,7 @@ int launch(const WArgs &a, hipStream_t st) {
   static bool attr = false;
   static int cap = 0;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    MaxDynamicLds{kern, lds};
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
     cap = nb * cu_count();
@@ -289,11 +289,7 @@ inline int cu_count() {
 // measured at cfg2, 8-row tiles 9.8 vs 11.5 us (L6), 12.7 vs 13.3 (L4), 16.5 vs 16.6 (L5)
 template <int CIN, int POOL, int NB>
 int launch_any(const WArgs &a, hipStream_t st) {
-  static int force = -1;
-  if (force < 0) {
-    const char *e = getenv("RA_WINO_TSY");
-    force = e ? atoi(e) : 0;
-  }
+  static const int force = env_int("RA_WINO_TSY", 0);
   const int tall = (a.W / TS) * (a.H / 16) * a.B * (a.Cout / (16 * NB));
   const bool small = force ? force == 8 : tall <= 2 * cu_count();
   return small ? launch<CIN, POOL, 8, NB>(a, st) : launch<CIN, POOL, 16, NB>(a, st);
@@ -630,20 +626,15 @@ int launch_pair(const PWArgs &a, hipStream_t st) {
   static bool attr = false;
   static int cap = 0;
   if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    MaxDynamicLds{kern, lds};
     int nb = 0;
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
     cap = nb * cu_count();
-    const char *e = getenv("RA_PAIRW_WGS");
-    if (e && atoi(e) > 0) cap = atoi(e);
+    if (const int wgs = env_int("RA_PAIRW_WGS", 0); wgs > 0) cap = wgs;
     attr = true;
   }
   const int tiles_x = a.W / TS, tiles_y = a.H / TSY, ntiles = tiles_x * tiles_y * a.B;
-  static int xcd = -1;  // RA_PAIRW_XCD=0: tuning aid, the interleaved tile walk
-  if (xcd < 0) {
-    const char *e = getenv("RA_PAIRW_XCD");
-    xcd = e ? atoi(e) : 1;
-  }
+  static const int xcd = env_int("RA_PAIRW_XCD", 1);  // =0: tuning aid, the interleaved tile walk
   const int grid = ntiles < cap ? ntiles : cap;
   PWArgs a2 = a;
   a2.xcd_map = (xcd && grid % 8 == 0 && grid >= 8) ? 1 : 0;
@@ -751,16 +742,9 @@ extern "C" int ra_conv_pair_wino_f32(const float *x, int B, int H, int W, const 
   // round 2 — row-block waves with the output transform in registers (244 VGPRs: 37.6 vs 39.0 us alone, but 48.9k vs
   // 49.8k instance-timesteps/s with four batches in flight) and role-split 8-wave workgroups (the same) — and removed
   // (git history: 58353f0, d1e62e4).
-  static int tsy = 0;  // RA_PAIRW_TSY=16: tuning aid
-  if (!tsy) {
-    const char *e = getenv("RA_PAIRW_TSY");
-    tsy = (e && atoi(e) == 16) ? 16 : 8;  // 8-row tiles: 128 VGPRs and 24 KB of LDS, 4 workgroups per CU (39.1 vs 42.5 us)
-  }
-  static int split = -1;  // RA_PAIRW_SPLIT=0: layer A on the float32 MFMA (rounds 2-4)
-  if (split < 0) {
-    const char *e = getenv("RA_PAIRW_SPLIT");
-    split = e ? atoi(e) : 1;
-  }
+  // RA_PAIRW_TSY=16: tuning aid.  8-row tiles: 128 VGPRs and 24 KB of LDS, 4 workgroups per CU (39.1 vs 42.5 us)
+  static const int tsy = env_int("RA_PAIRW_TSY", 8) == 16 ? 16 : 8;
+  static const int split = env_int("RA_PAIRW_SPLIT", 1);  // =0: layer A on the float32 MFMA (rounds 2-4)
   if (split && tsy == 8) return wino::launch_pair<8, true>(a, as_stream(stream));
   return tsy == 8 ? wino::launch_pair<8>(a, as_stream(stream)) : wino::launch_pair<16>(a, as_stream(stream));
 }

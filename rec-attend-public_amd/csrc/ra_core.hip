@@ -21,8 +21,7 @@ namespace ra {
 int tail_prio(int kind) {  // read on every call (an int parse): tests and A/B probes flip RA_TAIL_PRIO between launches / captures
   const char *m = getenv("RA_TAIL_PRIO_MASK");
   if (m && !(atoi(m) & kind)) return 0;
-  const char *e = getenv("RA_TAIL_PRIO");
-  const int v = e ? atoi(e) : 0;  // measured (profiles/r05_decode_schedule_probes.txt): no level, on no subset of the kernels, helps
+  const int v = env_int("RA_TAIL_PRIO", 0);  // measured (profiles/r05_decode_schedule_probes.txt): no level, on no subset of the kernels, helps
   return v < 0 ? 0 : (v > 3 ? 3 : v);
 }
 }  // namespace ra
@@ -55,8 +54,7 @@ int xcc_census_ok() {
 }
 namespace {
 int tickets_supported() {
-  const char *e = getenv("RA_TILE_TICKETS");
-  if (e && atoi(e) == 0) return 0;
+  if (env_int("RA_TILE_TICKETS", 1) == 0) return 0;
   return xcc_census_ok() == 1 ? 1 : 0;
 }
 }  // namespace
@@ -106,12 +104,7 @@ __global__ __launch_bounds__(256) void poison_lds_kernel(float *sink) {
 }  // namespace ra
 
 extern "C" int ra_debug_poison_lds(void *stream) {
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ra::poison_lds_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  static const ra::MaxDynamicLds lds_limit(ra::poison_lds_kernel, 160 * 1024);
   hipLaunchKernelGGL(ra::poison_lds_kernel, dim3(1024), dim3(256), 160 * 1024, ra::as_stream(stream),
                      static_cast<float *>(nullptr));
   return ra::launch_status("ra_debug_poison_lds");
@@ -140,11 +133,7 @@ extern "C" int ra_debug_park_xcd(int xcd, int n_wg, int lds_bytes, int millis, i
   if (xcd < 0 || xcd > 7 || n_wg <= 0 || n_wg > 64 || lds_bytes < 0 || lds_bytes > 160 * 1024 || millis < 0)
     return ra::fail(RA_E_INVALID, "ra_debug_park_xcd: bad argument");
   if (millis > 20000) millis = 20000;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ra::park_xcd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  static const ra::MaxDynamicLds lds_limit(ra::park_xcd_kernel, 160 * 1024);
   hipLaunchKernelGGL(ra::park_xcd_kernel, dim3(8 * n_wg), dim3(64), (size_t)lds_bytes, ra::as_stream(stream), xcd,
                      (unsigned long long)millis * 100000ull, resident);
   return ra::launch_status("ra_debug_park_xcd");

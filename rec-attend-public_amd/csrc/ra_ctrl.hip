@@ -372,12 +372,7 @@ extern "C" int ra_controller_f32(const ra_ctrl_desc *d, const float *feat, const
   if (in_lds) fl += featf;
   const size_t bytes = fl * sizeof(float);
   if (bytes > 160 * 1024) return fail(RA_E_SHAPE, "ra_controller_f32: %zu B of LDS", bytes);
-  static bool attr_set = false;  // idempotent; benign if raced
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ctrl::controller_kernel),
-                        hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  static const MaxDynamicLds lds_limit(ctrl::controller_kernel, 160 * 1024);
   hipLaunchKernelGGL(ctrl::controller_kernel, dim3(B), dim3(ctrl::kThreads), bytes, as_stream(stream),
                      *d, feat, wpacked, h_last, ctrl_out, glimpse_maps, attn, in_lds, tail_prio(1));
   return launch_status("ra_controller_f32");

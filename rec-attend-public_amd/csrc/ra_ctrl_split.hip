@@ -427,20 +427,13 @@ int launch(const ra_ctrl_desc &d, const float *feat, const float *wp, int B, flo
            hipStream_t st) {
   auto kern = controller_split_kernel<FR, false>;
   auto kern_xl = controller_split_kernel<FR, true>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern_xl),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  static const MaxDynamicLds lds_limit(kern, 160 * 1024), lds_limit_xl(kern_xl, 160 * 1024);
   // the XCD-local form wherever the device's workgroups report the XCC ids 0..7 (ra_core.hip's census); RA_CTRL_XCD=0: the old one
   static int xl = -1, xl_all = 0;
   if (xl < 0) {
-    const char *e = getenv("RA_CTRL_XCD");
-    xl_all = (e && atoi(e) == 2) ? 1 : 0;
-    if (e && atoi(e) == 0) xl = 0;
+    const int asked = env_int("RA_CTRL_XCD", 1);
+    xl_all = asked == 2 ? 1 : 0;
+    if (asked == 0) xl = 0;
     else if (const int c = xcc_census_ok(); c >= 0) xl = c;  // (-1: asked inside a stream capture — decide at the next launch)
   }
   // 8 pools of kTicketPoolStride words at the END of the caller's workspace (not behind THIS launch's images: a workspace sized for
@@ -836,18 +829,12 @@ int launch_batch(const ra_ctrl_desc &d, const float *feat, const float *wp, int 
                  float *gmaps, float *attn, unsigned *ws, size_t ws_bytes, int *status, size_t lds, int xcd_off, hipStream_t st) {
   auto kern = controller_batch_kernel<FR, NI, false>;
   auto kern_xl = controller_batch_kernel<FR, NI, true>;
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(kern_xl), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr_set = true;
-  }
+  static const MaxDynamicLds lds_limit(kern, 160 * 1024), lds_limit_xl(kern_xl, 160 * 1024);
   // the XCD-local form: only when the caller names an XCD offset (xcd_off >= 0: it vouches that concurrent launches use others),
   // the launch has at most 8 groups, and the device's workgroups report the XCC ids 0..7 (RA_CTRL_XCD=0: never)
   static int xl = -1;
   if (xl < 0) {
-    const char *e = getenv("RA_CTRL_XCD");
-    if (e && atoi(e) == 0) xl = 0;
+    if (env_int("RA_CTRL_XCD", 1) == 0) xl = 0;
     else if (const int c = xcc_census_ok(); c >= 0) xl = c;
   }
   unsigned *tickets = ws + ws_bytes / 4 - 8 * kTicketPoolStride;

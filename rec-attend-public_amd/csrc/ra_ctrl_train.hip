@@ -433,11 +433,7 @@ extern "C" int ra_ctrl_train_fwd_n_f32(int B, int G, int Cf, int hid, int iters,
     a.cW[l] = cW[l], a.cb[l] = cb[l];
   }
   const size_t lds = fwd_lds_floats(d) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ctrlt::ctrl_fwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  static const MaxDynamicLds lds_limit(ctrlt::ctrl_fwd_kernel, 160 * 1024);
   hipLaunchKernelGGL(ctrlt::ctrl_fwd_kernel, dim3(B), dim3(ctrlt::kThreads), lds, as_stream(stream), a);
   return launch_status("ra_ctrl_train_fwd_f32");
 }
@@ -473,11 +469,7 @@ extern "C" int ra_ctrl_train_bwd_n_f32(int B, int G, int Cf, int hid, int iters,
     a.cW[l] = cW[l];
   }
   const size_t lds = bwd_lds_floats(d) * sizeof(float);
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ctrlt::ctrl_bwd_kernel), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-    attr = true;
-  }
+  static const MaxDynamicLds lds_limit(ctrlt::ctrl_bwd_kernel, 160 * 1024);
   hipLaunchKernelGGL(ctrlt::ctrl_bwd_kernel, dim3(B), dim3(ctrlt::kThreads), lds, as_stream(stream), a);
   return launch_status("ra_ctrl_train_bwd_f32");
 }

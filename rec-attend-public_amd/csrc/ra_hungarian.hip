@@ -880,18 +880,11 @@ extern "C" int ra_hungarian_f32_dev(const float *weights, int B, int N, int M, f
   // BFS-queue ring after the staged data: the largest power of two that fits, at most 8192 entries
   // (RA_HUNG_RING=0 keeps the queue in global memory)
   const size_t ring_off = use_lds ? (lds + 15) / 16 * 16 : 0;
-  const char *ring_env = getenv("RA_HUNG_RING");  // read per call: the tests force the spill path
-  const int ring_cap = ring_env ? atoi(ring_env) : 8192;
+  const int ring_cap = ra::env_int("RA_HUNG_RING", 8192);  // read per call: the tests force the spill path
   int ring_n = 0;
   for (int r = 64; r <= ring_cap && ring_off + (size_t)(r + 64) * 4 <= 150 * 1024; r *= 2) ring_n = r;  // + 64: augment_wave64c's table
-  const char *bfs_env = getenv("RA_HUNG_BFS");  // 0: one pop at a time (tests run both forms)
-  const int chunked = (bfs_env ? atoi(bfs_env) : 1) && ring_n >= 64;
-  static bool attr = false;
-  if (!attr) {
-    (void)hipFuncSetAttribute(reinterpret_cast<const void *>(ra::hung::hungarian_kernel),
-                              hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    attr = true;
-  }
+  const int chunked = ra::env_int("RA_HUNG_BFS", 1) && ring_n >= 64;  // 0: one pop at a time (tests run both forms)
+  static const ra::MaxDynamicLds lds_limit(ra::hung::hungarian_kernel, 150 * 1024);
   hipLaunchKernelGGL(ra::hung::hungarian_kernel, dim3(B), dim3(64), ring_off + (size_t)(ring_n + 64) * 4,
                      ra::as_stream(stream), weights, N, M, matching, cover_x, cover_y, status_dev,
                      reinterpret_cast<char *>(ws), per, use_lds, ring_n, (int)ring_off, chunked);

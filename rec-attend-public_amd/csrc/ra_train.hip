@@ -576,11 +576,7 @@ __global__ __launch_bounds__(256) void bn_bwd_dx_kernel(const float *u, const fl
 constexpr int kSmallThreads = 1024;
 constexpr size_t kSmallElems = 65536;  // per group
 inline bool small_ok(int C, size_t elems, int which = 1) {
-  static int on = -1;  // RA_BN_SMALL=0: the multi-launch forms; 2: only the moments, 3: only the backward (debugging aids)
-  if (on < 0) {
-    const char *e = getenv("RA_BN_SMALL");
-    on = e ? atoi(e) : 1;
-  }
+  static const int on = env_int("RA_BN_SMALL", 1);  // =0: the multi-launch forms; 2: only the moments, 3: only the backward (debugging aids)
   return (on == 1 || on == which) && C >= 1 && C <= 64 && (C & (C - 1)) == 0 && elems <= kSmallElems;
 }
 __global__ __launch_bounds__(kSmallThreads) void bn_bwd_small_kernel(const float *u, const float *dy, const float *mean, const float *var,
@@ -1954,12 +1950,7 @@ __global__ __launch_bounds__(256) void wgrad_final_acc_rows_kernel(const float *
 namespace {
 inline int wgrad_grid_x(int ntiles) {
   // persistent workgroups: 4 per CU (38 KB of LDS each) hide the un-prefetched tile staging; 256 left 4 waves per CU
-  static int cap = 0;
-  if (!cap) {
-    const char *e = getenv("RA_WGRAD_WGS");
-    cap = e ? atoi(e) : 1024;
-    if (cap < 1) cap = 1;
-  }
+  static const int asked = env_int("RA_WGRAD_WGS", 1024), cap = asked < 1 ? 1 : asked;
   return ntiles < cap ? ntiles : cap;
 }
 }  // namespace
@@ -1998,12 +1989,7 @@ int wgrad_impl(const float *x, int Cin, int B, int Hs, int Ws, int upsample, con
   hipStream_t st = as_stream(stream);
 #define RA_WGRAD_T(NT, PACK, BF, PRE)                                                                             \
   {                                                                                                               \
-    static bool attr = false;                                                                                     \
-    if (!attr) {                                                                                                  \
-      (void)hipFuncSetAttribute(reinterpret_cast<const void *>(wgrad_kernel<NT, PACK, BF, PRE>),                  \
-                                hipFuncAttributeMaxDynamicSharedMemorySize, 100 * 1024);                         \
-      attr = true;                                                                                                \
-    }                                                                                                             \
+    static const MaxDynamicLds lds_limit(wgrad_kernel<NT, PACK, BF, PRE>, 100 * 1024);                            \
     hipLaunchKernelGGL((wgrad_kernel<NT, PACK, BF, PRE>), dim3(gx, chunks, slices), dim3(256), lds, st, x, du, B, Hs, Ws, Cin, \
                        ups, H, W, Cout, tiles_x, tiles_y, ntiles, ws, xtab, dutab, Bseg, fmt);                   \
   }
@@ -2015,29 +2001,13 @@ int wgrad_impl(const float *x, int Cin, int B, int Hs, int Ws, int upsample, con
   {                                                                                                               \
     if (bf16) RA_WGRAD_P(NT, PACK, true) else RA_WGRAD_P(NT, PACK, false)                                         \
   }
-  static int pre_env = -1;  // RA_WGRAD_PRE=0: tuning aid, no register prefetch of the next tile
-  if (pre_env < 0) {
-    const char *e = getenv("RA_WGRAD_PRE");
-    pre_env = e ? atoi(e) : 1;
-  }
+  static const int pre_env = env_int("RA_WGRAD_PRE", 1);  // =0: tuning aid, no register prefetch of the next tile
   const bool pre_ok = pre_env && (Cout & 3) == 0;
-  static int pack_ok = -1;  // RA_WGRAD_PACK=0: tuning aid, channel rows for every Cin
-  if (pack_ok < 0) {
-    const char *e = getenv("RA_WGRAD_PACK");
-    pack_ok = e ? atoi(e) : 1;
-  }
+  static const int pack_ok = env_int("RA_WGRAD_PACK", 1);  // =0: tuning aid, channel rows for every Cin
   const int pack = (pack_ok && (Cin == 4 || Cin == 8)) ? Cin : 0;
-  static int small_ok = -1;  // RA_WGRAD_SMALL=0: tuning aid, the 16x16x4 form for the 8-output-channel layers too
-  if (small_ok < 0) {
-    const char *e = getenv("RA_WGRAD_SMALL");
-    small_ok = e ? atoi(e) : 1;
-  }
+  static const int small_ok = env_int("RA_WGRAD_SMALL", 1);  // =0: tuning aid, the 16x16x4 form for the 8-output-channel layers too
   const bool small = small_ok && !bf16 && !ups && Cout == 8 && (Cin == 4 || Cin == 8);
-  static int t8_ok = -1;  // RA_WGRAD8=0: tuning aid, the 16-block form (wgrad_small_kernel) instead of the transposed-tile one
-  if (t8_ok < 0) {
-    const char *e = getenv("RA_WGRAD8");
-    t8_ok = e ? atoi(e) : 1;
-  }
+  static const int t8_ok = env_int("RA_WGRAD8", 1);  // =0: tuning aid, the 16-block form (wgrad_small_kernel) instead of the transposed-tile one
   const size_t seg_bytes = (size_t)(xtab ? Bseg : B) * H * W * 8 * 4;  // the larger of the two tensors of a segment
   // bf16 mode, stacked step: dU stored as bf16 and x either stored as bf16 (8 channels) or the float32 packed image (4 channels)
   const bool small_b = small_ok && t8_ok && bf16 && !ups && Cout == 8 && (fmt & 2) &&

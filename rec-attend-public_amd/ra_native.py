@@ -7,6 +7,7 @@ of the product path fails loudly.  Device pointers are taken from torch tensors
 """
 import ctypes as C
 import os
+import re
 
 # The HIP runtime multiplexes all streams of a process onto GPU_MAX_HW_QUEUES hardware queues
 # (default 4, the null stream and the graph-capture stream included) and reads the variable at its
@@ -17,10 +18,7 @@ os.environ.setdefault('GPU_MAX_HW_QUEUES', '8')
 _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(_HERE, 'librecattend.so')
 
-RA_ABI_VERSION = 113  # include/recattend.h: RA_ABI_VERSION
-RA_CONV_TRANSPOSED = 1
-RA_E_INVALID, RA_E_SHAPE, RA_E_WORKSPACE = -1, -2, -3  # include/recattend.h
-RA_ATTN_STRIDE = 16
+HEADER_PATH = os.path.join(os.path.dirname(_HERE), 'include', 'recattend.h')
 
 
 class RecAttendError(RuntimeError):
@@ -28,179 +26,68 @@ class RecAttendError(RuntimeError):
 
 
 class CtrlDesc(C.Structure):
-  """struct ra_ctrl_desc (include/recattend.h)."""
-  _fields_ = [(n, C.c_int) for n in ('G', 'Cf', 'hid', 'iters', 'n_gmlp', 'n_cmlp', 'mlp_dim',
-                                      'H', 'W', 'Fh', 'Fw', 'squash', 'fixed_var',
-                                      'dynamic_var', 'fixed_gamma')]
+  """struct ra_ctrl_desc; its _fields_ are read from the header below."""
 
 
-_P = C.c_void_p
-_I = C.c_int
-_F = C.c_float
-_Z = C.c_size_t
+_SCALARS = {'int': C.c_int, 'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t}
+_POINTEES = ('float', 'int', 'void', 'unsigned short')
 
-# name -> (restype, argtypes); must list every symbol of include/recattend.h
-SIGNATURES = {
-    'ra_version': (_I, []),
-    'ra_last_error_string': (C.c_char_p, []),
-    'ra_debug_poison_lds': (_I, [_P]),
-    'ra_debug_park_xcd': (_I, [_I, _I, _I, _I, _P, _P]),
-    'ra_gather_f32': (_I, [_P, _P, _Z, _P, _P]),
-    'ra_gemm_tn_acc_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _P]),
-    'ra_conv3x3_bf16_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _Z, _P, _I, _P]),
-    'ra_bn_act_pool_bf16_f32': (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
-    'ra_bn_act_pool_bwd_acc_bf16_f32': (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P, _I, _P]),
-    'ra_bn_act_pool_bwd_grouped_bf16_f32': (_I, [_P, _P, _P, _I, _F, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _I, _P]),
-    'ra_conv3x3_wgrad_acc_bf16_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _I, _I, _P, _P, _I, _P]),
-    'ra_colour_jitter_workspace_floats': (_Z, [_I]),
-    'ra_colour_jitter_f32': (_I, [_P, _I, _I, _F, _F, _F, _F, _P, _Z, _P, _P]),
-    'ra_hungarian_f32': (_I, [_P, _I, _I, _I, _P, _P, _P]),
-    'ra_hungarian_dev_workspace_bytes': (_Z, [_I, _I, _I]),
-    'ra_hungarian_f32_dev': (_I, [_P, _I, _I, _I, _P, _P, _P, _P, _P, _Z, _P]),
-    'ra_conv_cout_padded': (_I, [_I]),
-    'ra_conv_packed_floats': (_Z, [_I, _I]),
-    'ra_conv_pack_weights': (_I, [_P, _I, _I, _I, _P, _I, _P]),
-    'ra_conv_fold_bn': (_I, [_P, _P, _P, _P, _P, _I, _F, _P, _P]),
-    'ra_conv3x3_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
-    # nnlib.cnn / nnlib.dcnn layers of filter size 1, 5 or 7 (nnlib.py:131-257, :260-404)
-    'ra_conv_packed_floats_k': (_Z, [_I, _I, _I]),
-    'ra_conv_pack_weights_k': (_I, [_P, _I, _I, _I, _I, _P, _I, _P]),
-    'ra_convkxk_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _I, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
-    # the wide 3x3 layer and the head of fg_model (fg_model.py:112-194)
-    'ra_conv_wide_supported': (_I, [_I, _I]),
-    'ra_conv_wide_packed_floats': (_Z, [_I, _I]),
-    'ra_conv_wide_pack_weights': (_I, [_P, _I, _I, _I, _P, _I, _P]),
-    'ra_conv3x3_wide_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
-    'ra_fg_head_f32': (_I, [_P, _Z, _I, _I, _I, _P, _P, _P, _I, _P, _I, _P, _P]),
-    'ra_conv3x3_moments_part_floats': (_Z, [_I]),
-    'ra_conv3x3_moments_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P, _Z, _P, _P]),
-    'ra_bn_moments_from_partials_f32': (_I, [_P, _I, _I, _P, _P, _P]),
-    'ra_conv3x3_bf16ops_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
-    'ra_conv_pair_supported': (_I, [_I, _I, _I]),
-    'ra_conv_pair_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
-    'ra_ctrl_packed_floats': (_Z, [C.POINTER(CtrlDesc)]),
-    'ra_ctrl_pack_weights': (_I, [C.POINTER(CtrlDesc), _P, _P, _P, _P]),
-    'ra_controller_f32': (_I, [C.POINTER(CtrlDesc), _P, _P, _I, _P, _P, _P, _P, _P]),
-    'ra_ctrl_split_supported': (_I, [C.POINTER(CtrlDesc)]),
-    'ra_ctrl_split_packed_floats': (_Z, [C.POINTER(CtrlDesc)]),
-    'ra_ctrl_split_workspace_bytes': (_Z, [C.POINTER(CtrlDesc), _I]),
-    'ra_ctrl_split_pack_weights': (_I, [C.POINTER(CtrlDesc), _P, _P, _P, _P]),
-    'ra_controller_split_f32': (_I, [C.POINTER(CtrlDesc), _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P, _P]),
-    'ra_ctrl_batch_group_images': (_I, [C.POINTER(CtrlDesc), _I]),
-    'ra_ctrl_batch_supported': (_I, [C.POINTER(CtrlDesc)]),
-    'ra_ctrl_batch_workspace_bytes': (_Z, [C.POINTER(CtrlDesc), _I]),
-    'ra_controller_batch_f32': (_I, [C.POINTER(CtrlDesc), _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P, _P]),
-    'ra_controller_batch_xcd_f32': (_I, [C.POINTER(CtrlDesc), _P, _P, _I, _P, _P, _P, _P, _P, _Z, _P, _I, _P]),
-    'ra_gaussian_filter_f32': (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
-    'ra_extract_direct_f32': (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    'ra_extract_conv0_supported': (_I, [_I, _I, _I, _I, _I]),
-    'ra_extract_conv0_f32': (_I, [_P, _I, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _I, _I, _P, _P]),
-    'ra_paste_direct_f32': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _I, _I, _P, _Z, _I, _P]),
-    'ra_attn_box_direct_f32': (_I, [_P, _I, _I, _I, _I, _I, _F, _P, _Z, _P]),
-    'ra_ctrl_train_supported': (_I, [_I, _I, _I, _I, _I]),
-    'ra_ctrl_train_save_floats': (_Z, [_I, _I, _I, _I]),
-    'ra_ctrl_train_supported_n': (_I, [_I] * 8),
-    'ra_ctrl_train_save_floats_n': (_Z, [_I] * 5),
-    'ra_ctrl_train_fwd_n_f32': (_I, [_I] * 9 + [_P] * 12),
-    'ra_ctrl_train_bwd_n_f32': (_I, [_I] * 9 + [_P] * 12 + [_Z, _P, _Z, _P]),
-    'ra_ctrl_train_fwd_f32': (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    'ra_ctrl_train_bwd_f32': (_I, [_I, _I, _I, _I, _I, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P]),
-    'ra_resample_bwd_workspace_floats': (_Z, [_I, _I, _I]),
-    'ra_resample_bwd_f32': (_I, [_I, _P, _I, _I, _I, _P, _P, _P, _P, _I, _P, _I, _I, _I, _I, _I, _I, _P, _I, _P, _I, _P, _Z, _P, _P]),
-    'ra_extract_patch_dense_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    'ra_dense_f32': (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _P, _Z, _P]),
-    'ra_pack_input_f32': (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P]),
-    'ra_pack_input_plane_f32': (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P]),
-    'ra_canvas_max_f32': (_I, [_P, _I, _I, _P, _P, _I, _I, _I, _P]),
-    'ra_affine_act_f32': (_I, [_P, _P, _P, _Z, _I, _I, _P, _P]),
-    'ra_max_pool_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    'ra_pair_stats_workspace_floats': (_Z, [_I, _I]),
-    'ra_pair_stats_f32': (_I, [_P, _P, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
-    'ra_pair_stats_strided_f32': (_I, [_P, _Z, _Z, _P, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P, _P, _P, _P]),
-    'ra_gt_box_workspace_floats': (_Z, [_I, _I]),
-    'ra_gt_box_f32': (_I, [_P, _I, _I, _I, _I, _F, _F, _P, _Z, _P, _P, _P]),
-    'ra_knob_setup_f32': (_I, [_P, _I, _I, _P, _P, _P, _P, _P, _F, _I, _P, _P, _P, _P, _P]),
-    'ra_segm_match_workspace_bytes': (_Z, [_I, _I]),
-    'ra_segm_match_f32': (_I, [_P, _P, _I, _I, _P, _Z, _P, _P, _P]),
-    'ra_segm_match_host_block_bytes': (_Z, [_I, _I]),
-    'ra_segm_match_host_f32': (_I, [_P, _P, _I, _I, _P, _P, _Z, _I, _P, _P, _P]),
-    'ra_loss_stats_workspace_floats': (_Z, [_I]),
-    'ra_loss_stats_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _F, _P, _Z, _P, _P]),
-    'ra_postprocess_f32': (_I, [_P, _P, _I, _I, _I, _I, _F, _P, _P, _P, _P, _P]),
-    'ra_union_f32': (_I, [_P, _I, _I, _I, _P, _P]),
-    'ra_dilate_f32': (_I, [_P, _I, _I, _I, _I, _P, _P]),
-    'ra_resize_linear_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _P]),
-    'ra_bilateral5_f32': (_I, [_P, _I, _I, _I, _F, _F, _P, _P]),
-    'ra_remove_tiny_f32': (_I, [_P, _P, _P, _I, _I, _I, _F, _P]),
-    'ra_eval_metrics_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
-    'ra_random_transform_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    'ra_weighted_sum_f32': (_I, [_P, _P, _I, _I, _I, _P, _P]),
-    'ra_sem_foreground_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _F, _P, _P]),
-    'ra_instance_class_vote_workspace_floats': (_Z, [_I, _I, _I, _I, _I]),
-    'ra_instance_class_vote_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _Z, _P, _P, _P, _P]),
-    'ra_instance_class_pick_f32': (_I, [_P, _P, _I, _I, _I, _P, _P, _P]),
-    'ra_fill_f32': (_I, [_P, _Z, _F, _P]),
-    'ra_tile_tickets_bind': (_I, [_P, _I]),
-    'ra_tile_tickets_slot_bytes': (_I, []),
-    'ra_adam_step_f32': (_I, [_P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _F, _P]),
-    'ra_adam_step_guarded_f32': (_I, [_P, _P, _P, _P, _P, _Z, _F, _F, _F, _F, _F, _F, _P, _I, _I, _P]),
-    'ra_bn_workspace_floats': (_Z, [_I]),
-    'ra_bn_moments_f32': (_I, [_P, _Z, _I, _P, _Z, _P, _P, _P]),
-    'ra_bn_act_pool_f32': (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _P]),
-    'ra_bn_act_pool_bwd_f32': (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P]),
-    'ra_bn_act_pool_bwd_reduce_f32': (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P]),
-    'ra_bn_act_pool_bwd_dx_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, C.c_double, _F, _I, _I, _I, _I, _I, _I, _P, _P]),
-    'ra_conv_pack_weights_dev': (_I, [_P, _I, _I, _I, _P, _I, _P, _P]),
-    'ra_conv3x3_wgrad_workspace_floats': (_Z, [_I, _I, _I, _I, _I]),
-    'ra_conv3x3_wgrad_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _P, _P]),
-    'ra_conv3x3_wgrad_bf16ops_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _P, _P]),
-    'ra_conv_wino_supported': (_I, [_I, _I, _I, _I, _I]),
-    'ra_conv_wino_packed_floats': (_Z, [_I, _I]),
-    'ra_conv_wino_pack_weights': (_I, [_P, _I, _I, _P]),
-    'ra_conv_wino_f32': (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
-    'ra_conv_split_supported': (_I, [_I, _I, _I, _I, _I]),
-    'ra_conv_split_packed_halfs': (_Z, [_I, _I]),
-    'ra_conv_split_pack_weights': (_I, [_P, _I, _I, _P]),
-    'ra_conv_split_pack_weights_dev': (_I, [_P, _I, _I, _I, _P, _P]),
-    'ra_conv_split_f32': (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
-    'ra_conv_split_plane_f32': (_I, [_P, _I, _I, _I, _I, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
-    'ra_conv_pair_wino_supported': (_I, [_I, _I, _I, _I, _I, _I]),
-    'ra_conv_pair_wino_f32': (_I, [_P, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _P, _P]),
-    'ra_gauss_filter_f32': (_I, [_P, _P, _P, _I, _I, _I, _P, _P]),
-    'ra_gauss_filter_bwd_f32': (_I, [_P, _P, _P, _P, _I, _I, _I, _P, _P, _P, _P]),
-    'ra_loss_head_f32': (_I, [_P, _P, _P, _P, _P, _I, _I, _F, _P, _P]),
-    'ra_loss_head_bwd_f32': (_I, [_P] * 10 + [_I, _I, _I, _F] + [_P] * 6),
-    'ra_attn_head_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P]),
-    'ra_attn_head_rec_f32': (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _P, _P, _P]),
-    'ra_attn_head_bwd_f32': (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
-    'ra_knob_mix_f32': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
-    'ra_knob_mix_rec_f32': (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _P, _P, _P, _P, _P]),
-    'ra_knob_mix_bwd_f32': (_I, [_P, _P, _P, _I, _I, _P, _P, _P]),
-    'ra_gauss_filter_strided_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _P, _P]),
-    'ra_gauss_filter_strided_bwd_f32': (_I, [_P, _P, _P, _I, _I, _I, _P, _I, _I, _I, _P, _P, _P, _I, _P]),
-    'ra_lstm_cell_f32': (_I, [_P, _P, _I, _I, _P, _P, _P, _P]),
-    'ra_lstm_cell_bwd_f32': (_I, [_P, _P, _P, _P, _P, _I, _I, _P, _P, _P]),
-    'ra_conv3x3_wgrad_acc_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _I, _I, _P, _P, _P]),
-    'ra_box_iou_rects_workspace_floats': (_Z, [_I]),
-    'ra_box_iou_rects_f32': (_I, [_P, _P, _I, _I, _I, _I, _P, _Z, _P, _P]),
-    'ra_bn_act_pool_bwd_grouped_f32': (_I, [_P, _P, _P, _I, _F, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P]),
-    'ra_ptr_table': (_I, [_P, _I, _P, _P]),
-    'ra_conv3x3_wgrad_multi_acc_f32': (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _I, _I, _P, _P, _I, _P]),
-    'ra_conv3x3_wgrad_acc_bf16ops_f32': (_I, [_P, _I, _I, _I, _I, _I, _P, _I, _P, _Z, _P, _I, _I, _P, _P, _P]),
-    'ra_bn_act_pool_bwd_acc_f32': (_I, [_P, _P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _Z, _P, _P, _P, _P, _P, _P]),
-    'ra_canvas_step_f32': (_I, [_P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _I, _P, _P]),
-    'ra_subsample_odd_f32': (_I, [_P, _I, _I, _I, _I, _P, _P]),
-    'ra_weighted_sum_multi_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P]),
-    'ra_weighted_sum_multi_strided_f32': (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _Z, _Z, _P]),
-    'ra_conv_first_cache_supported': (_I, [_I, _I, _I, _I, _I, _I]),
-    'ra_conv_first_cache_floats': (_Z, [_I, _I, _I]),
-    'ra_conv_first_cache_f32': (_I, [_P, _I, _I, _I, _P, _I, _I, _P, _P]),
-    'ra_conv_pair_fill_cache_f32': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P]),
-    'ra_conv_pair_fill_cache_rider_f32': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P, _P, _Z, _F, _P]),
-    'ra_conv_pair_cached_f32': (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _P, _I, _P, _P, _P, _I, _I, _P, _P]),
-    'ra_greedy_match_f32': (_I, [_P, _I, _I, _P, _P]),
-    'ra_paste_score_direct_f32': (_I, [_P, _I, _I, _P, _I, _I, _I, _I, _I, _F, _I, _P, _P, _Z, _I, _P, _I, _P, _I, _P, _P, _P, _Z, _P]),
-}
+
+def _ctype(words, name):
+  """ctypes type of a C type given as its tokens (`const` dropped): a scalar, ra_ctrl_desc *, or any other data pointer."""
+  if words == ['ra_ctrl_desc', '*']:
+    return C.POINTER(CtrlDesc)
+  base = ' '.join(w for w in words if w != '*')
+  if '*' in words and words[-1] == '*' and base in _POINTEES:
+    return C.c_void_p
+  if len(words) == 1 and base in _SCALARS:
+    return _SCALARS[base]
+  raise RecAttendError('include/recattend.h: %s: no ctypes mapping for the type "%s"' % (name, ' '.join(words)))
+
+
+def read_header(text):
+  """(signatures, constants, ra_ctrl_desc field names) of the text of recattend.h.  signatures: {name: (restype,
+  [argtypes])} of every `ret ra_name(args);`, constants: {name: int} of every `#define RA_NAME integer`.  The header is
+  the only statement of the ABI, so a prototype this cannot split or a type it has no mapping for is an error, never a guess."""
+  text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
+  constants = {m.group(1): int(m.group(2))
+               for m in re.finditer(r'^#define[ \t]+(RA_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$', text, re.M)}
+  text = re.sub(r'^[ \t]*#.*$', '', text, flags=re.M)
+  struct = re.search(r'typedef\s+struct\s+ra_ctrl_desc\s*\{([^{}]*)\}\s*ra_ctrl_desc\s*;', text)
+  if struct is None:
+    raise RecAttendError('include/recattend.h: struct ra_ctrl_desc not found')
+  fields = []
+  for decl in filter(None, (d.strip() for d in struct.group(1).split(';'))):
+    if not re.match(r'int\s+\w+(\s*,\s*\w+)*$', decl):
+      raise RecAttendError('include/recattend.h: ra_ctrl_desc: member "%s" is not an int' % decl)
+    fields += re.findall(r'\w+', decl)[1:]
+  text = re.sub(r'(typedef\s+struct\s+\w+|enum)\s*\{[^{}]*\}\s*\w*\s*;', '', text)
+  text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r'\1', text, flags=re.S)
+  signatures = {}
+  for stmt in filter(None, (s.strip() for s in text.split(';'))):
+    m = re.match(r'([\w\s*]+?)\b(ra_\w+)\s*\(([^()]*)\)$', stmt)
+    if m is None:
+      raise RecAttendError('include/recattend.h: cannot split the prototype "%s"' % ' '.join(stmt.split()))
+    ret, name, params = m.groups()
+    ret = re.findall(r'\w+|\*', ret)
+    res = C.c_char_p if ret == ['const', 'char', '*'] else _ctype(ret, name)
+    args = []
+    if params.split() != ['void']:
+      for p in params.split(','):
+        words = [w for w in re.findall(r'\w+|\*', p) if w != 'const']
+        if len(words) < 2 or words[-1] == '*' or re.sub(r'[\w\s*]', '', p):
+          raise RecAttendError('include/recattend.h: %s: cannot split the parameter "%s"' % (name, ' '.join(p.split())))
+        args.append(_ctype(words[:-1], name))  # the last word is the parameter's name
+    signatures[name] = (res, args)
+  return signatures, constants, fields
+
+
+# name -> (restype, argtypes) of every symbol, the RA_* integer constants and the controller descriptor, all as
+# include/recattend.h states them
+with open(HEADER_PATH) as _f:
+  SIGNATURES, CONSTANTS, _fields = read_header(_f.read())
+CtrlDesc._fields_ = [(n, C.c_int) for n in _fields]
+globals().update(CONSTANTS)  # RA_ABI_VERSION, RA_E_*, RA_CONV_TRANSPOSED, RA_ATTN_STRIDE, RA_PASTE_*, RA_RESAMPLE_*
 
 _lib = None
 

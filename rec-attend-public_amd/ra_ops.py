@@ -41,6 +41,24 @@ def cout_padded(cout):
 FILTER_SIZES = (1, 3, 5, 7)  # the K1 filter sizes built (ra_convkxk_f32)
 
 
+def _filter_channels(w, cin_kernel, chan_map, transposed):
+  """(cin_w, cout, cin, chan_map, flags) of a filter w [f,f,Ci,Co] (transposed: [f,f,Co,Ci]) for a kernel input of cin_kernel
+  channels: what pack_conv_weights and pack_wide_weights hand to their pack entry points."""
+  cin_w, cout = (w.shape[3], w.shape[2]) if transposed else (w.shape[2], w.shape[3])
+  cin = cin_w if cin_kernel is None else int(cin_kernel)
+  if chan_map is None and cin != cin_w:
+    chan_map = list(range(cin_w)) + [-1] * (cin - cin_w)
+  return cin_w, cout, cin, chan_map, rn.RA_CONV_TRANSPOSED if transposed else 0
+
+
+def _chan_map_i32(chan_map, cin):
+  if chan_map is None:
+    return None
+  cm = np.ascontiguousarray(chan_map, dtype=np.int32)
+  assert cm.shape[0] == cin
+  return cm
+
+
 def pack_conv_weights(w, cin_kernel=None, chan_map=None, transposed=False):
   """TF-layout filter -> packed B-operand order (numpy, host).  w [f,f,Ci,Co] or, when
   transposed, the conv2d_transpose filter [f,f,Co,Ci]; f in FILTER_SIZES (3: ra_conv_pack_weights,
@@ -49,10 +67,7 @@ def pack_conv_weights(w, cin_kernel=None, chan_map=None, transposed=False):
   f = w.shape[0]
   if w.ndim != 4 or w.shape[1] != f or f not in FILTER_SIZES:
     raise rn.RecAttendError('filter of shape %r: square filters of size %s are built' % (w.shape, FILTER_SIZES))
-  cin_w, cout = (w.shape[3], w.shape[2]) if transposed else (w.shape[2], w.shape[3])
-  cin = cin_w if cin_kernel is None else int(cin_kernel)
-  if chan_map is None and cin != cin_w:
-    chan_map = list(range(cin_w)) + [-1] * (cin - cin_w)
+  cin_w, cout, cin, chan_map, flags = _filter_channels(w, cin_kernel, chan_map, transposed)
   if cout > 128 and f == 3 and conv_wide_supported(cin, cout):  # the wide layer's own order (conv_wide / conv2d_fused run it)
     return pack_wide_weights(w, cin_kernel=cin, chan_map=chan_map, transposed=transposed)
   if cout > 128 and f != 3 and conv_wide_supported(cin, cout):
@@ -61,11 +76,7 @@ def pack_conv_weights(w, cin_kernel=None, chan_map=None, transposed=False):
   if n == 0:
     raise rn.RecAttendError('unsupported conv shape Cin=%d Cout=%d' % (cin, cout))
   out = np.empty(n, dtype=np.float32)
-  cm = None
-  if chan_map is not None:
-    cm = np.ascontiguousarray(chan_map, dtype=np.int32)
-    assert cm.shape[0] == cin
-  flags = rn.RA_CONV_TRANSPOSED if transposed else 0
+  cm = _chan_map_i32(chan_map, cin)
   if f == 3:
     check(rn.lib().ra_conv_pack_weights(ptr(w), cin_w, cout, cin, ptr(cm), flags, ptr(out)), 'ra_conv_pack_weights')
   else:
@@ -105,11 +116,11 @@ def make_ctrl_desc(G, Cf, hid, iters, n_gmlp, n_cmlp, mlp_dim, H, W, Fh, Fw, squ
                      int(bool(fixed_var)), int(bool(dynamic_var)), int(bool(fixed_gamma)))
 
 
-def pack_ctrl_weights(desc, lstm, gmlp, cmlp):
-  """lstm: dict with keys w_xi,w_hi,b_i,...; gmlp/cmlp: lists [(w,b),...].  -> numpy."""
-  n = rn.lib().ra_ctrl_packed_floats(C.byref(desc))
+def _pack_ctrl(desc, lstm, gmlp, cmlp, count_fn, pack_fn, unsupported):
+  """The controller's weights in the order of the library's pack_fn, count_fn floats of them (numpy, host)."""
+  n = getattr(rn.lib(), count_fn)(C.byref(desc))
   if n == 0:
-    raise rn.RecAttendError('unsupported controller descriptor')
+    raise rn.RecAttendError(unsupported)
   order = ['w_xi', 'w_hi', 'b_i', 'w_xf', 'w_hf', 'b_f', 'w_xu', 'w_hu', 'b_u', 'w_xo', 'w_ho',
            'b_o']
   la = [_np32(lstm[k]) for k in order]
@@ -117,9 +128,13 @@ def pack_ctrl_weights(desc, lstm, gmlp, cmlp):
   ca = [_np32(a) for wb in cmlp for a in wb]
   arr = lambda xs: (C.c_void_p * len(xs))(*[x.ctypes.data for x in xs])
   out = np.empty(n, dtype=np.float32)
-  check(rn.lib().ra_ctrl_pack_weights(C.byref(desc), arr(la), arr(ga), arr(ca), ptr(out)),
-        'ra_ctrl_pack_weights')
+  check(getattr(rn.lib(), pack_fn)(C.byref(desc), arr(la), arr(ga), arr(ca), ptr(out)), pack_fn)
   return out
+
+
+def pack_ctrl_weights(desc, lstm, gmlp, cmlp):
+  """lstm: dict with keys w_xi,w_hi,b_i,...; gmlp/cmlp: lists [(w,b),...].  -> numpy."""
+  return _pack_ctrl(desc, lstm, gmlp, cmlp, 'ra_ctrl_packed_floats', 'ra_ctrl_pack_weights', 'unsupported controller descriptor')
 
 
 def ctrl_split_supported(desc):
@@ -127,19 +142,8 @@ def ctrl_split_supported(desc):
 
 
 def pack_ctrl_split_weights(desc, lstm, gmlp, cmlp):
-  n = rn.lib().ra_ctrl_split_packed_floats(C.byref(desc))
-  if n == 0:
-    raise rn.RecAttendError('descriptor not supported by the split controller')
-  order = ['w_xi', 'w_hi', 'b_i', 'w_xf', 'w_hf', 'b_f', 'w_xu', 'w_hu', 'b_u', 'w_xo', 'w_ho',
-           'b_o']
-  la = [_np32(lstm[k]) for k in order]
-  ga = [_np32(a) for wb in gmlp for a in wb]
-  ca = [_np32(a) for wb in cmlp for a in wb]
-  arr = lambda xs: (C.c_void_p * len(xs))(*[x.ctypes.data for x in xs])
-  out = np.empty(n, dtype=np.float32)
-  check(rn.lib().ra_ctrl_split_pack_weights(C.byref(desc), arr(la), arr(ga), arr(ca), ptr(out)),
-        'ra_ctrl_split_pack_weights')
-  return out
+  return _pack_ctrl(desc, lstm, gmlp, cmlp, 'ra_ctrl_split_packed_floats', 'ra_ctrl_split_pack_weights',
+                    'descriptor not supported by the split controller')
 
 
 _CUS = []
@@ -152,11 +156,15 @@ def cu_count():
   return _CUS[0]
 
 
-def ctrl_split_workspace(desc, B, device):
-  """Zero-filled exchange workspace (+ status word) for ONE stream of launches."""
-  nb = rn.lib().ra_ctrl_split_workspace_bytes(C.byref(desc), B)
+def _exchange_workspace(desc, B, device, bytes_fn):
+  nb = getattr(rn.lib(), bytes_fn)(C.byref(desc), B)
   return (torch.zeros((nb + 7) // 8, dtype=torch.int64, device=device),
           torch.zeros(1, dtype=torch.int32, device=device))
+
+
+def ctrl_split_workspace(desc, B, device):
+  """Zero-filled exchange workspace (+ status word) for ONE stream of launches."""
+  return _exchange_workspace(desc, B, device, 'ra_ctrl_split_workspace_bytes')
 
 
 def controller_split(desc, feat, wp, h_last, ctrl_out, gmaps, attn, ws, status):
@@ -178,9 +186,7 @@ def ctrl_batch_supported(desc):
 
 def ctrl_batch_workspace(desc, B, device):
   """Zero-filled exchange workspace (+ status word) of the group-shared controller, for ONE stream of launches."""
-  nb = rn.lib().ra_ctrl_batch_workspace_bytes(C.byref(desc), B)
-  return (torch.zeros((nb + 7) // 8, dtype=torch.int64, device=device),
-          torch.zeros(1, dtype=torch.int32, device=device))
+  return _exchange_workspace(desc, B, device, 'ra_ctrl_batch_workspace_bytes')
 
 
 def controller_batch(desc, feat, wp, h_last, ctrl_out, gmaps, attn, ws, status, xcd_offset=-1):
@@ -196,6 +202,19 @@ def controller_batch(desc, feat, wp, h_last, ctrl_out, gmaps, attn, ws, status, 
 # ---------------------------------------------------------------------------- device ops
 
 
+def _conv_out(src, cout, pool=1, upsample=False, out=None, checked_for=None):
+  """The output [B,Ho,Wo,cout] of a conv layer over src [B,Hs,Ws,.]: Ho, Wo = Hs, Ws (twice that with upsample) // pool.
+  A fresh tensor when out is None; checked_for: the wrapper that has a given out's shape checked."""
+  B, Hs, Ws = src.shape[:3]
+  up = 2 if upsample else 1
+  shape = (B, Hs * up // pool, Ws * up // pool, cout)
+  if out is None:
+    return torch.empty(shape, dtype=torch.float32, device=src.device)
+  if checked_for and tuple(out.shape) != shape:
+    raise rn.RecAttendError('%s: out of shape %r, expected %r' % (checked_for, tuple(out.shape), shape))
+  return out
+
+
 def conv3x3(src0, wp, scale, shift, cout, relu=True, pool=1, src1=None, upsample=False,
             out=None, plane=None, plane_chan=-1, bf16=False):
   """One fused conv layer.  src0 [B,Hs,Ws,C0] (+ src1 [B,Hs,Ws,C1]) -> [B,Ho,Wo,cout].
@@ -203,10 +222,7 @@ def conv3x3(src0, wp, scale, shift, cout, relu=True, pool=1, src1=None, upsample
   _need_cuda(src0, src1, wp, scale, shift, out)
   B, Hs, Ws, C0 = src0.shape
   C1 = 0 if src1 is None else src1.shape[3]
-  up = 2 if upsample else 1
-  Ho, Wo = Hs * up // pool, Ws * up // pool
-  if out is None:
-    out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=src0.device)
+  out = _conv_out(src0, cout, pool, upsample, out)
   fn = rn.lib().ra_conv3x3_bf16ops_f32 if bf16 else rn.lib().ra_conv3x3_f32
   check(fn(ptr(src0), C0, ptr(src1), C1, B, Hs, Ws, int(upsample), ptr(wp), ptr(scale), ptr(shift), int(cout),
            int(relu), int(pool), ptr(plane), int(plane_chan), ptr(out), rn.stream_ptr()),
@@ -228,10 +244,7 @@ def conv2d_fused(src0, wp, scale, shift, cout, ksize, relu=True, pool=1, src1=No
   _need_cuda(src0, src1, wp, scale, shift, out)
   B, Hs, Ws, C0 = src0.shape
   C1 = 0 if src1 is None else src1.shape[3]
-  up = 2 if upsample else 1
-  Ho, Wo = Hs * up // pool, Ws * up // pool
-  if out is None:
-    out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=src0.device)
+  out = _conv_out(src0, cout, pool, upsample, out)
   check(rn.lib().ra_convkxk_f32(ptr(src0), C0, ptr(src1), C1, B, Hs, Ws, int(upsample), ptr(wp), int(ksize), ptr(scale),
                                 ptr(shift), int(cout), int(relu), int(pool), ptr(plane), int(plane_chan), ptr(out),
                                 rn.stream_ptr()), 'ra_convkxk_f32')
@@ -249,20 +262,13 @@ def pack_wide_weights(w, cin_kernel=None, chan_map=None, transposed=False):
   w = _np32(w)
   if w.ndim != 4 or tuple(w.shape[:2]) != (3, 3):
     raise rn.RecAttendError('filter of shape %r: wide layers are built for 3x3 filters only' % (w.shape,))
-  cin_w, cout = (w.shape[3], w.shape[2]) if transposed else (w.shape[2], w.shape[3])
-  cin = cin_w if cin_kernel is None else int(cin_kernel)
-  if chan_map is None and cin != cin_w:
-    chan_map = list(range(cin_w)) + [-1] * (cin - cin_w)
+  cin_w, cout, cin, chan_map, flags = _filter_channels(w, cin_kernel, chan_map, transposed)
   n = rn.lib().ra_conv_wide_packed_floats(cin, cout)
   if n == 0:
     raise rn.RecAttendError('unsupported wide conv shape Cin=%d Cout=%d (Cin %% 4, <= 1024; Cout 129 .. 512, %% 16)' % (cin, cout))
   out = np.empty(n, dtype=np.float32)
-  cm = None
-  if chan_map is not None:
-    cm = np.ascontiguousarray(chan_map, dtype=np.int32)
-    assert cm.shape[0] == cin
-  check(rn.lib().ra_conv_wide_pack_weights(ptr(w), cin_w, cout, cin, ptr(cm), rn.RA_CONV_TRANSPOSED if transposed else 0,
-                                           ptr(out)), 'ra_conv_wide_pack_weights')
+  cm = _chan_map_i32(chan_map, cin)
+  check(rn.lib().ra_conv_wide_pack_weights(ptr(w), cin_w, cout, cin, ptr(cm), flags, ptr(out)), 'ra_conv_wide_pack_weights')
   return out
 
 
@@ -277,12 +283,7 @@ def conv_wide(src0, wp, scale, shift, cout, relu=True, pool=1, src1=None, upsamp
   n = rn.lib().ra_conv_wide_packed_floats(C0 + C1, int(cout))
   if n == 0 or wp.numel() != n or scale.numel() < cout or shift.numel() < cout:
     raise rn.RecAttendError('conv_wide: unsupported shape Cin=%d Cout=%d, or weights not packed for it' % (C0 + C1, cout))
-  up = 2 if upsample else 1
-  Ho, Wo = Hs * up // pool, Ws * up // pool
-  if out is None:
-    out = torch.empty((B, Ho, Wo, cout), dtype=torch.float32, device=src0.device)
-  elif tuple(out.shape) != (B, Ho, Wo, cout):
-    raise rn.RecAttendError('conv_wide: out of shape %r, expected %r' % (tuple(out.shape), (B, Ho, Wo, cout)))
+  out = _conv_out(src0, cout, pool, upsample, out, checked_for='conv_wide')
   check(rn.lib().ra_conv3x3_wide_f32(ptr(src0), C0, ptr(src1), C1, B, Hs, Ws, int(upsample), ptr(wp), ptr(scale), ptr(shift),
                                      int(cout), int(relu), int(pool), ptr(out), rn.stream_ptr()), 'ra_conv3x3_wide_f32')
   return out
@@ -379,8 +380,7 @@ def conv_split(x, wp, scale, shift, cout, relu=True, pool=1, out=None, plane=Non
   plane_chan of x (ra_conv_split_plane_f32)."""
   _need_cuda(x, wp, scale, shift, out, plane)
   B, H, W, cin = x.shape
-  if out is None:
-    out = torch.empty((B, H // pool, W // pool, cout), dtype=torch.float32, device=x.device)
+  out = _conv_out(x, cout, pool, out=out)
   if plane is not None:
     check(rn.lib().ra_conv_split_plane_f32(ptr(x), B, H, W, cin, ptr(plane), int(plane_chan), ptr(wp), ptr(scale), ptr(shift), int(cout),
                                            int(relu), int(pool), ptr(out), rn.stream_ptr()), 'ra_conv_split_plane_f32')
@@ -394,8 +394,7 @@ def conv_wino(x, wp, scale, shift, cout, relu=True, pool=1, out=None):
   """conv3x3 SAME + folded BN + ReLU + pool as Winograd F(2x2,3x3) (ra_conv_wino_f32).  x [B,H,W,Cin]."""
   _need_cuda(x, wp, scale, shift, out)
   B, H, W, cin = x.shape
-  if out is None:
-    out = torch.empty((B, H // pool, W // pool, cout), dtype=torch.float32, device=x.device)
+  out = _conv_out(x, cout, pool, out=out)
   check(rn.lib().ra_conv_wino_f32(ptr(x), B, H, W, cin, ptr(wp), ptr(scale), ptr(shift), int(cout), int(relu), int(pool),
                                   ptr(out), rn.stream_ptr()), 'ra_conv_wino_f32')
   return out
@@ -409,8 +408,7 @@ def conv_pair_wino(x, wpA, scA, shA, wpB_wino, scB, shB, reluA=True, reluB=True,
   """The fused pair 8 -> 16 -> 16, pool 2, with layer B as Winograd (ra_conv_pair_wino_f32).  x [B,H,W,8]."""
   _need_cuda(x, wpA, scA, shA, wpB_wino, scB, shB, out)
   B, H, W, _ = x.shape
-  if out is None:
-    out = torch.empty((B, H // 2, W // 2, 16), dtype=torch.float32, device=x.device)
+  out = _conv_out(x, 16, 2, out=out)
   check(rn.lib().ra_conv_pair_wino_f32(ptr(x), B, H, W, ptr(wpA), ptr(scA), ptr(shA), int(reluA), ptr(wpB_wino), ptr(scB),
                                        ptr(shB), int(reluB), ptr(out), rn.stream_ptr()), 'ra_conv_pair_wino_f32')
   return out
@@ -436,10 +434,7 @@ def conv_pair(src, wpA, scA, shA, coutA, wpB, scB, shB, coutB, poolB=1, upsample
   """Two fused conv layers (A: no pool / optional stride-2 transposed; B: pool 1|2)."""
   _need_cuda(src, wpA, scA, shA, wpB, scB, shB, out)
   B, Hs, Ws, C0 = src.shape
-  up = 2 if upsampleA else 1
-  Ho, Wo = Hs * up // poolB, Ws * up // poolB
-  if out is None:
-    out = torch.empty((B, Ho, Wo, coutB), dtype=torch.float32, device=src.device)
+  out = _conv_out(src, coutB, poolB, upsampleA, out)
   check(rn.lib().ra_conv_pair_f32(ptr(src), C0, B, Hs, Ws, int(upsampleA), ptr(wpA), ptr(scA),
                                   ptr(shA), int(coutA), int(reluA), ptr(wpB), ptr(scB), ptr(shB),
                                   int(coutB), int(reluB), int(poolB), ptr(plane), int(plane_chan),
@@ -527,7 +522,7 @@ def extract_conv0(img, chan0, attn, Fh, Fw, use_gamma, patch, w0, scale, shift, 
                                       rn.stream_ptr()), 'ra_extract_conv0_f32')
 
 
-PASTE_Y_PREFILLED, PASTE_CANVAS_FLOORED = 1, 2
+PASTE_Y_PREFILLED, PASTE_CANVAS_FLOORED = rn.RA_PASTE_Y_PREFILLED, rn.RA_PASTE_CANVAS_FLOORED
 
 
 def paste_direct(patch, pc, attn, beta, disable_overwrite, y_out, y_stride_b, H, W, canvas=None,
@@ -555,7 +550,7 @@ def paste_score_direct(patch, pc, attn, beta, disable_overwrite, y_out, y_stride
         'ra_paste_score_direct_f32')
 
 
-RESAMPLE_READ, RESAMPLE_WRITE, RESAMPLE_BOX = 0, 1, 2
+RESAMPLE_READ, RESAMPLE_WRITE, RESAMPLE_BOX = rn.RA_RESAMPLE_READ, rn.RA_RESAMPLE_WRITE, rn.RA_RESAMPLE_BOX
 
 
 def resample_bwd(mode, rec, H, W, Fh, Fw, X=None, chan0=0, C=None, dY=None, Y=None, Q=None, E=None, scale=None, div=None):

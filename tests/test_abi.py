@@ -1,8 +1,11 @@
 """The C-ABI library loads (no GPU needed) and exports every symbol include/recattend.h
-declares; the ctypes table (ra_native.SIGNATURES) covers exactly that set."""
+declares; the ctypes table (ra_native.SIGNATURES), which ra_native derives from that header, covers
+exactly that set, and a handful of its rows are pinned here literally."""
 import ctypes
 import os
 import re
+
+import pytest
 
 import ra_native as rn
 
@@ -32,6 +35,67 @@ def test_binding_table_matches_header():
   assert sorted(rn.SIGNATURES) == _header_symbols()
   rn.lib()  # resolves them all
   assert rn.lib().ra_version() == rn.RA_ABI_VERSION == _header_abi_version()
+
+
+_P, _I, _F, _Z, _D = ctypes.c_void_p, ctypes.c_int, ctypes.c_float, ctypes.c_size_t, ctypes.c_double
+_DESC = ctypes.POINTER(rn.CtrlDesc)
+# written out by hand from the header: between them every C type the reader maps (int, float, double, size_t, the data
+# pointers incl. `const float *const *` and `unsigned short *`, const ra_ctrl_desc *, the char * return, a void argument list)
+PINNED = {
+    'ra_version': (_I, []),
+    'ra_last_error_string': (ctypes.c_char_p, []),
+    'ra_fill_f32': (_I, [_P, _Z, _F, _P]),
+    'ra_hungarian_dev_workspace_bytes': (_Z, [_I, _I, _I]),
+    'ra_bn_act_pool_bwd_dx_f32': (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _D, _F, _I, _I, _I, _I, _I, _I, _P, _P]),
+    'ra_bn_act_pool_bf16_f32': (_I, [_P, _P, _P, _P, _P, _F, _I, _I, _I, _I, _I, _I, _P, _I, _P]),
+    'ra_ctrl_split_workspace_bytes': (_Z, [_DESC, _I]),
+    'ra_ctrl_pack_weights': (_I, [_DESC, _P, _P, _P, _P]),
+    'ra_controller_f32': (_I, [_DESC, _P, _P, _I, _P, _P, _P, _P, _P]),
+    'ra_conv3x3_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
+}
+
+
+def test_pinned_signatures():
+  for name, sig in PINNED.items():
+    assert rn.SIGNATURES[name] == sig, name
+  fn = rn.lib().ra_bn_act_pool_bwd_dx_f32
+  assert fn.restype is _I and list(fn.argtypes) == PINNED['ra_bn_act_pool_bwd_dx_f32'][1]
+
+
+def test_header_constants_and_descriptor():
+  assert (rn.RA_E_INVALID, rn.RA_E_SHAPE, rn.RA_E_WORKSPACE) == (-1, -2, -3)
+  assert rn.RA_CONV_TRANSPOSED == 1 and rn.RA_ATTN_STRIDE == 16
+  assert [n for n, _ in rn.CtrlDesc._fields_] == ['G', 'Cf', 'hid', 'iters', 'n_gmlp', 'n_cmlp', 'mlp_dim', 'H', 'W', 'Fh', 'Fw',
+                                                  'squash', 'fixed_var', 'dynamic_var', 'fixed_gamma']
+  assert all(t is ctypes.c_int for _, t in rn.CtrlDesc._fields_) and ctypes.sizeof(rn.CtrlDesc) == 15 * 4
+
+
+_SYNTHETIC = """
+#define RA_SEVEN 7
+#define RA_MINUS (-3) /* in parentheses */
+typedef struct ra_ctrl_desc { int G; int H, W; } ra_ctrl_desc;
+/* a comment with a call in it: ra_ghost(int x); */
+size_t ra_good(const ra_ctrl_desc *d, const float *const *w /*[n]*/, unsigned short *h, double x, float y);
+%s
+"""
+
+
+def test_reader_is_strict():
+  sigs, consts, fields = rn.read_header(_SYNTHETIC % 'int ra_none(void);')
+  assert sigs == {'ra_good': (_Z, [_DESC, _P, _P, _D, _F]), 'ra_none': (_I, [])}
+  assert consts == {'RA_SEVEN': 7, 'RA_MINUS': -3} and fields == ['G', 'H', 'W']
+  for bad, named in (('int ra_bad_arg(long n);', 'ra_bad_arg'),            # a type without a mapping
+                     ('long ra_bad_ret(int n);', 'ra_bad_ret'),
+                     ('int ra_bad_ptr(ra_other *p);', 'ra_bad_ptr'),
+                     ('int ra_callback(int (*fn)(int), int n);', 'ra_callback'),  # prototypes it cannot split
+                     ('int ra_unnamed(int, float *);', 'ra_unnamed'),
+                     ('int ra_array(int v[4]);', 'ra_array'),
+                     ('int ra_no_parens;', 'ra_no_parens')):
+    with pytest.raises(rn.RecAttendError) as e:
+      rn.read_header(_SYNTHETIC % bad)
+    assert named in str(e.value), bad
+  with pytest.raises(rn.RecAttendError):
+    rn.read_header('int ra_x(void);')  # no struct ra_ctrl_desc
 
 
 def test_argument_validation_without_gpu():
