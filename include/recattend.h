@@ -54,6 +54,84 @@ int ra_debug_poison_lds(void *stream);
  * when part of an XCD is taken: tests/test_full_model_gpu.py. */
 int ra_debug_park_xcd(int xcd, int n_wg, int lds_bytes, int millis, int *resident, void *stream);
 
+/* Test aid (no reference counterpart): the launch PLAN of a conv entry point.  The conv kernels pick their template instantiation
+ * on the host from the problem size; a plan query walks the very chain of choices the launch walks (one code path: the launch
+ * is that chain with plan == NULL) and, where the launch would be issued, fills plan[RA_PLAN_INTS] instead.  Nothing is
+ * launched and no device memory is touched.  The RA_* tuning variables count as they do for a launch.  Fields:
+ *   FAMILY   RA_PLAN_FAMILY_*: K1 = the conv3x3_mfma template (ra_conv3x3_f32 and its bf16 / moments / k x k parts), CONV8 = the
+ *            entry diverts to the 8- / 16-channel full-resolution kernels (then only FORM and NC = those channels are filled)
+ *   FORM     bits RA_PLAN_FORM_*: SWAP = channel-vector stores (else one value per lane), SUBPIXEL = the sub-pixel form of the
+ *            stride-2 transposed conv (else zero-stuffed), BF16 = bf16 operands, MOMENTS = batch moments in the epilogue, KXK =
+ *            a filter size other than 3
+ *   CK, NC, WN, GX, GY, KF   the template arguments: input channels per staged chunk, cout groups per wave, waves along cout,
+ *            pixel groups per wave in x / y, filter size
+ *   TILE_H, TILE_W, TILES_X, TILES_Y, NTILES   a workgroup's tile, tiles per image row / column, tiles of the launch
+ *   GRID, TILES_MIN, TILES_MAX   workgroups, and the fewest / most tiles one of them walks.  These need the device's CU count
+ *            and the kernel's occupancy: -1 where no device can be asked (every other field is a pure function of the shape).
+ *   XCD_MAP, TICKETS   1 = XCD-contiguous tile walk / tiles drawn as tickets (always 0 for K1)
+ * ra_conv3x3_plan: the shape arguments of ra_conv3x3_f32 (KF = 3, all flags 0), ra_convkxk_f32 (KF), ra_conv3x3_bf16ops_f32
+ * (bf16_operands), ra_conv3x3_moments_f32 (moments, with or without bf16_operands) and ra_conv3x3_bf16_f32 (bf16_operands,
+ * store_flags, moments = part != NULL); has_plane: a canvas plane is given.  Returns what the launch's argument checks return. */
+#define RA_PLAN_INTS 24
+#define RA_PLAN_FAMILY 0
+#define RA_PLAN_FORM 1
+#define RA_PLAN_CK 2
+#define RA_PLAN_NC 3
+#define RA_PLAN_WN 4
+#define RA_PLAN_GX 5
+#define RA_PLAN_GY 6
+#define RA_PLAN_KF 7
+#define RA_PLAN_TILE_H 8
+#define RA_PLAN_TILE_W 9
+#define RA_PLAN_TILES_X 10
+#define RA_PLAN_TILES_Y 11
+#define RA_PLAN_NTILES 12
+#define RA_PLAN_GRID 13
+#define RA_PLAN_TILES_MIN 14
+#define RA_PLAN_TILES_MAX 15
+#define RA_PLAN_XCD_MAP 16
+#define RA_PLAN_TICKETS 17
+#define RA_PLAN_CMID 18
+#define RA_PLAN_SLICES 19
+#define RA_PLAN_POOL 20
+#define RA_PLAN_FAMILY_K1 1
+#define RA_PLAN_FAMILY_CONV8 2
+#define RA_PLAN_FAMILY_PAIR 3
+#define RA_PLAN_FAMILY_SPLIT 4
+#define RA_PLAN_FAMILY_WINO 5
+#define RA_PLAN_FAMILY_PAIR_WINO 6
+#define RA_PLAN_FORM_SWAP 1
+#define RA_PLAN_FORM_SUBPIXEL 2
+#define RA_PLAN_FORM_BF16 4
+#define RA_PLAN_FORM_MOMENTS 8
+#define RA_PLAN_FORM_KXK 16
+#define RA_PLAN_FORM_PERSIST 32
+#define RA_PLAN_FORM_NPACKED 64
+#define RA_PLAN_FORM_CACHED 128
+#define RA_PLAN_FORM_SPLIT 256
+#define RA_PLAN_FORM_PLANE 512
+int ra_conv3x3_plan(int C0, int C1, int B, int Hs, int Ws, int upsample, int KF, int Cout, int pool, int has_plane,
+                    int bf16_operands, int moments, int store_flags, int *plan);
+/* The fused pair (FAMILY = PAIR): cache_form 0 = ra_conv_pair_f32 with these shape arguments, 1 = ra_conv_pair_fill_cache_f32,
+ * 2 = ra_conv_pair_cached_f32 (both: B, Hs, Ws and CoutB count; the rest is fixed by the form).  CK = layer A's input channels,
+ * CMID = layer A's output channels, NC = layer B's cout groups, GX / GY = layer B's pixel groups per wave (0 for the N-packed
+ * kernel, which has one geometry).  FORM bits: PERSIST = conv_pair_persist_mfma (a grid of resident workgroups walking
+ * tiles), NPACKED = the N-packed kernel conv_pair8_mfma, with CACHED = it reads layer A's cached partial sums and SPLIT = its
+ * layer B runs the split-precision bf16 form.  TICKETS = 1: tiles are drawn as tickets where a ticket scratch is bound.  The
+ * geometry and the whole N-packed plan need no device; whether the persistent kernel runs does (GRID, TILES_MIN, TILES_MAX
+ * = -1 and no PERSIST bit where no device can be asked and the shape admits that kernel). */
+int ra_conv_pair_plan(int Cin, int B, int Hs, int Ws, int upsampleA, int CoutA, int CoutB, int poolB, int has_plane,
+                      int cache_form, int *plan);
+/* K1s (FAMILY = SPLIT: ra_conv_split_f32, has_plane: ra_conv_split_plane_f32, FORM bit PLANE), Winograd (FAMILY = WINO:
+ * ra_conv_wino_f32) and the Winograd pair (FAMILY = PAIR_WINO: ra_conv_pair_wino_f32; FORM bit SPLIT = layer A in the
+ * split-precision bf16 form).  CK = input channels, NC = 16-channel blocks per workgroup, POOL, TILE_H (Winograd: TSY 8 or 16),
+ * SLICES = grid.y, the channel slices; GRID = grid.x, the persistent workgroups that share the NTILES tiles of one slice.
+ * XCD_MAP and TILES_MIN / TILES_MAX describe the static walk; TICKETS = 1: with a ticket scratch bound the tiles are drawn
+ * instead.  Every one of these grids follows the device's CU count (Winograd's tile height too): RA_E_INVALID without a device. */
+int ra_conv_split_plan(int B, int H, int W, int Cin, int Cout, int pool, int has_plane, int *plan);
+int ra_conv_wino_plan(int B, int H, int W, int Cin, int Cout, int pool, int *plan);
+int ra_conv_pair_wino_plan(int B, int H, int W, int *plan);
+
 /* ------------------------------------------------------------------------------------
  * Hungarian matching — replaces the TF custom op
  *   REGISTER_OP("Hungarian").Input("weights: float").Output("matching: float")

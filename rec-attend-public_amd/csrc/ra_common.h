@@ -149,4 +149,27 @@ struct TicketWalk {
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 
+// Plan queries (recattend.h, RA_PLAN_*): the fewest / most tiles a workgroup of a persistent grid walks.  Interleaved, workgroup
+// g takes tiles g, g + grid, ...; XCD-contiguous (xcd_map, grid % 8 == 0), XCD x = g % 8 walks the tiles [x * chunk, (x + 1) *
+// chunk), chunk = ceil(ntiles / 8), with its grid / 8 workgroups.
+inline void plan_walk(int *plan, int ntiles, int grid, int xcd_map) {
+  int lo = ntiles / grid, hi = ceil_div(ntiles, grid);
+  if (xcd_map) {
+    const int chunk = (ntiles + 7) >> 3, nwx = grid >> 3;
+    lo = hi = 0;
+    for (int x = 0; x < 8; ++x) {
+      const int n = x * chunk >= ntiles ? 0 : (x * chunk + chunk < ntiles ? chunk : ntiles - x * chunk);
+      lo = (x == 0 || n / nwx < lo) ? n / nwx : lo;
+      hi = ceil_div(n, nwx) > hi ? ceil_div(n, nwx) : hi;
+    }
+  }
+  plan[RA_PLAN_GRID] = grid, plan[RA_PLAN_NTILES] = ntiles, plan[RA_PLAN_XCD_MAP] = xcd_map;
+  plan[RA_PLAN_TILES_MIN] = lo, plan[RA_PLAN_TILES_MAX] = hi;
+}
+// 1 when a HIP device can be asked for its facts
+inline bool plan_have_device() {
+  int n = 0;
+  return hipGetDeviceCount(&n) == hipSuccess && n > 0;
+}
+
 }  // namespace ra

@@ -618,10 +618,22 @@ __global__ __launch_bounds__(256, (GX * GY * NC > 8) ? 1 : 2) void conv3x3_mfma(
 }
 
 template <int CK, int NC, int WN, int GX, int GY, bool SWAP, bool BF16 = false, bool MOM = false, bool UPS = false, int KF = 3>
-int launch_s(const Args &a, int B, hipStream_t st) {
+int launch_s(const Args &a, int B, hipStream_t st, int *plan) {
   using G = Geo<CK, NC, WN, GX, GY, KF>;
   auto kern = conv3x3_mfma<CK, NC, WN, GX, GY, SWAP, BF16, MOM, UPS, KF>;
   constexpr size_t lds = 2 * G::LDS_FLOATS * sizeof(float);
+  const int tiles_x = ceil_div(a.W, G::TW), tiles_y = ceil_div(a.H, G::TH);
+  const int ntiles = tiles_x * tiles_y * B;
+  if (plan) {  // ra_conv3x3_plan: the instantiation this chain of choices ended at; the grid where a device can be asked
+    plan[RA_PLAN_FAMILY] = RA_PLAN_FAMILY_K1;
+    plan[RA_PLAN_FORM] = (SWAP ? RA_PLAN_FORM_SWAP : 0) | (UPS ? RA_PLAN_FORM_SUBPIXEL : 0) | (BF16 ? RA_PLAN_FORM_BF16 : 0) |
+                         (MOM ? RA_PLAN_FORM_MOMENTS : 0) | (KF != 3 ? RA_PLAN_FORM_KXK : 0);
+    plan[RA_PLAN_CK] = CK, plan[RA_PLAN_NC] = NC, plan[RA_PLAN_WN] = WN, plan[RA_PLAN_GX] = GX, plan[RA_PLAN_GY] = GY;
+    plan[RA_PLAN_KF] = KF, plan[RA_PLAN_TILE_H] = G::TH, plan[RA_PLAN_TILE_W] = G::TW;
+    plan[RA_PLAN_TILES_X] = tiles_x, plan[RA_PLAN_TILES_Y] = tiles_y, plan[RA_PLAN_NTILES] = ntiles;
+    plan[RA_PLAN_GRID] = plan[RA_PLAN_TILES_MIN] = plan[RA_PLAN_TILES_MAX] = -1;
+    if (!plan_have_device()) return 0;
+  }
   static int wgs_per_cu = 0;  // idempotent lazy init
   if (!wgs_per_cu) {
     MaxDynamicLds{kern, lds};
@@ -629,10 +641,12 @@ int launch_s(const Args &a, int B, hipStream_t st) {
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256, lds) != hipSuccess || n < 1) n = 1;
     wgs_per_cu = n > 4 ? 4 : n;
   }
-  const int tiles_x = ceil_div(a.W, G::TW), tiles_y = ceil_div(a.H, G::TH);
-  const int ntiles = tiles_x * tiles_y * B;
   const int cap = wgs_per_cu * num_cus();
   const int grid = ntiles < cap ? ntiles : cap;
+  if (plan) {  // workgroup g walks tiles g, g + grid, ...
+    plan_walk(plan, ntiles, grid, 0);
+    return 0;
+  }
   if (a.nparts_out) *a.nparts_out = grid * G::WM;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a, tiles_x, tiles_y, ntiles);
   return launch_status(KF == 3 ? "ra_conv3x3_f32" : "ra_convkxk_f32");
@@ -651,34 +665,34 @@ inline bool ups_subpixel() {  // RA_CONV_UPS_SUBPIXEL=0: the zero-stuffed form o
   return on;
 }
 template <int CK, int NC, int WN, int GX, int GY>
-int launch(const Args &a, int B, hipStream_t st) {
+int launch(const Args &a, int B, hipStream_t st, int *plan) {
   // channel-vector stores pay off when there is no pooling and the channel count allows float4
   const bool swap = a.pool == 1 && (a.Cout & 3) == 0;
   if (a.mom_part && !swap)
     return ra::fail(RA_E_SHAPE, "ra_conv3x3_moments_f32: needs pool 1 and Cout %% 4 == 0 (Cout %d, pool %d)", a.Cout, a.pool);
 #if RA_K1_PART == 1  // bf16 operands
   if (swap) {
-    if (a.mom_part) return launch_s<CK, NC, WN, GX, GY, true, true, true>(a, B, st);
-    return launch_s<CK, NC, WN, GX, GY, true, true>(a, B, st);
+    if (a.mom_part) return launch_s<CK, NC, WN, GX, GY, true, true, true>(a, B, st, plan);
+    return launch_s<CK, NC, WN, GX, GY, true, true>(a, B, st, plan);
   }
-  return launch_s<CK, NC, WN, GX, GY, false, true>(a, B, st);
+  return launch_s<CK, NC, WN, GX, GY, false, true>(a, B, st, plan);
 #elif RA_K1_PART == 2  // float32 + batch moments
-  return launch_s<CK, NC, WN, GX, GY, true, false, true>(a, B, st);
+  return launch_s<CK, NC, WN, GX, GY, true, false, true>(a, B, st, plan);
 #else
   if (swap) {
     if constexpr (GX == 2 && GY == 2) {
-      if (a.ups && ups_subpixel()) return launch_s<CK, NC, WN, GX, GY, true, false, false, true>(a, B, st);
+      if (a.ups && ups_subpixel()) return launch_s<CK, NC, WN, GX, GY, true, false, false, true>(a, B, st, plan);
     }
-    return launch_s<CK, NC, WN, GX, GY, true>(a, B, st);
+    return launch_s<CK, NC, WN, GX, GY, true>(a, B, st, plan);
   }
-  return launch_s<CK, NC, WN, GX, GY, false>(a, B, st);
+  return launch_s<CK, NC, WN, GX, GY, false>(a, B, st, plan);
 #endif
 }
 
 // Tile geometry choice: the biggest tile that still yields >= ~2 workgroups per CU, narrow
 // (16-col) tiles when the image width would leave a 32-col tile more than half empty.
 template <int CK, int NC, int WN>
-int dispatch_geo(const Args &a, int B, hipStream_t st) {
+int dispatch_geo(const Args &a, int B, hipStream_t st, int *plan) {
   constexpr int WM = 4 / WN;
   auto wgs = [&](int gx, int gy) {
     return (long)ceil_div(a.W, 8 * gx) * ceil_div(a.H, 2 * gy * WM) * B;
@@ -692,39 +706,39 @@ int dispatch_geo(const Args &a, int B, hipStream_t st) {
   // form on one-group tiles has 4 x the workgroups at the same chain length per wave and wins (RA_CONV_UPS_MIN_WGS, profiles/r06_k1s_sweep.txt)
   static const int ups_min = env_int("RA_CONV_UPS_MIN_WGS", 96);
   if (!force && a.ups && a.pool == 1 && (a.Cout & 3) == 0 && !a.mom_part && ups_subpixel() && wgs(2, 2) >= ups_min)
-    return launch<CK, NC, WN, 2, 2>(a, B, st);
+    return launch<CK, NC, WN, 2, 2>(a, B, st, plan);
 #endif
-  if (force == 42) return launch<CK, NC, WN, 4, 2>(a, B, st);
-  if (force == 41) return launch<CK, NC, WN, 4, 1>(a, B, st);
-  if (force == 22) return launch<CK, NC, WN, 2, 2>(a, B, st);
-  if (force == 21) return launch<CK, NC, WN, 2, 1>(a, B, st);
+  if (force == 42) return launch<CK, NC, WN, 4, 2>(a, B, st, plan);
+  if (force == 41) return launch<CK, NC, WN, 4, 1>(a, B, st, plan);
+  if (force == 22) return launch<CK, NC, WN, 2, 2>(a, B, st, plan);
+  if (force == 21) return launch<CK, NC, WN, 2, 1>(a, B, st, plan);
   if (!narrow) {
-    if (wgs(4, 2) >= want) return launch<CK, NC, WN, 4, 2>(a, B, st);
-    if (wgs(4, 1) >= want) return launch<CK, NC, WN, 4, 1>(a, B, st);
+    if (wgs(4, 2) >= want) return launch<CK, NC, WN, 4, 2>(a, B, st, plan);
+    if (wgs(4, 1) >= want) return launch<CK, NC, WN, 4, 1>(a, B, st, plan);
   }
-  if (wgs(2, 2) >= want) return launch<CK, NC, WN, 2, 2>(a, B, st);
+  if (wgs(2, 2) >= want) return launch<CK, NC, WN, 2, 2>(a, B, st, plan);
 #if RA_K1_PART == 0
   // round 6: ONE pixel group per wave (8-column tiles) where even the smallest two-group geometry leaves most of the chip
   // without a workgroup — the patch-sized layers with many channels (KITTI's attention DCNN: 128 -> 64 at 12 x 12 is 288
   // dependent k-steps per pixel group; two groups per wave and 96 workgroups made it 16.5 us whatever the batch).  RA_CONV_TINY_WGS:
   // the workgroup count of the (2, 1) geometry below which the (1, 1) form is taken (0 = never).
   static const int tiny = env_int("RA_CONV_TINY_WGS", 200);
-  if (force == 11 || (!force && wgs(2, 1) < tiny)) return launch<CK, NC, WN, 1, 1>(a, B, st);
+  if (force == 11 || (!force && wgs(2, 1) < tiny)) return launch<CK, NC, WN, 1, 1>(a, B, st, plan);
 #endif
-  return launch<CK, NC, WN, 2, 1>(a, B, st);
+  return launch<CK, NC, WN, 2, 1>(a, B, st, plan);
 }
 
 // Cout groups per wave (NC) x waves along cout (WN).  Small problems (few tiles) split the cout
 // groups over more waves so that each wave's serial MFMA chain is shorter.
 template <int CK>
-int dispatch_cout(const Args &a, int B, hipStream_t st) {
+int dispatch_cout(const Args &a, int B, hipStream_t st, int *plan) {
   const long tiles_big = (long)ceil_div(a.W, 16) * ceil_div(a.H, 8) * B;  // 8x16 tiles, WN = 1
   const bool small = tiles_big < 256;
   switch (a.CoutP) {
-    case 16: return dispatch_geo<CK, 1, 1>(a, B, st);
-    case 32: return small ? dispatch_geo<CK, 1, 2>(a, B, st) : dispatch_geo<CK, 2, 1>(a, B, st);
-    case 64: return small ? dispatch_geo<CK, 1, 4>(a, B, st) : dispatch_geo<CK, 2, 2>(a, B, st);
-    case 128: return dispatch_geo<CK, 2, 4>(a, B, st);
+    case 16: return dispatch_geo<CK, 1, 1>(a, B, st, plan);
+    case 32: return small ? dispatch_geo<CK, 1, 2>(a, B, st, plan) : dispatch_geo<CK, 2, 1>(a, B, st, plan);
+    case 64: return small ? dispatch_geo<CK, 1, 4>(a, B, st, plan) : dispatch_geo<CK, 2, 2>(a, B, st, plan);
+    case 128: return dispatch_geo<CK, 2, 4>(a, B, st, plan);
     default: return fail(RA_E_SHAPE, "ra_conv3x3_f32: CoutP %d unsupported", a.CoutP);
   }
 }
@@ -738,15 +752,15 @@ int dispatch_cout(const Args &a, int B, hipStream_t st) {
 #define RA_K1_DISPATCH k1_dispatch_moments
 #else
 #define RA_K1_DISPATCH k1_dispatch_plain
-int k1_dispatch_bf16(const Args &a, int B, hipStream_t st);
-int k1_dispatch_moments(const Args &a, int B, hipStream_t st);
-int k1_dispatch_kxk(const Args &a, int KF, int B, hipStream_t st);
+int k1_dispatch_bf16(const Args &a, int B, hipStream_t st, int *plan);
+int k1_dispatch_moments(const Args &a, int B, hipStream_t st, int *plan);
+int k1_dispatch_kxk(const Args &a, int KF, int B, hipStream_t st, int *plan);
 #endif
-int RA_K1_DISPATCH(const Args &a, int B, hipStream_t st) {
+int RA_K1_DISPATCH(const Args &a, int B, hipStream_t st, int *plan) {
   switch (chunk_of(a.C0 + a.C1)) {
-    case 16: return dispatch_cout<16>(a, B, st);
-    case 8: return dispatch_cout<8>(a, B, st);
-    default: return dispatch_cout<4>(a, B, st);
+    case 16: return dispatch_cout<16>(a, B, st, plan);
+    case 8: return dispatch_cout<8>(a, B, st, plan);
+    default: return dispatch_cout<4>(a, B, st, plan);
   }
 }
 
@@ -755,33 +769,33 @@ namespace {
 // The plain form only: pixels as the A operand (every pool / Cout), the zero-stuffed stride-2 transposed conv, and three tile
 // geometries — the 32 x 16 tile where it still yields ~2 workgroups per CU, else 16-col tiles, else one pixel group per wave.
 template <int KF, int CK, int NC, int WN>
-int kxk_geo(const Args &a, int B, hipStream_t st) {
+int kxk_geo(const Args &a, int B, hipStream_t st, int *plan) {
   constexpr int WM = 4 / WN;
   auto wgs = [&](int gx, int gy) { return (long)ceil_div(a.W, 8 * gx) * ceil_div(a.H, 2 * gy * WM) * B; };
   const bool narrow = (a.W % 32 != 0) && (a.W % 32 <= 16);
-  if (!narrow && wgs(4, 2) >= 512) return launch_s<CK, NC, WN, 4, 2, false, false, false, false, KF>(a, B, st);
-  if (wgs(2, 1) >= 200) return launch_s<CK, NC, WN, 2, 1, false, false, false, false, KF>(a, B, st);
-  return launch_s<CK, NC, WN, 1, 1, false, false, false, false, KF>(a, B, st);
+  if (!narrow && wgs(4, 2) >= 512) return launch_s<CK, NC, WN, 4, 2, false, false, false, false, KF>(a, B, st, plan);
+  if (wgs(2, 1) >= 200) return launch_s<CK, NC, WN, 2, 1, false, false, false, false, KF>(a, B, st, plan);
+  return launch_s<CK, NC, WN, 1, 1, false, false, false, false, KF>(a, B, st, plan);
 }
 template <int KF, int CK>
-int kxk_cout(const Args &a, int B, hipStream_t st) {
+int kxk_cout(const Args &a, int B, hipStream_t st, int *plan) {
   const bool small = (long)ceil_div(a.W, 16) * ceil_div(a.H, 8) * B < 256;  // as dispatch_cout
   switch (a.CoutP) {
-    case 16: return kxk_geo<KF, CK, 1, 1>(a, B, st);
-    case 32: return small ? kxk_geo<KF, CK, 1, 2>(a, B, st) : kxk_geo<KF, CK, 2, 1>(a, B, st);
-    case 64: return small ? kxk_geo<KF, CK, 1, 4>(a, B, st) : kxk_geo<KF, CK, 2, 2>(a, B, st);
-    case 128: return kxk_geo<KF, CK, 2, 4>(a, B, st);
+    case 16: return kxk_geo<KF, CK, 1, 1>(a, B, st, plan);
+    case 32: return small ? kxk_geo<KF, CK, 1, 2>(a, B, st, plan) : kxk_geo<KF, CK, 2, 1>(a, B, st, plan);
+    case 64: return small ? kxk_geo<KF, CK, 1, 4>(a, B, st, plan) : kxk_geo<KF, CK, 2, 2>(a, B, st, plan);
+    case 128: return kxk_geo<KF, CK, 2, 4>(a, B, st, plan);
     default: return fail(RA_E_SHAPE, "ra_convkxk_f32: CoutP %d unsupported", a.CoutP);
   }
 }
 }  // namespace
 
-int k1_dispatch_kxk(const Args &a, int KF, int B, hipStream_t st) {
+int k1_dispatch_kxk(const Args &a, int KF, int B, hipStream_t st, int *plan) {
   const int ck = chunk_of_k(KF, a.C0 + a.C1);
   switch (KF) {
-    case 1: return ck == 16 ? kxk_cout<1, 16>(a, B, st) : ck == 8 ? kxk_cout<1, 8>(a, B, st) : kxk_cout<1, 4>(a, B, st);
-    case 5: return ck == 8 ? kxk_cout<5, 8>(a, B, st) : kxk_cout<5, 4>(a, B, st);
-    case 7: return kxk_cout<7, 4>(a, B, st);
+    case 1: return ck == 16 ? kxk_cout<1, 16>(a, B, st, plan) : ck == 8 ? kxk_cout<1, 8>(a, B, st, plan) : kxk_cout<1, 4>(a, B, st, plan);
+    case 5: return ck == 8 ? kxk_cout<5, 8>(a, B, st, plan) : kxk_cout<5, 4>(a, B, st, plan);
+    case 7: return kxk_cout<7, 4>(a, B, st, plan);
     default: return fail(RA_E_SHAPE, "ra_convkxk_f32: filter size %d not built (1, 3, 5, 7)", KF);
   }
 }
@@ -884,11 +898,21 @@ int run(const void *x, int Cin, int in_bf16, int B, int H, int W, const float *w
 }  // namespace conv8
 }  // namespace ra
 
+// the entry diverts to the 8- / 16-channel full-resolution kernels (ra_conv8.hip): not a K1 form, reported as its own family
+static int plan_conv8(int *plan, int form, int channels) {
+  plan[RA_PLAN_FAMILY] = RA_PLAN_FAMILY_CONV8;
+  plan[RA_PLAN_FORM] = form;
+  plan[RA_PLAN_NC] = channels;
+  return 0;
+}
+
 static int conv3x3_entry(const float *src0, int C0, const float *src1, int C1, int B, int Hs, int Ws, int upsample,
                          const float *wpacked, const float *scale, const float *shift, int Cout, int relu, int pool,
                          const float *plane, int plane_chan, float *y, void *stream, int bf16, float *mom_part = nullptr,
-                         int *nparts = nullptr, int store_flags = 0, int KF = 3) {
-  if (!src0 || !wpacked || !scale || !shift || !y || B <= 0 || Hs <= 0 || Ws <= 0 || C0 <= 0 ||
+                         int *nparts = nullptr, int store_flags = 0, int KF = 3, int *plan = nullptr) {
+  // plan != nullptr (ra_conv3x3_plan): the same checks and the same chain of choices, ending in a record instead of a launch;
+  // src1 / plane / mom_part are then mere non-null marks and no pointer is followed
+  if ((!plan && (!src0 || !wpacked || !scale || !shift || !y)) || B <= 0 || Hs <= 0 || Ws <= 0 || C0 <= 0 ||
       C1 < 0 || (C1 > 0 && !src1))
     return ra::fail(RA_E_INVALID, "ra_conv3x3_f32: bad argument");
   if (!kf_built(KF)) return ra::fail(RA_E_SHAPE, "ra_convkxk_f32: filter size %d not built (1, 3, 5, 7)", KF);
@@ -950,20 +974,20 @@ static int conv3x3_entry(const float *src0, int C0, const float *src1, int C1, i
     // transposed conv reads z[o + j - (KF - 1 - pad_lo)], pad_lo = max(KF - 2, 0) / 2, of z[2i] = x[i] — on the staged
     // U[2i + 1] = x[i] (U[m] = z[m - 1]) that is origin KF - 2 - pad_lo: -1, 2, 3 for KF = 1, 5, 7
     a.org = a.ups ? KF - 2 - (KF > 2 ? KF - 2 : 0) / 2 : KF / 2;
-    return ra::conv::k1_dispatch_kxk(a, KF, B, st);
+    return ra::conv::k1_dispatch_kxk(a, KF, B, st, plan);
   }
   // bf16 mode, eight output channels at full resolution: the bf16-LDS kernel (ra_conv8.hip)
   if (a.bf16 && !C1 && !a.ups && pool == 1 && !plane && ra::conv8::takes(C0, Cout, a.in_bf16, B, a.H, a.W))
-    return ra::conv8::run(src0, C0, a.in_bf16, B, a.H, a.W, wpacked, scale, shift, relu, y, a.out_bf16, mom_part, nparts,
+    return plan ? plan_conv8(plan, RA_PLAN_FORM_BF16 | (mom_part ? RA_PLAN_FORM_MOMENTS : 0), Cout) : ra::conv8::run(src0, C0, a.in_bf16, B, a.H, a.W, wpacked, scale, shift, relu, y, a.out_bf16, mom_part, nparts,
                           ra::conv::num_cus(), st, Cout);
-  if (a.bf16) return ra::conv::k1_dispatch_bf16(a, B, st);
+  if (a.bf16) return ra::conv::k1_dispatch_bf16(a, B, st, plan);
   // float32, eight output channels at full resolution (training: forward with moments, data gradients): the 16-block MFMA form
   if (!C1 && !a.ups && pool == 1 && !plane && ra::conv8::takes_f32(C0, Cout, B, a.H, a.W))
-    return ra::conv8::run(src0, C0, -1, B, a.H, a.W, wpacked, scale, shift, relu, y, 0, mom_part, nparts, ra::conv::num_cus(), st, 8);
+    return plan ? plan_conv8(plan, mom_part ? RA_PLAN_FORM_MOMENTS : 0, 8) : ra::conv8::run(src0, C0, -1, B, a.H, a.W, wpacked, scale, shift, relu, y, 0, mom_part, nparts, ra::conv::num_cus(), st, 8);
   if (!C1 && !a.ups && pool == 1 && !plane && ra::conv8::takes16_f32(C0, Cout, B, a.H, a.W))  // 16 channels at half resolution
-    return ra::conv8::run16_f32(src0, C0, B, a.H, a.W, wpacked, scale, shift, relu, y, mom_part, nparts, ra::conv::num_cus(), st);
-  if (a.mom_part) return ra::conv::k1_dispatch_moments(a, B, st);
-  return ra::conv::k1_dispatch_plain(a, B, st);
+    return plan ? plan_conv8(plan, mom_part ? RA_PLAN_FORM_MOMENTS : 0, 16) : ra::conv8::run16_f32(src0, C0, B, a.H, a.W, wpacked, scale, shift, relu, y, mom_part, nparts, ra::conv::num_cus(), st);
+  if (a.mom_part) return ra::conv::k1_dispatch_moments(a, B, st, plan);
+  return ra::conv::k1_dispatch_plain(a, B, st, plan);
 }
 
 extern "C" int ra_conv3x3_f32(const float *src0, int C0, const float *src1, int C1, int B, int Hs,
@@ -1019,5 +1043,15 @@ extern "C" int ra_conv3x3_bf16_f32(const void *src0, int C0, const void *src1, i
   return conv3x3_entry(static_cast<const float *>(src0), C0, static_cast<const float *>(src1), C1, B, Hs, Ws, upsample, wpacked, scale,
                        shift, Cout, relu, part ? 1 : pool, nullptr, -1, static_cast<float *>(y), stream, 1, part, part ? nparts : nullptr,
                        store_flags);
+}
+
+extern "C" int ra_conv3x3_plan(int C0, int C1, int B, int Hs, int Ws, int upsample, int KF, int Cout, int pool, int has_plane,
+                               int bf16_operands, int moments, int store_flags, int *plan) {
+  if (!plan) return ra::fail(RA_E_INVALID, "ra_conv3x3_plan: bad argument");
+  for (int i = 0; i < RA_PLAN_INTS; ++i) plan[i] = 0;
+  static float mark;  // never read or written: a non-null stand-in for the optional pointers
+  return conv3x3_entry(nullptr, C0, C1 > 0 ? &mark : nullptr, C1, B, Hs, Ws, upsample, nullptr, nullptr, nullptr, Cout, 0,
+                       moments ? 1 : pool, has_plane ? &mark : nullptr, has_plane ? 0 : -1, nullptr, nullptr, bf16_operands ? 1 : 0,
+                       moments ? &mark : nullptr, nullptr, store_flags, KF, plan);
 }
 #endif  // RA_K1_PART == 0

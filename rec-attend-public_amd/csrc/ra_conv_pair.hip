@@ -1104,13 +1104,12 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 
 }
 
 template <int CINA, bool CACHED = false, bool SPLIT = false>
-int launch8(const PArgs &a_in, int B, hipStream_t st) {
+int launch8(const PArgs &a_in, int B, hipStream_t st, int *plan) {
   using G = NGeo<CINA>;
   PArgs a = a_in;
   a.bytes_y = (int)((size_t)B * a.Ho * a.Wo * a.CoutB * sizeof(float));
   auto kern = conv_pair8_mfma<CINA, CACHED, SPLIT>;
   constexpr size_t lds = (size_t)(((G::LH * G::LW * (CACHED ? 1 : CINA) + 3) & ~3) + (SPLIT ? 3 * G::AHS * G::AW * 4 : G::MID_FLOATS)) * sizeof(float);
-  static const MaxDynamicLds lds_limit(kern, lds);
   const int tiles_x = ceil_div(a.W, G::TW), tiles_y = ceil_div(a.H, G::TH);
   const int ntiles = tiles_x * tiles_y * B;
   // RA_PAIR8_WGS: tuning aid, persistent workgroups (default 3 per CU).  The cached form (122 VGPRs) could run 4 workgroups
@@ -1121,7 +1120,17 @@ int launch8(const PArgs &a_in, int B, hipStream_t st) {
   PArgs a2 = a;
   const int grid = ntiles < wgs ? ntiles : wgs;
   a2.xcd_map = (xcd && grid % 8 == 0 && grid >= 8) ? 1 : 0;
-  a2.tickets = (CACHED && ntiles >= kTicketMinTilesPerWg * grid) ? take_ticket_slots(1, grid) : nullptr;  // the steady-state form; bound scratch only
+  const bool draws = CACHED && ntiles >= kTicketMinTilesPerWg * grid;  // the steady-state form; bound scratch only
+  if (plan) {  // ra_conv_pair_plan: no device fact in this form's choices
+    plan[RA_PLAN_FAMILY] = RA_PLAN_FAMILY_PAIR;
+    plan[RA_PLAN_FORM] = RA_PLAN_FORM_NPACKED | (CACHED ? RA_PLAN_FORM_CACHED : 0) | (SPLIT ? RA_PLAN_FORM_SPLIT : 0);
+    plan[RA_PLAN_CK] = CINA, plan[RA_PLAN_CMID] = 8, plan[RA_PLAN_KF] = 3, plan[RA_PLAN_TILE_H] = G::TH, plan[RA_PLAN_TILE_W] = G::TW;
+    plan[RA_PLAN_TILES_X] = tiles_x, plan[RA_PLAN_TILES_Y] = tiles_y, plan[RA_PLAN_TICKETS] = draws ? 1 : 0;
+    plan_walk(plan, ntiles, grid, a2.xcd_map);
+    return 0;
+  }
+  static const MaxDynamicLds lds_limit(kern, lds);
+  a2.tickets = draws ? take_ticket_slots(1, grid) : nullptr;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a2, tiles_x, tiles_y, ntiles);
   return launch_status("ra_conv_pair_f32");
 }
@@ -1185,14 +1194,27 @@ inline void cache_dims(int H, int W, int &rows, int &ngx) {
 }
 
 template <int CINA, int CMID, int NCB, int GX, int GYB>
-int launch(const PArgs &a, int B, hipStream_t st) {
+int launch(const PArgs &a, int B, hipStream_t st, int *plan) {
   using G = PGeo<CINA, CMID, NCB, GX, GYB>;
   auto kern = conv_pair_mfma<CINA, CMID, NCB, GX, GYB>;
   constexpr size_t lds = (size_t)(G::IN_FLOATS + G::MID_FLOATS) * sizeof(float);
   static_assert(lds <= 160 * 1024, "pair tile does not fit LDS");
-  static const MaxDynamicLds lds_limit(kern, lds);
   const int tiles_x = ceil_div(a.W, G::TWB), tiles_y = ceil_div(a.H, G::THB);
   const int ntiles = tiles_x * tiles_y * B;
+  if (plan) {  // ra_conv_pair_plan: the geometry is a function of the shape; whether the persistent kernel runs needs the device
+    plan[RA_PLAN_FAMILY] = RA_PLAN_FAMILY_PAIR;
+    plan[RA_PLAN_CK] = CINA, plan[RA_PLAN_CMID] = CMID, plan[RA_PLAN_NC] = NCB, plan[RA_PLAN_GX] = GX, plan[RA_PLAN_GY] = GYB;
+    plan[RA_PLAN_KF] = 3, plan[RA_PLAN_TILE_H] = G::THB, plan[RA_PLAN_TILE_W] = G::TWB;
+    plan[RA_PLAN_TILES_X] = tiles_x, plan[RA_PLAN_TILES_Y] = tiles_y, plan[RA_PLAN_NTILES] = ntiles;
+    plan[RA_PLAN_GRID] = ntiles, plan[RA_PLAN_TILES_MIN] = plan[RA_PLAN_TILES_MAX] = 1;
+    if (!(G::NCHA == 1 && G::NCHB == 1) || a.ups || a.plane) return 0;  // never the persistent kernel
+    if (!plan_have_device()) {
+      plan[RA_PLAN_GRID] = plan[RA_PLAN_TILES_MIN] = plan[RA_PLAN_TILES_MAX] = -1;
+      return 0;
+    }
+  } else {
+    static const MaxDynamicLds lds_limit(kern, lds);
+  }
   if constexpr (G::NCHA == 1 && G::NCHB == 1) {
     // plain single-chunk pairs (controller CNN L2+L3 at full size): persistent workgroups, weights
     // loaded once, the next tile's input prefetched into registers behind the MFMA phases
@@ -1209,17 +1231,23 @@ int launch(const PArgs &a, int B, hipStream_t st) {
       cap = nb * cus;
     }
     if (pers && !a.ups && !a.plane && ntiles > cap && a.bytes0 > 0) {
+      if (plan) {
+        plan[RA_PLAN_FORM] = RA_PLAN_FORM_PERSIST;
+        plan_walk(plan, ntiles, cap, 0);
+        return 0;
+      }
       hipLaunchKernelGGL((conv_pair_persist_mfma<CINA, CMID, NCB, GX, GYB>), dim3(cap), dim3(256), lds, st, a, tiles_x,
                          tiles_y, ntiles);
       return launch_status("ra_conv_pair_f32");
     }
   }
+  if (plan) return 0;
   hipLaunchKernelGGL(kern, dim3(ntiles), dim3(256), lds, st, a, tiles_x, tiles_y);
   return launch_status("ra_conv_pair_f32");
 }
 
 template <int CINA, int CMID, int NCB>
-int dispatch_geo(const PArgs &a, int B, hipStream_t st) {
+int dispatch_geo(const PArgs &a, int B, hipStream_t st, int *plan) {
   using Big = PGeo<CINA, CMID, NCB, 4, 2>;
   constexpr bool big_fits = (size_t)(Big::IN_FLOATS + Big::MID_FLOATS) * 4 <= 80 * 1024;
   const bool narrow = (a.W % 32 != 0) && (a.W % 32 <= 16);
@@ -1229,28 +1257,28 @@ int dispatch_geo(const PArgs &a, int B, hipStream_t st) {
   // (cfg2 L2+L3: 41.8 us at 32x8 against 47.4 at 32x16 and 45.3 one-shot; profiles/r02)
   constexpr bool single_chunk = Big::NCHA == 1 && Big::NCHB == 1;
   if (!force && single_chunk && !a.ups && !a.plane && !narrow && wgs(4, 1) >= 2048)
-    return launch<CINA, CMID, NCB, 4, 1>(a, B, st);
+    return launch<CINA, CMID, NCB, 4, 1>(a, B, st, plan);
   if constexpr (big_fits) {
-    if (force == 42 || (!force && !narrow && wgs(4, 2) >= 512)) return launch<CINA, CMID, NCB, 4, 2>(a, B, st);
+    if (force == 42 || (!force && !narrow && wgs(4, 2) >= 512)) return launch<CINA, CMID, NCB, 4, 2>(a, B, st, plan);
   }
-  if (force == 41 || (!force && !narrow)) return launch<CINA, CMID, NCB, 4, 1>(a, B, st);
-  if (force == 22 || (!force && wgs(2, 2) >= 512)) return launch<CINA, CMID, NCB, 2, 2>(a, B, st);
-  return launch<CINA, CMID, NCB, 2, 1>(a, B, st);
+  if (force == 41 || (!force && !narrow)) return launch<CINA, CMID, NCB, 4, 1>(a, B, st, plan);
+  if (force == 22 || (!force && wgs(2, 2) >= 512)) return launch<CINA, CMID, NCB, 2, 2>(a, B, st, plan);
+  return launch<CINA, CMID, NCB, 2, 1>(a, B, st, plan);
 }
 
 template <int CINA, int CMID>
-int dispatch_b(const PArgs &a, int B, hipStream_t st) {
-  if (a.CoutBP == 16) return dispatch_geo<CINA, CMID, 1>(a, B, st);
-  if (a.CoutBP == 32) return dispatch_geo<CINA, CMID, 2>(a, B, st);
+int dispatch_b(const PArgs &a, int B, hipStream_t st, int *plan) {
+  if (a.CoutBP == 16) return dispatch_geo<CINA, CMID, 1>(a, B, st, plan);
+  if (a.CoutBP == 32) return dispatch_geo<CINA, CMID, 2>(a, B, st, plan);
   return fail(RA_E_SHAPE, "ra_conv_pair_f32: CoutB %d unsupported", a.CoutB);
 }
 
 template <int CINA>
-int dispatch_mid(const PArgs &a, int cmid, int B, hipStream_t st) {
+int dispatch_mid(const PArgs &a, int cmid, int B, hipStream_t st, int *plan) {
   switch (cmid) {
-    case 8: return dispatch_b<CINA, 8>(a, B, st);
-    case 16: return dispatch_b<CINA, 16>(a, B, st);
-    case 32: return dispatch_b<CINA, 32>(a, B, st);
+    case 8: return dispatch_b<CINA, 8>(a, B, st, plan);
+    case 16: return dispatch_b<CINA, 16>(a, B, st, plan);
+    case 32: return dispatch_b<CINA, 32>(a, B, st, plan);
     default: return fail(RA_E_SHAPE, "ra_conv_pair_f32: CoutA %d unsupported", cmid);
   }
 }
@@ -1312,12 +1340,12 @@ int pair_args_cache(cpair::PArgs &a, const float *cache, int B, const char *what
 }
 }  // namespace
 
-extern "C" int ra_conv_pair_f32(const float *src, int Cin, int B, int Hs, int Ws, int upsampleA,
-                                const float *wpA, const float *scaleA, const float *shiftA, int CoutA,
-                                int reluA, const float *wpB, const float *scaleB, const float *shiftB,
-                                int CoutB, int reluB, int poolB, const float *plane, int plane_chan,
-                                float *y, void *stream) {
-  if (!src || !wpA || !scaleA || !shiftA || !wpB || !scaleB || !shiftB || !y || B <= 0 || Hs <= 0 ||
+// plan != nullptr (ra_conv_pair_plan): the same checks and choices, ending in a record instead of a launch; `plane` is then a mere
+// non-null mark and no pointer is followed
+static int pair_entry(const float *src, int Cin, int B, int Hs, int Ws, int upsampleA, const float *wpA, const float *scaleA,
+                      const float *shiftA, int CoutA, int reluA, const float *wpB, const float *scaleB, const float *shiftB,
+                      int CoutB, int reluB, int poolB, const float *plane, int plane_chan, float *y, void *stream, int *plan) {
+  if ((!plan && (!src || !wpA || !scaleA || !shiftA || !wpB || !scaleB || !shiftB || !y)) || B <= 0 || Hs <= 0 ||
       Ws <= 0)
     return fail(RA_E_INVALID, "ra_conv_pair_f32: bad argument");
   if (!ra_conv_pair_supported(Cin, CoutA, CoutB))
@@ -1333,15 +1361,24 @@ extern "C" int ra_conv_pair_f32(const float *src, int Cin, int B, int Hs, int Ws
   static int no8 = -1;  // RA_PAIR_NO8=1: tuning aid, disables the N-packed kernel
   if (no8 < 0) no8 = getenv("RA_PAIR_NO8") ? 1 : 0;
   if (!no8 && CoutA == 8 && CoutB <= 8 && poolB == 2 && !a.ups && bytes0 < (1u << 31) && a.W > 16) {
-    if (Cin == 4) return cpair::launch8<4>(a, B, st);
-    if (Cin == 8) return cpair::launch8<8>(a, B, st);
+    if (Cin == 4) return cpair::launch8<4>(a, B, st, plan);
+    if (Cin == 8) return cpair::launch8<8>(a, B, st, plan);
   }
   switch (Cin) {
-    case 4: return cpair::dispatch_mid<4>(a, CoutA, B, st);
-    case 8: return cpair::dispatch_mid<8>(a, CoutA, B, st);
-    case 16: return cpair::dispatch_mid<16>(a, CoutA, B, st);
-    default: return cpair::dispatch_mid<32>(a, CoutA, B, st);
+    case 4: return cpair::dispatch_mid<4>(a, CoutA, B, st, plan);
+    case 8: return cpair::dispatch_mid<8>(a, CoutA, B, st, plan);
+    case 16: return cpair::dispatch_mid<16>(a, CoutA, B, st, plan);
+    default: return cpair::dispatch_mid<32>(a, CoutA, B, st, plan);
   }
+}
+
+extern "C" int ra_conv_pair_f32(const float *src, int Cin, int B, int Hs, int Ws, int upsampleA,
+                                const float *wpA, const float *scaleA, const float *shiftA, int CoutA,
+                                int reluA, const float *wpB, const float *scaleB, const float *shiftB,
+                                int CoutB, int reluB, int poolB, const float *plane, int plane_chan,
+                                float *y, void *stream) {
+  return pair_entry(src, Cin, B, Hs, Ws, upsampleA, wpA, scaleA, shiftA, CoutA, reluA, wpB, scaleB, shiftB, CoutB, reluB, poolB, plane,
+                    plane_chan, y, stream, nullptr);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -1372,6 +1409,11 @@ extern "C" int ra_conv_first_cache_f32(const float *src, int B, int H, int W, co
   return launch_status("ra_conv_first_cache_f32");
 }
 
+static int fill_cache_entry(const float *src, const float *plane, int plane_chan, int B, int H, int W, const float *wpA,
+                            const float *scaleA, const float *shiftA, int reluA, const float *wpB, const float *scaleB,
+                            const float *shiftB, int CoutB, int reluB, float *cache, float *y, float *fill_dst, size_t fill_floats,
+                            float fill_value, void *stream, int *plan);
+
 extern "C" int ra_conv_pair_fill_cache_f32(const float *src, const float *plane, int plane_chan, int B, int H, int W,
                                            const float *wpA, const float *scaleA, const float *shiftA, int reluA,
                                            const float *wpB, const float *scaleB, const float *shiftB, int CoutB,
@@ -1385,7 +1427,15 @@ extern "C" int ra_conv_pair_fill_cache_rider_f32(const float *src, const float *
                                                  const float *wpB, const float *scaleB, const float *shiftB, int CoutB,
                                                  int reluB, float *cache, float *y, float *fill_dst, size_t fill_floats,
                                                  float fill_value, void *stream) {
-  if (!src || !plane || !cache || !wpA || !scaleA || !shiftA || !wpB || !scaleB || !shiftB || !y || B <= 0)
+  return fill_cache_entry(src, plane, plane_chan, B, H, W, wpA, scaleA, shiftA, reluA, wpB, scaleB, shiftB, CoutB, reluB, cache, y,
+                          fill_dst, fill_floats, fill_value, stream, nullptr);
+}
+
+static int fill_cache_entry(const float *src, const float *plane, int plane_chan, int B, int H, int W, const float *wpA,
+                            const float *scaleA, const float *shiftA, int reluA, const float *wpB, const float *scaleB,
+                            const float *shiftB, int CoutB, int reluB, float *cache, float *y, float *fill_dst, size_t fill_floats,
+                            float fill_value, void *stream, int *plan) {
+  if (plan ? B <= 0 : !src || !plane || !cache || !wpA || !scaleA || !shiftA || !wpB || !scaleB || !shiftB || !y || B <= 0)
     return fail(RA_E_INVALID, "ra_conv_pair_fill_cache_f32: bad argument");
   if (fill_dst && ((reinterpret_cast<uintptr_t>(fill_dst) & 15) || (fill_floats & 3) || fill_floats * 4 >= (1ull << 31)))
     return fail(RA_E_SHAPE, "ra_conv_pair_fill_cache_rider_f32: the fill must be 16-byte aligned, a multiple of 4 floats, < 2 GiB");
@@ -1399,14 +1449,24 @@ extern "C" int ra_conv_pair_fill_cache_rider_f32(const float *src, const float *
   a.rider_dst = fill_floats ? fill_dst : nullptr;
   a.rider_quads = (int)(fill_floats / 4);
   a.rider_val = fill_value;
-  return cpair::launch8<4, false>(a, B, as_stream(stream));
+  return cpair::launch8<4, false>(a, B, as_stream(stream), plan);
 }
+
+static int cached_entry(const float *cache, const float *plane, int plane_chan, int B, int H, int W, const float *wpA,
+                        const float *scaleA, const float *shiftA, int reluA, const float *wpB, const float *scaleB,
+                        const float *shiftB, int CoutB, int reluB, float *y, void *stream, int *plan);
 
 extern "C" int ra_conv_pair_cached_f32(const float *cache, const float *plane, int plane_chan, int B, int H, int W,
                                        const float *wpA, const float *scaleA, const float *shiftA, int reluA,
                                        const float *wpB, const float *scaleB, const float *shiftB, int CoutB,
                                        int reluB, float *y, void *stream) {
-  if (!cache || !plane || !wpA || !scaleA || !shiftA || !wpB || !scaleB || !shiftB || !y || B <= 0)
+  return cached_entry(cache, plane, plane_chan, B, H, W, wpA, scaleA, shiftA, reluA, wpB, scaleB, shiftB, CoutB, reluB, y, stream, nullptr);
+}
+
+static int cached_entry(const float *cache, const float *plane, int plane_chan, int B, int H, int W, const float *wpA,
+                        const float *scaleA, const float *shiftA, int reluA, const float *wpB, const float *scaleB,
+                        const float *shiftB, int CoutB, int reluB, float *y, void *stream, int *plan) {
+  if (plan ? B <= 0 : !cache || !plane || !wpA || !scaleA || !shiftA || !wpB || !scaleB || !shiftB || !y || B <= 0)
     return fail(RA_E_INVALID, "ra_conv_pair_cached_f32: bad argument");
   if (!ra_conv_first_cache_supported(4, 8, CoutB, 2, H, W) || plane_chan < 0 || plane_chan > 3)
     return fail(RA_E_SHAPE, "ra_conv_pair_cached_f32: unsupported shape");
@@ -1414,6 +1474,21 @@ extern "C" int ra_conv_pair_cached_f32(const float *cache, const float *plane, i
   cpair::PArgs a = pair_args(plane, 4, B, H, W, 0, wpA, scaleA, shiftA, 8, reluA, wpB, scaleB, shiftB, CoutB, reluB, 2, plane, plane_chan, y);
   if (int rc = pair_args_cache(a, cache, B, "ra_conv_pair_cached_f32")) return rc;
   static const int split = env_int("RA_PAIR8_SPLIT", 1);  // =0: layer B on the float32 MFMA (rounds 2-4) instead of the split-precision bf16 form
-  if (split) return cpair::launch8<4, true, true>(a, B, as_stream(stream));
-  return cpair::launch8<4, true>(a, B, as_stream(stream));
+  if (split) return cpair::launch8<4, true, true>(a, B, as_stream(stream), plan);
+  return cpair::launch8<4, true>(a, B, as_stream(stream), plan);
+}
+
+extern "C" int ra_conv_pair_plan(int Cin, int B, int Hs, int Ws, int upsampleA, int CoutA, int CoutB, int poolB, int has_plane,
+                                 int cache_form, int *plan) {
+  if (!plan) return fail(RA_E_INVALID, "ra_conv_pair_plan: bad argument");
+  for (int i = 0; i < RA_PLAN_INTS; ++i) plan[i] = 0;
+  static float mark;  // never read or written: a non-null stand-in for the canvas plane
+  if (cache_form == 1)
+    return fill_cache_entry(nullptr, &mark, 3, B, Hs, Ws, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, CoutB, 0, nullptr, nullptr,
+                            nullptr, 0, 0.0f, nullptr, plan);
+  if (cache_form == 2)
+    return cached_entry(nullptr, &mark, 3, B, Hs, Ws, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, CoutB, 0, nullptr, nullptr, plan);
+  if (cache_form) return fail(RA_E_INVALID, "ra_conv_pair_plan: cache_form %d", cache_form);
+  return pair_entry(nullptr, Cin, B, Hs, Ws, upsampleA, nullptr, nullptr, nullptr, CoutA, 0, nullptr, nullptr, nullptr, CoutB, 0, poolB,
+                    has_plane ? &mark : nullptr, has_plane ? 0 : -1, nullptr, nullptr, plan);
 }

@@ -358,16 +358,25 @@ inline int cu_count() {
 }
 
 template <int CIN, int POOL, int NB, bool PL = false>
-int launch(const SArgs &a, hipStream_t st) {
+int launch(const SArgs &a, hipStream_t st, int *plan) {
   auto kern = conv_split_kernel<CIN, POOL, NB, PL>;
   constexpr int lds = Geo<CIN, NB>::LDS;
-  static const MaxDynamicLds lds_limit(kern, lds);
   const int tiles_x = (a.W + TW - 1) / TW, tiles_y = (a.H + Geo<CIN, NB>::TH - 1) / Geo<CIN, NB>::TH, ntiles = tiles_x * tiles_y * a.B, slices = a.Cout / (16 * NB);
   int gx = Geo<CIN, NB>::OCC * cu_count() / slices;  // one workgroup per CU (141 KB of LDS at Cin = 32), two where their LDS fits (Geo::OCC)
   if (gx < 1) gx = 1;
   if (gx > ntiles) gx = ntiles;
   SArgs a2 = a;
-  a2.tickets = ntiles >= kTicketMinTilesPerWg * gx ? take_ticket_slots(slices, gx) : nullptr;  // several tiles per workgroup and a bound scratch: drawn tiles
+  const bool draws = ntiles >= kTicketMinTilesPerWg * gx;  // several tiles per workgroup and a bound scratch: drawn tiles
+  if (plan) {  // ra_conv_split_plan
+    plan[RA_PLAN_FAMILY] = RA_PLAN_FAMILY_SPLIT, plan[RA_PLAN_FORM] = PL ? RA_PLAN_FORM_PLANE : 0;
+    plan[RA_PLAN_CK] = CIN, plan[RA_PLAN_NC] = NB, plan[RA_PLAN_KF] = 3, plan[RA_PLAN_POOL] = POOL, plan[RA_PLAN_SLICES] = slices;
+    plan[RA_PLAN_TILE_H] = Geo<CIN, NB>::TH, plan[RA_PLAN_TILE_W] = TW, plan[RA_PLAN_TILES_X] = tiles_x, plan[RA_PLAN_TILES_Y] = tiles_y;
+    plan[RA_PLAN_TICKETS] = draws ? 1 : 0;
+    plan_walk(plan, ntiles, gx, 0);
+    return 0;
+  }
+  static const MaxDynamicLds lds_limit(kern, lds);
+  a2.tickets = draws ? take_ticket_slots(slices, gx) : nullptr;
   hipLaunchKernelGGL(kern, dim3(gx, slices), dim3(256), lds, st, a2, tiles_x, tiles_y, ntiles);
   return launch_status("ra_conv_split_f32");
 }
@@ -474,8 +483,9 @@ extern "C" int ra_conv_split_pack_weights(const float *w, int Cin, int Cout, uns
 namespace ra {
 namespace csplit {
 int run(const float *x, int B, int H, int W, int Cin, const float *plane, int plane_chan, const unsigned short *wpacked, const float *scale,
-        const float *shift, int Cout, int relu, int pool, float *y, void *stream, const char *who) {
-  if (!x || !wpacked || !scale || !shift || !y || B <= 0) return fail(RA_E_INVALID, "%s: bad argument", who);
+        const float *shift, int Cout, int relu, int pool, float *y, void *stream, const char *who, int *plan = nullptr) {
+  // plan != nullptr (ra_conv_split_plan): the same checks and choices, ending in a record instead of a launch
+  if ((!plan && (!x || !wpacked || !scale || !shift || !y)) || B <= 0) return fail(RA_E_INVALID, "%s: bad argument", who);
   if (!ra_conv_split_supported(Cin, Cout, pool, H, W))
     return fail(RA_E_SHAPE, "%s: Cin=%d Cout=%d pool=%d %dx%d", who, Cin, Cout, pool, H, W);
   if (plane && (plane_chan < 0 || plane_chan >= Cin)) return fail(RA_E_INVALID, "%s: plane_chan %d outside [0, %d)", who, plane_chan, Cin);
@@ -502,18 +512,18 @@ int run(const float *x, int B, int H, int W, int Cin, const float *plane, int pl
 #define RA_CS(CIN_)                                                                                             \
   if (Cin == CIN_) {                                                                                            \
     if (plane) {                                                                                                \
-      if (two) return pool == 2 ? launch<CIN_, 2, 2, true>(a, st) : launch<CIN_, 1, 2, true>(a, st);            \
-      return pool == 2 ? launch<CIN_, 2, 1, true>(a, st) : launch<CIN_, 1, 1, true>(a, st);                     \
+      if (two) return pool == 2 ? launch<CIN_, 2, 2, true>(a, st, plan) : launch<CIN_, 1, 2, true>(a, st, plan);            \
+      return pool == 2 ? launch<CIN_, 2, 1, true>(a, st, plan) : launch<CIN_, 1, 1, true>(a, st, plan);                     \
     }                                                                                                           \
-    if (two) return pool == 2 ? launch<CIN_, 2, 2>(a, st) : launch<CIN_, 1, 2>(a, st);                          \
-    return pool == 2 ? launch<CIN_, 2, 1>(a, st) : launch<CIN_, 1, 1>(a, st);                                   \
+    if (two) return pool == 2 ? launch<CIN_, 2, 2>(a, st, plan) : launch<CIN_, 1, 2>(a, st, plan);                          \
+    return pool == 2 ? launch<CIN_, 2, 1>(a, st, plan) : launch<CIN_, 1, 1>(a, st, plan);                                   \
   }
   RA_CS(16)
   RA_CS(24)
   RA_CS(32)
 #undef RA_CS
   if (plane) return fail(RA_E_SHAPE, "%s: the plane form is built for Cin 16 / 24 / 32", who);
-  return pool == 2 ? launch<64, 2, 1>(a, st) : launch<64, 1, 1>(a, st);
+  return pool == 2 ? launch<64, 2, 1>(a, st, plan) : launch<64, 1, 1>(a, st, plan);
 }
 }  // namespace csplit
 }  // namespace ra
@@ -528,4 +538,13 @@ extern "C" int ra_conv_split_plane_f32(const float *x, int B, int H, int W, int 
                                        float *y, void *stream) {
   if (!plane) return fail(RA_E_INVALID, "ra_conv_split_plane_f32: null plane");
   return csplit::run(x, B, H, W, Cin, plane, plane_chan, wpacked, scale, shift, Cout, relu, pool, y, stream, "ra_conv_split_plane_f32");
+}
+
+extern "C" int ra_conv_split_plan(int B, int H, int W, int Cin, int Cout, int pool, int has_plane, int *plan) {
+  if (!plan) return fail(RA_E_INVALID, "ra_conv_split_plan: bad argument");
+  for (int i = 0; i < RA_PLAN_INTS; ++i) plan[i] = 0;
+  if (!plan_have_device()) return fail(RA_E_INVALID, "ra_conv_split_plan: the grid is the device's CU count: no device");
+  static float mark;  // never read or written: a non-null stand-in for the canvas plane
+  return csplit::run(nullptr, B, H, W, Cin, has_plane ? &mark : nullptr, 0, nullptr, nullptr, nullptr, Cout, 0, pool, nullptr, nullptr,
+                     "ra_conv_split_plan", plan);
 }

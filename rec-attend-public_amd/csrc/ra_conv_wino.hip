@@ -251,7 +251,7 @@ __global__ __launch_bounds__(256, 2) void conv_wino_mfma(const WArgs a, int tile
 inline int cu_count();
 
 template <int CIN, int POOL, int TSY, int NB>
-int launch(const WArgs &a, hipStream_t st) {
+int launch(const WArgs &a, hipStream_t st, int *plan) {
   auto kern = conv_wino_mfma<CIN, POOL, TSY, NB>;
   constexpr size_t lds = (size_t)((TSY + 2) * WS * (CIN + 2) + 8 * 16 * TEX) * sizeof(float);
   static bool attr = false;
@@ -269,7 +269,16 @@ int launch(const WArgs &a, hipStream_t st) {
   if (gx > ntiles) gx = ntiles;
   WArgs a2 = a;  // XCD-contiguous tile walk when the grid's rows are whole rounds of the 8 XCDs
   a2.xcd_map = (gx % 8 == 0) ? 1 : 0;
-  a2.tickets = ntiles >= kTicketMinTilesPerWg * gx ? take_ticket_slots(slices, gx) : nullptr;  // several tiles per workgroup and a bound scratch: drawn tiles
+  const bool draws = ntiles >= kTicketMinTilesPerWg * gx;  // several tiles per workgroup and a bound scratch: drawn tiles
+  if (plan) {  // ra_conv_wino_plan
+    plan[RA_PLAN_FAMILY] = RA_PLAN_FAMILY_WINO;
+    plan[RA_PLAN_CK] = CIN, plan[RA_PLAN_NC] = NB, plan[RA_PLAN_KF] = 3, plan[RA_PLAN_POOL] = POOL, plan[RA_PLAN_SLICES] = slices;
+    plan[RA_PLAN_TILE_H] = TSY, plan[RA_PLAN_TILE_W] = TS, plan[RA_PLAN_TILES_X] = tiles_x, plan[RA_PLAN_TILES_Y] = tiles_y;
+    plan[RA_PLAN_TICKETS] = draws ? 1 : 0;
+    plan_walk(plan, ntiles, gx, a2.xcd_map);
+    return 0;
+  }
+  a2.tickets = draws ? take_ticket_slots(slices, gx) : nullptr;
   hipLaunchKernelGGL(kern, dim3(gx, slices), dim3(256), lds, st, a2, tiles_x, tiles_y, ntiles);
   return launch_status("ra_conv_wino_f32");
 }
@@ -288,11 +297,11 @@ inline int cu_count() {
 // 16-row tiles only when they give every CU more than two workgroups (RA_WINO_TSY=8|16 forces one form):
 // measured at cfg2, 8-row tiles 9.8 vs 11.5 us (L6), 12.7 vs 13.3 (L4), 16.5 vs 16.6 (L5)
 template <int CIN, int POOL, int NB>
-int launch_any(const WArgs &a, hipStream_t st) {
+int launch_any(const WArgs &a, hipStream_t st, int *plan) {
   static const int force = env_int("RA_WINO_TSY", 0);
   const int tall = (a.W / TS) * (a.H / 16) * a.B * (a.Cout / (16 * NB));
   const bool small = force ? force == 8 : tall <= 2 * cu_count();
-  return small ? launch<CIN, POOL, 8, NB>(a, st) : launch<CIN, POOL, 16, NB>(a, st);
+  return small ? launch<CIN, POOL, 8, NB>(a, st, plan) : launch<CIN, POOL, 16, NB>(a, st, plan);
 }
 
 // -------------------------------------------------------------------------------------------------
@@ -618,7 +627,7 @@ __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 
 }
 
 template <int TSY, bool SPLIT = false>
-int launch_pair(const PWArgs &a, hipStream_t st) {
+int launch_pair(const PWArgs &a, hipStream_t st, int *plan) {
   auto kern = conv_pair_wino_mfma<TSY, SPLIT>;
   constexpr int inf = SPLIT ? 3 * (TSY + 4) * (TS + 4) * 4 : (TSY + 4) * (TS + 4) * 8;
   constexpr int r0 = inf > 8 * 16 * 20 ? inf : 8 * 16 * 20;
@@ -640,7 +649,16 @@ int launch_pair(const PWArgs &a, hipStream_t st) {
   a2.xcd_map = (xcd && grid % 8 == 0 && grid >= 8) ? 1 : 0;
   // (this pair from 6 tiles per workgroup: at 4 — cfg2's batch of 8 alone — drawing costs it 2 us of 33, at 8 — the 16 images of a
   // pipeline slot — 1.3 of 66 against 9-14 us saved next to another slot's tail)
-  a2.tickets = ntiles >= 2 * kTicketMinTilesPerWg * grid ? take_ticket_slots(1, grid) : nullptr;
+  const bool draws = ntiles >= 2 * kTicketMinTilesPerWg * grid;
+  if (plan) {  // ra_conv_pair_wino_plan
+    plan[RA_PLAN_FAMILY] = RA_PLAN_FAMILY_PAIR_WINO, plan[RA_PLAN_FORM] = SPLIT ? RA_PLAN_FORM_SPLIT : 0;
+    plan[RA_PLAN_CK] = 8, plan[RA_PLAN_CMID] = 16, plan[RA_PLAN_NC] = 1, plan[RA_PLAN_KF] = 3, plan[RA_PLAN_POOL] = 2, plan[RA_PLAN_SLICES] = 1;
+    plan[RA_PLAN_TILE_H] = TSY, plan[RA_PLAN_TILE_W] = TS, plan[RA_PLAN_TILES_X] = tiles_x, plan[RA_PLAN_TILES_Y] = tiles_y;
+    plan[RA_PLAN_TICKETS] = draws ? 1 : 0;
+    plan_walk(plan, ntiles, grid, a2.xcd_map);
+    return 0;
+  }
+  a2.tickets = draws ? take_ticket_slots(1, grid) : nullptr;
   hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, st, a2, tiles_x, tiles_y, ntiles);
   return launch_status("ra_conv_pair_wino_f32");
 }
@@ -680,9 +698,10 @@ extern "C" int ra_conv_wino_pack_weights(const float *w, int Cin, int Cout, floa
   return 0;
 }
 
-extern "C" int ra_conv_wino_f32(const float *x, int B, int H, int W, int Cin, const float *wpacked, const float *scale,
-                                const float *shift, int Cout, int relu, int pool, float *y, void *stream) {
-  if (!x || !wpacked || !scale || !shift || !y || B <= 0) return fail(RA_E_INVALID, "ra_conv_wino_f32: bad argument");
+// plan != nullptr (ra_conv_wino_plan): the same checks and choices, ending in a record instead of a launch
+static int wino_entry(const float *x, int B, int H, int W, int Cin, const float *wpacked, const float *scale, const float *shift, int Cout,
+                      int relu, int pool, float *y, void *stream, int *plan) {
+  if ((!plan && (!x || !wpacked || !scale || !shift || !y)) || B <= 0) return fail(RA_E_INVALID, "ra_conv_wino_f32: bad argument");
   if (!ra_conv_wino_supported(Cin, Cout, pool, H, W))
     return fail(RA_E_SHAPE, "ra_conv_wino_f32: Cin=%d Cout=%d pool=%d %dx%d", Cin, Cout, pool, H, W);
   const size_t bytes = (size_t)B * H * W * Cin * sizeof(float);
@@ -702,21 +721,32 @@ extern "C" int ra_conv_wino_f32(const float *x, int B, int H, int W, int Cin, co
   a.xcd_map = 0;
   hipStream_t st = as_stream(stream);
   if (Cout % 32) {  // 16 output channels per workgroup
-    if (Cin == 16) return pool == 2 ? wino::launch_any<16, 2, 1>(a, st) : wino::launch_any<16, 1, 1>(a, st);
-    return pool == 2 ? wino::launch_any<32, 2, 1>(a, st) : wino::launch_any<32, 1, 1>(a, st);
+    if (Cin == 16) return pool == 2 ? wino::launch_any<16, 2, 1>(a, st, plan) : wino::launch_any<16, 1, 1>(a, st, plan);
+    return pool == 2 ? wino::launch_any<32, 2, 1>(a, st, plan) : wino::launch_any<32, 1, 1>(a, st, plan);
   }
-  if (Cin == 16) return pool == 2 ? wino::launch_any<16, 2, 2>(a, st) : wino::launch_any<16, 1, 2>(a, st);
-  return pool == 2 ? wino::launch_any<32, 2, 2>(a, st) : wino::launch_any<32, 1, 2>(a, st);
+  if (Cin == 16) return pool == 2 ? wino::launch_any<16, 2, 2>(a, st, plan) : wino::launch_any<16, 1, 2>(a, st, plan);
+  return pool == 2 ? wino::launch_any<32, 2, 2>(a, st, plan) : wino::launch_any<32, 1, 2>(a, st, plan);
+}
+
+extern "C" int ra_conv_wino_f32(const float *x, int B, int H, int W, int Cin, const float *wpacked, const float *scale,
+                                const float *shift, int Cout, int relu, int pool, float *y, void *stream) {
+  return wino_entry(x, B, H, W, Cin, wpacked, scale, shift, Cout, relu, pool, y, stream, nullptr);
+}
+
+extern "C" int ra_conv_wino_plan(int B, int H, int W, int Cin, int Cout, int pool, int *plan) {
+  if (!plan) return fail(RA_E_INVALID, "ra_conv_wino_plan: bad argument");
+  for (int i = 0; i < RA_PLAN_INTS; ++i) plan[i] = 0;
+  if (!plan_have_device()) return fail(RA_E_INVALID, "ra_conv_wino_plan: the tile height and the grid follow the device's CU count: no device");
+  return wino_entry(nullptr, B, H, W, Cin, nullptr, nullptr, nullptr, Cout, 0, pool, nullptr, nullptr, plan);
 }
 
 extern "C" int ra_conv_pair_wino_supported(int Cin, int CoutA, int CoutB, int poolB, int H, int W) {
   return Cin == 8 && CoutA == 16 && CoutB == 16 && poolB == 2 && H > 0 && W > 0 && H % wino::TS == 0 && W % wino::TS == 0;
 }
 
-extern "C" int ra_conv_pair_wino_f32(const float *x, int B, int H, int W, const float *wpA, const float *scaleA,
-                                     const float *shiftA, int reluA, const float *wpB_wino, const float *scaleB,
-                                     const float *shiftB, int reluB, float *y, void *stream) {
-  if (!x || !wpA || !scaleA || !shiftA || !wpB_wino || !scaleB || !shiftB || !y || B <= 0)
+static int pair_wino_entry(const float *x, int B, int H, int W, const float *wpA, const float *scaleA, const float *shiftA, int reluA,
+                           const float *wpB_wino, const float *scaleB, const float *shiftB, int reluB, float *y, void *stream, int *plan) {
+  if ((!plan && (!x || !wpA || !scaleA || !shiftA || !wpB_wino || !scaleB || !shiftB || !y)) || B <= 0)
     return fail(RA_E_INVALID, "ra_conv_pair_wino_f32: bad argument");
   if (!ra_conv_pair_wino_supported(8, 16, 16, 2, H, W)) return fail(RA_E_SHAPE, "ra_conv_pair_wino_f32: %dx%d", H, W);
   const size_t bytes = (size_t)B * H * W * 8 * sizeof(float);
@@ -745,6 +775,19 @@ extern "C" int ra_conv_pair_wino_f32(const float *x, int B, int H, int W, const 
   // RA_PAIRW_TSY=16: tuning aid.  8-row tiles: 128 VGPRs and 24 KB of LDS, 4 workgroups per CU (39.1 vs 42.5 us)
   static const int tsy = env_int("RA_PAIRW_TSY", 8) == 16 ? 16 : 8;
   static const int split = env_int("RA_PAIRW_SPLIT", 1);  // =0: layer A on the float32 MFMA (rounds 2-4)
-  if (split && tsy == 8) return wino::launch_pair<8, true>(a, as_stream(stream));
-  return tsy == 8 ? wino::launch_pair<8>(a, as_stream(stream)) : wino::launch_pair<16>(a, as_stream(stream));
+  if (split && tsy == 8) return wino::launch_pair<8, true>(a, as_stream(stream), plan);
+  return tsy == 8 ? wino::launch_pair<8>(a, as_stream(stream), plan) : wino::launch_pair<16>(a, as_stream(stream), plan);
+}
+
+extern "C" int ra_conv_pair_wino_f32(const float *x, int B, int H, int W, const float *wpA, const float *scaleA,
+                                     const float *shiftA, int reluA, const float *wpB_wino, const float *scaleB,
+                                     const float *shiftB, int reluB, float *y, void *stream) {
+  return pair_wino_entry(x, B, H, W, wpA, scaleA, shiftA, reluA, wpB_wino, scaleB, shiftB, reluB, y, stream, nullptr);
+}
+
+extern "C" int ra_conv_pair_wino_plan(int B, int H, int W, int *plan) {
+  if (!plan) return fail(RA_E_INVALID, "ra_conv_pair_wino_plan: bad argument");
+  for (int i = 0; i < RA_PLAN_INTS; ++i) plan[i] = 0;
+  if (!plan_have_device()) return fail(RA_E_INVALID, "ra_conv_pair_wino_plan: the grid follows the device's CU count and occupancy: no device");
+  return pair_wino_entry(nullptr, B, H, W, nullptr, nullptr, nullptr, 0, nullptr, nullptr, nullptr, 0, nullptr, nullptr, plan);
 }

@@ -230,6 +230,53 @@ def conv3x3(src0, wp, scale, shift, cout, relu=True, pool=1, src1=None, upsample
   return out
 
 
+# ---- launch plans (recattend.h, RA_PLAN_*): which template instantiation, grid and tile walk a conv entry point would launch
+_PLAN_FAMILIES = {v: k[len('RA_PLAN_FAMILY_'):].lower() for k, v in rn.CONSTANTS.items() if k.startswith('RA_PLAN_FAMILY_')}
+_PLAN_FORMS = sorted((v, k[len('RA_PLAN_FORM_'):].lower()) for k, v in rn.CONSTANTS.items() if k.startswith('RA_PLAN_FORM_'))
+_PLAN_FIELDS = sorted((v, k[len('RA_PLAN_'):].lower()) for k, v in rn.CONSTANTS.items()
+                      if k.startswith('RA_PLAN_') and not k.startswith(('RA_PLAN_FAMILY_', 'RA_PLAN_FORM_')) and k != 'RA_PLAN_INTS')
+
+
+def plan_dict(rec):
+  """A plan record (the RA_PLAN_INTS ints a ra_*_plan query fills) as a dict: 'family' by name, 'form' as the sorted tuple
+  of its bits' names, every other RA_PLAN_* field as an int."""
+  out = {field: rec[i] for i, field in _PLAN_FIELDS}
+  out['family'] = _PLAN_FAMILIES[rec[rn.RA_PLAN_FAMILY]]
+  out['form'] = tuple(sorted(n for bit, n in _PLAN_FORMS if rec[rn.RA_PLAN_FORM] & bit))
+  return out
+
+
+def _plan(name, *args):
+  """plan_dict of the record the query `name` fills.  Host only: nothing is launched."""
+  rec = (C.c_int * rn.RA_PLAN_INTS)()
+  check(getattr(rn.lib(), name)(*([int(a) for a in args] + [rec])), name)
+  return plan_dict(rec)
+
+
+def conv3x3_plan(c0, c1, B, Hs, Ws, cout, pool=1, upsample=False, ksize=3, plane=False, bf16=False, moments=False, store_flags=0):
+  """Plan of conv3x3 / conv2d_fused (ksize) / the bf16-operand and moments entry points on these shape arguments.  Needs no
+  device; without one grid, tiles_min and tiles_max are -1."""
+  return _plan('ra_conv3x3_plan', c0, c1, B, Hs, Ws, bool(upsample), ksize, cout, pool, bool(plane), bool(bf16), bool(moments), store_flags)
+
+
+def conv_pair_plan(cin, B, Hs, Ws, couta, coutb, poolB=2, upsampleA=False, plane=False, cache_form=0):
+  """Plan of conv_pair (cache_form 0), conv_pair_fill_cache (1) or conv_pair_cached (2).  The geometry and the N-packed
+  kernel's plan need no device; whether the persistent kernel runs does (grid -1 without one)."""
+  return _plan('ra_conv_pair_plan', cin, B, Hs, Ws, bool(upsampleA), couta, coutb, poolB, bool(plane), cache_form)
+
+
+def conv_split_plan(B, H, W, cin, cout, pool=1, plane=False):
+  return _plan('ra_conv_split_plan', B, H, W, cin, cout, pool, bool(plane))
+
+
+def conv_wino_plan(B, H, W, cin, cout, pool=1):
+  return _plan('ra_conv_wino_plan', B, H, W, cin, cout, pool)
+
+
+def conv_pair_wino_plan(B, H, W):
+  return _plan('ra_conv_pair_wino_plan', B, H, W)
+
+
 def conv2d_fused(src0, wp, scale, shift, cout, ksize, relu=True, pool=1, src1=None, upsample=False, out=None, plane=None,
                  plane_chan=-1):
   """conv3x3 for a ksize x ksize filter, ksize in FILTER_SIZES; wp = pack_conv_weights of that filter.  ksize = 3 IS

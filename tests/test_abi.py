@@ -52,6 +52,11 @@ PINNED = {
     'ra_ctrl_pack_weights': (_I, [_DESC, _P, _P, _P, _P]),
     'ra_controller_f32': (_I, [_DESC, _P, _P, _I, _P, _P, _P, _P, _P]),
     'ra_conv3x3_f32': (_I, [_P, _I, _P, _I, _I, _I, _I, _I, _P, _P, _P, _I, _I, _I, _P, _I, _P, _P]),
+    'ra_conv3x3_plan': (_I, [_I] * 13 + [_P]),
+    'ra_conv_pair_plan': (_I, [_I] * 10 + [_P]),
+    'ra_conv_split_plan': (_I, [_I] * 7 + [_P]),
+    'ra_conv_wino_plan': (_I, [_I] * 6 + [_P]),
+    'ra_conv_pair_wino_plan': (_I, [_I] * 3 + [_P]),
 }
 
 
@@ -110,6 +115,28 @@ def test_argument_validation_without_gpu():
   rc = lib.ra_hungarian_f32(None, 1, 2, 2, None, None, None)
   assert rc == -1
   assert lib.ra_resample_bwd_workspace_floats(8, 48, 4) == 8 * 48 * 8 and lib.ra_ctrl_train_supported(256, 64, 256, 5, 9) == 1
+
+
+def test_plan_queries_without_gpu():
+  """The launch-plan queries are host code: K1's whole plan and the pair's geometry need no device, the launch's own argument
+  checks answer a bad shape, and nothing is written but the record."""
+  lib = rn.lib()
+  assert rn.RA_PLAN_INTS >= 21 and len({v for k, v in rn.CONSTANTS.items() if k.startswith('RA_PLAN_') and not k.startswith(
+      ('RA_PLAN_FAMILY_', 'RA_PLAN_FORM_', 'RA_PLAN_INTS'))}) == 21  # the record's indices are distinct
+  rec = (ctypes.c_int * rn.RA_PLAN_INTS)()
+  # 16 -> 32 channels, 128 images of 18 x 50, pool 2: 512 workgroups of the 32 x 16 tile, two cout groups per wave, plain stores
+  assert lib.ra_conv3x3_plan(16, 0, 128, 18, 50, 0, 3, 32, 2, 0, 0, 0, 0, rec) == 0
+  got = {k: rec[getattr(rn, 'RA_PLAN_' + k)] for k in ('FAMILY', 'FORM', 'CK', 'NC', 'WN', 'GX', 'GY', 'KF', 'TILE_H', 'TILE_W', 'NTILES')}
+  assert got == dict(FAMILY=rn.RA_PLAN_FAMILY_K1, FORM=0, CK=16, NC=2, WN=1, GX=4, GY=2, KF=3, TILE_H=16, TILE_W=32, NTILES=512), got
+  assert lib.ra_conv3x3_plan(16, 0, 128, 18, 50, 0, 3, 32, 1, 0, 0, 0, 0, rec) == 0 and rec[rn.RA_PLAN_FORM] == rn.RA_PLAN_FORM_SWAP
+  assert lib.ra_conv3x3_plan(6, 0, 1, 8, 8, 0, 3, 8, 1, 0, 0, 0, 0, rec) == rn.RA_E_SHAPE       # C0 % 4, as the launch answers
+  assert lib.ra_conv3x3_plan(8, 0, 1, 8, 8, 0, 4, 8, 1, 0, 0, 0, 0, rec) == rn.RA_E_SHAPE       # filter size 4
+  assert lib.ra_conv3x3_plan(8, 0, 1, 8, 8, 0, 3, 8, 1, 0, 0, 0, 0, None) == rn.RA_E_INVALID
+  # the N-packed pair: 900 tiles on its 768 workgroups, XCD-contiguous, one or two tiles each
+  assert lib.ra_conv_pair_plan(4, 225, 18, 34, 0, 8, 8, 2, 0, 0, rec) == 0
+  assert rec[rn.RA_PLAN_FAMILY] == rn.RA_PLAN_FAMILY_PAIR and rec[rn.RA_PLAN_FORM] == rn.RA_PLAN_FORM_NPACKED
+  assert [rec[i] for i in (rn.RA_PLAN_NTILES, rn.RA_PLAN_GRID, rn.RA_PLAN_TILES_MIN, rn.RA_PLAN_TILES_MAX, rn.RA_PLAN_XCD_MAP)] == [900, 768, 1, 2, 1]
+  assert lib.ra_conv_pair_plan(4, 1, 16, 16, 0, 12, 8, 2, 0, 0, rec) == rn.RA_E_SHAPE           # CoutA 12
 
 
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):

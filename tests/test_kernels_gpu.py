@@ -30,7 +30,7 @@ CONV_CASES = [
     (2, 16, 16, 32, 64, 2, True),
     (2, 8, 8, 64, 64, 2, True),
     (1, 128, 128, 4, 8, 1, True),
-    (8, 64, 64, 16, 16, 2, True),   # many workgroups -> big tile geometry
+    (8, 64, 64, 16, 16, 2, True),   # 256 workgroups of the two-group (2, 1) geometry (the plan query; (4, 2) needs 512 of its own: test_conv_forms_gpu.py)
     (1, 12, 12, 64, 96, 2, True),   # KITTI attn cnn last layer (Cout 96 -> 128 padded)
     (1, 20, 36, 24, 16, 2, True),   # Cityscapes packed input (24 ch), ragged tiles
     (1, 6, 10, 4, 1, 1, True),      # Cout = 1, tiny
@@ -182,7 +182,7 @@ PAIR_CASES = [
     (2, 12, 12, 32, 16, 16, 1, True),   # d2+d3
     (1, 24, 24, 16, 8, 8, 1, True),     # d4+d5
     (1, 20, 36, 8, 8, 1, 1, False),     # CoutB = 1, ragged tiles
-    (8, 128, 128, 4, 8, 8, 2, False),   # many tiles -> big geometry
+    (8, 128, 128, 4, 8, 8, 2, False),   # N-packed kernel, 256 tiles on 256 workgroups, XCD-contiguous (the generic pair's geometries: test_conv_forms_gpu.py)
     (2, 50, 70, 4, 8, 8, 2, False),     # N-packed kernel, ragged tiles on both edges
     (1, 18, 34, 8, 8, 5, 2, False),     # N-packed kernel, Cin = 8, CoutB < 8
     (1, 16, 32, 4, 8, 8, 2, False),     # N-packed kernel, exactly one tile
@@ -761,7 +761,7 @@ def test_adam_step_matches_tf_adam(cuda):
     (1, 32, 32, 16, 32, 2, False),
     (2, 64, 32, 16, 16, 2, True),    # L3 shape class: one block of 16 output channels per workgroup
     (1, 16, 48, 32, 16, 1, True),
-    (8, 128, 128, 32, 32, 2, True),  # cfg2's L5 itself: persistent workgroups, several tiles each
+    (8, 128, 128, 32, 32, 2, True),  # cfg2's L5 itself: TSY = 8, 1024 tiles on 512 persistent workgroups, two each, XCD-contiguous (the plan query)
 ])
 def test_conv_winograd(cuda, B, H, W, Ci, Co, pool, relu):
   """ra_conv_wino_f32 (Winograd F(2x2,3x3) on the MFMA) against the float64 direct convolution and
