@@ -758,11 +758,12 @@ __global__ __launch_bounds__(256) void paste_win_kernel(const float *__restrict_
 using namespace ra;
 
 namespace {
-// paste_win_kernel where its shape conditions hold (the decode loop's launches), the general kernel otherwise
+// paste_win_kernel where its shape conditions hold (the decode loop's launches), the general kernel otherwise.
+// plan != nullptr (ra_paste_plan): the same chain of choices, ending in a record instead of a launch; no pointer is followed.
 template <int MODE>
 void launch_paste(int extra_wg, const float *patch, int Cp, int pc, const float *attn_rec, int B, int H, int W, int Fh,
                   int Fw, float beta, int disable_overwrite, float *canvas, float *img, int Ci, int canvas_chan,
-                  float *y_out, size_t y_stride_b, int flags, attnd::ScoreArgs sc, void *stream) {
+                  float *y_out, size_t y_stride_b, int flags, attnd::ScoreArgs sc, void *stream, int *plan = nullptr) {
   const attnd::PasteGeo pg = attnd::paste_geo();
   const int rb = pg.rows == 8 ? 8 : 4;
   const bool a16 = ((reinterpret_cast<uintptr_t>(y_out) | reinterpret_cast<uintptr_t>(canvas) |
@@ -772,12 +773,28 @@ void launch_paste(int extra_wg, const float *patch, int Cp, int pc, const float 
                       (MODE == 1 || (canvas && !img && Cp == 1 && pc == 0));
   if (!win_ok) {
     const size_t lds = (size_t)(pg.rows * Fw > 8 ? pg.rows * Fw : 8) * sizeof(float);
+    if (plan) {
+      plan[RA_PASTE_PLAN_KERNEL] = RA_PASTE_KERNEL_GENERAL;
+      plan[RA_PASTE_PLAN_ROWS] = pg.rows;
+      plan[RA_PASTE_PLAN_GRID_X] = ceil_div(H, pg.rows) + extra_wg;
+      plan[RA_PASTE_PLAN_THREADS] = pg.threads;
+      plan[RA_PASTE_PLAN_LDS] = (int)lds;
+      return;
+    }
     hipLaunchKernelGGL(attnd::paste_direct_kernel<MODE>, dim3(ceil_div(H, pg.rows) + extra_wg, B), dim3(pg.threads), lds,
                        as_stream(stream), patch, Cp, pc, attn_rec, H, W, Fh, Fw, beta, disable_overwrite, canvas, img, Ci,
                        canvas_chan, y_out, y_stride_b, flags, pg.rows, sc);
     return;
   }
   const size_t lds = (size_t)rb * 256 * 16 + (size_t)(rb * Fw + Fh * Fw + 16) * sizeof(float);
+  if (plan) {
+    plan[RA_PASTE_PLAN_KERNEL] = RA_PASTE_KERNEL_WINDOW;
+    plan[RA_PASTE_PLAN_ROWS] = rb;
+    plan[RA_PASTE_PLAN_GRID_X] = ceil_div(H, rb) + extra_wg;
+    plan[RA_PASTE_PLAN_THREADS] = 256;
+    plan[RA_PASTE_PLAN_LDS] = (int)lds;
+    return;
+  }
   if (rb == 8)
     hipLaunchKernelGGL((attnd::paste_win_kernel<MODE, 8>), dim3(ceil_div(H, 8) + extra_wg, B), dim3(256), lds,
                        as_stream(stream), patch, attn_rec, H, W, Fh, Fw, beta, disable_overwrite, canvas, y_out, y_stride_b,
@@ -846,6 +863,25 @@ extern "C" int ra_attn_box_direct_f32(const float *attn_rec, int B, int H, int W
   launch_paste<1>(0, nullptr, 1, 0, attn_rec, B, H, W, Fh, Fw, beta, 0, nullptr, nullptr, 0, -1, box_out, stride_b, 0,
                   attnd::ScoreArgs{}, stream);
   return launch_status("ra_attn_box_direct_f32");
+}
+
+extern "C" int ra_paste_plan(int mode, int B, int H, int W, int Fh, int Fw, int Cp, int pc, int has_canvas, int has_img,
+                             size_t y_stride_b, int aligned16, int *plan) {
+  if (!plan || (mode != 0 && mode != 1) || B <= 0 || H <= 0 || W <= 0 || Fh <= 0 || Fw <= 0 ||
+      (mode == 0 && (Cp <= 0 || pc < 0 || pc >= Cp)))
+    return fail(RA_E_INVALID, "ra_paste_plan: bad argument");
+  for (int i = 0; i < RA_PASTE_PLAN_INTS; ++i) plan[i] = 0;
+  // stand-ins for the pointers, with the alignment and presence asked about: the chain only looks at their low bits and
+  // at whether they are null
+  float *const there = reinterpret_cast<float *>(uintptr_t(64));
+  float *const y_out = reinterpret_cast<float *>(uintptr_t(aligned16 ? 64 : 68));
+  if (mode == 0)
+    launch_paste<0>(0, there, Cp, pc, nullptr, B, H, W, Fh, Fw, 0.0f, 0, has_canvas ? there : nullptr, has_img ? there : nullptr,
+                    0, -1, y_out, y_stride_b, 0, attnd::ScoreArgs{}, nullptr, plan);
+  else
+    launch_paste<1>(0, nullptr, 1, 0, nullptr, B, H, W, Fh, Fw, 0.0f, 0, nullptr, nullptr, 0, -1, y_out, y_stride_b, 0,
+                    attnd::ScoreArgs{}, nullptr, plan);
+  return 0;
 }
 
 extern "C" int ra_paste_score_direct_f32(const float *patch, int Cp, int pc, const float *attn_rec, int B, int H,

@@ -597,6 +597,18 @@ def paste_score_direct(patch, pc, attn, beta, disable_overwrite, y_out, y_stride
         'ra_paste_score_direct_f32')
 
 
+def paste_plan(mode, B, H, W, Fh, Fw, Cp=1, pc=0, has_canvas=True, has_img=False, y_stride_b=None, aligned16=True):
+  """ra_paste_plan: which kernel paste_direct / paste_score_direct (mode 'paste') or attn_box_direct (mode 'box') launches on
+  these arguments, as a dict kernel ('general' | 'window'), rows, grid_x, threads, lds.  Host only: nothing is launched."""
+  rec = (C.c_int * rn.RA_PASTE_PLAN_INTS)()
+  stride = H * W if y_stride_b is None else y_stride_b
+  check(rn.lib().ra_paste_plan({'paste': 0, 'box': 1}[mode], int(B), int(H), int(W), int(Fh), int(Fw), int(Cp), int(pc),
+                               int(bool(has_canvas)), int(bool(has_img)), int(stride), int(bool(aligned16)), rec), 'ra_paste_plan')
+  return {'kernel': {rn.RA_PASTE_KERNEL_GENERAL: 'general', rn.RA_PASTE_KERNEL_WINDOW: 'window'}[rec[rn.RA_PASTE_PLAN_KERNEL]],
+          'rows': rec[rn.RA_PASTE_PLAN_ROWS], 'grid_x': rec[rn.RA_PASTE_PLAN_GRID_X], 'threads': rec[rn.RA_PASTE_PLAN_THREADS],
+          'lds': rec[rn.RA_PASTE_PLAN_LDS]}
+
+
 RESAMPLE_READ, RESAMPLE_WRITE, RESAMPLE_BOX = rn.RA_RESAMPLE_READ, rn.RA_RESAMPLE_WRITE, rn.RA_RESAMPLE_BOX
 
 

@@ -57,6 +57,7 @@ PINNED = {
     'ra_conv_split_plan': (_I, [_I] * 7 + [_P]),
     'ra_conv_wino_plan': (_I, [_I] * 6 + [_P]),
     'ra_conv_pair_wino_plan': (_I, [_I] * 3 + [_P]),
+    'ra_paste_plan': (_I, [_I] * 10 + [_Z, _I, _P]),
 }
 
 
@@ -137,6 +138,22 @@ def test_plan_queries_without_gpu():
   assert rec[rn.RA_PLAN_FAMILY] == rn.RA_PLAN_FAMILY_PAIR and rec[rn.RA_PLAN_FORM] == rn.RA_PLAN_FORM_NPACKED
   assert [rec[i] for i in (rn.RA_PLAN_NTILES, rn.RA_PLAN_GRID, rn.RA_PLAN_TILES_MIN, rn.RA_PLAN_TILES_MAX, rn.RA_PLAN_XCD_MAP)] == [900, 768, 1, 2, 1]
   assert lib.ra_conv_pair_plan(4, 1, 16, 16, 0, 12, 8, 2, 0, 0, rec) == rn.RA_E_SHAPE           # CoutA 12
+  # the paste: the decode loop's launch (canvas plane, one-channel patch) takes the window kernel, 4 rows per workgroup; a
+  # packed patch channel, an image-channel canvas or a misaligned y_out the general one
+  prec = (ctypes.c_int * rn.RA_PASTE_PLAN_INTS)()
+  fields = (rn.RA_PASTE_PLAN_KERNEL, rn.RA_PASTE_PLAN_ROWS, rn.RA_PASTE_PLAN_GRID_X, rn.RA_PASTE_PLAN_THREADS, rn.RA_PASTE_PLAN_LDS)
+  assert len(set(fields)) == 5 and max(fields) < rn.RA_PASTE_PLAN_INTS
+  assert lib.ra_paste_plan(0, 8, 128, 128, 48, 48, 1, 0, 1, 0, 128 * 128, 1, prec) == 0
+  assert [prec[i] for i in fields] == [rn.RA_PASTE_KERNEL_WINDOW, 4, 32, 256, 4 * 256 * 16 + (4 * 48 + 48 * 48 + 16) * 4]
+  for args in ((0, 8, 128, 128, 48, 48, 4, 2, 1, 0, 128 * 128, 1), (0, 8, 128, 128, 48, 48, 1, 0, 0, 1, 128 * 128, 1),
+               (0, 8, 128, 128, 48, 48, 1, 0, 1, 0, 128 * 128, 0), (1, 8, 126, 130, 48, 48, 1, 0, 0, 0, 126 * 130, 1)):
+    assert lib.ra_paste_plan(*args, prec) == 0
+    assert [prec[i] for i in fields] == [rn.RA_PASTE_KERNEL_GENERAL, 4, (args[2] + 3) // 4, 256, 4 * 48 * 4], args
+  assert lib.ra_paste_plan(1, 8, 126, 128, 48, 48, 0, 0, 0, 0, 126 * 128, 1, prec) == 0 and prec[rn.RA_PASTE_PLAN_GRID_X] == 32
+  assert prec[rn.RA_PASTE_PLAN_KERNEL] == rn.RA_PASTE_KERNEL_WINDOW                            # the box ignores Cp / pc
+  assert lib.ra_paste_plan(0, 8, 128, 128, 48, 48, 1, 1, 1, 0, 128 * 128, 1, prec) == rn.RA_E_INVALID   # pc >= Cp, as the launch answers
+  assert lib.ra_paste_plan(2, 8, 128, 128, 48, 48, 1, 0, 1, 0, 128 * 128, 1, prec) == rn.RA_E_INVALID
+  assert lib.ra_paste_plan(0, 8, 128, 128, 48, 48, 1, 0, 1, 0, 128 * 128, 1, None) == rn.RA_E_INVALID
 
 
 def test_missing_library_fails_loudly(tmp_path, monkeypatch):
