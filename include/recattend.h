@@ -816,6 +816,37 @@ int ra_instance_class_pick_f32(const float *vote, const float *conf, int B, int 
                                void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The matching step of the Cityscapes instance-level evaluation (csrc/ra_instance_overlap.hip), cited as lines of
+ * data_api/cityscapes_scripts/evaluation/evalInstanceLevelSemanticLabeling.py unless a file is named.  gt_ids is int32
+ * [B,H,W]: the values of *_gtFine_instanceIds.png, a label id below 1000 or labelId * 1000 + k.  H * W < 2^31.
+ *
+ * ra_gt_instance_catalog_i32 — instances2dict.py:37-40 with instance.py:26-27, np.unique(gt, return_counts=True) per
+ *   image: ids[b, 0 .. count[b]) the distinct ids in ascending order (-1 beyond), pixels[b, .] their pixel counts (0
+ *   beyond); ids, pixels int32 [B, RA_OVERLAP_MAX_GT], count, status int32 [B].  Ids live in [0, 65535], the range of the
+ *   16-bit PNG, and an image has at most RA_OVERLAP_MAX_GT distinct ids: that cap is a constant of the kernels and rests on
+ *   no measurement of the real dataset (which this project cannot read).  status[b] is 0 or a sum of RA_GT_STATUS_RANGE
+ *   (an id outside [0, 65535] was met) and RA_GT_STATUS_COUNT (more distinct ids than the cap: the smallest
+ *   RA_OVERLAP_MAX_GT of those kept are listed); such ids are counted in a reject slot and never index anything, and the
+ *   other images of the batch are unaffected.  ws: ra_gt_instance_catalog_workspace_ints(B, H, W) ints.
+ * ra_instance_overlap_f32 — :306-307, :333: a pixel belongs to prediction t of image b where y[b,t] != 0 (y float32
+ *   [B,T,H,W]); pred_pixels[b,t] is their number and inter[b,t,g] the number of them on catalogue entry g (gt_ids ==
+ *   ids[b,g]; 0 for g >= count[b]); inter int32 [B,T,RA_OVERLAP_MAX_GT], pred_pixels int32 [B,T].  ids, count: what
+ *   ra_gt_instance_catalog_i32 wrote.  Pixels whose id is not in the catalogue count in pred_pixels only.  y and gt_ids
+ *   are read once each (16-byte loads when H * W % 4 == 0 and both are 16-byte aligned); integer counters, workgroup
+ *   partials in ws (ra_instance_overlap_workspace_ints(B, T, H, W) ints) added by a second launch: exact, and the same on
+ *   every run.  1 <= T <= 32, else RA_E_SHAPE and nothing is launched.
+ * ---------------------------------------------------------------------------------- */
+#define RA_OVERLAP_MAX_GT 256
+#define RA_GT_STATUS_RANGE 1
+#define RA_GT_STATUS_COUNT 2
+size_t ra_gt_instance_catalog_workspace_ints(int B, int H, int W);
+int ra_gt_instance_catalog_i32(const int *gt_ids, int B, int H, int W, int *ws, size_t ws_ints, int *ids, int *pixels,
+                               int *count, int *status, void *stream);
+size_t ra_instance_overlap_workspace_ints(int B, int T, int H, int W);
+int ra_instance_overlap_f32(const float *y, const int *gt_ids, const int *ids, const int *count, int B, int T, int H, int W,
+                            int *ws, size_t ws_ints, int *inter, int *pred_pixels, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Training step (full_model.py:1039-1057).
  * ra_adam_step_f32 — gradient clip + Adam on one flat float32 bucket of n parameters:
  *   g = clip(grads * grad_scale + wd_coef * params, -clip, clip)   (wd_coef nullable; the

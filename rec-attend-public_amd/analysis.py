@@ -216,3 +216,183 @@ class RenderCityScapesOutputAnalyzer(object):
 
   def finalize(self):
     pass
+
+
+# ---- Cityscapes instance-level AP (data_api/cityscapes_scripts/evaluation/evalInstanceLevelSemanticLabeling.py) ----
+# Line numbers below are that script's.  The pixel work (assignGt2Preds' count_nonzero per prediction and ground-truth
+# instance, :306-333) runs on the device (ops.gt_instance_catalog, ops.instance_overlap); what is left is a few hundred
+# integers per image, the MATCH RECORD, and float64 NumPy on those.
+AP_MIN_REGION_SIZES = [100, 1000, 1000]            # :136; only the first is used without distances (:386-389)
+AP_DISTANCE_THS = [float('inf'), 100.0, 50.0]      # :138
+AP_DISTANCE_CONFS = [-float('inf'), 0.5, 0.5]      # :140
+# label ids with ignoreInEval in helpers/labels.py (:282-286); its id -1 (license plate) cannot occur in a 16-bit image
+AP_VOID_LABEL_IDS = (0, 1, 2, 3, 4, 5, 6, 9, 10, 14, 15, 16, 18, 29, 30)
+
+
+def _ap_overlaps():
+  import numpy as np
+  return np.arange(0.5, 1., 0.05)
+
+
+def cityscapes_match_record(gt_ids, gt_pixels, inter, pred_pixels, label_id, conf):
+  """The match record of one image (assignGt2Preds, :260-353) from host arrays: gt_ids, gt_pixels [G] the image's catalogue
+  (distinct raw values of the instance-id image, ascending, and their pixel counts), inter [T,G] and pred_pixels [T] the
+  overlap counts, label_id [T] (-1 = not written), conf [T].  A prediction is kept when its label is one of the eight
+  evaluated classes and it has pixels (:297-311); its confidence is what the script would read back from the text file,
+  float('%f' % conf); its void intersection is the sum of inter over entries whose RAW value is an ignoreInEval label id
+  (:282-286,:321).  Returns a dict of arrays: gt_id, gt_pixels [G]; pred_label, pred_pixels, pred_void [P] int64, pred_conf
+  [P] float64, inter [P,G] int64."""
+  import numpy as np
+  gt_ids = np.asarray(gt_ids, np.int64).reshape(-1)
+  gt_pixels = np.asarray(gt_pixels, np.int64).reshape(-1)
+  inter = np.asarray(inter, np.int64).reshape(-1, gt_ids.size)
+  pred_pixels = np.asarray(pred_pixels, np.int64).reshape(-1)
+  label_id = np.asarray(label_id, np.int64).reshape(-1)
+  conf = np.asarray(conf, np.float64).reshape(-1)
+  evaluated = [l for _, l in CITYSCAPES_LABELS]
+  keep = np.array([int(l) in evaluated and int(n) > 0 for l, n in zip(label_id, pred_pixels)], bool)
+  void = np.isin(gt_ids, AP_VOID_LABEL_IDS)
+  return {'gt_id': gt_ids, 'gt_pixels': gt_pixels, 'pred_label': label_id[keep], 'pred_pixels': pred_pixels[keep],
+          'pred_void': inter[keep][:, void].sum(axis=1), 'pred_conf': np.array([float('%f' % c) for c in conf[keep]], np.float64),
+          'inter': inter[keep]}
+
+
+def _ap_of_curve(y_true, y_score, hard_fns):
+  """:490-543: the area under the precision-recall curve of the examples (y_true 0 / 1, y_score), one point per distinct
+  score plus the point (recall 0, precision 1), integrated with steps of half the recall difference of the neighbours."""
+  import numpy as np
+  order = np.argsort(y_score, kind='stable')
+  score, true = y_score[order], y_true[order]
+  below_incl = np.cumsum(true)
+  _, first = np.unique(score, return_index=True)
+  n_true = below_incl[-1]
+  below = np.where(first > 0, below_incl[first - 1], 0.0)  # true examples scored below each threshold
+  tp = n_true - below
+  fp = (score.size - first) - tp
+  fn = below + hard_fns
+  precision = np.append(tp / (tp + fp), 1.0)
+  recall = np.append(tp / (tp + fn), 0.0)
+  ext = np.concatenate([recall[:1], recall, [0.0]])
+  return float(np.dot(precision, 0.5 * (ext[:-2] - ext[2:])))
+
+
+def cityscapes_ap(records, min_region=AP_MIN_REGION_SIZES[0]):
+  """evaluateMatches (:356-551) without distance terms (distanceAvailable = False) on a list of match records -> ap
+  [1, 8 classes, 10 overlaps] float64.  Per class and overlap threshold, per image: a ground-truth instance (raw id >= 1000,
+  at least min_region pixels) is matched by every prediction of its class with IoU above the threshold; the best-scored one
+  makes it a true example and every other one a false positive (:438-445); an instance without a match is a hard false
+  negative.  A prediction that matches no ground-truth entry of its class at all (groups and small instances included) is
+  a false positive unless more than the threshold of its pixels lie on void, on a group (raw id < 1000) or on an instance
+  below min_region (:468-483).  A class with no ground truth and no prediction gives NaN, with ground truth only 0.  Should
+  every prediction of a class be ignored and no instance be matched there are no examples at all; the script fails on that
+  (an index into an empty cumulative sum), here the AP is 0."""
+  import numpy as np
+  overlaps = _ap_overlaps()
+  ap = np.zeros((1, len(CITYSCAPES_LABELS), len(overlaps)), np.float64)
+  for li, (_, label) in enumerate(CITYSCAPES_LABELS):
+    per_image = []
+    have_gt = have_pred = False
+    for r in records:
+      gid = r['gt_id']
+      cols = np.where(np.where(gid < 1000, gid, gid // 1000) == label)[0]
+      rows = np.where(r['pred_label'] == label)[0]
+      gpix = r['gt_pixels'][cols].astype(np.float64)
+      ppix = r['pred_pixels'][rows].astype(np.float64)
+      inter = r['inter'][np.ix_(rows, cols)].astype(np.float64)
+      iou = inter / (gpix[None, :] + ppix[:, None] - inter) if inter.size else inter  # > 0 wherever the union is
+      real = (gid[cols] >= 1000) & (r['gt_pixels'][cols] >= min_region)
+      ignore = r['pred_void'][rows].astype(np.float64) + (inter * ((gid[cols] < 1000).astype(np.float64) +
+                                                                   (r['gt_pixels'][cols] < min_region))[None, :]).sum(axis=1)
+      have_gt |= bool(real.any())
+      have_pred |= rows.size > 0
+      per_image.append((inter > 0, iou, real, ignore / np.maximum(ppix, 1.0), r['pred_conf'][rows]))
+    for oi, th in enumerate(overlaps):
+      if not (have_gt and have_pred):
+        ap[0, li, oi] = 0.0 if have_gt else float('nan')
+        continue
+      trues, scores, hard_fns = [], [], 0
+      for touch, iou, real, ignored, conf in per_image:
+        hit = touch & (iou > th)
+        for g in np.where(real)[0]:
+          c = np.sort(conf[hit[:, g]])
+          if c.size == 0:
+            hard_fns += 1
+            continue
+          trues += [1.0] + [0.0] * (c.size - 1)  # the best score is the match, the others are false positives
+          scores += [c[-1]] + c[:-1].tolist()
+        lone = ~hit.any(axis=1) & (ignored <= th)
+        trues += [0.0] * int(lone.sum())
+        scores += conf[lone].tolist()
+      ap[0, li, oi] = _ap_of_curve(np.array(trues), np.array(scores), hard_fns) if trues else 0.0
+  return ap
+
+
+def cityscapes_ap_averages(ap):
+  """computeAverages (:553-579) without distance terms: allAp = the mean over classes and overlaps that are not NaN, allAp50% the
+  same at overlap 0.5, and per class 'ap' (the mean over the overlaps) and 'ap50%'."""
+  import warnings
+  import numpy as np
+  with warnings.catch_warnings():
+    warnings.simplefilter('ignore', RuntimeWarning)  # a mean over nothing but NaN is NaN, as in the script
+    avg = {'allAp': float(np.nanmean(ap[0])), 'allAp50%': float(np.nanmean(ap[0, :, 0])), 'classes': {}}
+  for li, (name, _) in enumerate(CITYSCAPES_LABELS):
+    avg['classes'][name] = {'ap': float(np.average(ap[0, li, :])), 'ap50%': float(ap[0, li, 0])}
+  return avg
+
+
+def cityscapes_ap_result(records):
+  """The dict of prepareJSONDataForResults (:644-654) for a list of match records."""
+  ap = cityscapes_ap(records)
+  return {'averages': cityscapes_ap_averages(ap), 'overlaps': _ap_overlaps().tolist(), 'minRegionSizes': list(AP_MIN_REGION_SIZES),
+          'distanceThresholds': list(AP_DISTANCE_THS), 'minStereoDensities': list(AP_DISTANCE_CONFS),
+          'instLabels': [n for n, _ in CITYSCAPES_LABELS], 'resultApMatrix': ap.tolist()}
+
+
+def cityscapes_ap_table(averages):
+  """printResults (:581-642) without colour codes and distance columns, as one string."""
+  row = lambda what, a, b: '{:<15}'.format(what) + ':' + '{:>15.3f}'.format(a) + '{:>15.3f}'.format(b)
+  lines = ['', '#' * 50, '{:<15}'.format('what') + ':' + '{:>15}'.format('AP') + '{:>15}'.format('AP_50%'), '#' * 50]
+  lines += [row(name, averages['classes'][name]['ap'], averages['classes'][name]['ap50%']) for name, _ in CITYSCAPES_LABELS]
+  lines += ['-' * 50, row('average', averages['allAp'], averages['allAp50%']), '']
+  return '\n'.join(lines)
+
+
+class CityscapesAPAnalyzer(object):
+  """The scorer behind the output stage: AP and AP50% of the Cityscapes instance-level evaluation, from the masks while they
+  are on the device.  names: as for RenderCityScapesOutputAnalyzer.  stage(results) takes what
+  cityscapes_eval.iter_label_instances yields — 'y_out' [B,T,H,W], 'conf' [B,T], 'label_id' int32 [B,T] (-1 = not written),
+  'indices' — plus 'gt_ids' int32 [B,H,W] on the device, runs the catalogue and the overlap kernel (once per 32 predictions; T
+  itself is not limited) and keeps one match record per image (cityscapes_match_record); 'conf' and 'label_id' may also be host arrays (scores read from text files keep
+  their float64 value that way).  finalize(path) evaluates all staged images, writes the result as JSON when given a path,
+  prints the table and returns the dict.  One process: records of several ranks are not merged here."""
+
+  def __init__(self, names):
+    self.names = list(names)
+    self.records = []  # (name, match record) per staged image
+
+  def stage(self, results):
+    import numpy as np
+    y, gt = results['y_out'], results['gt_ids']
+    indices = [int(i) for i in results['indices']]
+    img_names = [str(self.names[i]) for i in indices]
+    host = lambda a: a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+    catalog = ops.gt_instance_catalog(gt, names=img_names)
+    # the counts of one prediction do not depend on the others: more than the kernel's 32 go in several launches on one catalogue
+    parts = [ops.instance_overlap(y[:, t0:t0 + ops.OVERLAP_MAX_T].contiguous(), gt, catalog)
+             for t0 in range(0, y.shape[1], ops.OVERLAP_MAX_T)]
+    inter, pred = (torch.cat(p, dim=1) for p in zip(*parts))
+    ids, pixels, count = (host(t) for t in catalog)
+    inter, pred, lab, conf = host(inter), host(pred), host(results['label_id']), host(results['conf'])
+    for ii, name in enumerate(img_names):
+      n = int(count[ii])
+      self.records.append((name, cityscapes_match_record(ids[ii, :n], pixels[ii, :n], inter[ii, :, :n], pred[ii], lab[ii], conf[ii])))
+
+  def finalize(self, path=None, quiet=False):
+    import json
+    result = cityscapes_ap_result([r for _, r in self.records])
+    if path is not None:
+      with open(path, 'w') as f:
+        json.dump(result, f, indent=4, sort_keys=True)
+    if not quiet:
+      print(cityscapes_ap_table(result['averages']))
+    return result

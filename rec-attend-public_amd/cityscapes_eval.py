@@ -9,7 +9,8 @@ Like the reference it does not run the model.  --input is an .npz with
   y_out     [N,h,w,C]   the pre-stage's semantic map (fg_model_pack.py's y_out / full_model's y_in; channel 0 = background),
 and optionally y_gt_full [N,T,H,W] + s_gt [N,T] (ground truth at the labels' size: the --analyzers then run per threshold),
 names (N file names, default 'image_<i>') and full_size (H, W; default: y_gt_full's size, else 1024 x 2048 for
---dataset cityscapes and the network size otherwise).
+--dataset cityscapes and the network size otherwise), and gt_instance_ids [N,H,W] (the values of the *_gtFine_instanceIds.png files
+at full_size: then the Cityscapes instance-level AP is computed as well, see below).
 
 Per image (write_log, :148-205), all on the device, batch by batch:
   1. + 2. the foreground mask of the semantic map at full size, FG_THRESHOLD = 0.3 (ops.sem_foreground);
@@ -22,6 +23,10 @@ Per image (write_log, :148-205), all on the device, batch by batch:
   5. <output>/output_<split>/cityscapes/<run>/<name>.txt + one 8-bit PNG per written instance
      (analysis.RenderCityScapesOutputAnalyzer); every threshold writes into the same folder, as in the reference, so the last
      threshold of the list is what remains on disk.
+  6. with gt_instance_ids in --input: AP and AP50% of the reference's last step (run_cityscapes_eval.sh:51,
+     evalInstanceLevelSemanticLabeling.py) per threshold from the masks on the device (analysis.CityscapesAPAnalyzer), written
+     to <output>/output_<split>/resultInstanceLevelSemanticLabeling.json: the script's structure for the LAST threshold — what
+     the files left on disk would score — plus a key 'thresholds' with the averages of every threshold.
 The per-threshold means of the analyzers go to <output>/output_<split>/metrics.yaml.  Two names of the reference's default
 --analyzers list (and of its --test list), fg_iou_all and bg_iou_all, accumulate over the whole dataset (analysis.py:834-900)
 and are not built: the default lists run without them and say so on standard output; naming one explicitly is an error.
@@ -164,6 +169,11 @@ def main(argv=None):
   os.makedirs(out_dir, exist_ok=True)
   thresholds = opt['threshold_list']
   renders = [analysis.RenderCityScapesOutputAnalyzer(os.path.join(out_dir, 'cityscapes'), names) for _ in thresholds]
+  have_ids = 'gt_instance_ids' in data
+  all_ids = data['gt_instance_ids'] if have_ids else None  # the largest array of the file: inflated once, not once per batch
+  if have_ids and tuple(all_ids.shape) != (N, H, W):
+    raise RecAttendError('--input: gt_instance_ids is %s, expected %s (N images at full_size)' % (tuple(all_ids.shape), (N, H, W)))
+  scorers = [analysis.CityscapesAPAnalyzer(names) for _ in thresholds] if have_ids else []
   acc = [{n: [] for n in an_names} for _ in thresholds]
   bs = max(1, min(opt['batch_size'], MAX_BATCH_ELEMS // max(1, T * H * W)))
   dev = torch.device('cuda', torch.cuda.current_device())
@@ -172,6 +182,7 @@ def main(argv=None):
     b1 = min(hi, b0 + bs)
     gt = up(data['y_gt_full'][b0:b1]) if have_gt else None
     sg = up(data['s_gt'][b0:b1]) if have_gt else None
+    ids = torch.as_tensor(np.ascontiguousarray(all_ids[b0:b1], dtype=np.int32)).to(dev) if have_ids else None
     chain = iter_label_instances(up(data['y_out_ins'][b0:b1]), up(data['s_out'][b0:b1]), up(data['y_out'][b0:b1]), (H, W),
                                  thresholds, opt['remove_tiny'])
     for tt, res in enumerate(chain):
@@ -183,6 +194,9 @@ def main(argv=None):
         for n in an_names:
           acc[tt][n].append(analysis.create_analyzer(n)(res).cpu().numpy())
       renders[tt].stage(res)
+      if have_ids:
+        res['gt_ids'] = ids
+        scorers[tt].stage(res)
   for r in renders:
     r.finalize()
   summary = {}
@@ -191,6 +205,13 @@ def main(argv=None):
     summary['%.2f' % th] = {n: {'mean': float(v.mean()) if v.size else 0.0, 'count': int(v.size)} for n, v in vals.items()}
   with open(os.path.join(out_dir, 'metrics.yaml'), 'w') as f:
     yaml.safe_dump(summary, f)
+  if have_ids:
+    import json
+    results = [sc.finalize(quiet=True) for sc in scorers]
+    out = dict(results[-1], thresholds={'%.2f' % th: r['averages'] for th, r in zip(thresholds, results)})
+    with open(os.path.join(out_dir, 'resultInstanceLevelSemanticLabeling.json'), 'w') as f:
+      json.dump(out, f, indent=4, sort_keys=True)
+    print(analysis.cityscapes_ap_table(out['averages']))
   print('images [%d, %d) -> %s' % (lo, hi, os.path.join(out_dir, 'cityscapes')))
   return renders
 

@@ -1128,3 +1128,81 @@ def instance_class_pick(vote, conf):
   check(rn.lib().ra_instance_class_pick_f32(ptr(vote), ptr(conf), B, T, Cc, ptr(idx), ptr(lab), rn.stream_ptr()),
         'ra_instance_class_pick_f32')
   return idx, lab
+
+
+# ---------------------------------------------------------------------------- Cityscapes instance-level AP: the matching step
+MAX_GT = rn.RA_OVERLAP_MAX_GT  # distinct ids per image: a constant of the kernels, resting on no measurement of the dataset
+OVERLAP_MAX_T = 32   # predictions per launch of ra_instance_overlap_f32
+OVERLAP_MAX_B = 65535  # images per launch (the grid's y extent)
+
+
+def _need_cuda_i32(t, what):
+  if not t.is_cuda:
+    raise rn.RecAttendError('recattend kernels need CUDA (HIP) tensors; got a CPU tensor for %s. There is no CPU fallback.' % what)
+  if t.dtype != torch.int32:
+    raise rn.RecAttendError('%s must be an int32 tensor, got %s' % (what, t.dtype))
+  if not t.is_contiguous():
+    raise rn.RecAttendError('%s must be contiguous, got strides %s for shape %s' % (what, tuple(t.stride()), tuple(t.shape)))
+
+
+def gt_instance_catalog(gt_ids, check_status=True, names=None):
+  """instances2dict.py:37-40 on the device: gt_ids int32 [B,H,W] (the values of *_gtFine_instanceIds.png) -> (ids, pixels,
+  count): int32 [B,MAX_GT] the distinct ids of every image in ascending order (-1 beyond count) and their pixel counts, int32
+  [B] how many there are (ra_gt_instance_catalog_i32).  check_status (one device-to-host copy of B ints): an image with an
+  id outside [0, 65535] or with more than MAX_GT distinct ids raises RecAttendError naming it (names[b], else its index);
+  with check_status=False the status words are returned as a fourth tensor instead."""
+  _need_cuda_i32(gt_ids, 'gt_ids')
+  if gt_ids.dim() != 3 or min(gt_ids.shape) < 1:
+    raise rn.RecAttendError('gt_instance_catalog: gt_ids must be [B,H,W], got %s' % (tuple(gt_ids.shape),))
+  B, H, W = gt_ids.shape
+  if H * W >= 1 << 31 or B > OVERLAP_MAX_B:
+    raise rn.RecAttendError('gt_instance_catalog: B=%d, H * W = %d (B <= %d, H * W < 2^31)' % (B, H * W, OVERLAP_MAX_B))
+  dev = gt_ids.device
+  n = rn.lib().ra_gt_instance_catalog_workspace_ints(B, H, W)
+  ws = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+  ids = torch.empty((B, MAX_GT), dtype=torch.int32, device=dev)
+  pixels = torch.empty((B, MAX_GT), dtype=torch.int32, device=dev)
+  count = torch.empty((B,), dtype=torch.int32, device=dev)
+  status = torch.empty((B,), dtype=torch.int32, device=dev)
+  check(rn.lib().ra_gt_instance_catalog_i32(ptr(gt_ids), B, H, W, ptr(ws), n, ptr(ids), ptr(pixels), ptr(count), ptr(status),
+                                            rn.stream_ptr()), 'ra_gt_instance_catalog_i32')
+  if not check_status:
+    return ids, pixels, count, status
+  for b, st in enumerate(status.cpu().tolist()):
+    if st:
+      why = []
+      if st & rn.RA_GT_STATUS_RANGE:
+        why.append('an instance id outside [0, 65535]')
+      if st & rn.RA_GT_STATUS_COUNT:
+        why.append('more than %d distinct instance ids' % MAX_GT)
+      raise rn.RecAttendError('gt_instance_catalog: image %s has %s' % (names[b] if names is not None else b, ' and '.join(why)))
+  return ids, pixels, count
+
+
+def instance_overlap(y, gt_ids, catalog):
+  """evalInstanceLevelSemanticLabeling.py:306-307,:333 for every prediction and ground-truth entry at once: y float32
+  [B,T,H,W] (a pixel belongs to prediction t where y != 0), gt_ids int32 [B,H,W], catalog = gt_instance_catalog(gt_ids) ->
+  (inter int32 [B,T,MAX_GT], pred_pixels int32 [B,T]) (ra_instance_overlap_f32).  Exact integer counts."""
+  _need_cuda(y)
+  _need_cuda_i32(gt_ids, 'gt_ids')
+  ids, count = catalog[0], catalog[2]
+  _need_cuda_i32(ids, 'catalog ids')
+  _need_cuda_i32(count, 'catalog count')
+  if y.dim() != 4 or gt_ids.dim() != 3 or min(y.shape) < 1:
+    raise rn.RecAttendError('instance_overlap: y must be [B,T,H,W] and gt_ids [B,H,W], got %s and %s' % (
+        tuple(y.shape), tuple(gt_ids.shape)))
+  B, T, H, W = y.shape
+  if tuple(gt_ids.shape) != (B, H, W) or tuple(ids.shape) != (B, MAX_GT) or tuple(count.shape) != (B,):
+    raise rn.RecAttendError('instance_overlap: y %s, gt_ids %s, catalog ids %s, count %s do not belong together' % (
+        tuple(y.shape), tuple(gt_ids.shape), tuple(ids.shape), tuple(count.shape)))
+  if T > OVERLAP_MAX_T or H * W >= 1 << 31 or B > OVERLAP_MAX_B:
+    raise rn.RecAttendError('instance_overlap: B=%d, T=%d, H * W = %d (B <= %d, T <= %d, H * W < 2^31)' % (
+        B, T, H * W, OVERLAP_MAX_B, OVERLAP_MAX_T))
+  dev = y.device
+  n = rn.lib().ra_instance_overlap_workspace_ints(B, T, H, W)
+  ws = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+  inter = torch.empty((B, T, MAX_GT), dtype=torch.int32, device=dev)
+  pred = torch.empty((B, T), dtype=torch.int32, device=dev)
+  check(rn.lib().ra_instance_overlap_f32(ptr(y), ptr(gt_ids), ptr(ids), ptr(count), B, T, H, W, ptr(ws), n, ptr(inter), ptr(pred),
+                                         rn.stream_ptr()), 'ra_instance_overlap_f32')
+  return inter, pred
