@@ -52,6 +52,29 @@ struct [[maybe_unused]] MaxDynamicLds {
   }
 };
 
+// ---- Device facts a persistent launch sizes its grid with ------------------------------------------------------------------
+// Compute units of the current device, asked once per process; 256 (an MI355X) when the device cannot be asked or reports <= 0.
+// Defined here, not in ra_core.hip: the stand-alone probes under tools/ compile one conv source without the library's core.
+inline int cu_count() {
+  static const int n = [] {
+    int dev = 0;
+    hipDeviceProp_t prop;
+    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess && prop.multiProcessorCount > 0)
+      return (int)prop.multiProcessorCount;
+    return 256;
+  }();
+  return n;
+}
+// A kernel's resident workgroups (of 256 threads) per CU at `lds` bytes of dynamic LDS, at least 1; raises the kernel's LDS limit
+// to `lds` first.  A launch function keeps the result in a `static`: asked once per instantiation, at its first launch.
+template <typename K>
+int wgs_per_cu(K kern, size_t lds) {
+  MaxDynamicLds{kern, lds};
+  int n = 0;
+  if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256, lds) != hipSuccess || n < 1) n = 1;
+  return n;
+}
+
 // Wave priority of the decode loop's LATENCY-bound kernels (controller, patch-sized convs, extract, paste, score).  In the
 // decode pipeline they share every SIMD with another batch's MFMA-bound controller-CNN waves, and the arbiter deals issue
 // slots oldest-first: a tail wave's few hundred dependent instructions each queue behind the other waves' 32-cycle MFMAs.

@@ -23,7 +23,7 @@
 // This file is compiled four times (Makefile): RA_K1_PART 0 = the decode loop's float32 kernels + every host entry
 // point, 1 = the bf16-operand variants, 2 = float32 with batch moments in the epilogue (the training forward), 3 = the
 // decode loop's float32 kernels for filter sizes 1, 5 and 7 (ra_convkxk_f32).  The sets of template instantiations build
-// in parallel; part 0's entry forwards to the other parts' dispatchers.
+// in parallel; part 0 chooses the form of every launch (choose_form) and hands it to the part that builds its kernel.
 #ifndef RA_K1_PART
 #define RA_K1_PART 0
 #endif
@@ -32,18 +32,6 @@ namespace ra {
 namespace conv {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-inline int num_cus() {
-  static int n = 0;
-  if (!n) {
-    int dev = 0;
-    hipDeviceProp_t prop;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess)
-      n = prop.multiProcessorCount;
-    if (n <= 0) n = 256;
-  }
-  return n;
-}
 
 struct Args {
   const float *src0;
@@ -617,31 +605,37 @@ __global__ __launch_bounds__(256, (GX * GY * NC > 8) ? 1 : 2) void conv3x3_mfma(
   }
 }
 
-template <int CK, int NC, int WN, int GX, int GY, bool SWAP, bool BF16 = false, bool MOM = false, bool UPS = false, int KF = 3>
-int launch_s(const Args &a, int B, hipStream_t st, int *plan) {
+// The K1 form a shape takes, as a value: choose_form() below is the policy, instantiate() the map to the kernel built for it.
+struct Form {
+  int ck;        // input channels per staged chunk
+  int nc, wn;    // cout groups of 16 per wave x waves along cout
+  int gx, gy;    // pixel groups per wave: the tile is 8 gx columns x 2 gy (4 / wn) rows
+  int kf;        // filter size
+  bool swap;     // weights as the A operand: channel-vector stores (SWAP)
+  bool ups;      // the sub-pixel form of the stride-2 transposed conv (UPS)
+  bool bf16;     // bf16 operands
+  bool moments;  // batch moments in the epilogue (MOM)
+};
+
+template <int CK, int NC, int WN, int GX, int GY, bool SWAP, bool BF16, bool MOM, bool UPS, int KF>
+int launch_s(const Form &f, const Args &a, int B, hipStream_t st, int *plan) {
   using G = Geo<CK, NC, WN, GX, GY, KF>;
   auto kern = conv3x3_mfma<CK, NC, WN, GX, GY, SWAP, BF16, MOM, UPS, KF>;
   constexpr size_t lds = 2 * G::LDS_FLOATS * sizeof(float);
   const int tiles_x = ceil_div(a.W, G::TW), tiles_y = ceil_div(a.H, G::TH);
   const int ntiles = tiles_x * tiles_y * B;
-  if (plan) {  // ra_conv3x3_plan: the instantiation this chain of choices ended at; the grid where a device can be asked
+  if (plan) {  // ra_conv3x3_plan: the form that was chosen; the grid where a device can be asked
     plan[RA_PLAN_FAMILY] = RA_PLAN_FAMILY_K1;
-    plan[RA_PLAN_FORM] = (SWAP ? RA_PLAN_FORM_SWAP : 0) | (UPS ? RA_PLAN_FORM_SUBPIXEL : 0) | (BF16 ? RA_PLAN_FORM_BF16 : 0) |
-                         (MOM ? RA_PLAN_FORM_MOMENTS : 0) | (KF != 3 ? RA_PLAN_FORM_KXK : 0);
-    plan[RA_PLAN_CK] = CK, plan[RA_PLAN_NC] = NC, plan[RA_PLAN_WN] = WN, plan[RA_PLAN_GX] = GX, plan[RA_PLAN_GY] = GY;
-    plan[RA_PLAN_KF] = KF, plan[RA_PLAN_TILE_H] = G::TH, plan[RA_PLAN_TILE_W] = G::TW;
+    plan[RA_PLAN_FORM] = (f.swap ? RA_PLAN_FORM_SWAP : 0) | (f.ups ? RA_PLAN_FORM_SUBPIXEL : 0) | (f.bf16 ? RA_PLAN_FORM_BF16 : 0) |
+                         (f.moments ? RA_PLAN_FORM_MOMENTS : 0) | (f.kf != 3 ? RA_PLAN_FORM_KXK : 0);
+    plan[RA_PLAN_CK] = f.ck, plan[RA_PLAN_NC] = f.nc, plan[RA_PLAN_WN] = f.wn, plan[RA_PLAN_GX] = f.gx, plan[RA_PLAN_GY] = f.gy;
+    plan[RA_PLAN_KF] = f.kf, plan[RA_PLAN_TILE_H] = G::TH, plan[RA_PLAN_TILE_W] = G::TW;
     plan[RA_PLAN_TILES_X] = tiles_x, plan[RA_PLAN_TILES_Y] = tiles_y, plan[RA_PLAN_NTILES] = ntiles;
     plan[RA_PLAN_GRID] = plan[RA_PLAN_TILES_MIN] = plan[RA_PLAN_TILES_MAX] = -1;
     if (!plan_have_device()) return 0;
   }
-  static int wgs_per_cu = 0;  // idempotent lazy init
-  if (!wgs_per_cu) {
-    MaxDynamicLds{kern, lds};
-    int n = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&n, kern, 256, lds) != hipSuccess || n < 1) n = 1;
-    wgs_per_cu = n > 4 ? 4 : n;
-  }
-  const int cap = wgs_per_cu * num_cus();
+  static const int resident = wgs_per_cu(kern, lds);
+  const int cap = (resident > 4 ? 4 : resident) * cu_count();
   const int grid = ntiles < cap ? ntiles : cap;
   if (plan) {  // workgroup g walks tiles g, g + grid, ...
     plan_walk(plan, ntiles, grid, 0);
@@ -658,148 +652,167 @@ int launch_s(const Args &a, int B, hipStream_t st, int *plan) {
 inline int chunk_of(int Cin) { return (Cin % 16 == 0) ? 16 : (Cin % 8 == 0) ? 8 : 4; }
 inline int chunk_of_k(int KF, int Cin) { return KF <= 3 ? chunk_of(Cin) : (KF == 5 && Cin % 8 == 0) ? 8 : 4; }
 
-#if RA_K1_PART != 3
-namespace {  // the dispatch chain differs between the parts of this file (RA_K1_PART): internal linkage, one per part
-inline bool ups_subpixel() {  // RA_CONV_UPS_SUBPIXEL=0: the zero-stuffed form of rounds 1-5 (A/B aid)
-  static const bool on = env_int("RA_CONV_UPS_SUBPIXEL", 1) != 0;
-  return on;
-}
-template <int CK, int NC, int WN, int GX, int GY>
-int launch(const Args &a, int B, hipStream_t st, int *plan) {
-  // channel-vector stores pay off when there is no pooling and the channel count allows float4
-  const bool swap = a.pool == 1 && (a.Cout & 3) == 0;
-  if (a.mom_part && !swap)
-    return ra::fail(RA_E_SHAPE, "ra_conv3x3_moments_f32: needs pool 1 and Cout %% 4 == 0 (Cout %d, pool %d)", a.Cout, a.pool);
+// ---- From a Form to the kernel built for it: no policy here.  Each part of this file (RA_K1_PART) builds its own set ------------
+namespace {  // the sets differ between the parts: internal linkage, one chain per part
+template <int KF, int CK, int NC, int WN, int GX, int GY>
+int instantiate_flags(const Form &f, const Args &a, int B, hipStream_t st, int *plan) {
 #if RA_K1_PART == 1  // bf16 operands
-  if (swap) {
-    if (a.mom_part) return launch_s<CK, NC, WN, GX, GY, true, true, true>(a, B, st, plan);
-    return launch_s<CK, NC, WN, GX, GY, true, true>(a, B, st, plan);
-  }
-  return launch_s<CK, NC, WN, GX, GY, false, true>(a, B, st, plan);
+  if (f.moments) return launch_s<CK, NC, WN, GX, GY, true, true, true, false, KF>(f, a, B, st, plan);
+  if (f.swap) return launch_s<CK, NC, WN, GX, GY, true, true, false, false, KF>(f, a, B, st, plan);
+  return launch_s<CK, NC, WN, GX, GY, false, true, false, false, KF>(f, a, B, st, plan);
 #elif RA_K1_PART == 2  // float32 + batch moments
-  return launch_s<CK, NC, WN, GX, GY, true, false, true>(a, B, st, plan);
+  return launch_s<CK, NC, WN, GX, GY, true, false, true, false, KF>(f, a, B, st, plan);
+#elif RA_K1_PART == 3  // the plain form only
+  return launch_s<CK, NC, WN, GX, GY, false, false, false, false, KF>(f, a, B, st, plan);
 #else
-  if (swap) {
-    if constexpr (GX == 2 && GY == 2) {
-      if (a.ups && ups_subpixel()) return launch_s<CK, NC, WN, GX, GY, true, false, false, true>(a, B, st, plan);
-    }
-    return launch_s<CK, NC, WN, GX, GY, true>(a, B, st, plan);
+  if constexpr (GX == 2 && GY == 2) {
+    if (f.ups) return launch_s<CK, NC, WN, GX, GY, true, false, false, true, KF>(f, a, B, st, plan);
   }
-  return launch_s<CK, NC, WN, GX, GY, false>(a, B, st, plan);
+  if (f.swap) return launch_s<CK, NC, WN, GX, GY, true, false, false, false, KF>(f, a, B, st, plan);
+  return launch_s<CK, NC, WN, GX, GY, false, false, false, false, KF>(f, a, B, st, plan);
 #endif
+}
+template <int KF, int CK, int NC, int WN>
+int instantiate_geo(const Form &f, const Args &a, int B, hipStream_t st, int *plan) {
+#if RA_K1_PART == 0
+  if (f.ups) return instantiate_flags<KF, CK, NC, WN, 2, 2>(f, a, B, st, plan);  // the sub-pixel kernels exist on (2, 2) alone
+#endif
+  switch (10 * f.gx + f.gy) {
+    case 42: return instantiate_flags<KF, CK, NC, WN, 4, 2>(f, a, B, st, plan);
+#if RA_K1_PART != 3
+    case 41: return instantiate_flags<KF, CK, NC, WN, 4, 1>(f, a, B, st, plan);
+    case 22: return instantiate_flags<KF, CK, NC, WN, 2, 2>(f, a, B, st, plan);
+#endif
+    case 21: return instantiate_flags<KF, CK, NC, WN, 2, 1>(f, a, B, st, plan);
+#if RA_K1_PART == 0 || RA_K1_PART == 3
+    case 11: return instantiate_flags<KF, CK, NC, WN, 1, 1>(f, a, B, st, plan);
+#endif
+  }
+  return fail(RA_E_SHAPE, "K1: no kernel built with %d x %d pixel groups per wave in part %d", f.gx, f.gy, RA_K1_PART);
+}
+template <int KF, int CK>
+int instantiate_cout(const Form &f, const Args &a, int B, hipStream_t st, int *plan) {
+  switch (10 * f.nc + f.wn) {
+    case 11: return instantiate_geo<KF, CK, 1, 1>(f, a, B, st, plan);
+    case 12: return instantiate_geo<KF, CK, 1, 2>(f, a, B, st, plan);
+    case 21: return instantiate_geo<KF, CK, 2, 1>(f, a, B, st, plan);
+    case 14: return instantiate_geo<KF, CK, 1, 4>(f, a, B, st, plan);
+    case 22: return instantiate_geo<KF, CK, 2, 2>(f, a, B, st, plan);
+    case 24: return instantiate_geo<KF, CK, 2, 4>(f, a, B, st, plan);
+  }
+  return fail(RA_E_SHAPE, "K1: no kernel built with %d cout groups x %d waves", f.nc, f.wn);
+}
+}  // namespace
+
+// this part's map; part 0's entry (run, below) chooses the form and hands it to the part that builds it
+#if RA_K1_PART == 1
+#define RA_K1_INSTANTIATE instantiate_bf16
+#elif RA_K1_PART == 2
+#define RA_K1_INSTANTIATE instantiate_moments
+#elif RA_K1_PART == 3
+#define RA_K1_INSTANTIATE instantiate_kxk
+#else
+#define RA_K1_INSTANTIATE instantiate_plain
+int instantiate_bf16(const Form &f, const Args &a, int B, hipStream_t st, int *plan);
+int instantiate_moments(const Form &f, const Args &a, int B, hipStream_t st, int *plan);
+int instantiate_kxk(const Form &f, const Args &a, int B, hipStream_t st, int *plan);
+#endif
+int RA_K1_INSTANTIATE(const Form &f, const Args &a, int B, hipStream_t st, int *plan) {
+  switch (100 * f.kf + f.ck) {
+#if RA_K1_PART != 3
+    case 316: return instantiate_cout<3, 16>(f, a, B, st, plan);
+    case 308: return instantiate_cout<3, 8>(f, a, B, st, plan);
+    case 304: return instantiate_cout<3, 4>(f, a, B, st, plan);
+#else  // KF in {1, 5, 7}, the chunks chunk_of_k gives them (nnlib.cnn / nnlib.dcnn layers of another filter size)
+    case 116: return instantiate_cout<1, 16>(f, a, B, st, plan);
+    case 108: return instantiate_cout<1, 8>(f, a, B, st, plan);
+    case 104: return instantiate_cout<1, 4>(f, a, B, st, plan);
+    case 508: return instantiate_cout<5, 8>(f, a, B, st, plan);
+    case 504: return instantiate_cout<5, 4>(f, a, B, st, plan);
+    case 704: return instantiate_cout<7, 4>(f, a, B, st, plan);
+#endif
+  }
+  return fail(RA_E_SHAPE, "ra_convkxk_f32: filter size %d not built (1, 3, 5, 7)", f.kf);
 }
 
-// Tile geometry choice: the biggest tile that still yields >= ~2 workgroups per CU, narrow
-// (16-col) tiles when the image width would leave a 32-col tile more than half empty.
-template <int CK, int NC, int WN>
-int dispatch_geo(const Args &a, int B, hipStream_t st, int *plan) {
-  constexpr int WM = 4 / WN;
-  auto wgs = [&](int gx, int gy) {
-    return (long)ceil_div(a.W, 8 * gx) * ceil_div(a.H, 2 * gy * WM) * B;
-  };
+#if RA_K1_PART == 0
+// ---- The policy: which form a shape takes.  Every threshold, tuning variable and rule of K1's choice is in this function -------
+// part: the part of this file whose kernels are asked for — 0 float32, 1 bf16 operands, 2 float32 + batch moments, 3 a KF x KF
+// filter, KF in {1, 5, 7}: the plain form only (pixels as the A operand at every pool / Cout, the zero-stuffed stride-2 transposed
+// conv) on three tile geometries.
+int choose_form(const Args &a, int B, int part, int KF, Form &f) {
+  const bool kxk = part == 3;
+  f = Form{};
+  f.kf = KF;
+  f.ck = chunk_of_k(KF, a.C0 + a.C1);
+  f.bf16 = part == 1;
+  f.moments = a.mom_part != nullptr;
+
+  // Cout groups per wave (nc) x waves along cout (wn).  Small problems (few tiles) split the cout
+  // groups over more waves so that each wave's serial MFMA chain is shorter.
+  const bool small = (long)ceil_div(a.W, 16) * ceil_div(a.H, 8) * B < 256;  // 8x16 tiles, wn = 1
+  switch (a.CoutP) {
+    case 16: f.nc = 1, f.wn = 1; break;
+    case 32: f.nc = small ? 1 : 2, f.wn = small ? 2 : 1; break;
+    case 64: f.nc = small ? 1 : 2, f.wn = small ? 4 : 2; break;
+    case 128: f.nc = 2, f.wn = 4; break;
+    default: return fail(RA_E_SHAPE, "%s: CoutP %d unsupported", kxk ? "ra_convkxk_f32" : "ra_conv3x3_f32", a.CoutP);
+  }
+
+  // channel-vector stores pay off when there is no pooling and the channel count allows float4
+  f.swap = !kxk && a.pool == 1 && (a.Cout & 3) == 0;
+  if (f.moments && !f.swap)
+    return fail(RA_E_SHAPE, "ra_conv3x3_moments_f32: needs pool 1 and Cout %% 4 == 0 (Cout %d, pool %d)", a.Cout, a.pool);
+
+  // Tile geometry: the biggest tile that still yields >= ~2 workgroups per CU, narrow (16-col) tiles when the image width would
+  // leave a 32-col tile more than half empty.
+  auto wgs = [&](int gx, int gy) { return (long)ceil_div(a.W, 8 * gx) * ceil_div(a.H, 2 * gy * (4 / f.wn)) * B; };
+  auto geo = [&](int gx, int gy) { f.gx = gx, f.gy = gy; };
   const bool narrow = (a.W % 32 != 0) && (a.W % 32 <= 16);
   const long want = 512;
-  static const int force = env_int("RA_CONV_GEO", 0);  // =<gx><gy> (e.g. 41) forces a geometry: tuning aid only
-#if RA_K1_PART == 0
+  constexpr int kTiny = 200;
+  static const int force_env = env_int("RA_CONV_GEO", 0);  // =<gx><gy> (e.g. 41) forces a geometry: tuning aid only
+  static const int ups_min = env_int("RA_CONV_UPS_MIN_WGS", 96);
+  static const int tiny_env = env_int("RA_CONV_TINY_WGS", kTiny);
+  static const bool subpixel = env_int("RA_CONV_UPS_SUBPIXEL", 1) != 0;  // =0: the zero-stuffed form of rounds 1-5 (A/B aid)
+  const int force = kxk ? 0 : force_env;  // the k x k kernels read no tuning variable
   // a stride-2 transposed conv without pooling runs its sub-pixel form (UPS), which lives on the (2, 2) geometry
   // ... where that geometry still yields enough workgroups: with few (a lone batch of 8 CVPPP patches: 16-72) the zero-stuffed
-  // form on one-group tiles has 4 x the workgroups at the same chain length per wave and wins (RA_CONV_UPS_MIN_WGS, profiles/r06_k1s_sweep.txt)
-  static const int ups_min = env_int("RA_CONV_UPS_MIN_WGS", 96);
-  if (!force && a.ups && a.pool == 1 && (a.Cout & 3) == 0 && !a.mom_part && ups_subpixel() && wgs(2, 2) >= ups_min)
-    return launch<CK, NC, WN, 2, 2>(a, B, st, plan);
-#endif
-  if (force == 42) return launch<CK, NC, WN, 4, 2>(a, B, st, plan);
-  if (force == 41) return launch<CK, NC, WN, 4, 1>(a, B, st, plan);
-  if (force == 22) return launch<CK, NC, WN, 2, 2>(a, B, st, plan);
-  if (force == 21) return launch<CK, NC, WN, 2, 1>(a, B, st, plan);
-  if (!narrow) {
-    if (wgs(4, 2) >= want) return launch<CK, NC, WN, 4, 2>(a, B, st, plan);
-    if (wgs(4, 1) >= want) return launch<CK, NC, WN, 4, 1>(a, B, st, plan);
-  }
-  if (wgs(2, 2) >= want) return launch<CK, NC, WN, 2, 2>(a, B, st, plan);
-#if RA_K1_PART == 0
+  // form on one-group tiles has 4 x the workgroups at the same chain length per wave and wins (RA_CONV_UPS_MIN_WGS, profiles/r06_k1s_sweep.txt).
+  // This gate is the ONLY place the sub-pixel form is chosen: a layer it rejects — RA_CONV_GEO forced, RA_CONV_UPS_MIN_WGS raised
+  // above the ladder's 512, RA_CONV_UPS_SUBPIXEL=0 — runs zero-stuffed, also on the (2, 2) geometry; RA_CONV_UPS_MIN_WGS=0
+  // selects sub-pixel wherever it applies.  (At the defaults the ladder's (2, 2) needs 512 >= 96 workgroups: the gate has taken it.)
+  if (part == 0 && !force && a.ups && f.swap && !f.moments && subpixel && wgs(2, 2) >= ups_min) {
+    f.ups = true;
+    geo(2, 2);
+  } else if (force == 42) geo(4, 2);
+  else if (force == 41) geo(4, 1);
+  else if (force == 22) geo(2, 2);
+  else if (force == 21) geo(2, 1);
+  else if (!narrow && wgs(4, 2) >= want) geo(4, 2);
+  else if (!kxk && !narrow && wgs(4, 1) >= want) geo(4, 1);  // k x k: the geometries (4, 2) / (2, 1) / (1, 1) only
+  else if (!kxk && wgs(2, 2) >= want) geo(2, 2);
   // round 6: ONE pixel group per wave (8-column tiles) where even the smallest two-group geometry leaves most of the chip
   // without a workgroup — the patch-sized layers with many channels (KITTI's attention DCNN: 128 -> 64 at 12 x 12 is 288
   // dependent k-steps per pixel group; two groups per wave and 96 workgroups made it 16.5 us whatever the batch).  RA_CONV_TINY_WGS:
-  // the workgroup count of the (2, 1) geometry below which the (1, 1) form is taken (0 = never).
-  static const int tiny = env_int("RA_CONV_TINY_WGS", 200);
-  if (force == 11 || (!force && wgs(2, 1) < tiny)) return launch<CK, NC, WN, 1, 1>(a, B, st, plan);
-#endif
-  return launch<CK, NC, WN, 2, 1>(a, B, st, plan);
+  // the workgroup count of the (2, 1) geometry below which the (1, 1) form is taken (0 = never); parts 1 and 2 build no (1, 1) kernels.
+  else if (kxk ? wgs(2, 1) < kTiny : part == 0 && (force == 11 || (!force && wgs(2, 1) < tiny_env))) geo(1, 1);
+  else geo(2, 1);
+  return 0;
 }
 
-// Cout groups per wave (NC) x waves along cout (WN).  Small problems (few tiles) split the cout
-// groups over more waves so that each wave's serial MFMA chain is shorter.
-template <int CK>
-int dispatch_cout(const Args &a, int B, hipStream_t st, int *plan) {
-  const long tiles_big = (long)ceil_div(a.W, 16) * ceil_div(a.H, 8) * B;  // 8x16 tiles, WN = 1
-  const bool small = tiles_big < 256;
-  switch (a.CoutP) {
-    case 16: return dispatch_geo<CK, 1, 1>(a, B, st, plan);
-    case 32: return small ? dispatch_geo<CK, 1, 2>(a, B, st, plan) : dispatch_geo<CK, 2, 1>(a, B, st, plan);
-    case 64: return small ? dispatch_geo<CK, 1, 4>(a, B, st, plan) : dispatch_geo<CK, 2, 2>(a, B, st, plan);
-    case 128: return dispatch_geo<CK, 2, 4>(a, B, st, plan);
-    default: return fail(RA_E_SHAPE, "ra_conv3x3_f32: CoutP %d unsupported", a.CoutP);
+// the form is chosen once, here, and handed to the part that builds its kernels
+int run(const Args &a, int B, int part, int KF, hipStream_t st, int *plan) {
+  Form f;
+  if (const int rc = choose_form(a, B, part, KF, f)) return rc;
+  switch (part) {
+    case 1: return instantiate_bf16(f, a, B, st, plan);
+    case 2: return instantiate_moments(f, a, B, st, plan);
+    case 3: return instantiate_kxk(f, a, B, st, plan);
+    default: return instantiate_plain(f, a, B, st, plan);
   }
 }
-
-}  // namespace
-
-// this part's dispatcher (the chain of template choices above); parts 1 and 2 export theirs to part 0's entry
-#if RA_K1_PART == 1
-#define RA_K1_DISPATCH k1_dispatch_bf16
-#elif RA_K1_PART == 2
-#define RA_K1_DISPATCH k1_dispatch_moments
-#else
-#define RA_K1_DISPATCH k1_dispatch_plain
-int k1_dispatch_bf16(const Args &a, int B, hipStream_t st, int *plan);
-int k1_dispatch_moments(const Args &a, int B, hipStream_t st, int *plan);
-int k1_dispatch_kxk(const Args &a, int KF, int B, hipStream_t st, int *plan);
-#endif
-int RA_K1_DISPATCH(const Args &a, int B, hipStream_t st, int *plan) {
-  switch (chunk_of(a.C0 + a.C1)) {
-    case 16: return dispatch_cout<16>(a, B, st, plan);
-    case 8: return dispatch_cout<8>(a, B, st, plan);
-    default: return dispatch_cout<4>(a, B, st, plan);
-  }
-}
-
-#else  // RA_K1_PART == 3: K1 with a KF x KF filter, KF in {1, 5, 7} (nnlib.cnn / nnlib.dcnn layers of another filter size)
-namespace {
-// The plain form only: pixels as the A operand (every pool / Cout), the zero-stuffed stride-2 transposed conv, and three tile
-// geometries — the 32 x 16 tile where it still yields ~2 workgroups per CU, else 16-col tiles, else one pixel group per wave.
-template <int KF, int CK, int NC, int WN>
-int kxk_geo(const Args &a, int B, hipStream_t st, int *plan) {
-  constexpr int WM = 4 / WN;
-  auto wgs = [&](int gx, int gy) { return (long)ceil_div(a.W, 8 * gx) * ceil_div(a.H, 2 * gy * WM) * B; };
-  const bool narrow = (a.W % 32 != 0) && (a.W % 32 <= 16);
-  if (!narrow && wgs(4, 2) >= 512) return launch_s<CK, NC, WN, 4, 2, false, false, false, false, KF>(a, B, st, plan);
-  if (wgs(2, 1) >= 200) return launch_s<CK, NC, WN, 2, 1, false, false, false, false, KF>(a, B, st, plan);
-  return launch_s<CK, NC, WN, 1, 1, false, false, false, false, KF>(a, B, st, plan);
-}
-template <int KF, int CK>
-int kxk_cout(const Args &a, int B, hipStream_t st, int *plan) {
-  const bool small = (long)ceil_div(a.W, 16) * ceil_div(a.H, 8) * B < 256;  // as dispatch_cout
-  switch (a.CoutP) {
-    case 16: return kxk_geo<KF, CK, 1, 1>(a, B, st, plan);
-    case 32: return small ? kxk_geo<KF, CK, 1, 2>(a, B, st, plan) : kxk_geo<KF, CK, 2, 1>(a, B, st, plan);
-    case 64: return small ? kxk_geo<KF, CK, 1, 4>(a, B, st, plan) : kxk_geo<KF, CK, 2, 2>(a, B, st, plan);
-    case 128: return kxk_geo<KF, CK, 2, 4>(a, B, st, plan);
-    default: return fail(RA_E_SHAPE, "ra_convkxk_f32: CoutP %d unsupported", a.CoutP);
-  }
-}
-}  // namespace
-
-int k1_dispatch_kxk(const Args &a, int KF, int B, hipStream_t st, int *plan) {
-  const int ck = chunk_of_k(KF, a.C0 + a.C1);
-  switch (KF) {
-    case 1: return ck == 16 ? kxk_cout<1, 16>(a, B, st, plan) : ck == 8 ? kxk_cout<1, 8>(a, B, st, plan) : kxk_cout<1, 4>(a, B, st, plan);
-    case 5: return ck == 8 ? kxk_cout<5, 8>(a, B, st, plan) : kxk_cout<5, 4>(a, B, st, plan);
-    case 7: return kxk_cout<7, 4>(a, B, st, plan);
-    default: return fail(RA_E_SHAPE, "ra_convkxk_f32: filter size %d not built (1, 3, 5, 7)", KF);
-  }
-}
-#endif  // RA_K1_PART
+#endif  // RA_K1_PART == 0
 
 }  // namespace conv
 }  // namespace ra
@@ -906,46 +919,63 @@ static int plan_conv8(int *plan, int form, int channels) {
   return 0;
 }
 
-static int conv3x3_entry(const float *src0, int C0, const float *src1, int C1, int B, int Hs, int Ws, int upsample,
-                         const float *wpacked, const float *scale, const float *shift, int Cout, int relu, int pool,
-                         const float *plane, int plane_chan, float *y, void *stream, int bf16, float *mom_part = nullptr,
-                         int *nparts = nullptr, int store_flags = 0, int KF = 3, int *plan = nullptr) {
-  // plan != nullptr (ra_conv3x3_plan): the same checks and the same chain of choices, ending in a record instead of a launch;
+// One request to the K1 entry: the public entries below name what they pass, and what they leave out stays unset
+struct ConvRequest {
+  const float *src0 = nullptr, *src1 = nullptr;
+  int C0 = 0, C1 = 0, B = 0, Hs = 0, Ws = 0, upsample = 0;
+  const float *wpacked = nullptr, *scale = nullptr, *shift = nullptr;
+  int Cout = 0, relu = 0, pool = 1;
+  const float *plane = nullptr;  // the canvas plane standing in for channel plane_chan of src0
+  int plane_chan = -1;
+  float *y = nullptr;
+  void *stream = nullptr;
+  int bf16 = 0;                // bf16 operands
+  float *mom_part = nullptr;   // batch moments: the partial records, and where their count goes
+  int *nparts = nullptr;
+  int store_flags = 0;         // bf16 storage of src0 / src1 (bit 0) and y (bit 1)
+  int KF = 3;
+  int *plan = nullptr;         // ra_conv3x3_plan: a record instead of a launch
+};
+
+static int conv3x3_entry(const ConvRequest &r) {
+  const int C0 = r.C0, C1 = r.C1, B = r.B, Hs = r.Hs, Ws = r.Ws, Cout = r.Cout, pool = r.pool, KF = r.KF;
+  int *const plan = r.plan;
+  // plan != nullptr (ra_conv3x3_plan): the same checks and the same choice of form, ending in a record instead of a launch;
   // src1 / plane / mom_part are then mere non-null marks and no pointer is followed
-  if ((!plan && (!src0 || !wpacked || !scale || !shift || !y)) || B <= 0 || Hs <= 0 || Ws <= 0 || C0 <= 0 ||
-      C1 < 0 || (C1 > 0 && !src1))
+  if ((!plan && (!r.src0 || !r.wpacked || !r.scale || !r.shift || !r.y)) || B <= 0 || Hs <= 0 || Ws <= 0 || C0 <= 0 ||
+      C1 < 0 || (C1 > 0 && !r.src1))
     return ra::fail(RA_E_INVALID, "ra_conv3x3_f32: bad argument");
   if (!kf_built(KF)) return ra::fail(RA_E_SHAPE, "ra_convkxk_f32: filter size %d not built (1, 3, 5, 7)", KF);
-  if (KF != 3 && (bf16 || mom_part || store_flags))
+  if (KF != 3 && (r.bf16 || r.mom_part || r.store_flags))
     return ra::fail(RA_E_INVALID, "ra_convkxk_f32: filter size %d: float32 operands, no batch moments", KF);
   if (C0 % 4 || C1 % 4) return ra::fail(RA_E_SHAPE, "ra_conv3x3_f32: C0=%d C1=%d must be %% 4", C0, C1);
   ra::conv::Args a;
   a.org = 1;
   // patch-sized launches (the attention CNN / decoder on 48 x 48 and below: <= 32 K conv pixels) are links of the decode
   // loop's serial tail, a few us each, and run beside other batches' controller CNNs in the pipeline
-  a.prio = ((size_t)B * Hs * Ws * (upsample ? 4 : 1) <= 32768) ? ra::tail_prio(2) : 0;
-  a.bf16 = bf16;
-  a.in_bf16 = (bf16 && (store_flags & 1)) ? 1 : 0;
-  a.out_bf16 = (bf16 && (store_flags & 2)) ? 1 : 0;
-  if (store_flags && (!bf16 || plane)) return ra::fail(RA_E_INVALID, "ra_conv3x3_bf16_f32: bf16 storage needs the bf16-operand kernels, no canvas plane");
-  a.mom_part = mom_part;
-  a.nparts_out = nparts;
-  a.src0 = src0;
-  a.src1 = src1;
-  a.wp = wpacked;
-  a.scale = scale;
-  a.shift = shift;
-  a.y = y;
+  a.prio = ((size_t)B * Hs * Ws * (r.upsample ? 4 : 1) <= 32768) ? ra::tail_prio(2) : 0;
+  a.bf16 = r.bf16;
+  a.in_bf16 = (r.bf16 && (r.store_flags & 1)) ? 1 : 0;
+  a.out_bf16 = (r.bf16 && (r.store_flags & 2)) ? 1 : 0;
+  if (r.store_flags && (!r.bf16 || r.plane)) return ra::fail(RA_E_INVALID, "ra_conv3x3_bf16_f32: bf16 storage needs the bf16-operand kernels, no canvas plane");
+  a.mom_part = r.mom_part;
+  a.nparts_out = r.nparts;
+  a.src0 = r.src0;
+  a.src1 = r.src1;
+  a.wp = r.wpacked;
+  a.scale = r.scale;
+  a.shift = r.shift;
+  a.y = r.y;
   a.C0 = C0;
   a.C1 = C1;
   a.Hs = Hs;
   a.Ws = Ws;
-  a.ups = upsample ? 1 : 0;
+  a.ups = r.upsample ? 1 : 0;
   a.H = Hs * (1 + a.ups);
   a.W = Ws * (1 + a.ups);
   a.Cout = Cout;
   a.CoutP = ra_conv_cout_padded(Cout);
-  a.relu = relu;
+  a.relu = r.relu;
   a.pool = pool;
   if (!a.CoutP) return ra::fail(RA_E_SHAPE, "ra_conv3x3_f32: Cout %d", Cout);
   if (pool != 1 && pool != 2) return ra::fail(RA_E_SHAPE, "ra_conv3x3_f32: pool %d", pool);
@@ -960,42 +990,52 @@ static int conv3x3_entry(const float *src0, int C0, const float *src1, int C1, i
     a.bytes0 = (int)n0;
     a.bytes1 = (int)n1;
     a.bytes_y = (int)ny;
-    a.plane = plane;
-    a.plane_chan = plane_chan;
+    a.plane = r.plane;
+    a.plane_chan = r.plane_chan;
     a.bytes_p = (int)((size_t)B * Hs * Ws * 4);
-    if (plane && (plane_chan < 0 || plane_chan >= C0))
-      return ra::fail(RA_E_INVALID, "ra_conv3x3_f32: plane channel %d of %d", plane_chan, C0);
+    if (r.plane && (r.plane_chan < 0 || r.plane_chan >= C0))
+      return ra::fail(RA_E_INVALID, "ra_conv3x3_f32: plane channel %d of %d", r.plane_chan, C0);
   }
   // a chunk may not straddle the src0/src1 boundary at finer than 4 channels (always true) but
   // the chunk index arithmetic needs C0 % 4 == 0 only: chunks are resolved per channel group.
-  hipStream_t st = ra::as_stream(stream);
+  hipStream_t st = ra::as_stream(r.stream);
   if (KF != 3) {
     // window origin (oracle conv2d / conv2d_transpose, TF SAME): stride 1, plain or transposed, is centred; the stride-2
     // transposed conv reads z[o + j - (KF - 1 - pad_lo)], pad_lo = max(KF - 2, 0) / 2, of z[2i] = x[i] — on the staged
     // U[2i + 1] = x[i] (U[m] = z[m - 1]) that is origin KF - 2 - pad_lo: -1, 2, 3 for KF = 1, 5, 7
     a.org = a.ups ? KF - 2 - (KF > 2 ? KF - 2 : 0) / 2 : KF / 2;
-    return ra::conv::k1_dispatch_kxk(a, KF, B, st, plan);
+    return ra::conv::run(a, B, 3, KF, st, plan);
   }
-  // bf16 mode, eight output channels at full resolution: the bf16-LDS kernel (ra_conv8.hip)
-  if (a.bf16 && !C1 && !a.ups && pool == 1 && !plane && ra::conv8::takes(C0, Cout, a.in_bf16, B, a.H, a.W))
-    return plan ? plan_conv8(plan, RA_PLAN_FORM_BF16 | (mom_part ? RA_PLAN_FORM_MOMENTS : 0), Cout) : ra::conv8::run(src0, C0, a.in_bf16, B, a.H, a.W, wpacked, scale, shift, relu, y, a.out_bf16, mom_part, nparts,
-                          ra::conv::num_cus(), st, Cout);
-  if (a.bf16) return ra::conv::k1_dispatch_bf16(a, B, st, plan);
+  // the 8- / 16-channel full-resolution kernels (ra_conv8.hip) take a layer without a second source, upsampling, pooling or plane
+  const bool plain_layer = !C1 && !a.ups && pool == 1 && !r.plane;
+  const int mom_form = r.mom_part ? RA_PLAN_FORM_MOMENTS : 0;
+  // bf16 mode, eight output channels at full resolution: the bf16-LDS kernel
+  if (a.bf16 && plain_layer && ra::conv8::takes(C0, Cout, a.in_bf16, B, a.H, a.W))
+    return plan ? plan_conv8(plan, RA_PLAN_FORM_BF16 | mom_form, Cout)
+                : ra::conv8::run(r.src0, C0, a.in_bf16, B, a.H, a.W, r.wpacked, r.scale, r.shift, r.relu, r.y, a.out_bf16, r.mom_part,
+                                 r.nparts, ra::cu_count(), st, Cout);
+  if (a.bf16) return ra::conv::run(a, B, 1, KF, st, plan);
   // float32, eight output channels at full resolution (training: forward with moments, data gradients): the 16-block MFMA form
-  if (!C1 && !a.ups && pool == 1 && !plane && ra::conv8::takes_f32(C0, Cout, B, a.H, a.W))
-    return plan ? plan_conv8(plan, mom_part ? RA_PLAN_FORM_MOMENTS : 0, 8) : ra::conv8::run(src0, C0, -1, B, a.H, a.W, wpacked, scale, shift, relu, y, 0, mom_part, nparts, ra::conv::num_cus(), st, 8);
-  if (!C1 && !a.ups && pool == 1 && !plane && ra::conv8::takes16_f32(C0, Cout, B, a.H, a.W))  // 16 channels at half resolution
-    return plan ? plan_conv8(plan, mom_part ? RA_PLAN_FORM_MOMENTS : 0, 16) : ra::conv8::run16_f32(src0, C0, B, a.H, a.W, wpacked, scale, shift, relu, y, mom_part, nparts, ra::conv::num_cus(), st);
-  if (a.mom_part) return ra::conv::k1_dispatch_moments(a, B, st, plan);
-  return ra::conv::k1_dispatch_plain(a, B, st, plan);
+  if (plain_layer && ra::conv8::takes_f32(C0, Cout, B, a.H, a.W))
+    return plan ? plan_conv8(plan, mom_form, 8)
+                : ra::conv8::run(r.src0, C0, -1, B, a.H, a.W, r.wpacked, r.scale, r.shift, r.relu, r.y, 0, r.mom_part, r.nparts,
+                                 ra::cu_count(), st, 8);
+  if (plain_layer && ra::conv8::takes16_f32(C0, Cout, B, a.H, a.W))  // 16 channels at half resolution
+    return plan ? plan_conv8(plan, mom_form, 16)
+                : ra::conv8::run16_f32(r.src0, C0, B, a.H, a.W, r.wpacked, r.scale, r.shift, r.relu, r.y, r.mom_part, r.nparts,
+                                       ra::cu_count(), st);
+  return ra::conv::run(a, B, a.mom_part ? 2 : 0, KF, st, plan);
 }
 
 extern "C" int ra_conv3x3_f32(const float *src0, int C0, const float *src1, int C1, int B, int Hs,
                               int Ws, int upsample, const float *wpacked, const float *scale,
                               const float *shift, int Cout, int relu, int pool, const float *plane,
                               int plane_chan, float *y, void *stream) {
-  return conv3x3_entry(src0, C0, src1, C1, B, Hs, Ws, upsample, wpacked, scale, shift, Cout, relu, pool, plane,
-                       plane_chan, y, stream, 0);
+  ConvRequest r;
+  r.src0 = src0, r.C0 = C0, r.src1 = src1, r.C1 = C1, r.B = B, r.Hs = Hs, r.Ws = Ws, r.upsample = upsample;
+  r.wpacked = wpacked, r.scale = scale, r.shift = shift, r.Cout = Cout, r.relu = relu, r.y = y, r.stream = stream;
+  r.pool = pool, r.plane = plane, r.plane_chan = plane_chan;
+  return conv3x3_entry(r);
 }
 
 // nnlib.cnn / nnlib.dcnn layers of filter size KF in {1, 3, 5, 7} (nnlib.py:131-257, :260-404); wpacked from
@@ -1003,13 +1043,16 @@ extern "C" int ra_conv3x3_f32(const float *src0, int C0, const float *src1, int 
 extern "C" int ra_convkxk_f32(const float *src0, int C0, const float *src1, int C1, int B, int Hs, int Ws, int upsample,
                               const float *wpacked, int KF, const float *scale, const float *shift, int Cout, int relu, int pool,
                               const float *plane, int plane_chan, float *y, void *stream) {
-  return conv3x3_entry(src0, C0, src1, C1, B, Hs, Ws, upsample, wpacked, scale, shift, Cout, relu, pool, plane, plane_chan, y,
-                       stream, 0, nullptr, nullptr, 0, KF);
+  ConvRequest r;
+  r.src0 = src0, r.C0 = C0, r.src1 = src1, r.C1 = C1, r.B = B, r.Hs = Hs, r.Ws = Ws, r.upsample = upsample;
+  r.wpacked = wpacked, r.scale = scale, r.shift = shift, r.Cout = Cout, r.relu = relu, r.y = y, r.stream = stream;
+  r.pool = pool, r.plane = plane, r.plane_chan = plane_chan, r.KF = KF;
+  return conv3x3_entry(r);
 }
 
 extern "C" size_t ra_conv3x3_moments_part_floats(int Cout) {
   const int cp = ra_conv_cout_padded(Cout);
-  return (size_t)4 * ra::conv::num_cus() * 4 * cp * 4;  // <= 4 workgroups per CU x 4 wave rows x CoutP records of 4 floats
+  return (size_t)4 * ra::cu_count() * 4 * cp * 4;  // <= 4 workgroups per CU x 4 wave rows x CoutP records of 4 floats
 }
 
 extern "C" int ra_conv3x3_moments_f32(const float *src0, int C0, const float *src1, int C1, int B, int Hs, int Ws,
@@ -1018,16 +1061,22 @@ extern "C" int ra_conv3x3_moments_f32(const float *src0, int C0, const float *sr
                                       void *stream) {
   if (!part || !nparts || part_floats < ra_conv3x3_moments_part_floats(Cout))
     return ra::fail(RA_E_WORKSPACE, "ra_conv3x3_moments_f32: partial buffer");
-  return conv3x3_entry(src0, C0, src1, C1, B, Hs, Ws, upsample, wpacked, scale, shift, Cout, relu, 1, nullptr, -1, y, stream,
-                       bf16_operands ? 1 : 0, part, nparts);
+  ConvRequest r;
+  r.src0 = src0, r.C0 = C0, r.src1 = src1, r.C1 = C1, r.B = B, r.Hs = Hs, r.Ws = Ws, r.upsample = upsample;
+  r.wpacked = wpacked, r.scale = scale, r.shift = shift, r.Cout = Cout, r.relu = relu, r.y = y, r.stream = stream;
+  r.pool = 1, r.bf16 = bf16_operands ? 1 : 0, r.mom_part = part, r.nparts = nparts;
+  return conv3x3_entry(r);
 }
 
 extern "C" int ra_conv3x3_bf16ops_f32(const float *src0, int C0, const float *src1, int C1, int B, int Hs,
                                       int Ws, int upsample, const float *wpacked, const float *scale,
                                       const float *shift, int Cout, int relu, int pool, const float *plane,
                                       int plane_chan, float *y, void *stream) {
-  return conv3x3_entry(src0, C0, src1, C1, B, Hs, Ws, upsample, wpacked, scale, shift, Cout, relu, pool, plane,
-                       plane_chan, y, stream, 1);
+  ConvRequest r;
+  r.src0 = src0, r.C0 = C0, r.src1 = src1, r.C1 = C1, r.B = B, r.Hs = Hs, r.Ws = Ws, r.upsample = upsample;
+  r.wpacked = wpacked, r.scale = scale, r.shift = shift, r.Cout = Cout, r.relu = relu, r.y = y, r.stream = stream;
+  r.pool = pool, r.plane = plane, r.plane_chan = plane_chan, r.bf16 = 1;
+  return conv3x3_entry(r);
 }
 
 // The bf16 mode's layers between themselves (model_opt['compute_dtype'] = 'bf16', DESIGN.md "Mixed precision"): bf16
@@ -1040,9 +1089,11 @@ extern "C" int ra_conv3x3_bf16_f32(const void *src0, int C0, const void *src1, i
                                    void *y, float *part, size_t part_floats, int *nparts, int store_flags, void *stream) {
   if (part && (!nparts || part_floats < ra_conv3x3_moments_part_floats(Cout)))
     return ra::fail(RA_E_WORKSPACE, "ra_conv3x3_bf16_f32: partial buffer");
-  return conv3x3_entry(static_cast<const float *>(src0), C0, static_cast<const float *>(src1), C1, B, Hs, Ws, upsample, wpacked, scale,
-                       shift, Cout, relu, part ? 1 : pool, nullptr, -1, static_cast<float *>(y), stream, 1, part, part ? nparts : nullptr,
-                       store_flags);
+  ConvRequest r;
+  r.src0 = static_cast<const float *>(src0), r.C0 = C0, r.src1 = static_cast<const float *>(src1), r.C1 = C1, r.B = B, r.Hs = Hs, r.Ws = Ws, r.upsample = upsample;
+  r.wpacked = wpacked, r.scale = scale, r.shift = shift, r.Cout = Cout, r.relu = relu, r.y = static_cast<float *>(y), r.stream = stream;
+  r.pool = part ? 1 : pool, r.bf16 = 1, r.mom_part = part, r.nparts = part ? nparts : nullptr, r.store_flags = store_flags;
+  return conv3x3_entry(r);
 }
 
 extern "C" int ra_conv3x3_plan(int C0, int C1, int B, int Hs, int Ws, int upsample, int KF, int Cout, int pool, int has_plane,
@@ -1050,8 +1101,10 @@ extern "C" int ra_conv3x3_plan(int C0, int C1, int B, int Hs, int Ws, int upsamp
   if (!plan) return ra::fail(RA_E_INVALID, "ra_conv3x3_plan: bad argument");
   for (int i = 0; i < RA_PLAN_INTS; ++i) plan[i] = 0;
   static float mark;  // never read or written: a non-null stand-in for the optional pointers
-  return conv3x3_entry(nullptr, C0, C1 > 0 ? &mark : nullptr, C1, B, Hs, Ws, upsample, nullptr, nullptr, nullptr, Cout, 0,
-                       moments ? 1 : pool, has_plane ? &mark : nullptr, has_plane ? 0 : -1, nullptr, nullptr, bf16_operands ? 1 : 0,
-                       moments ? &mark : nullptr, nullptr, store_flags, KF, plan);
+  ConvRequest r;
+  r.C0 = C0, r.src1 = C1 > 0 ? &mark : nullptr, r.C1 = C1, r.B = B, r.Hs = Hs, r.Ws = Ws, r.upsample = upsample;
+  r.Cout = Cout, r.pool = moments ? 1 : pool, r.plane = has_plane ? &mark : nullptr, r.plane_chan = has_plane ? 0 : -1;
+  r.bf16 = bf16_operands ? 1 : 0, r.mom_part = moments ? &mark : nullptr, r.store_flags = store_flags, r.KF = KF, r.plan = plan;
+  return conv3x3_entry(r);
 }
 #endif  // RA_K1_PART == 0

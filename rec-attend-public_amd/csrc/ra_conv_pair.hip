@@ -10,12 +10,10 @@
 #include <cstdlib>
 
 #include "ra_common.h"
+#include "ra_split3.h"
 
 namespace ra {
 namespace cpair {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef unsigned u32x4r __attribute__((ext_vector_type(4)));
 
 struct PArgs {
   const float *src;
@@ -551,27 +549,10 @@ struct NGeo {
 // (-DRA_P8_NOBAR: the tile loop's barriers dropped — timing only, results wrong).
 #ifdef RA_PROBE8
 __device__ long long *ra_probe8_buf;
-#define RA_P8_DECL long long p8_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, p8_t = (long long)__builtin_readcyclecounter(), p8_t0 = (long long)wall_clock64()
-#define RA_P8_AT(k)                                                 \
-  do {                                                              \
-    __builtin_amdgcn_sched_barrier(0);                              \
-    const long long n_ = (long long)__builtin_readcyclecounter();   \
-    p8_acc[k] += n_ - p8_t;                                         \
-    p8_t = n_;                                                      \
-    __builtin_amdgcn_sched_barrier(0);                              \
-  } while (0)
-#define RA_P8_END                                                                   \
-  do {                                                                              \
-    if (threadIdx.x == 0 && ra_probe8_buf) {                                        \
-      p8_acc[7] = (long long)wall_clock64() - p8_t0;                                \
-      for (int k_ = 0; k_ < 8; ++k_) ra_probe8_buf[(size_t)blockIdx.x * 8 + k_] = p8_acc[k_]; \
-    }                                                                               \
-  } while (0)
-#else
-#define RA_P8_DECL
-#define RA_P8_AT(k)
-#define RA_P8_END
+#define RA_PHASE_PROBE_BUF ra_probe8_buf
+#define RA_PHASE_PROBE_WG blockIdx.x
 #endif
+#include "ra_phase_probe.h"
 #ifdef RA_P8_NOBAR
 #define RA_P8_SYNC() __builtin_amdgcn_s_waitcnt(0xc07f)  /* lgkmcnt(0) only */
 #else
@@ -591,22 +572,6 @@ __device__ long long *ra_probe8_buf;
 // sum |a b| against 2.3e-7 for the float32 chain).  Phase A writes its output as three bf16 tiles [pixel][8 channels]
 // (hi / mid / lo); a K = 32 block of phase B is one row ky of the 3 x 4 tap window x 8 channels, so a lane's whole A operand
 // of a block and piece is ONE ds_read_b128 (lane kb = window column), and the filter is 3 x 3 x 4 registers per lane.
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8v __attribute__((ext_vector_type(8)));
-__device__ inline unsigned pk_bf16(float lo, float hi) {  // v_cvt_pk_bf16_f32: two floats -> two bf16 (RNE), `lo` in the low half
-  typedef float f32x2c __attribute__((ext_vector_type(2)));
-  typedef __bf16 bf16x2c __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2c{lo, hi}, bf16x2c));
-}
-// (a, b) -> three packed bf16 pairs H, M, L with a = a_H + a_M + a_L exactly (every difference below is exact in float32)
-__device__ inline void split3_pair(float a, float b, unsigned &H, unsigned &M, unsigned &L) {
-  H = pk_bf16(a, b);
-  float ra = a - __builtin_bit_cast(float, H << 16), rb = b - __builtin_bit_cast(float, H & 0xffff0000u);
-  M = pk_bf16(ra, rb);
-  ra -= __builtin_bit_cast(float, M << 16);
-  rb -= __builtin_bit_cast(float, M & 0xffff0000u);
-  L = pk_bf16(ra, rb);
-}
 template <int CINA, bool CACHED, bool SPLIT = false>
 __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 3) : 4) : RA_PAIR8_OCC) void conv_pair8_mfma(const PArgs a, int tiles_x, int tiles_y, int ntiles) {
   using G = NGeo<CINA>;
@@ -621,7 +586,6 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 
   float *tin = lds;              // [LH][LW] records [ksub][cg]  (channel = 4*cg + ksub); CACHED: the canvas only
   float *tmid = lds + IN_FLOATS;  // [AHS][AW] records [ksub][cg], 8 channels
   typedef typename vec_of<NCGA>::type avecA;
-  typedef float f32x2 __attribute__((ext_vector_type(2)));
 
   const int tid = threadIdx.x, lane = tid & 63;
   // dynamic tile tickets (a.tickets, ra_common.h): the workgroup draws its tiles from its XCD's pool instead of walking them
@@ -832,7 +796,7 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 
   bool have = dyn ? tile >= 0 : tile < t_end;
   TC cur = split(have ? tile : 0), nxt = cur;
   if (have) fetch(cur);
-  RA_P8_DECL;
+  RA_PHASE_DECL;
   // the padded groups read LDS this kernel never writes; whatever an earlier kernel left there
   // must not be NaN/Inf (their results are discarded, but keep the arithmetic clean)
   for (int e = tid; e < (IN_FLOATS + MIDF) / 4; e += 256)
@@ -847,7 +811,7 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 
   const int r_end = ((int)blockIdx.x + 1) * r_chunk < a.rider_quads ? ((int)blockIdx.x + 1) * r_chunk : a.rider_quads;
   const int my_tiles = t_end > t_first ? (t_end - t_first + nwx - 1) / nwx : 1;
   const int r_per_tile = (r_chunk + 256 * my_tiles - 1) / (256 * my_tiles);
-  const u32x4r r_bits = __builtin_bit_cast(u32x4r, f32x4{a.rider_val, a.rider_val, a.rider_val, a.rider_val});
+  const u32x4 r_bits = __builtin_bit_cast(u32x4, f32x4{a.rider_val, a.rider_val, a.rider_val, a.rider_val});
   bool have_n = false;
   f32x4 cpre[CACHED ? G::GPW : 1];
   auto load_cache = [&](const TC &tc) {
@@ -900,7 +864,7 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 
     }
     if (dyn) tk.publish(tk_sh);
     RA_P8_SYNC();
-    RA_P8_AT(0);  // staged + barrier
+    RA_PHASE_AT(0);  // staged + barrier
     if (dyn) {
       tk.read_next(tk_sh);
       tk.request();  // the draw for the tile after next: older than the prefetch loads below, in flight across this tile
@@ -938,7 +902,7 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 
           acc[s] = fill ? f32x4{0.f, 0.f, 0.f, 0.f} : shA4;
         }
       }
-      RA_P8_AT(1);  // layer A's cached sums have arrived (accumulators initialised)
+      RA_PHASE_AT(1);  // layer A's cached sums have arrived (accumulators initialised)
       if constexpr (CACHED) {
 #pragma unroll
         for (int ky = 0; ky < 3; ++ky) {
@@ -1002,11 +966,10 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 
           split3_pair(o[0], o[1], H01, M01, L01);
           split3_pair(o[2], o[3], H23, M23, L23);
           if (live) {
-            typedef unsigned u32x2t __attribute__((ext_vector_type(2)));
             unsigned char *d0 = reinterpret_cast<unsigned char *>(tmid) + pix * 16 + coA0 * 2;
-            *reinterpret_cast<u32x2t *>(d0) = u32x2t{H01, H23};
-            *reinterpret_cast<u32x2t *>(d0 + PLANE_B) = u32x2t{M01, M23};
-            *reinterpret_cast<u32x2t *>(d0 + 2 * PLANE_B) = u32x2t{L01, L23};
+            *reinterpret_cast<u32x2 *>(d0) = u32x2{H01, H23};
+            *reinterpret_cast<u32x2 *>(d0 + PLANE_B) = u32x2{M01, M23};
+            *reinterpret_cast<u32x2 *>(d0 + 2 * PLANE_B) = u32x2{L01, L23};
           }
         } else if (live) {
           // float32 tile, records [ksub][cg] (channel c at 2 (c & 3) + (c >> 2)): this lane's channels sit two floats apart
@@ -1016,9 +979,9 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 
         }
       }
     }
-    RA_P8_AT(2);  // phase A computed and written to the LDS tile
+    RA_PHASE_AT(2);  // phase A computed and written to the LDS tile
     RA_P8_SYNC();
-    RA_P8_AT(3);  // barrier
+    RA_PHASE_AT(3);  // barrier
 
     // ---------------- phase B: layer B out of tmid, BN + ReLU + 2x2 max-pool -> global ----------------
 #if RA_PAIR8_CACHE_AHEAD
@@ -1058,8 +1021,8 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 
             for (int t = 0; t < 6; ++t)
 #pragma unroll
               for (int u = 0; u < 2; ++u)
-                acc[2 * gh + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8v, av[u][PA[t]]),
-                                                                          __builtin_bit_cast(bf16x8v, wB[ky][PB[t]]), acc[2 * gh + u], 0, 0, 0);
+                acc[2 * gh + u] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, av[u][PA[t]]),
+                                                                          __builtin_bit_cast(bf16x8, wB[ky][PB[t]]), acc[2 * gh + u], 0, 0, 0);
           }
       } else {
 #pragma unroll
@@ -1094,9 +1057,9 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? (RA_PAIR8_CACHE_AHEAD ? 2 : 
         __builtin_amdgcn_raw_buffer_store_b32(__builtin_bit_cast(unsigned, ov), ry, (int)off, 0, 0);
       }
     }
-    RA_P8_AT(4);  // phase B, pooled and stored
+    RA_PHASE_AT(4);  // phase B, pooled and stored
   }
-  RA_P8_END;
+  RA_PHASE_END;
   if constexpr (!CACHED) {
     if (rider)  // what rounding left of this workgroup's share (and all of it for a workgroup without tiles)
       for (; r_idx < r_end; r_idx += 256) __builtin_amdgcn_raw_buffer_store_b128(r_bits, rr, r_idx * 16, 0, 0);
@@ -1218,18 +1181,8 @@ int launch(const PArgs &a, int B, hipStream_t st, int *plan) {
   if constexpr (G::NCHA == 1 && G::NCHB == 1) {
     // plain single-chunk pairs (controller CNN L2+L3 at full size): persistent workgroups, weights
     // loaded once, the next tile's input prefetched into registers behind the MFMA phases
-    static int pers = -1, cap = 0;
-    if (pers < 0) {
-      pers = env_int("RA_PAIR_PERSIST", 1);
-      auto kp = conv_pair_persist_mfma<CINA, CMID, NCB, GX, GYB>;
-      MaxDynamicLds{kp, lds};
-      int nb = 0;
-      if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kp, 256, lds) != hipSuccess || nb < 1) nb = 1;
-      hipDeviceProp_t prop;
-      int dev = 0, cus = 256;
-      if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-      cap = nb * cus;
-    }
+    static const int pers = env_int("RA_PAIR_PERSIST", 1);
+    static const int cap = wgs_per_cu(conv_pair_persist_mfma<CINA, CMID, NCB, GX, GYB>, lds) * cu_count();
     if (pers && !a.ups && !a.plane && ntiles > cap && a.bytes0 > 0) {
       if (plan) {
         plan[RA_PLAN_FORM] = RA_PLAN_FORM_PERSIST;

@@ -24,16 +24,10 @@
 #include <cstring>
 
 #include "ra_common.h"
+#include "ra_split3.h"
 
 namespace ra {
 namespace csplit {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
-typedef short s16x8 __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int TW = 16;                     // output tile width (conv resolution); its height TH is 16, or 8 at Cin = 64 (Geo)
 constexpr int WSX = TW + 2;                // staged window width
@@ -76,45 +70,14 @@ struct Geo {
   static constexpr int OCC = 2 * (LDS + 64) <= 160 * 1024 ? 2 : 1;
 };
 
-__device__ inline unsigned pk_bf16(float lo, float hi) {
-  typedef __bf16 bf16x2c __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2c));
-}
-// (a, b) -> packed bf16 pairs H, M, L with a = a_H + a_M + a_L exactly (each difference is exact in float32)
-__device__ inline void split3_pair(float a, float b, unsigned &H, unsigned &M, unsigned &L) {
-  H = pk_bf16(a, b);
-  float ra = a - __builtin_bit_cast(float, H << 16), rb = b - __builtin_bit_cast(float, H & 0xffff0000u);
-  M = pk_bf16(ra, rb);
-  ra -= __builtin_bit_cast(float, M << 16);
-  rb -= __builtin_bit_cast(float, M & 0xffff0000u);
-  L = pk_bf16(ra, rb);
-}
-
 // tools/split_probe.hip builds this file with -DRA_PROBES: wave 0 of every workgroup accumulates the shader-clock time between
 // points of the tile loop (as RA_PROBE8 in ra_conv_pair.hip) and leaves the sums in ra_probes_buf[workgroup][8]
 #ifdef RA_PROBES
 __device__ long long *ra_probes_buf;
-#define RA_PS_DECL long long ps_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, ps_t = (long long)__builtin_readcyclecounter(), ps_t0 = (long long)wall_clock64()
-#define RA_PS_AT(k)                                                \
-  do {                                                             \
-    __builtin_amdgcn_sched_barrier(0);                             \
-    const long long n_ = (long long)__builtin_readcyclecounter();  \
-    ps_acc[k] += n_ - ps_t;                                        \
-    ps_t = n_;                                                     \
-    __builtin_amdgcn_sched_barrier(0);                             \
-  } while (0)
-#define RA_PS_END                                                                    \
-  do {                                                                               \
-    if (threadIdx.x == 0 && ra_probes_buf) {                                         \
-      ps_acc[7] = (long long)wall_clock64() - ps_t0;                                 \
-      for (int k_ = 0; k_ < 8; ++k_) ra_probes_buf[((size_t)blockIdx.y * gridDim.x + blockIdx.x) * 8 + k_] = ps_acc[k_]; \
-    }                                                                                \
-  } while (0)
-#else
-#define RA_PS_DECL
-#define RA_PS_AT(k)
-#define RA_PS_END
+#define RA_PHASE_PROBE_BUF ra_probes_buf
+#define RA_PHASE_PROBE_WG (size_t)blockIdx.y * gridDim.x + blockIdx.x
 #endif
+#include "ra_phase_probe.h"
 template <int CIN, int POOL, int NB, bool PL = false>  // PL: channel a.plane_chan of x comes from the plane a.plane (the first layer's canvas)
 __global__ __launch_bounds__(256, (Geo<CIN, NB>::OCC)) void conv_split_kernel(const SArgs a, int tiles_x, int tiles_y, int ntiles) {
   using G = Geo<CIN, NB>;
@@ -124,7 +87,7 @@ __global__ __launch_bounds__(256, (Geo<CIN, NB>::OCC)) void conv_split_kernel(co
   unsigned char *tin = lds;               // three bf16 tiles [WSY][WSP][RS]
   unsigned char *wl = lds + 3 * PLANE;    // the slice's filter pieces
   const int tid = threadIdx.x, lane = tid & 63;
-  RA_PS_DECL;
+  RA_PHASE_DECL;
   // dynamic tile tickets (a.tickets): tiles are drawn from this XCD's pool of the channel slice instead of walked
   __shared__ unsigned tk_sh[2];
   TicketWalk tk;
@@ -228,12 +191,12 @@ __global__ __launch_bounds__(256, (Geo<CIN, NB>::OCC)) void conv_split_kernel(co
     const int e = tid + 256 * i;
     if (e < NWQ) reinterpret_cast<u32x4 *>(wl)[e] = wtmp[i];
   }
-  RA_PS_AT(0);  // prologue: constants, filter copy, first window(s) requested
+  RA_PHASE_AT(0);  // prologue: constants, filter copy, first window(s) requested
 
   // a window's registers -> three bf16 tiles in LDS, between the tile loop's two barriers
   auto stage = [&](f32x4(&pre)[NIT], float(&ppl)[PL ? NIT : 1]) {
     __syncthreads();  // the previous tile's operand reads are complete (and, first time round, the filter copy is issued)
-    RA_PS_AT(1);  // top barrier
+    RA_PHASE_AT(1);  // top barrier
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
       f32x4 v = pre[i];
@@ -255,10 +218,10 @@ __global__ __launch_bounds__(256, (Geo<CIN, NB>::OCC)) void conv_split_kernel(co
         *reinterpret_cast<u32x2 *>(rec + 2 * PLANE) = u32x2{L0, L1};
       }
     }
-    RA_PS_AT(2);  // window arrived, split into three bf16 tiles, stored
+    RA_PHASE_AT(2);  // window arrived, split into three bf16 tiles, stored
     if (dyn) tk.publish(tk_sh);
     __syncthreads();
-    RA_PS_AT(3);  // staging barrier
+    RA_PHASE_AT(3);  // staging barrier
   };
 
   // the k-loop and the epilogue of one staged tile
@@ -295,7 +258,7 @@ __global__ __launch_bounds__(256, (Geo<CIN, NB>::OCC)) void conv_split_kernel(co
                                                                  acc[g][nb], 0, 0, 0);
       }
     }
-    RA_PS_AT(4);  // next window requested + the k-loop (9 blocks x 4 groups x 6 products x NB)
+    RA_PHASE_AT(4);  // next window requested + the k-loop (9 blocks x 4 groups x 6 products x NB)
     // epilogue: lane (column n = m, D rows 4 kb + r) holds the four elements r = (dy, dx) of pooling window kb = (wy, wx) of group g
     const int wy = kb >> 1, wx = kb & 1;
 #pragma unroll
@@ -319,7 +282,7 @@ __global__ __launch_bounds__(256, (Geo<CIN, NB>::OCC)) void conv_split_kernel(co
           }
         }
       }
-    RA_PS_AT(5);  // epilogue: scale / shift, pool, ReLU, stores issued
+    RA_PHASE_AT(5);  // epilogue: scale / shift, pool, ReLU, stores issued
   };
 
   if (dyn) {
@@ -343,18 +306,7 @@ __global__ __launch_bounds__(256, (Geo<CIN, NB>::OCC)) void conv_split_kernel(co
       compute(tile + gstep);
     }
   }
-  RA_PS_END;
-}
-
-inline int cu_count() {
-  static int cus = 0;
-  if (!cus) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-  }
-  return cus;
+  RA_PHASE_END;
 }
 
 template <int CIN, int POOL, int NB, bool PL = false>

@@ -27,6 +27,7 @@
 // ablation builds), the rest is per-workgroup fixed cost — filter load 1.5, first rows, exchange,
 // stores — that the two workgroups of a CU pay in lockstep because every tile starts at once.
 #include "ra_common.h"
+#include "ra_split3.h"
 
 #ifndef RA_PAIRW_SPLIT_OCC
 #define RA_PAIRW_SPLIT_OCC 3  // workgroups per CU of the fused L2+L3 pair's SPLIT form
@@ -34,8 +35,6 @@
 namespace ra {
 namespace wino {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int TS = 16;       // output tile width (and height of the tall form)
 constexpr int WS = TS + 2;   // staged window width
@@ -248,21 +247,11 @@ __global__ __launch_bounds__(256, 2) void conv_wino_mfma(const WArgs a, int tile
   }
 }
 
-inline int cu_count();
-
 template <int CIN, int POOL, int TSY, int NB>
 int launch(const WArgs &a, hipStream_t st, int *plan) {
   auto kern = conv_wino_mfma<CIN, POOL, TSY, NB>;
   constexpr size_t lds = (size_t)((TSY + 2) * WS * (CIN + 2) + 8 * 16 * TEX) * sizeof(float);
-  static bool attr = false;
-  static int cap = 0;
-  if (!attr) {
-    MaxDynamicLds{kern, lds};
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
-    cap = nb * cu_count();
-    attr = true;
-  }
+  static const int cap = wgs_per_cu(kern, lds) * cu_count();
   const int tiles_x = a.W / TS, tiles_y = a.H / TSY, ntiles = tiles_x * tiles_y * a.B, slices = a.Cout / (16 * NB);
   int gx = cap / slices;
   if (gx < 1) gx = 1;
@@ -281,17 +270,6 @@ int launch(const WArgs &a, hipStream_t st, int *plan) {
   a2.tickets = draws ? take_ticket_slots(slices, gx) : nullptr;
   hipLaunchKernelGGL(kern, dim3(gx, slices), dim3(256), lds, st, a2, tiles_x, tiles_y, ntiles);
   return launch_status("ra_conv_wino_f32");
-}
-
-inline int cu_count() {
-  static int cus = 0;
-  if (!cus) {
-    hipDeviceProp_t prop;
-    int dev = 0;
-    cus = 256;
-    if (hipGetDevice(&dev) == hipSuccess && hipGetDeviceProperties(&prop, dev) == hipSuccess) cus = prop.multiProcessorCount;
-  }
-  return cus;
 }
 
 // 16-row tiles only when they give every CU more than two workgroups (RA_WINO_TSY=8|16 forces one form):
@@ -328,46 +306,14 @@ struct PWArgs {
 // tiles [pixel][8 channels] (the exact three-piece split of every float32 value, made once per staged element), a K = 32
 // block is four taps x 8 channels (three blocks for the nine taps), a lane's A operand of a block and piece is one
 // ds_read_b128, and six piece products per block replace eight float32 MFMAs.
-typedef short s16x8w __attribute__((ext_vector_type(8)));
-typedef __bf16 bf16x8w __attribute__((ext_vector_type(8)));
-typedef unsigned u32x2w __attribute__((ext_vector_type(2)));
-__device__ inline unsigned pk_bf16w(float lo, float hi) {
-  typedef __bf16 bf16x2c __attribute__((ext_vector_type(2)));
-  return __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{lo, hi}, bf16x2c));
-}
-__device__ inline void split3_pairw(float a, float b, unsigned &H, unsigned &M, unsigned &L) {  // a = a_H + a_M + a_L exactly
-  H = pk_bf16w(a, b);
-  float ra = a - __builtin_bit_cast(float, H << 16), rb = b - __builtin_bit_cast(float, H & 0xffff0000u);
-  M = pk_bf16w(ra, rb);
-  ra -= __builtin_bit_cast(float, M << 16);
-  rb -= __builtin_bit_cast(float, M & 0xffff0000u);
-  L = pk_bf16w(ra, rb);
-}
 // tools/pairw_probe.hip builds this file with -DRA_PROBEW: wave 0 of every workgroup accumulates the shader-clock time between a
 // few points of conv_pair_wino_mfma's tile loop and leaves the sums in ra_probew_buf[workgroup][8] (as RA_PROBE8 in ra_conv_pair.hip)
 #ifdef RA_PROBEW
 __device__ long long *ra_probew_buf;
-#define RA_PW_DECL long long pw_acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, pw_t = (long long)__builtin_readcyclecounter(), pw_t0 = (long long)wall_clock64()
-#define RA_PW_AT(k)                                                \
-  do {                                                             \
-    __builtin_amdgcn_sched_barrier(0);                             \
-    const long long n_ = (long long)__builtin_readcyclecounter();  \
-    pw_acc[k] += n_ - pw_t;                                        \
-    pw_t = n_;                                                     \
-    __builtin_amdgcn_sched_barrier(0);                             \
-  } while (0)
-#define RA_PW_END                                                                    \
-  do {                                                                               \
-    if (threadIdx.x == 0 && ra_probew_buf) {                                         \
-      pw_acc[7] = (long long)wall_clock64() - pw_t0;                                 \
-      for (int k_ = 0; k_ < 8; ++k_) ra_probew_buf[(size_t)blockIdx.x * 8 + k_] = pw_acc[k_]; \
-    }                                                                                \
-  } while (0)
-#else
-#define RA_PW_DECL
-#define RA_PW_AT(k)
-#define RA_PW_END
+#define RA_PHASE_PROBE_BUF ra_probew_buf
+#define RA_PHASE_PROBE_WG blockIdx.x
 #endif
+#include "ra_phase_probe.h"
 template <int TSY, bool SPLIT = false>
 __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 2) void conv_pair_wino_mfma(const PWArgs a, int tiles_x, int tiles_y, int ntiles) {
   constexpr int CINA = 8, CMID = 16, KK = CMID / 4, S = CMID + 2, NMB = TSY / 4;
@@ -395,7 +341,7 @@ __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 
 
   // layer A: direct-form B operands (9 taps x 2 channel groups) and epilogue constants of column m
   float bA[SPLIT ? 1 : 9][2];
-  s16x8w wA[SPLIT ? 3 : 1][SPLIT ? 3 : 1];  // SPLIT: block blk, k-slot j = input channel j of tap 4 blk + ksub, column m, three pieces
+  s16x8 wA[SPLIT ? 3 : 1][SPLIT ? 3 : 1];  // SPLIT: block blk, k-slot j = input channel j of tap 4 blk + ksub, column m, three pieces
   if constexpr (SPLIT) {
 #pragma unroll
     for (int blk = 0; blk < 3; ++blk) {
@@ -407,7 +353,7 @@ __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 
         const float w0 = a.wpA[(size_t)((tp * 2 + (j >> 2)) * 4 + (j & 3)) * a.CoutAP + m];
         const float w1 = a.wpA[(size_t)((tp * 2 + ((j + 1) >> 2)) * 4 + ((j + 1) & 3)) * a.CoutAP + m];
         unsigned H, M, L;
-        split3_pairw(ok ? w0 : 0.f, ok ? w1 : 0.f, H, M, L);
+        split3_pair(ok ? w0 : 0.f, ok ? w1 : 0.f, H, M, L);
         wA[blk][0][j] = (short)(H & 0xffffu), wA[blk][0][j + 1] = (short)(H >> 16);
         wA[blk][1][j] = (short)(M & 0xffffu), wA[blk][1][j + 1] = (short)(M >> 16);
         wA[blk][2][j] = (short)(L & 0xffffu), wA[blk][2][j + 1] = (short)(L >> 16);
@@ -474,24 +420,24 @@ __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 
     tile = tk.cur >= 0 ? tk.cur : t_end;
   }
   if (tile < t_end) fetch(tile);
-  RA_PW_DECL;
+  RA_PHASE_DECL;
   for (; tile < t_end; tile = tnext) {
     const int b = tile / per, trem = tile - b * per;
     const int ty = trem / tiles_x, tx = trem - ty * tiles_x;
     __syncthreads();  // the previous tile's phase B (exchange reads) is complete
-    RA_PW_AT(0);  // top barrier
+    RA_PHASE_AT(0);  // top barrier
 #pragma unroll
     for (int i = 0; i < NIT; ++i) {
       const int e = tid + 256 * i, cg = e & 1, pix = e >> 1;
       if constexpr (SPLIT) {
         unsigned H0, M0, L0, H1, M1, L1;  // channels 4 cg .. 4 cg + 3 of the pixel: 8 bytes of its record in each of the three tiles
-        split3_pairw(pre[i].x, pre[i].y, H0, M0, L0);
-        split3_pairw(pre[i].z, pre[i].w, H1, M1, L1);
+        split3_pair(pre[i].x, pre[i].y, H0, M0, L0);
+        split3_pair(pre[i].z, pre[i].w, H1, M1, L1);
         if (e < NPI * 2) {
           unsigned char *rec = reinterpret_cast<unsigned char *>(tinp) + pix * 16 + cg * 8;
-          *reinterpret_cast<u32x2w *>(rec) = u32x2w{H0, H1};
-          *reinterpret_cast<u32x2w *>(rec + PLB) = u32x2w{M0, M1};
-          *reinterpret_cast<u32x2w *>(rec + 2 * PLB) = u32x2w{L0, L1};
+          *reinterpret_cast<u32x2 *>(rec) = u32x2{H0, H1};
+          *reinterpret_cast<u32x2 *>(rec + PLB) = u32x2{M0, M1};
+          *reinterpret_cast<u32x2 *>(rec + 2 * PLB) = u32x2{L0, L1};
         }
         continue;
       }
@@ -503,7 +449,7 @@ __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 
     }
     if (dyn) tk.publish(tk_sh);
     __syncthreads();
-    RA_PW_AT(1);  // staged (split into three bf16 tiles) + barrier
+    RA_PHASE_AT(1);  // staged (split into three bf16 tiles) + barrier
     if (dyn) {
       tk.read_next(tk_sh);
       tk.request();  // older than the prefetch loads below: consumed with them at the next tile's staging
@@ -530,12 +476,12 @@ __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 
         for (int blk = 0; blk < 3; ++blk)
 #pragma unroll
           for (int s = 0; s < GPW; ++s) {
-            s16x8w av[3];
+            s16x8 av[3];
 #pragma unroll
-            for (int pc = 0; pc < 3; ++pc) av[pc] = *reinterpret_cast<const s16x8w *>(tb + ain[s] + toff[blk] + pc * PLB);
+            for (int pc = 0; pc < 3; ++pc) av[pc] = *reinterpret_cast<const s16x8 *>(tb + ain[s] + toff[blk] + pc * PLB);
 #pragma unroll
             for (int t = 0; t < 6; ++t)
-              acc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8w, wA[blk][PB[t]]), __builtin_bit_cast(bf16x8w, av[PA[t]]),
+              acc[s] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(__builtin_bit_cast(bf16x8, wA[blk][PB[t]]), __builtin_bit_cast(bf16x8, av[PA[t]]),
                                                                acc[s], 0, 0, 0);
           }
       } else {
@@ -551,7 +497,7 @@ __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 
           for (int s = 0; s < GPW; ++s) acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(bA[tap][cg], av[s][cg], acc[s], 0, 0, 0);
       }
       }
-      RA_PW_AT(2);  // layer A's MFMAs
+      RA_PHASE_AT(2);  // layer A's MFMAs
 #pragma unroll
       for (int s = 0; s < GPW; ++s) {
         const int g = p + 4 * s;
@@ -573,9 +519,9 @@ __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 
         }
       }
     }
-    RA_PW_AT(3);  // layer A's epilogue -> tin
+    RA_PHASE_AT(3);  // layer A's epilogue -> tin
     __syncthreads();
-    RA_PW_AT(4);  // barrier
+    RA_PHASE_AT(4);  // barrier
 
     // ---------------- phase B: Winograd F(2x2, 3x3) out of tin (see conv_wino_mfma) ----------------
 #pragma unroll 1
@@ -595,7 +541,7 @@ __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 
 #pragma unroll
         for (int q = 0; q < 4; ++q) acc[q] = __builtin_amdgcn_mfma_f32_16x16x4f32(bw[q][kk], v[q], acc[q], 0, 0, 0);  // D^T (see conv_wino_mfma)
       }
-      RA_PW_AT(5);  // phase B: input transform + 16 MFMAs of the row block
+      RA_PHASE_AT(5);  // phase B: input transform + 16 MFMAs of the row block
       if (mblk) __syncthreads();  // the previous row block's exchange has been consumed
       {
         const f32x4 t0 = acc[0] + acc[1] + acc[2];
@@ -620,10 +566,10 @@ __global__ __launch_bounds__(256, TSY == 8 ? (SPLIT ? RA_PAIRW_SPLIT_OCC : 4) : 
         const int oty = ty * (TSY / 2) + 2 * mblk + (tl >> 3), otx = tx * 8 + (tl & 7);
         a.y[((size_t)(b * Ho + oty) * Wo + otx) * 16 + eco] = best;
       }
-      RA_PW_AT(6);  // phase B: exchange, output transform, BN + ReLU + pool, store
+      RA_PHASE_AT(6);  // phase B: exchange, output transform, BN + ReLU + pool, store
     }
   }
-  RA_PW_END;
+  RA_PHASE_END;
 }
 
 template <int TSY, bool SPLIT = false>
@@ -632,16 +578,9 @@ int launch_pair(const PWArgs &a, hipStream_t st, int *plan) {
   constexpr int inf = SPLIT ? 3 * (TSY + 4) * (TS + 4) * 4 : (TSY + 4) * (TS + 4) * 8;
   constexpr int r0 = inf > 8 * 16 * 20 ? inf : 8 * 16 * 20;
   constexpr size_t lds = (size_t)(r0 + ((TSY + 2) * WS + 16) * 18) * sizeof(float);
-  static bool attr = false;
-  static int cap = 0;
-  if (!attr) {
-    MaxDynamicLds{kern, lds};
-    int nb = 0;
-    if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&nb, kern, 256, lds) != hipSuccess || nb < 1) nb = 1;
-    cap = nb * cu_count();
-    if (const int wgs = env_int("RA_PAIRW_WGS", 0); wgs > 0) cap = wgs;
-    attr = true;
-  }
+  static const int resident = wgs_per_cu(kern, lds) * cu_count();
+  static const int wgs = env_int("RA_PAIRW_WGS", 0);  // > 0: tuning aid, the persistent grid
+  static const int cap = wgs > 0 ? wgs : resident;
   const int tiles_x = a.W / TS, tiles_y = a.H / TSY, ntiles = tiles_x * tiles_y * a.B;
   static const int xcd = env_int("RA_PAIRW_XCD", 1);  // =0: tuning aid, the interleaved tile walk
   const int grid = ntiles < cap ? ntiles : cap;
