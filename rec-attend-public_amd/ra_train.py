@@ -220,7 +220,7 @@ def allreduce_sums(t):
 # HIP kernels.  torch is the tape and the memory; what runs on the GPU:
 #   * every conv layer of the three CNNs — forward (MFMA conv, BN batch moments, normalise + ReLU +
 #     pool) and backward (BN / pool / ReLU adjoint, backward-data on the MFMA conv kernel with the
-#     flipped packing, backward-weight on MFMA) — ConvBNActPool, csrc/ra_train.hip + ra_conv.hip;
+#     flipped packing, backward-weight on MFMA) — ConvBNActPool, csrc/ra_train.hip + ra_wgrad.hip + ra_conv.hip;
 #   * the pairwise soft IoU of the two losses and its adjoint — PairIoU, csrc/ra_loss.hip;
 #   * the ground-truth boxes and both Hungarian matchings (device solver), clip + Adam;
 #   * the attention resample — box, read, write — forward on the decode loop's banded kernels and backward

@@ -10,6 +10,7 @@ import torch
 
 import ra_native as rn
 import ra_ops as ops
+from wgrad_form_cases import _wgrad_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -88,17 +89,8 @@ def test_conv8_float32_vs_float64(cuda, cin, cout, relu):
   np.testing.assert_allclose(var.cpu().numpy(), flat.var(0, unbiased=False).cpu().numpy(), rtol=1e-5)
 
 
-# ---- the filter gradient of the same layers (csrc/ra_train.hip wgrad8_kernel: Cout = 8, Cin in {4, 8}, float32, both tiles
+# ---- the filter gradient of the same layers (csrc/ra_wgrad.hip wgrad8_kernel: Cout = 8, Cin in {4, 8}, float32, both tiles
 # HBM -> LDS directly; wgrad_kernel for the other channel counts) on shapes ragged against its 8 x 32 tiles
-def _wgrad_ref(x, du):
-  """dW[ky,kx,ci,co] = sum over pixels of x[.. + tap, ci] * du[.., co] (SAME padding), db = sum du, in float64 on the device."""
-  xi = torch.nn.functional.pad(x.double(), (0, 0, 1, 1, 1, 1))
-  B, H, W, Co = du.shape
-  d = du.double()
-  dw = torch.stack([torch.stack([torch.einsum('bhwc,bhwd->cd', xi[:, ky:ky + H, kx:kx + W], d) for kx in range(3)]) for ky in range(3)])
-  return dw, d.sum(dim=(0, 1, 2))
-
-
 def _rel(a, b):
   return float((a.double() - b).abs().max() / b.abs().max().clamp_min(1e-30))
 
