@@ -847,6 +847,52 @@ int ra_instance_overlap_f32(const float *y, const int *gt_ids, const int *ids, c
                             int *ws, size_t ws_ints, int *inter, int *pred_pixels, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Evaluating the pre-stage fg_model (csrc/ra_fg_eval.hip).
+ *
+ * ra_fg_stats_f32 — the sums behind the six statistics the reference's Evaluator logs (fg_model_train.py:131-133), replacing
+ *   the loss head of fg_model.py:196-248 at eval: logits [npix, nsc + no] (what ra_fg_head_f32 reads; the sigmoid / softmax
+ *   are evaluated with its expressions, unquantised), y_gt [npix, nsc], d_gt [npix, no] (NULL when no == 0); nsc 1 .. 16,
+ *   no 0 | 8.  sums: RA_FG_STAT_COUNT doubles —
+ *     INTER_SOFT, SUM_SOFT, SUM_GT   sum y g, sum y, sum g of modellib.f_iou_all (modellib.py:171-181) over the foreground
+ *                                    channels: the only channel for nsc == 1, channels 1 .. nsc - 1 otherwise (:208-218);
+ *     INTER_HARD, SUM_HARD           the same with y replaced by hard = [logit > 0] (nsc == 1, :209) or [logit[c] == max_c
+ *                                    logit] (:213-214; every maximum counts, as tf.equal does);
+ *     SEG_CE                         sum f_bce(y, g) (nsc == 1) or sum f_ce(y, g) over ALL channels (:221-226,
+ *                                    modellib.py:418-427), NOT yet divided by the pixel count;
+ *     MASK                           sum m, m = g (nsc == 1) or max over c >= 1 of g[c] (:201-206); 0 when no == 0;
+ *     ORI_CE, ORI_CORRECT            sum f_ce(d, d_gt) m and sum [argmax d_logit == argmax d_gt] m, first maximum on both
+ *                                    sides (:235-246); 0 when no == 0.
+ *   The hard quantities are taken on the LOGITS, not on rounded probabilities: equal in exact arithmetic, and float32
+ *   rounding of a softmax must not invent ties.  float32 within a pixel, float64 and a fixed order from there on, no
+ *   floating-point atomics: the same bits on every run.  ws: ra_fg_stats_workspace_bytes(npix) bytes, 8-byte aligned.
+ * ra_fg_sweep_counts_f32 — the counters of analysis.py:834-906 (ForegroundIOUAnalyzer / BackgroundIOUAnalyzer) for every
+ *   threshold of fg_model_eval.py:166-173 at once: src [N,Hs,Ws] the soft foreground at network size, gt uint8 [N,H,W] the
+ *   full-size labels summed over the instances (:142-143; values above 1 where instances overlap count as a * b and b.sum()
+ *   count them), thresholds: K floats in HOST memory, 1 <= K <= RA_FG_SWEEP_MAX_K.  With v = bilateralFilter(resize(src,
+ *   (W, H)), 5, 10, 10) (:106-117; the arithmetic of ra_resize_linear_f32 + ra_bilateral5_f32, evaluated per tile and never
+ *   written) counts [N, RA_FG_SWEEP_SLOTS] receives, per image, count_a[k] = #{v > thr[k]} at slot k, sum_ab[k] = sum of gt
+ *   over those pixels at slot RA_FG_SWEEP_MAX_K + k, and sum_b = sum of gt at slot 2 RA_FG_SWEEP_MAX_K; slots of k >= K are
+ *   0.  counts is cleared on the stream first; integer atomics, so the result does not depend on the order.  H * W < 2^31.
+ * ---------------------------------------------------------------------------------- */
+#define RA_FG_STAT_INTER_SOFT 0
+#define RA_FG_STAT_SUM_SOFT 1
+#define RA_FG_STAT_SUM_GT 2
+#define RA_FG_STAT_INTER_HARD 3
+#define RA_FG_STAT_SUM_HARD 4
+#define RA_FG_STAT_SEG_CE 5
+#define RA_FG_STAT_ORI_CE 6
+#define RA_FG_STAT_ORI_CORRECT 7
+#define RA_FG_STAT_MASK 8
+#define RA_FG_STAT_COUNT 9
+#define RA_FG_SWEEP_MAX_K 16
+#define RA_FG_SWEEP_SLOTS 33
+size_t ra_fg_stats_workspace_bytes(size_t npix);
+int ra_fg_stats_f32(const float *logits, const float *y_gt, const float *d_gt, size_t npix, int nsc, int no, void *ws,
+                    size_t ws_bytes, double *sums, void *stream);
+int ra_fg_sweep_counts_f32(const float *src, const unsigned char *gt, int N, int Hs, int Ws, int H, int W,
+                           const float *thresholds, int K, unsigned long long *counts, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Training step (full_model.py:1039-1057).
  * ra_adam_step_f32 — gradient clip + Adam on one flat float32 bucket of n parameters:
  *   g = clip(grads * grad_scale + wd_coef * params, -clip, clip)   (wd_coef nullable; the

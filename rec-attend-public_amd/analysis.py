@@ -5,7 +5,9 @@
 (ops.eval_metrics: pairwise intersections on the MFMA streaming kernel + one small metrics
 kernel), cached on the dict.  Of the analyzers that render images or write CSV files (:52-311,
 :790-900) only RenderCityScapesOutputAnalyzer (:196-267, the Cityscapes instance-level output) is built; the others are
-out of scope."""
+out of scope.  ForegroundIOUAnalyzer / BackgroundIOUAnalyzer (:834-906) accumulate over a whole dataset, in
+exact integers, from the counters of ops.fg_sweep_counts; fg_model_eval.py drives them and they are not per-image functions,
+so ANALYZERS does not list them."""
 import os
 
 import torch
@@ -396,3 +398,61 @@ class CityscapesAPAnalyzer(object):
     if not quiet:
       print(cityscapes_ap_table(result['averages']))
     return result
+
+
+# ---------------------------------------------------------------------------- whole-dataset foreground / background IoU
+def _fg_counts_of(results, index):
+  """(count_a, sum_ab, sum_b, pixels) of one stage() call as Python integers: from results['fg_counts'] (what
+  ops.fg_sweep_counts returns; `index` picks the threshold) or from binary device tensors results['y_out'] / results['y_gt']
+  [N,H,W] ([N,T,H,W]: the maximum over T first, analysis.py:849-851)."""
+  if 'fg_counts' in results:
+    c = results['fg_counts']
+    ca, sab = c['count_a'], c['sum_ab']
+    n = len(c['sum_b'])
+    pick = (lambda a: [int(v[index]) for v in a]) if getattr(ca, 'ndim', 2) == 2 else (lambda a: [int(v) for v in a])
+    return sum(pick(ca)), sum(pick(sab)), sum(int(v) for v in c['sum_b']), int(c['pixels']) * n
+  a, b = results['y_out'], results['y_gt']
+  if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.is_cuda):
+    raise ops.rn.RecAttendError('the whole-dataset IoU analyzers take results[\'fg_counts\'] or device tensors y_out / y_gt; '
+                                'there is no CPU path')
+  if a.dim() == 4:
+    a, b = a.max(dim=1).values, b.max(dim=1).values
+  if a.shape != b.shape or a.dim() != 3:
+    raise ops.rn.RecAttendError('y_out %s and y_gt %s must both be [N,H,W] (or [N,T,H,W])' % (tuple(a.shape), tuple(b.shape)))
+  a, b = a.to(torch.int64), b.to(torch.int64)
+  return int(a.sum()), int((a * b).sum()), int(b.sum()), int(a.numel())
+
+
+class ForegroundIOUAnalyzer(object):
+  """analysis.py:834-867: IoU over an entire dataset, not per image — inter = sum a b, union = sum a + sum b - inter over every
+  staged image, a the thresholded output and b the ground truth summed over the instances (b > 1 where instances overlap
+  counts as a * b and b.sum() count it).  The sums are kept as exact Python integers; finalize() divides once in float64."""
+
+  def __init__(self, name='FG IOU ALL', fname=None, index=0):
+    self.name, self.fname, self.index = name, fname, index
+    self.inter = self.union = 0
+
+  def stage(self, results):
+    count_a, sum_ab, sum_b, _ = _fg_counts_of(results, self.index)
+    self.inter += sum_ab                     # :852
+    self.union += count_a + sum_b - sum_ab   # :853
+
+  def finalize(self):
+    iou = self.inter / self.union if self.union else float('nan')  # :865 (0 / 0 there); integers: one rounding, float64
+    print('{:17s}{:7.4f}'.format(self.name, iou))  # :866
+    return iou
+
+
+class BackgroundIOUAnalyzer(ForegroundIOUAnalyzer):
+  """analysis.py:870-906: the same for the background, _a = 1 - a and _b = 1 - b, written out as it stands there: with b > 1
+  the products (1 - a)(1 - b) are negative where a = 0, and so is what this returns."""
+
+  def __init__(self, name='BG IOU ALL', fname=None, index=0):
+    ForegroundIOUAnalyzer.__init__(self, name, fname, index)
+
+  def stage(self, results):
+    count_a, sum_ab, sum_b, pixels = _fg_counts_of(results, self.index)
+    inter = pixels - count_a - sum_b + sum_ab                  # :891: sum (1 - a)(1 - b)
+    union = (pixels - count_a) + (pixels - sum_b) - inter      # :892: sum _a + sum _b - inter
+    self.inter += inter
+    self.union += union

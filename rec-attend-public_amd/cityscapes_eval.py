@@ -29,7 +29,8 @@ Per image (write_log, :148-205), all on the device, batch by batch:
      the files left on disk would score — plus a key 'thresholds' with the averages of every threshold.
 The per-threshold means of the analyzers go to <output>/output_<split>/metrics.yaml.  Two names of the reference's default
 --analyzers list (and of its --test list), fg_iou_all and bg_iou_all, accumulate over the whole dataset (analysis.py:834-900)
-and are not built: the default lists run without them and say so on standard output; naming one explicitly is an error.
+and are not built HERE: the default lists run without them and say so on standard output; naming one explicitly is an error
+(the two accumulators themselves are analysis.ForegroundIOUAnalyzer / BackgroundIOUAnalyzer, driven by fg_model_eval.py).
 
 --lrr_seg, --foreground_folder and --render_gt are accepted and refused: they read files of the authors' machines (LRR .mat
 files, a foreground folder, the HDF5 dataset); --lrr_filename is accepted and unused (its default there is a path of that

@@ -77,6 +77,12 @@ CITYSCAPES_EVAL_FLAGS = [  # EvalArgsParser + CityscapesEvalArgsParser, cmd_args
     ('render_gt', _B, False), ('lrr_seg', _B, False), ('lrr_filename', _S, None),
 ]
 
+FG_EVAL_FLAGS = [  # EvalArgsParser + FGEvalArgsParser, cmd_args_parser.py:143-151, fg_model_eval.py:195-203
+    ('threshold_list', _S, None), ('render_ori', _B, False), ('render_soft', _B, False), ('render_gt', _B, False),
+    ('model_id', _S, None), ('batch_size', _I, 32), ('results', _S, './results'), ('output', _S, None),
+    ('split', _S, 'valid'), ('prefetch', _B, False), ('queue_size', _I, 50), ('num_worker', _I, 4),
+]
+
 
 def add_flags(parser, table):
   for name, kind, default in table:

@@ -10,6 +10,7 @@
 #include <cmath>
 
 #include "ra_common.h"
+#include "ra_resample.h"
 
 namespace ra {
 namespace eval {
@@ -89,37 +90,15 @@ __global__ __launch_bounds__(256) void dilate_kernel(const float *y, int H, int 
   out[(size_t)n * H * W + e] = m;
 }
 
-// upsample_single (postprocess.py:93-106): cv2.resize(a, (W, H), INTER_LINEAR) then cv2.bilateralFilter(b, 5, 10, 10).
-//   resize: pixel centres aligned — source coordinate (d + 0.5) * (src / dst) - 0.5, clamped to the image, two-tap linear
-//   weights in float32 (cv2's float path; its 8-bit path uses fixed-point coefficients);
-//   bilateral: d = 5 -> radius 2, the CIRCULAR neighbourhood dy^2 + dx^2 <= 4 (13 pixels), weight
-//   exp(-(dy^2 + dx^2) / (2 * 10^2)) * exp(-(v - v0)^2 / (2 * 10^2)), borders reflected without the edge pixel
-//   (BORDER_REFLECT_101).  cv2 evaluates the colour weight from an interpolated table; this is the formula the table
-//   approximates (the two cannot be compared here: cv2 is not part of this stack).
+// upsample_single (postprocess.py:93-106): cv2.resize(a, (W, H), INTER_LINEAR) then cv2.bilateralFilter(b, 5, 10, 10), one
+// plane kernel each.  The arithmetic of a pixel — the two-tap resize, the 13-tap circular neighbourhood, BORDER_REFLECT_101 —
+// is ra_resample.h's, shared with the fused threshold sweep of ra_fg_eval.hip.
 __global__ __launch_bounds__(256) void resize_linear_kernel(const float *y, int Hs, int Ws, int H, int W, float *out) {
   const int n = blockIdx.y;
   const int e = blockIdx.x * 256 + threadIdx.x;
   if (e >= H * W) return;
   const int r = e / W, c = e - r * W;
-  const float sy = (float)Hs / (float)H, sx = (float)Ws / (float)W;
-  float fy = ((float)r + 0.5f) * sy - 0.5f, fx = ((float)c + 0.5f) * sx - 0.5f;
-  int y0 = (int)floorf(fy), x0 = (int)floorf(fx);
-  fy -= (float)y0;
-  fx -= (float)x0;
-  if (y0 < 0) y0 = 0, fy = 0.f;
-  if (y0 >= Hs - 1) y0 = Hs - 1, fy = 0.f;
-  if (x0 < 0) x0 = 0, fx = 0.f;
-  if (x0 >= Ws - 1) x0 = Ws - 1, fx = 0.f;
-  const int y1 = y0 + 1 < Hs ? y0 + 1 : y0, x1 = x0 + 1 < Ws ? x0 + 1 : x0;
-  const float *p = y + (size_t)n * Hs * Ws;
-  const float top = p[y0 * Ws + x0] * (1.f - fx) + p[y0 * Ws + x1] * fx;
-  const float bot = p[y1 * Ws + x0] * (1.f - fx) + p[y1 * Ws + x1] * fx;
-  out[(size_t)n * H * W + e] = top * (1.f - fy) + bot * fy;
-}
-__device__ inline int reflect101(int i, int n) {
-  if (n == 1) return 0;
-  while (i < 0 || i >= n) i = i < 0 ? -i : 2 * (n - 1) - i;
-  return i;
+  out[(size_t)n * H * W + e] = resample::resize_linear_at(y + (size_t)n * Hs * Ws, Hs, Ws, H, W, r, c);
 }
 __global__ __launch_bounds__(256) void bilateral5_kernel(const float *y, int H, int W, float sigma_color, float sigma_space, float *out) {
   const int n = blockIdx.y;
@@ -127,17 +106,8 @@ __global__ __launch_bounds__(256) void bilateral5_kernel(const float *y, int H, 
   if (e >= H * W) return;
   const int r = e / W, c = e - r * W;
   const float *p = y + (size_t)n * H * W;
-  const float v0 = p[e], gc = -0.5f / (sigma_color * sigma_color), gs = -0.5f / (sigma_space * sigma_space);
-  float num = 0.f, den = 0.f;
-  for (int dy = -2; dy <= 2; ++dy)
-    for (int dx = -2; dx <= 2; ++dx) {
-      if (dy * dy + dx * dx > 4) continue;
-      const float v = p[reflect101(r + dy, H) * W + reflect101(c + dx, W)];
-      const float w = expf((float)(dy * dy + dx * dx) * gs + (v - v0) * (v - v0) * gc);
-      num += w * v;
-      den += w;
-    }
-  out[(size_t)n * H * W + e] = num / den;
+  const auto at = [&](int dy, int dx) { return p[resample::reflect101(r + dy, H) * W + resample::reflect101(c + dx, W)]; };
+  out[(size_t)n * H * W + e] = resample::bilateral5_at(at, p[e], resample::bilateral_gain(sigma_space), resample::bilateral_gain(sigma_color));
 }
 
 // remove_tiny_single (postprocess.py:126-136): planes of at most `threshold` pixels vanish

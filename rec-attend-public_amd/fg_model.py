@@ -7,7 +7,8 @@ through fg_model_pack.py and the dataset reader as 8-bit images).
 `load_weights()` under the checkpoint names of get_save_var (fg_model.py:270-285) and `prestage()`.  The net is nnlib.cnn
 followed by nnlib.dcnn with skip connections; layers of up to 128 output channels run K1, wider ones the wide kernel
 (ra_ops.conv_wide), the head is one kernel (ra_ops.fg_head).  Eval only: `phase_train = True` and the outputs of the loss
-raise RecAttendError.
+raise RecAttendError.  `Model.statistics(x, y_gt, d_gt)` gives the numbers the reference's Evaluator logs (the IoUs, the losses,
+the orientation accuracy) from one pass over the logits (ra_ops.fg_statistics); fg_model_eval.py is the command line.
 """
 import numpy as np
 import torch
@@ -200,6 +201,44 @@ class Model(dict):
       ops.fg_head(lg[k * Bs:(k + 1) * Bs], d['nsc'], d['no'], quantise=quantise, y_out=sb['y_in'], d_out=sb['d_in'], x=sb['x'],
                   packed=sb['img'])
     return eng.glob['y_in'], eng.glob['d_in']
+
+  def statistics(self, x, y_gt, d_gt=None):
+    """What the reference's Evaluator logs for this net (fg_model_train.py:131-133; fg_model.py:196-248) on one batch, as a dict
+    of Python floats computed in float64 from one pass over the logits (ops.fg_statistics): iou_soft, iou_hard,
+    foreground_loss (-iou_soft for segm_loss_fn 'iou', the summed (b)ce / (B H W) for 'bce'), loss, and with orientation
+    orientation_ce and orientation_acc (NaN where the ground truth has no foreground pixel, as the reference's 0 / 0).
+    x [B,H,W,inp_depth]; y_gt [B,H,W] or [B,H,W,nsc]; d_gt [B,H,W,8] with orientation.  The hard IoU and the accuracy are
+    taken on the logits, see ops.fg_statistics.  The outputs of the loss stay refused by run(): nothing here trains."""
+    d = self.dims
+    nsc, no = d['nsc'], d['no']
+    seg = self.opt.get('segm_loss_fn', 'iou')
+    if seg not in ('iou', 'bce'):
+      raise RecAttendError('fg_model.statistics: segm_loss_fn %r (iou | bce)' % (seg,))
+    for name, t in (('x', x), ('y_gt', y_gt), ('d_gt', d_gt)):
+      if t is not None and not (isinstance(t, torch.Tensor) and t.is_cuda):
+        raise RecAttendError('fg_model.statistics: %s must be a device tensor; there is no CPU path' % name)
+    self._check_input(x)
+    B, H, W = (int(v) for v in x.shape[:3])
+    if tuple(y_gt.shape) not in (((B, H, W), (B, H, W, 1)) if nsc == 1 else ((B, H, W, nsc),)):
+      raise RecAttendError('fg_model.statistics: y_gt of shape %r for x %r and %d semantic classes' % (tuple(y_gt.shape), tuple(x.shape), nsc))
+    if d_gt is not None and not no:
+      raise RecAttendError('fg_model.statistics: d_gt given, but the net was built without add_orientation')
+    if no and (d_gt is None or tuple(d_gt.shape) != (B, H, W, no)):
+      raise RecAttendError('fg_model.statistics: the net has orientation classes: d_gt must be [%d,%d,%d,%d], got %r' % (
+          B, H, W, no, None if d_gt is None else tuple(d_gt.shape)))
+    f32 = lambda t: t.to(dtype=torch.float32).contiguous()
+    s = ops.fg_statistics(self.logits(f32(x)), f32(y_gt), f32(d_gt) if no else None, nsc, no)
+    f_iou_all = lambda inter, a, b: inter / (a + b - inter + 1e-5)  # modellib.py:171-181
+    out = {'iou_soft': f_iou_all(s['inter_soft'], s['sum_soft'], s['sum_gt']),
+           'iou_hard': f_iou_all(s['inter_hard'], s['sum_hard'], s['sum_gt'])}
+    out['foreground_loss'] = -out['iou_soft'] if seg == 'iou' else s['seg_ce'] / float(B * H * W)  # :221-233
+    out['loss'] = out['foreground_loss']
+    if no:
+      nan = float('nan')
+      out['orientation_ce'] = s['ori_ce'] / s['mask'] if s['mask'] else (nan if s['ori_ce'] == 0 else s['ori_ce'] * float('inf'))
+      out['orientation_acc'] = s['ori_correct'] / s['mask'] if s['mask'] else nan  # :244-245: 0 / 0
+      out['loss'] = out['foreground_loss'] + out['orientation_ce']  # :240
+    return out
 
   def run(self, outputs, feed, as_numpy=False):
     single = isinstance(outputs, str)

@@ -1,0 +1,159 @@
+#!/usr/bin/env python
+"""Entry point with the flag surface of the reference's fg_model_eval.py (:195-216 + EvalArgsParser): tells whether a set of
+fg_model weights is any good.  For every threshold of --threshold_list (default 0.3) the foreground and background IoU over
+the WHOLE data set at the labels' size (analysis.py:834-906, fg_iou_all / bg_iou_all), and, where ground truth at network size
+is given, the statistics the reference's Evaluator logs while it trains the pre-stage (fg_model_train.py:131-133).
+
+The model is restored from <results>/<model_id>/{model_opt.yaml, weights.npz} exactly as fg_model_pack.py does.  --input is an
+.npz with
+  x           [N,h,w,3]   the images at network size,
+  fg_gt_full  [N,H,W]     uint8: the full-size labels summed over the instances (fg_model_eval.py:142-143; 2 and more where
+                          instances overlap, counted as the reference's a * b and b.sum() count them),
+and optionally names (N file names, default 'image_<i>') and y_gt [N,h,w] or [N,h,w,nsc] (+ d_gt [N,h,w,8] for a net with
+orientation): then fg_model.Model.statistics runs on every batch and the means over the batches are reported, as the
+Evaluator averages them.  All images of one archive share one full size: a stated limit, as in cityscapes_eval.py.
+
+Per batch, on the device (write_log, :134-173): y_out of the net; the foreground plane is y_out[..., 0] for one semantic class
+and 1 - y_out[..., 0] for several (channel 0 is the background: the convention of ops.sem_foreground — the reference's runner
+only works for one class); ops.fg_sweep_counts evaluates bilateralFilter(resize(plane), 5, 10, 10) (:106-117) tile by tile,
+compares it with every threshold and returns integer counters, from which analysis.ForegroundIOUAnalyzer /
+BackgroundIOUAnalyzer accumulate.  The full-size soft map is materialised (pp.upsample) only for the images that are written.
+
+Outputs: <output>/metrics.yaml — per threshold fg_iou_all, bg_iou_all and the four integer totals (count_a, sum_ab, sum_b,
+pixels), plus 'statistics' when ground truth at network size was given; <output>/<NN>/<name>.png, NN = int(threshold * 100)
+(:66) — the thresholded full-size map times 255 (RenderForegroundAnalyzer); <output>/soft/ and <output>/gt/ under
+--render_soft / --render_gt (the soft map and the labels, times 255 and clipped to 8 bits).  --output defaults to
+<results>/<model_id>/output (:184-186).  --render_ori is accepted and refused: it needs the colour orientation image of
+data_api/orientation.py, and utils/png.py writes 8-bit grey only.
+
+No more than MAX_BATCH_ELEMS floats of one tensor are alive per batch; there is no CPU path: without a GPU the script raises
+RecAttendError."""
+import argparse
+import os
+
+import numpy as np
+import yaml
+
+import cmd_args_parser as cap
+from ra_native import RecAttendError
+
+MAX_BATCH_ELEMS = 1 << 29  # floats of one [B,H,W] plane at full size (2 GiB)
+REFUSED = {
+    'render_ori': '--render_ori renders the orientation classes as a colour image (data_api/orientation.py); utils/png.py writes '
+                  '8-bit grey only, so it is not built',
+}
+STAT_NAMES = ('iou_soft', 'iou_hard', 'foreground_loss', 'loss', 'orientation_ce', 'orientation_acc')
+
+
+def build_parser():
+  p = argparse.ArgumentParser(description='Eval fg output')
+  cap.add_flags(p, cap.FG_EVAL_FLAGS)
+  cap.add_flags(p, cap.DATA_FLAGS)
+  p.add_argument('--input', default=None, help='.npz with x [N,h,w,3], fg_gt_full [N,H,W] uint8 (+ names, y_gt, d_gt)')
+  return p
+
+
+def make_opt(args):
+  """FGEvalArgsParser.make_opt (:205-216)."""
+  for flag, why in REFUSED.items():
+    if getattr(args, flag):
+      raise RecAttendError(why)
+  opt = {k: getattr(args, k) for k in ('model_id', 'batch_size', 'results', 'output', 'render_gt', 'render_soft', 'render_ori')}
+  opt['split'] = args.split.split(',')
+  opt['threshold_list'] = [0.3] if args.threshold_list is None else [float(t) for t in args.threshold_list.split(',')]
+  return opt
+
+
+def _write_planes(folder, names, planes):
+  """planes: uint8 [B,H,W] on the host -> <folder>/<name>.png"""
+  from utils import png
+  os.makedirs(folder, exist_ok=True)
+  for name, img in zip(names, planes):
+    png.write_gray8(os.path.join(folder, os.path.splitext(os.path.basename(name))[0] + '.png'), img)
+
+
+def foreground_plane(y_out):
+  """y_out [B,h,w,nsc] -> the soft foreground [B,h,w]: the only channel, or 1 - the background channel."""
+  return (y_out[..., 0] if y_out.shape[-1] == 1 else 1.0 - y_out[..., 0]).contiguous()
+
+
+def main(argv=None):
+  import torch
+  args = build_parser().parse_args(argv)
+  opt = make_opt(args)
+  if args.model_id is None:
+    raise Exception('You must provide model ID')  # cmd_args_parser.py:154-155
+  if args.input is None:
+    raise RecAttendError('--input is required: an .npz with x [N,h,w,3] and fg_gt_full [N,H,W]')
+  if not torch.cuda.is_available():
+    raise RecAttendError('fg_model_eval runs on the GPU; no device is available and there is no CPU fallback')
+  import analysis
+  import fg_model_pack
+  import ra_ops as ops
+  from utils import postprocess as pp
+  thresholds = opt['threshold_list']
+  if not 1 <= len(thresholds) <= ops.FG_SWEEP_MAX_K:
+    raise RecAttendError('--threshold_list: %d thresholds (1 .. %d)' % (len(thresholds), ops.FG_SWEEP_MAX_K))
+  out_dir = opt['output'] if opt['output'] is not None else os.path.join(args.results, args.model_id, 'output')
+  model = fg_model_pack.restore_model(args.results, args.model_id)
+  data = np.load(args.input, allow_pickle=False)
+  for k in ('x', 'fg_gt_full'):
+    if k not in data:
+      raise RecAttendError('--input lacks %s' % k)
+  x_all, gt_all = data['x'], data['fg_gt_full']
+  N = x_all.shape[0]
+  if gt_all.ndim != 3 or gt_all.shape[0] != N or gt_all.dtype != np.uint8:
+    raise RecAttendError('--input: fg_gt_full is %s %s, expected uint8 [%d,H,W] (one full size per archive)' % (
+        gt_all.dtype, tuple(gt_all.shape), N))
+  H, W = gt_all.shape[1:]
+  names = [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(N)]
+  have_stats = 'y_gt' in data
+  y_gt_all = data['y_gt'] if have_stats else None
+  d_gt_all = data['d_gt'] if have_stats and 'd_gt' in data else None
+  fg_an = [analysis.ForegroundIOUAnalyzer('fg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]  # :62-69
+  bg_an = [analysis.BackgroundIOUAnalyzer('bg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]
+  totals = [{'count_a': 0, 'sum_ab': 0, 'sum_b': 0, 'pixels': 0} for _ in thresholds]
+  stats = []
+  os.makedirs(out_dir, exist_ok=True)
+  bs = max(1, min(opt['batch_size'], MAX_BATCH_ELEMS // max(1, H * W)))
+  dev = torch.device('cuda', torch.cuda.current_device())
+  up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+  to8 = lambda t: (t * 255.0).clamp(0, 255).to(torch.uint8).cpu().numpy()
+  for b0 in range(0, N, bs):
+    b1 = min(N, b0 + bs)
+    x = up(x_all[b0:b1])
+    gt = torch.as_tensor(np.ascontiguousarray(gt_all[b0:b1])).to(dev)
+    soft = foreground_plane(model.run('y_out', {'x': x, 'phase_train': False}))
+    counts = ops.fg_sweep_counts(soft, gt, thresholds)
+    res = {'fg_counts': counts, 'indices': list(range(b0, b1))}
+    for k in range(len(thresholds)):
+      fg_an[k].stage(res)
+      bg_an[k].stage(res)
+      totals[k]['count_a'] += int(counts['count_a'][:, k].sum())
+      totals[k]['sum_ab'] += int(counts['sum_ab'][:, k].sum())
+      totals[k]['sum_b'] += int(counts['sum_b'].sum())
+      totals[k]['pixels'] += counts['pixels'] * (b1 - b0)
+    full = pp.upsample(soft, (H, W))  # the rendering path only: :146, :166-173
+    for t in thresholds:
+      _write_planes(os.path.join(out_dir, '{:02d}'.format(int(t * 100))), names[b0:b1], to8((full > float(t)).to(torch.float32)))
+    if opt['render_soft']:
+      _write_planes(os.path.join(out_dir, 'soft'), names[b0:b1], to8(full))
+    if opt['render_gt']:
+      _write_planes(os.path.join(out_dir, 'gt'), names[b0:b1], to8(gt.to(torch.float32)))
+    if have_stats:
+      stats.append(model.statistics(x, up(y_gt_all[b0:b1]), None if d_gt_all is None else up(d_gt_all[b0:b1])))
+  summary = {}
+  for k, t in enumerate(thresholds):
+    summary['%.2f' % t] = dict(totals[k], fg_iou_all=float(fg_an[k].finalize()), bg_iou_all=float(bg_an[k].finalize()))
+  if have_stats:
+    summary['statistics'] = {n: float(np.mean([s[n] for s in stats])) for n in STAT_NAMES if n in stats[0]}
+    for n, v in summary['statistics'].items():
+      print('{:17s}{:7.4f}'.format(n, v))
+  with open(os.path.join(out_dir, 'metrics.yaml'), 'w') as f:
+    yaml.safe_dump(summary, f)
+  print('%d images -> %s' % (N, out_dir))
+  return summary
+
+
+if __name__ == '__main__':
+  main()

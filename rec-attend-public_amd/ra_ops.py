@@ -1206,3 +1206,77 @@ def instance_overlap(y, gt_ids, catalog):
   check(rn.lib().ra_instance_overlap_f32(ptr(y), ptr(gt_ids), ptr(ids), ptr(count), B, T, H, W, ptr(ws), n, ptr(inter), ptr(pred),
                                          rn.stream_ptr()), 'ra_instance_overlap_f32')
   return inter, pred
+
+
+# ---------------------------------------------------------------------------- evaluating the pre-stage fg_model
+FG_STAT_NAMES = ('inter_soft', 'sum_soft', 'sum_gt', 'inter_hard', 'sum_hard', 'seg_ce', 'ori_ce', 'ori_correct', 'mask')  # RA_FG_STAT_*
+FG_SWEEP_MAX_K = rn.RA_FG_SWEEP_MAX_K
+
+
+def fg_statistics(logits, y_gt, d_gt, nsc, no):
+  """The sums behind the statistics of fg_model.py:196-248, in one pass over the logits [..., nsc + no] of the pre-stage
+  (ra_fg_stats_f32): y_gt [..., nsc] (or [...] for nsc == 1), d_gt [..., 8] or None -> {name: float} over FG_STAT_NAMES,
+  float64.  The hard quantities are taken on the logits ([logit > 0]; [logit == max logit], every maximum; the first maximum
+  of the orientation logits), not on the rounded probabilities: the two agree in exact arithmetic, and float32 rounding of a
+  softmax must not invent ties.  One device-to-host copy of nine doubles."""
+  nsc, no = int(nsc), int(no)
+  if not 1 <= nsc <= 16 or no not in (0, 8):
+    raise rn.RecAttendError('fg_statistics: nsc %d (1 .. 16), no %d (0 | 8)' % (nsc, no))
+  if (d_gt is not None) != bool(no):
+    raise rn.RecAttendError('fg_statistics: d_gt goes with no = 8 and only with it (no = %d, d_gt %s)' % (
+        no, 'given' if d_gt is not None else 'missing'))
+  _need_cuda(logits, y_gt, d_gt)
+  if logits.dim() < 1 or logits.shape[-1] != nsc + no or logits.numel() == 0:
+    raise rn.RecAttendError('fg_statistics: logits %s for nsc %d + no %d channels' % (tuple(logits.shape), nsc, no))
+  npix = logits.numel() // (nsc + no)
+  if y_gt.numel() != npix * nsc or (no and d_gt.numel() != npix * no):
+    raise rn.RecAttendError('fg_statistics: logits %s, y_gt %s, d_gt %s do not belong together' % (
+        tuple(logits.shape), tuple(y_gt.shape), None if d_gt is None else tuple(d_gt.shape)))
+  dev = logits.device
+  n = rn.lib().ra_fg_stats_workspace_bytes(npix)
+  ws = torch.empty((max(n // 8, 1),), dtype=torch.float64, device=dev)
+  sums = torch.empty((len(FG_STAT_NAMES),), dtype=torch.float64, device=dev)
+  check(rn.lib().ra_fg_stats_f32(ptr(logits), ptr(y_gt), ptr(d_gt), npix, nsc, no, ptr(ws), n, ptr(sums), rn.stream_ptr()),
+        'ra_fg_stats_f32')
+  return dict(zip(FG_STAT_NAMES, sums.cpu().tolist()))
+
+
+def _sweep_thresholds(thresholds):
+  thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+  if not 1 <= thr.size <= FG_SWEEP_MAX_K:
+    raise rn.RecAttendError('fg_sweep_counts: %d thresholds (1 .. %d)' % (thr.size, FG_SWEEP_MAX_K))
+  return thr
+
+
+def fg_sweep_counts_device(src, gt, thresholds, out=None):
+  """ra_fg_sweep_counts_f32 without the copy to the host: src float32 [N,Hs,Ws], gt uint8 [N,H,W], thresholds (host values)
+  -> int64 device tensor [N, RA_FG_SWEEP_SLOTS] (count_a at [:, :K], sum_ab at [:, 16:16 + K], sum_b at [:, 32])."""
+  thr = _sweep_thresholds(thresholds)
+  if not (isinstance(src, torch.Tensor) and isinstance(gt, torch.Tensor)) or not src.is_cuda or not gt.is_cuda:
+    raise rn.RecAttendError('fg_sweep_counts needs CUDA (HIP) tensors; got a CPU tensor. There is no CPU fallback.')
+  if src.dtype != torch.float32 or gt.dtype != torch.uint8 or not src.is_contiguous() or not gt.is_contiguous():
+    raise rn.RecAttendError('fg_sweep_counts: src must be contiguous float32 and gt contiguous uint8, got %s and %s' % (src.dtype, gt.dtype))
+  if src.dim() != 3 or gt.dim() != 3 or src.shape[0] != gt.shape[0] or min(src.shape) < 1 or min(gt.shape) < 1:
+    raise rn.RecAttendError('fg_sweep_counts: src must be [N,Hs,Ws] and gt [N,H,W], got %s and %s' % (tuple(src.shape), tuple(gt.shape)))
+  N, Hs, Ws = src.shape
+  H, W = gt.shape[1:]
+  if H * W >= 1 << 31 or Hs * Ws >= 1 << 31 or N > 65535:
+    raise rn.RecAttendError('fg_sweep_counts: N=%d, %d x %d -> %d x %d (N <= 65535, planes below 2^31 pixels)' % (N, Hs, Ws, H, W))
+  if out is None:
+    out = torch.empty((N, rn.RA_FG_SWEEP_SLOTS), dtype=torch.int64, device=src.device)
+  elif tuple(out.shape) != (N, rn.RA_FG_SWEEP_SLOTS) or out.dtype != torch.int64 or not out.is_cuda or not out.is_contiguous():
+    raise rn.RecAttendError('fg_sweep_counts: out must be a contiguous int64 device tensor [%d, %d]' % (N, rn.RA_FG_SWEEP_SLOTS))
+  check(rn.lib().ra_fg_sweep_counts_f32(ptr(src), ptr(gt), N, Hs, Ws, H, W, ptr(thr), int(thr.size), ptr(out), rn.stream_ptr()),
+        'ra_fg_sweep_counts_f32')
+  return out
+
+
+def fg_sweep_counts(src, gt, thresholds):
+  """fg_model_eval.py:134-178 up to the analyzers' sums, for every threshold at once: src float32 [N,Hs,Ws] (the soft
+  foreground at network size), gt uint8 [N,H,W] (the full-size labels summed over the instances; 2 and more where instances
+  overlap) -> {'count_a' [N,K], 'sum_ab' [N,K], 'sum_b' [N], 'pixels': H * W, 'thresholds'}: NumPy int64 on the host,
+  with a = [bilateralFilter(resize(src), 5, 10, 10) > threshold], which is never written (ra_fg_sweep_counts_f32)."""
+  c = fg_sweep_counts_device(src, gt, thresholds).cpu().numpy()
+  K = len(_sweep_thresholds(thresholds))
+  return {'count_a': c[:, :K].copy(), 'sum_ab': c[:, FG_SWEEP_MAX_K:FG_SWEEP_MAX_K + K].copy(), 'sum_b': c[:, 2 * FG_SWEEP_MAX_K].copy(),
+          'pixels': int(gt.shape[1] * gt.shape[2]), 'thresholds': [float(t) for t in _sweep_thresholds(thresholds)]}
