@@ -9,12 +9,13 @@
 // (they are shared by all examples, so they stay L2/MALL resident).  This is a latency-bound
 // GEMV chain, not a roofline kernel.
 #include "ra_common.h"
+#include "ra_ctrl_parts.h"
 
 namespace ra {
 namespace ctrl {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kThreads = 1024;
+constexpr int kThreads = kCtrlWgThreads;
 constexpr int kRed = 4096;         // floats of reduction scratch
 constexpr int kMaxFeatLds = 24576; // floats (96 KiB) of feature map kept in LDS
 
@@ -83,24 +84,6 @@ __device__ void gemv(const float *xs, int K, const float *__restrict__ Wt, int N
   __syncthreads();
 }
 
-__device__ inline float sigm(float z) { return 1.0f / (1.0f + expf(-z)); }
-
-__device__ float block_reduce(float v, bool is_max, float *red) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float other = __shfl_xor(v, o);
-    v = is_max ? fmaxf(v, other) : v + other;
-  }
-  __syncthreads();
-  if ((t & 63) == 0) red[t >> 6] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < kThreads / 64; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  __syncthreads();
-  return r;
-}
-
 __global__ __launch_bounds__(kThreads) void controller_kernel(const ra_ctrl_desc d,
                                                                const float *feat,
                                                                const float *__restrict__ wp,
@@ -141,22 +124,7 @@ __global__ __launch_bounds__(kThreads) void controller_kernel(const ra_ctrl_desc
     if (gmaps)
       for (int g = t; g < G; g += kThreads) gmaps[((size_t)b * d.iters + it) * G + g] = gm[g];
     // glimpse[c] = sum_g feat[g,c] * map[g]   (full_model.py:680)
-    {
-      const int parts = kThreads / Cf;  // Cf <= 1024
-      const int c = t % Cf, part = t / Cf;
-      if (part < parts) {
-        float s = 0.0f;
-        for (int g = part; g < G; g += parts) s += fsrc[(size_t)g * Cf + c] * gm[g];
-        red[part * Cf + c] = s;
-      }
-      __syncthreads();
-      if (t < Cf) {
-        float s = 0.0f;
-        for (int p = 0; p < parts; ++p) s += red[p * Cf + t];
-        xh[t] = s;
-      }
-      __syncthreads();
-    }
+    glimpse_readout(fsrc, gm, G, Cf, red, xh);
     // LSTM (nnlib.py:641-646): columns gate-major i, f, o, u
     gemv(xh, Cf + hid, wp + L.lstm_w, 4 * hid, va, red);
     if (t < hid) {
@@ -191,14 +159,14 @@ __global__ __launch_bounds__(kThreads) void controller_kernel(const ra_ctrl_desc
             o1[n] += bb[n];
             mx = fmaxf(mx, o1[n]);
           }
-          mx = block_reduce(mx, true, red);
+          mx = block_reduce16(mx, true, red);
           float sum = 0.0f;
           for (int n = t; n < No; n += kThreads) {
             const float e = expf(o1[n] - mx);
             o1[n] = e;
             sum += e;
           }
-          sum = block_reduce(sum, false, red);
+          sum = block_reduce16(sum, false, red);
           for (int n = t; n < Gp; n += kThreads) gm[n] = (n < No) ? o1[n] / sum : 0.0f;
           __syncthreads();
         }
@@ -227,32 +195,7 @@ __global__ __launch_bounds__(kThreads) void controller_kernel(const ra_ctrl_desc
     const float *co = in;  // 9 outputs
     if (t < hid && h_last) h_last[(size_t)b * hid + t] = xh[Cf + t];
     if (t < 9 && ctrl_out) ctrl_out[(size_t)b * 9 + t] = co[t];
-    if (t == 0 && attn) {
-      float *r = attn + (size_t)b * RA_ATTN_STRIDE;
-      float cn[2] = {co[0], co[1]}, ls[2] = {co[2], co[3]};
-      if (d.squash) {  // full_model.py:695-697
-        cn[0] = tanhf(cn[0]);
-        cn[1] = tanhf(cn[1]);
-        ls[0] = -log1pf(expf(ls[0]));
-        ls[1] = -log1pf(expf(ls[1]));
-      }
-      const float dim[2] = {(float)d.H, (float)d.W}, fs[2] = {(float)d.Fh, (float)d.Fw};
-      for (int k = 0; k < 2; ++k) {
-        const float ctr = (cn[k] + 1.0f) * (dim[k] / 2.0f);  // modellib.py:761-763
-        const float size = expf(ls[k]) * dim[k];             // modellib.py:821-823
-        float lv = d.fixed_var ? 0.0f : logf(size) - logf(fs[k]);  // modellib.py:791-792
-        if (d.dynamic_var) lv = co[4 + k];
-        r[0 + k] = ctr;
-        r[2 + k] = size;
-        r[4 + k] = lv;
-        r[9 + k] = cn[k];
-        r[11 + k] = ls[k];
-      }
-      r[6] = d.fixed_gamma ? 1.0f : expf(co[6]);  // full_model.py:711-719
-      r[7] = expf(co[7]);
-      r[8] = d.fixed_gamma ? 2.0f : co[8];
-      r[13] = r[14] = r[15] = 0.0f;
-    }
+    if (t == 0 && attn) store_attn_record(d, co, attn + (size_t)b * RA_ATTN_STRIDE);
   }
 }
 

@@ -14,8 +14,10 @@
 // Results are identical in structure to the single-workgroup kernel (same products, different
 // summation grouping; float32 round-off class).
 #include <cstdlib>
+#include <type_traits>
 
 #include "ra_common.h"
+#include "ra_ctrl_parts.h"
 
 namespace ra {
 namespace ctrl2 {
@@ -27,6 +29,7 @@ constexpr int kP = 16;         // workgroups per image
 constexpr int kThreads = 256;  // 4 waves
 constexpr int kMaxFeatRegs = 96;
 constexpr unsigned kSpinLimit = 4000000u;
+constexpr int kMaxResidentWgs = 224;  // spinning workgroups of one launch: the 256 CUs less a margin of 32
 
 struct Layout {            // per-slice packed weights (floats), identical for every slice
   int us, gs, K, NL;       // units per slice, logits per slice, Cf + hid, 4 * us
@@ -87,6 +90,12 @@ __host__ __device__ inline size_t ws_words_per_image(const ra_ctrl_desc &d) {
   return 2 + 2 * granules_per_image(d);  // 32-bit words: [generation, pad] + 8-byte granules
 }
 
+// dynamic LDS of the per-image form: the slice, 4 * 256 partial sums, [glimpse ; h], the hidden vector, the logits, red4
+__host__ inline size_t lds_bytes(const ra_ctrl_desc &d) {
+  const Layout L = layout(d);
+  return (L.slice + 4 * (size_t)kThreads + round_up(L.K, 4) + d.hid + round_up(kP * L.gs, 4) + 64) * sizeof(float);
+}
+
 __host__ inline int supported(const ra_ctrl_desc &d) {
   if (d.hid % kP || d.hid > kThreads || d.Cf <= 0 || kThreads % d.Cf || d.n_gmlp < 1 ||
       d.n_gmlp > 8 || d.n_cmlp < 1 || d.n_cmlp > 8 || d.G <= 0 || d.G > 4096 || d.iters <= 0 ||
@@ -94,64 +103,113 @@ __host__ inline int supported(const ra_ctrl_desc &d) {
     return 0;
   if (kThreads % (d.hid / kP) || kThreads % (4 * (d.hid / kP))) return 0;
   if ((size_t)d.G * d.Cf > (size_t)kMaxFeatRegs * kThreads) return 0;
-  const Layout L = layout(d);
-  if (4 * L.us > kThreads) return 0;
-  const size_t lds = (L.slice + 4 * (size_t)kThreads + round_up(L.K, 4) + d.hid +
-                      round_up(kP * L.gs, 4) + 64) * sizeof(float);
-  return lds <= 160 * 1024;
+  if (4 * layout(d).us > kThreads) return 0;
+  return lds_bytes(d) <= 160 * 1024;
 }
 
-__device__ inline void publish(u64 *g, unsigned tag, float v) {
-  __hip_atomic_store(g, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED,
-                     __HIP_MEMORY_SCOPE_AGENT);
-}
-
-// every thread gathers values t, t+256, ... of an n-value exchange into dst (LDS)
-__device__ inline void gather(const u64 *g, int n, unsigned tag, float *dst, int *err) {
-  for (int i = threadIdx.x; i < n; i += kThreads) {
-    unsigned spins = 0;
-    u64 x;
-    while (true) {
-      x = __hip_atomic_load(g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-      if ((unsigned)(x >> 32) == tag) break;
-      if (++spins > kSpinLimit) {
-        *err = 1;  // a peer workgroup never arrived: report instead of hanging
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    dst[i] = __uint_as_float((unsigned)x);
-  }
-  __syncthreads();
-}
-
-// XCD-local exchange (the XL form of the per-image kernel): when the 16 workgroups of an image sit on ONE XCD, that XCD's L2 is
-// their coherence point — a granule is a plain 8-byte store (the vector L1 writes through) and a poll is a load that only
-// bypasses the CU's L1 (sc0), 0.3-0.5 us a round instead of the ~2.5 us of an agent-scope exchange through the memory fabric
+// The all-gather of a team of workgroups (the group kernel's; controller_split_kernel keeps helpers of its own, below): 8-byte {tag, value} granules behind the generation word of the
+// workspace block wsb.  XL = false: a granule is one relaxed agent-scope atomic store, a poll one relaxed agent-scope load.
+// XL = true, the XCD-local forms: when the workgroups of a team sit on ONE XCD, that XCD's L2 is their coherence point — a
+// granule is a plain 8-byte store (the vector L1 writes through) and a poll is a load that only bypasses the CU's L1 (sc0),
+// 0.3-0.5 us a round instead of the ~2.5 us of an agent-scope exchange through the memory fabric
 // (tools/xcd_barrier_probe.hip; the 13 gathers of a timestep were 37 of the launch's 63 us).
 typedef unsigned u32x2g __attribute__((ext_vector_type(2)));
-__device__ inline void publish_l2(__amdgpu_buffer_rsrc_t r, int idx, unsigned tag, float v) {
-  __builtin_amdgcn_raw_buffer_store_b64(u32x2g{__float_as_uint(v), tag}, r, idx * 8, 0, 0);
-}
-__device__ inline void gather_l2(__amdgpu_buffer_rsrc_t r, int first, int n, unsigned tag, float *dst, int *err) {
-  for (int i = threadIdx.x; i < n; i += kThreads) {
-    unsigned spins = 0;
-    u32x2g x;
-    while (true) {
-      x = __builtin_amdgcn_raw_buffer_load_b64(r, (first + i) * 8, 0, (int)0x80000001u);  // sc0 (past the L1), volatile
-      if (x.y == tag) break;
-      if (++spins > kSpinLimit) {
-        *err = 1;
-        break;
-      }
-      __builtin_amdgcn_s_sleep(1);
-    }
-    dst[i] = __uint_as_float(x.x);
-  }
-  __syncthreads();
-}
+template <bool XL>
+struct Exchange {
+  u64 *gran;
+  __amdgpu_buffer_rsrc_t rs;
+  unsigned tag;  // this launch's generation
+  int err = 0;   // a peer workgroup never arrived: reported through the status word instead of hanging
 
-__device__ inline float sigm(float z) { return 1.0f / (1.0f + expf(-z)); }
+  __device__ __forceinline__ Exchange(unsigned *wsb, size_t granules)
+      : gran(reinterpret_cast<u64 *>(wsb + 2)),
+        rs(__builtin_amdgcn_make_buffer_rsrc(gran, 0, (int)(granules * 8), 0x00020000)),
+        tag(wsb[0] + 1u) {}
+
+  __device__ __forceinline__ void publish(size_t idx, float v) const {
+    if constexpr (XL)
+      __builtin_amdgcn_raw_buffer_store_b64(u32x2g{__float_as_uint(v), tag}, rs, (int)idx * 8, 0, 0);
+    else
+      __hip_atomic_store(gran + idx, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  }
+
+  // one poll of granule idx: {value bits, tag}
+  __device__ __forceinline__ u32x2g load(size_t idx) const {
+    if constexpr (XL) {
+      return __builtin_amdgcn_raw_buffer_load_b64(rs, (int)idx * 8, 0, (int)0x80000001u);  // sc0 (past the L1), volatile
+    } else {
+      const u64 x = __hip_atomic_load(gran + idx, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      return u32x2g{(unsigned)x, (unsigned)(x >> 32)};
+    }
+  }
+
+  // The poll loop: granules first .. first + total, store(e, value) once for each as it arrives.  A thread owns up to INFLIGHT
+  // granules per pass and polls them TOGETHER (all loads in flight, then the tag checks): in the group kernel, polled one
+  // after the other, eight L2 round trips per gather made it slower than the one-workgroup form.  A granule that never
+  // arrives is not stored.
+  template <int INFLIGHT, class Store>
+  __device__ __forceinline__ void poll(size_t first, int total, Store store) {
+    for (int base = 0; base < total; base += kThreads * INFLIGHT) {
+      unsigned pending = 0;
+#pragma unroll
+      for (int j = 0; j < INFLIGHT; ++j)
+        if (base + threadIdx.x + kThreads * j < total) pending |= 1u << j;
+      unsigned spins = 0;
+      while (pending) {
+        u32x2g x[INFLIGHT];
+#pragma unroll
+        for (int j = 0; j < INFLIGHT; ++j)
+          if (pending & (1u << j)) x[j] = load(first + base + threadIdx.x + kThreads * j);
+#pragma unroll
+        for (int j = 0; j < INFLIGHT; ++j)
+          if ((pending & (1u << j)) && x[j].y == tag) {
+            store(base + threadIdx.x + kThreads * j, __uint_as_float(x[j].x));
+            pending &= ~(1u << j);
+          }
+        if (pending) {
+          if (++spins > kSpinLimit) {
+            err = 1;
+            break;
+          }
+          __builtin_amdgcn_s_sleep(1);
+        }
+      }
+    }
+    __syncthreads();
+  }
+
+  // all workgroups of the team: n values per image, images i < nimg, from granule first on: granule (i * n + j) -> dst[i * stride + j] (LDS)
+  template <int INFLIGHT>
+  __device__ __forceinline__ void gather(size_t first, int n, int nimg, float *dst, int stride) {
+    poll<INFLIGHT>(first, n * nimg, [&](int e, float v) {
+      const int i = e / n, c = e - i * n;
+      dst[i * stride + c] = v;
+    });
+  }
+};
+
+// weight slice p -> LDS (stays for the whole launch): batches of 16 independent 16-byte loads per thread: the fill is
+// latency-, not bandwidth-bound, so keep many loads in flight before the first LDS store
+__device__ __forceinline__ void fill_slice(float *W, const float *__restrict__ wp, int p, const Layout &L) {
+  const int t = threadIdx.x;
+  const f32x4 *src = reinterpret_cast<const f32x4 *>(wp + (size_t)p * L.slice);
+  f32x4 *dst = reinterpret_cast<f32x4 *>(W);
+  const int n4 = (int)(L.slice / 4);
+  constexpr int U = 16;
+  for (int e0 = t; e0 < n4; e0 += kThreads * U) {
+    f32x4 tmp[U];
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e = e0 + u * kThreads;
+      tmp[u] = src[e < n4 ? e : n4 - 1];
+    }
+#pragma unroll
+    for (int u = 0; u < U; ++u) {
+      const int e = e0 + u * kThreads;
+      if (e < n4) dst[e] = tmp[u];
+    }
+  }
+}
 
 __device__ float block_reduce(float v, bool is_max, float *red4) {
 #pragma unroll
@@ -199,6 +257,89 @@ __device__ inline int any_gemv(const float *Wm, int n, const float *x, int K, fl
   __syncthreads();
   *ncol_out = ncol;
   return parts;
+}
+
+// The tail of image b, run by ONE workgroup: the controller MLP on its final h (LDS; weights from L2), then the h_last,
+// ctrl_out and attention-record stores.  o1 / o2: two LDS vectors of >= max(mlp_dim, 9) floats the layers ping-pong
+// between; scratch: 256 floats of partial sums.
+__device__ __forceinline__ void finish_image(const ra_ctrl_desc &d, const Layout &L, const float *__restrict__ wp, const float *h,
+                                             float *o1, float *o2, float *scratch, int b, float *h_last, float *ctrl_out,
+                                             float *attn) {
+  const int t = threadIdx.x;
+  const float *in = h;
+  for (int l = 0; l < d.n_cmlp; ++l) {
+    const int N = L.cm_out[l], Kin = L.cm_in[l];
+    const float *Wc = wp + L.cm_w[l], *bc = wp + L.cm_b[l];
+    const bool last = (l == d.n_cmlp - 1);
+    int ncol;
+    const int parts = any_gemv(Wc, N, in, Kin, scratch, &ncol);
+    if (t < N) {
+      float a = bc[t];
+      for (int q = 0; q < parts; ++q) a += scratch[q * ncol + t];
+      o1[t] = last ? a : fmaxf(a, 0.0f);
+    }
+    __syncthreads();
+    in = o1;
+    float *tmp = o1;
+    o1 = o2;
+    o2 = tmp;
+  }
+  const float *co = in;
+  if (t < d.hid && h_last) h_last[(size_t)b * d.hid + t] = h[t];
+  if (t < 9 && ctrl_out) ctrl_out[(size_t)b * 9 + t] = co[t];
+  if (t == 0 && attn) store_attn_record(d, co, attn + (size_t)b * RA_ATTN_STRIDE);
+}
+
+// controller_split_kernel keeps its own exchange helpers and its own slice fill and tail, the text it had before the group kernel
+// moved onto Exchange / fill_slice / finish_image: written through them its production instantiation <64, true> took 57.4-57.5 us
+// per launch at cfg2 against 56.8-56.9 (profiles/ctrl_forms.txt), outside what a refactor may cost.
+__device__ inline void publish(u64 *g, unsigned tag, float v) {
+  __hip_atomic_store(g, ((u64)tag << 32) | (u64)__float_as_uint(v), __ATOMIC_RELAXED,
+                     __HIP_MEMORY_SCOPE_AGENT);
+}
+
+// every thread gathers values t, t+256, ... of an n-value exchange into dst (LDS)
+__device__ inline void gather(const u64 *g, int n, unsigned tag, float *dst, int *err) {
+  for (int i = threadIdx.x; i < n; i += kThreads) {
+    unsigned spins = 0;
+    u64 x;
+    while (true) {
+      x = __hip_atomic_load(g + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      if ((unsigned)(x >> 32) == tag) break;
+      if (++spins > kSpinLimit) {
+        *err = 1;  // a peer workgroup never arrived: report instead of hanging
+        break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+    }
+    dst[i] = __uint_as_float((unsigned)x);
+  }
+  __syncthreads();
+}
+
+// XCD-local exchange (the XL form of the per-image kernel): when the 16 workgroups of an image sit on ONE XCD, that XCD's L2 is
+// their coherence point — a granule is a plain 8-byte store (the vector L1 writes through) and a poll is a load that only
+// bypasses the CU's L1 (sc0), 0.3-0.5 us a round instead of the ~2.5 us of an agent-scope exchange through the memory fabric
+// (tools/xcd_barrier_probe.hip; the 13 gathers of a timestep were 37 of the launch's 63 us).
+__device__ inline void publish_l2(__amdgpu_buffer_rsrc_t r, int idx, unsigned tag, float v) {
+  __builtin_amdgcn_raw_buffer_store_b64(u32x2g{__float_as_uint(v), tag}, r, idx * 8, 0, 0);
+}
+__device__ inline void gather_l2(__amdgpu_buffer_rsrc_t r, int first, int n, unsigned tag, float *dst, int *err) {
+  for (int i = threadIdx.x; i < n; i += kThreads) {
+    unsigned spins = 0;
+    u32x2g x;
+    while (true) {
+      x = __builtin_amdgcn_raw_buffer_load_b64(r, (first + i) * 8, 0, (int)0x80000001u);  // sc0 (past the L1), volatile
+      if (x.y == tag) break;
+      if (++spins > kSpinLimit) {
+        *err = 1;
+        break;
+      }
+      __builtin_amdgcn_s_sleep(1);
+    }
+    dst[i] = __uint_as_float(x.x);
+  }
+  __syncthreads();
 }
 
 // XL = false: grid (16, B), workgroup (p, b) = blockIdx; the image's workgroups are dealt over all eight XCDs and exchange
@@ -387,32 +528,7 @@ __global__ __launch_bounds__(kThreads) void controller_split_kernel(
     const float *co = in;
     if (t < hid && h_last) h_last[(size_t)b * hid + t] = xh[Cf + t];
     if (t < 9 && ctrl_out) ctrl_out[(size_t)b * 9 + t] = co[t];
-    if (t == 0 && attn) {
-      float *r = attn + (size_t)b * RA_ATTN_STRIDE;
-      float cn[2] = {co[0], co[1]}, ls[2] = {co[2], co[3]};
-      if (d.squash) {  // full_model.py:695-697
-        cn[0] = tanhf(cn[0]);
-        cn[1] = tanhf(cn[1]);
-        ls[0] = -log1pf(expf(ls[0]));
-        ls[1] = -log1pf(expf(ls[1]));
-      }
-      const float dim[2] = {(float)d.H, (float)d.W}, fs[2] = {(float)d.Fh, (float)d.Fw};
-      for (int k = 0; k < 2; ++k) {
-        const float ctr = (cn[k] + 1.0f) * (dim[k] / 2.0f);
-        const float size = expf(ls[k]) * dim[k];
-        float lv = d.fixed_var ? 0.0f : logf(size) - logf(fs[k]);
-        if (d.dynamic_var) lv = co[4 + k];
-        r[0 + k] = ctr;
-        r[2 + k] = size;
-        r[4 + k] = lv;
-        r[9 + k] = cn[k];
-        r[11 + k] = ls[k];
-      }
-      r[6] = d.fixed_gamma ? 1.0f : expf(co[6]);
-      r[7] = expf(co[7]);
-      r[8] = d.fixed_gamma ? 2.0f : co[8];
-      r[13] = r[14] = r[15] = 0.0f;
-    }
+    if (t == 0 && attn) store_attn_record(d, co, attn + (size_t)b * RA_ATTN_STRIDE);
     // new generation for the next launch: every peer of this image has read ws[0] long ago (this
     // workgroup could not have finished its last gather otherwise)
     if (t == 0)
@@ -421,24 +537,45 @@ __global__ __launch_bounds__(kThreads) void controller_split_kernel(
   if (err && status) atomicMax(status, 1);
 }
 
+// May a launch use the XCD-local forms?  1 wherever the device's workgroups report the XCC ids 0..7 (ra_core.hip's census),
+// 0 where they do not or RA_CTRL_XCD=0 asks for the agent-scope exchange, -1 while the census cannot tell (asked inside a
+// stream capture: that launch runs the agent-scope form and the next one asks again).  *both: RA_CTRL_XCD=2.
+inline int xcd_local(int *both = nullptr) {
+  static int xl = -1, xl_both = 0;
+  if (xl < 0) {
+    const int asked = env_int("RA_CTRL_XCD", 1);
+    xl_both = asked == 2 ? 1 : 0;
+    if (asked == 0) xl = 0;
+    else if (const int c = xcc_census_ok(); c >= 0) xl = c;
+  }
+  if (both) *both = xl_both;
+  return xl;
+}
+
+// the XCD-local forms' role tickets: 8 pools of kTicketPoolStride words at the END of the caller's workspace (not behind THIS
+// launch's images: a workspace sized for more images than it is launched with keeps its granules and its role tickets apart)
+inline unsigned *ticket_pools(unsigned *ws, size_t ws_bytes) { return ws + ws_bytes / 4 - kTicketSlotWords; }
+
+// f(std::integral_constant<int, FR>) for the smallest FR built that holds fr feature registers per thread
+template <class F>
+int with_feat_regs(int fr, F &&f) {
+  if (fr <= 4) return f(std::integral_constant<int, 4>());
+  if (fr <= 16) return f(std::integral_constant<int, 16>());
+  if (fr <= 32) return f(std::integral_constant<int, 32>());
+  if (fr <= 64) return f(std::integral_constant<int, 64>());
+  return f(std::integral_constant<int, 96>());
+}
+
 template <int FR>
 int launch(const ra_ctrl_desc &d, const float *feat, const float *wp, int B, float *h_last,
-           float *ctrl_out, float *gmaps, float *attn, unsigned *ws, size_t ws_bytes, int *status, size_t lds,
-           hipStream_t st) {
+           float *ctrl_out, float *gmaps, float *attn, unsigned *ws, size_t ws_bytes, int *status, hipStream_t st) {
   auto kern = controller_split_kernel<FR, false>;
   auto kern_xl = controller_split_kernel<FR, true>;
   static const MaxDynamicLds lds_limit(kern, 160 * 1024), lds_limit_xl(kern_xl, 160 * 1024);
-  // the XCD-local form wherever the device's workgroups report the XCC ids 0..7 (ra_core.hip's census); RA_CTRL_XCD=0: the old one
-  static int xl = -1, xl_all = 0;
-  if (xl < 0) {
-    const int asked = env_int("RA_CTRL_XCD", 1);
-    xl_all = asked == 2 ? 1 : 0;
-    if (asked == 0) xl = 0;
-    else if (const int c = xcc_census_ok(); c >= 0) xl = c;  // (-1: asked inside a stream capture — decide at the next launch)
-  }
-  // 8 pools of kTicketPoolStride words at the END of the caller's workspace (not behind THIS launch's images: a workspace sized for
-  // more images than it is launched with keeps its granules and its role tickets apart)
-  unsigned *tickets = ws + ws_bytes / 4 - 8 * kTicketPoolStride;
+  const size_t lds = lds_bytes(d);
+  unsigned *tickets = ticket_pools(ws, ws_bytes);
+  int xl_all;
+  const int xl = xcd_local(&xl_all);
   // up to 8 images: one team per XCD, 16 of its 32 CUs — as much headroom as the grid (16, B) form has on the whole chip.  9-14
   // images would put two teams on some XCDs and need ALL their CUs: those launches keep the grid (16, B) form (RA_CTRL_XCD=2: both)
   if (xl == 1 && (B <= 8 || xl_all))
@@ -487,79 +624,6 @@ __host__ inline int batch_supported(const ra_ctrl_desc &d) {
   while (gsp < L.gs) gsp <<= 1;
   if (gsp > 64 || L.us * NI > kThreads || d.Cf > kThreads) return 0;
   return batch_lds_bytes<NI>(d) <= 160 * 1024;
-}
-
-// n values per image, images i < nimg: granule (i * n + j) -> dst[i * stride + j].  A thread owns up to 8
-// granules per pass and polls them TOGETHER (all loads in flight, then the tag checks): polled one after
-// the other, eight L2 round trips per gather made the kernel slower than the one-workgroup form.
-__device__ inline void gather_multi(const u64 *g, int n, int nimg, unsigned tag, float *dst, int stride, int *err) {
-  const int total = n * nimg;
-  for (int base = 0; base < total; base += kThreads * 8) {
-    unsigned pending = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (base + threadIdx.x + kThreads * j < total) pending |= 1u << j;
-    unsigned spins = 0;
-    while (pending) {
-      u64 x[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (pending & (1u << j))
-          x[j] = __hip_atomic_load(g + base + threadIdx.x + kThreads * j, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if ((pending & (1u << j)) && (unsigned)(x[j] >> 32) == tag) {
-          const int e = base + threadIdx.x + kThreads * j;
-          const int i = e / n, c = e - i * n;
-          dst[i * stride + c] = __uint_as_float((unsigned)x[j]);
-          pending &= ~(1u << j);
-        }
-      if (pending) {
-        if (++spins > kSpinLimit) {
-          *err = 1;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-  }
-  __syncthreads();
-}
-
-// ... the same through the XCD's L2 (the XL form of K2b, round 6): granules are plain 8-byte stores of the producer, polled
-// with loads that bypass this CU's L1 — as gather_l2 above, eight in flight per thread.
-__device__ inline void gather_multi_l2(__amdgpu_buffer_rsrc_t r, size_t first, int n, int nimg, unsigned tag, float *dst, int stride, int *err) {
-  const int total = n * nimg;
-  for (int base = 0; base < total; base += kThreads * 8) {
-    unsigned pending = 0;
-#pragma unroll
-    for (int j = 0; j < 8; ++j)
-      if (base + threadIdx.x + kThreads * j < total) pending |= 1u << j;
-    unsigned spins = 0;
-    while (pending) {
-      u32x2g x[8];
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if (pending & (1u << j))
-          x[j] = __builtin_amdgcn_raw_buffer_load_b64(r, (int)(first + base + threadIdx.x + kThreads * j) * 8, 0, (int)0x80000001u);
-#pragma unroll
-      for (int j = 0; j < 8; ++j)
-        if ((pending & (1u << j)) && x[j].y == tag) {
-          const int e = base + threadIdx.x + kThreads * j;
-          const int i = e / n, c = e - i * n;
-          dst[i * stride + c] = __uint_as_float(x[j].x);
-          pending &= ~(1u << j);
-        }
-      if (pending) {
-        if (++spins > kSpinLimit) {
-          *err = 1;
-          break;
-        }
-        __builtin_amdgcn_s_sleep(1);
-      }
-    }
-  }
-  __syncthreads();
 }
 
 // out[i][col] = sum_k x[i][k] * W[k][col] for the images of the group; ncol a power of two <= 64, n real columns;
@@ -630,38 +694,9 @@ __global__ __launch_bounds__(kThreads) void controller_batch_kernel(const ra_ctr
   float *va = xh + NI * Kp;                // [NI][hid] hidden MLP vector
   float *gm = va + NI * hid;               // [NI][Gxp] logits -> glimpse map
   unsigned *wsg = ws + (size_t)grp * ws_words_per_group<NI>(d);
-  const unsigned tag = wsg[0] + 1u;
-  u64 *gran = reinterpret_cast<u64 *>(wsg + 2);
-  const __amdgpu_buffer_rsrc_t grs = __builtin_amdgcn_make_buffer_rsrc(gran, 0, (int)(granules_per_group<NI>(d) * 8), 0x00020000);
-  int err = 0;
-  auto publish = [&](u64 *g, unsigned tg, float v) {  // (shadows the agent-scope helper: g is an address inside `gran`)
-    if constexpr (XL) publish_l2(grs, (int)(g - gran), tg, v);
-    else ctrl2::publish(g, tg, v);
-  };
-  auto gather_multi = [&](const u64 *g, int n, int nimg_, unsigned tg, float *dst, int stride, int *e) {
-    if constexpr (XL) gather_multi_l2(grs, (size_t)(g - gran), n, nimg_, tg, dst, stride, e);
-    else ctrl2::gather_multi(g, n, nimg_, tg, dst, stride, e);
-  };
+  Exchange<XL> ex(wsg, granules_per_group<NI>(d));
 
-  {  // weight slice -> LDS (stays for the whole launch)
-    const f32x4 *src = reinterpret_cast<const f32x4 *>(wp + (size_t)p * L.slice);
-    f32x4 *dst = reinterpret_cast<f32x4 *>(W);
-    const int n4 = (int)(L.slice / 4);
-    constexpr int U = 16;
-    for (int e0 = t; e0 < n4; e0 += kThreads * U) {
-      f32x4 tmp[U];
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int e = e0 + u * kThreads;
-        tmp[u] = src[e < n4 ? e : n4 - 1];
-      }
-#pragma unroll
-      for (int u = 0; u < U; ++u) {
-        const int e = e0 + u * kThreads;
-        if (e < n4) dst[e] = tmp[u];
-      }
-    }
-  }
+  fill_slice(W, wp, p, L);
   // this workgroup reads out the glimpse of image `mine` (the first nimg workgroups publish theirs)
   const int mine = p % nimg;
   float fr[FR];
@@ -698,11 +733,11 @@ __global__ __launch_bounds__(kThreads) void controller_batch_kernel(const ra_ctr
       if (t < Cf && p < nimg) {
         float a = 0.0f;
         for (int q = 0; q < gstep; ++q) a += red[q * Cf + t];
-        publish(gran + goff + (size_t)mine * Cf + t, tag, a);
+        ex.publish(goff + (size_t)mine * Cf + t, a);
       }
       __syncthreads();
     }
-    gather_multi(gran + goff, Cf, nimg, tag, xh, Kp, &err);
+    ex.template gather<8>(goff, Cf, nimg, xh, Kp);
     goff += (size_t)NI * Cf;
     // ---- LSTM slice, all images ----
     {
@@ -717,10 +752,10 @@ __global__ __launch_bounds__(kThreads) void controller_batch_kernel(const ra_ctr
         }
         const float gi = sigm(pre[0]), gf = sigm(pre[1]), go = sigm(pre[2]), u = tanhf(pre[3]);
         cst = gf * cst + gi * u;
-        publish(gran + goff + (size_t)ci * hid + p * us + cu, tag, go * tanhf(cst));
+        ex.publish(goff + (size_t)ci * hid + p * us + cu, go * tanhf(cst));
       }
     }
-    gather_multi(gran + goff, hid, nimg, tag, xh + Cf, Kp, &err);
+    ex.template gather<8>(goff, hid, nimg, xh + Cf, Kp);
     goff += (size_t)NI * hid;
     if (it == d.iters - 1) break;
     // ---- glimpse MLP hidden layers (relu) ----
@@ -731,9 +766,9 @@ __global__ __launch_bounds__(kThreads) void controller_batch_kernel(const ra_ctr
       if (t < us * NI && ci < nimg) {
         float a = W[L.gh_b[l] + cu];
         for (int q = 0; q < parts; ++q) a += red[(q * NI + ci) * us + cu];
-        publish(gran + goff + (size_t)ci * hid + p * us + cu, tag, fmaxf(a, 0.0f));
+        ex.publish(goff + (size_t)ci * hid + p * us + cu, fmaxf(a, 0.0f));
       }
-      gather_multi(gran + goff, hid, nimg, tag, va, hid, &err);
+      ex.template gather<8>(goff, hid, nimg, va, hid);
       goff += (size_t)NI * hid;
       in = va;
       ins = hid;
@@ -746,9 +781,9 @@ __global__ __launch_bounds__(kThreads) void controller_batch_kernel(const ra_ctr
       if (t < ncol * NI && li < nimg && lu < gs) {
         float a = W[L.gl_b + lu];
         for (int q = 0; q < parts; ++q) a += red[(q * NI + li) * ncol + lu];
-        publish(gran + goff + (size_t)li * Gx + p * gs + lu, tag, a);
+        ex.publish(goff + (size_t)li * Gx + p * gs + lu, a);
       }
-      gather_multi(gran + goff, Gx, nimg, tag, gm, Gxp, &err);
+      ex.template gather<8>(goff, Gx, nimg, gm, Gxp);
       goff += (size_t)NI * Gx;
       const int wave = t >> 6, lane = t & 63;
       for (int i = wave; i < nimg; i += kThreads / 64) {
@@ -765,79 +800,26 @@ __global__ __launch_bounds__(kThreads) void controller_batch_kernel(const ra_ctr
     }
   }
 
-  if (p < nimg) {
-    // ---- controller MLP + attention decode of image p (weights from L2) ----
-    const int b = b0 + p;
-    const float *in = xh + p * Kp + Cf;
-    float *o1 = va + p * hid, *o2 = red;  // va row p is this workgroup's own; red is free now
-    for (int l = 0; l < d.n_cmlp; ++l) {
-      const int N = L.cm_out[l], Kin = L.cm_in[l];
-      const float *Wc = wp + L.cm_w[l], *bc = wp + L.cm_b[l];
-      const bool last = (l == d.n_cmlp - 1);
-      int ncol;
-      float *scratch = red + 2 * kThreads;  // one partial per thread; red is [256 * NI], o2 uses its first hid <= 256 floats
-      const int parts = any_gemv(Wc, N, in, Kin, scratch, &ncol);
-      if (t < N) {
-        float a = bc[t];
-        for (int q = 0; q < parts; ++q) a += scratch[q * ncol + t];
-        o1[t] = last ? a : fmaxf(a, 0.0f);
-      }
-      __syncthreads();
-      in = o1;
-      float *tmp = o1;
-      o1 = o2;
-      o2 = tmp;
-    }
-    const float *co = in;
-    if (t < hid && h_last) h_last[(size_t)b * hid + t] = xh[p * Kp + Cf + t];
-    if (t < 9 && ctrl_out) ctrl_out[(size_t)b * 9 + t] = co[t];
-    if (t == 0 && attn) {
-      float *r = attn + (size_t)b * RA_ATTN_STRIDE;
-      float cn[2] = {co[0], co[1]}, ls[2] = {co[2], co[3]};
-      if (d.squash) {
-        cn[0] = tanhf(cn[0]);
-        cn[1] = tanhf(cn[1]);
-        ls[0] = -log1pf(expf(ls[0]));
-        ls[1] = -log1pf(expf(ls[1]));
-      }
-      const float dim[2] = {(float)d.H, (float)d.W}, fs[2] = {(float)d.Fh, (float)d.Fw};
-      for (int k = 0; k < 2; ++k) {
-        const float ctr = (cn[k] + 1.0f) * (dim[k] / 2.0f);
-        const float size = expf(ls[k]) * dim[k];
-        float lv = d.fixed_var ? 0.0f : logf(size) - logf(fs[k]);
-        if (d.dynamic_var) lv = co[4 + k];
-        r[0 + k] = ctr;
-        r[2 + k] = size;
-        r[4 + k] = lv;
-        r[9 + k] = cn[k];
-        r[11 + k] = ls[k];
-      }
-      r[6] = d.fixed_gamma ? 1.0f : expf(co[6]);
-      r[7] = expf(co[7]);
-      r[8] = d.fixed_gamma ? 2.0f : co[8];
-      r[13] = r[14] = r[15] = 0.0f;
-    }
-  }
+  // the tail of image p: va row p is this workgroup's own; red is free now ([256 * NI]: the layers' second vector in its
+  // first hid <= 256 floats, one partial sum per thread behind 2 * 256)
+  if (p < nimg) finish_image(d, L, wp, xh + p * Kp + Cf, va + p * hid, red, red + 2 * kThreads, b0 + p, h_last, ctrl_out, attn);
   // new generation for the next launch: workgroup 0 could not have finished its last gather unless every peer
   // had published with this tag, i.e. had read wsg[0]
-  if (p == 0 && t == 0) __hip_atomic_store(wsg, tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-  if (err && status) atomicMax(status, 1);
+  if (p == 0 && t == 0) __hip_atomic_store(wsg, ex.tag, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+  if (ex.err && status) atomicMax(status, 1);
 }
 
 template <int FR, int NI>
 int launch_batch(const ra_ctrl_desc &d, const float *feat, const float *wp, int B, float *h_last, float *ctrl_out,
-                 float *gmaps, float *attn, unsigned *ws, size_t ws_bytes, int *status, size_t lds, int xcd_off, hipStream_t st) {
+                 float *gmaps, float *attn, unsigned *ws, size_t ws_bytes, int *status, int xcd_off, hipStream_t st) {
   auto kern = controller_batch_kernel<FR, NI, false>;
   auto kern_xl = controller_batch_kernel<FR, NI, true>;
   static const MaxDynamicLds lds_limit(kern, 160 * 1024), lds_limit_xl(kern_xl, 160 * 1024);
+  const size_t lds = batch_lds_bytes<NI>(d);
+  unsigned *tickets = ticket_pools(ws, ws_bytes);
   // the XCD-local form: only when the caller names an XCD offset (xcd_off >= 0: it vouches that concurrent launches use others),
-  // the launch has at most 8 groups, and the device's workgroups report the XCC ids 0..7 (RA_CTRL_XCD=0: never)
-  static int xl = -1;
-  if (xl < 0) {
-    if (env_int("RA_CTRL_XCD", 1) == 0) xl = 0;
-    else if (const int c = xcc_census_ok(); c >= 0) xl = c;
-  }
-  unsigned *tickets = ws + ws_bytes / 4 - 8 * kTicketPoolStride;
+  // the launch has at most 8 groups, and xcd_local() allows it
+  const int xl = xcd_local();
   if (xl == 1 && xcd_off >= 0 && ceil_div(B, NI) <= 8)
     hipLaunchKernelGGL(kern_xl, dim3(8 * kP), dim3(kThreads), lds, st, d, feat, wp, B, h_last, ctrl_out, gmaps, attn, ws, status,
                        tail_prio(1), tickets, xcd_off & 7);
@@ -864,7 +846,7 @@ extern "C" size_t ra_ctrl_split_packed_floats(const ra_ctrl_desc *d) {
 
 extern "C" size_t ra_ctrl_split_workspace_bytes(const ra_ctrl_desc *d, int B) {
   if (!d || B <= 0 || !ctrl2::supported(*d)) return 0;
-  return ((size_t)B * ctrl2::ws_words_per_image(*d) + 8 * kTicketPoolStride) * 4;  // + the XCD-local form's role tickets
+  return ((size_t)B * ctrl2::ws_words_per_image(*d) + kTicketSlotWords) * 4;  // + the XCD-local form's role tickets
 }
 
 extern "C" int ra_ctrl_split_pack_weights(const ra_ctrl_desc *d, const float *const *lstm_w,
@@ -917,21 +899,14 @@ extern "C" int ra_controller_split_f32(const ra_ctrl_desc *d, const float *feat,
                                        void *stream) {
   if (!d || !feat || !wpacked || !ws || B <= 0) return fail(RA_E_INVALID, "ra_controller_split_f32: bad argument");
   if (!ctrl2::supported(*d)) return fail(RA_E_SHAPE, "ra_controller_split_f32: unsupported descriptor");
-  if (B * ctrl2::kP > 224) return fail(RA_E_SHAPE, "ra_controller_split_f32: B=%d exceeds co-residency (14)", B);
+  if (B * ctrl2::kP > ctrl2::kMaxResidentWgs) return fail(RA_E_SHAPE, "ra_controller_split_f32: B=%d exceeds co-residency (%d)", B,
+                                                                  ctrl2::kMaxResidentWgs / ctrl2::kP);
   if (ws_bytes < ra_ctrl_split_workspace_bytes(d, B)) return fail(RA_E_WORKSPACE, "ra_controller_split_f32: workspace");
-  const ctrl2::Layout L = ctrl2::layout(*d);
-  const size_t lds = (L.slice + 4 * (size_t)ctrl2::kThreads + round_up(L.K, 4) + d->hid +
-                      round_up(ctrl2::kP * L.gs, 4) + 64) * sizeof(float);
-  const int fr = ceil_div(d->G * d->Cf, ctrl2::kThreads);
-  hipStream_t st = as_stream(stream);
   unsigned *w = reinterpret_cast<unsigned *>(ws);
-#define RA_C2(FR) return ctrl2::launch<FR>(*d, feat, wpacked, B, h_last, ctrl_out, glimpse_maps, attn, w, ws_bytes, status_dev, lds, st)
-  if (fr <= 4) RA_C2(4);
-  if (fr <= 16) RA_C2(16);
-  if (fr <= 32) RA_C2(32);
-  if (fr <= 64) RA_C2(64);
-  RA_C2(96);
-#undef RA_C2
+  return ctrl2::with_feat_regs(ceil_div(d->G * d->Cf, ctrl2::kThreads), [&](auto FR) {
+    return ctrl2::launch<decltype(FR)::value>(*d, feat, wpacked, B, h_last, ctrl_out, glimpse_maps, attn, w, ws_bytes, status_dev,
+                                              as_stream(stream));
+  });
 }
 
 // ---- K2b: one group of 16 workgroups per 4 or 8 images (weights packed as for ra_controller_split_f32) ----
@@ -946,7 +921,7 @@ extern "C" size_t ra_ctrl_batch_workspace_bytes(const ra_ctrl_desc *d, int B) {
   if (!d || B <= 0 || !ctrl2::batch_supported<4>(*d)) return 0;
   const int g = ctrl2::group_images(*d, B);
   // (+ the role tickets of the XCD-local form, at the end: 8 pools of one 128-byte line)
-  return ((size_t)ceil_div(B, g) * (g == 8 ? ctrl2::ws_words_per_group<8>(*d) : ctrl2::ws_words_per_group<4>(*d)) + 8 * kTicketPoolStride) * 4;
+  return ((size_t)ceil_div(B, g) * (g == 8 ? ctrl2::ws_words_per_group<8>(*d) : ctrl2::ws_words_per_group<4>(*d)) + kTicketSlotWords) * 4;
 }
 
 extern "C" int ra_controller_batch_f32(const ra_ctrl_desc *d, const float *feat, const float *wpacked, int B,
@@ -961,20 +936,14 @@ extern "C" int ra_controller_batch_xcd_f32(const ra_ctrl_desc *d, const float *f
   if (!d || !feat || !wpacked || !ws || B <= 0) return fail(RA_E_INVALID, "ra_controller_batch_f32: bad argument");
   if (!ctrl2::batch_supported<4>(*d)) return fail(RA_E_SHAPE, "ra_controller_batch_f32: unsupported descriptor");
   const int g = ctrl2::group_images(*d, B);
-  if (ceil_div(B, g) * ctrl2::kP > 224)
-    return fail(RA_E_SHAPE, "ra_controller_batch_f32: B=%d exceeds co-residency (%d)", B, 14 * g);
+  if (ceil_div(B, g) * ctrl2::kP > ctrl2::kMaxResidentWgs)
+    return fail(RA_E_SHAPE, "ra_controller_batch_f32: B=%d exceeds co-residency (%d)", B, ctrl2::kMaxResidentWgs / ctrl2::kP * g);
   if (ws_bytes < ra_ctrl_batch_workspace_bytes(d, B)) return fail(RA_E_WORKSPACE, "ra_controller_batch_f32: workspace");
-  const size_t lds = g == 8 ? ctrl2::batch_lds_bytes<8>(*d) : ctrl2::batch_lds_bytes<4>(*d);
-  const int fr = ceil_div(d->G * d->Cf, ctrl2::kThreads);
-  hipStream_t st = as_stream(stream);
   unsigned *w = reinterpret_cast<unsigned *>(ws);
-#define RA_C3(FR)                                                                                                        \
-  return g == 8 ? ctrl2::launch_batch<FR, 8>(*d, feat, wpacked, B, h_last, ctrl_out, glimpse_maps, attn, w, ws_bytes, status_dev, lds, xcd_offset, st) \
-                : ctrl2::launch_batch<FR, 4>(*d, feat, wpacked, B, h_last, ctrl_out, glimpse_maps, attn, w, ws_bytes, status_dev, lds, xcd_offset, st)
-  if (fr <= 4) RA_C3(4);
-  if (fr <= 16) RA_C3(16);
-  if (fr <= 32) RA_C3(32);
-  if (fr <= 64) RA_C3(64);
-  RA_C3(96);
-#undef RA_C3
+  return ctrl2::with_feat_regs(ceil_div(d->G * d->Cf, ctrl2::kThreads), [&](auto FR) {
+    constexpr int fr = decltype(FR)::value;
+    hipStream_t st = as_stream(stream);
+    return g == 8 ? ctrl2::launch_batch<fr, 8>(*d, feat, wpacked, B, h_last, ctrl_out, glimpse_maps, attn, w, ws_bytes, status_dev, xcd_offset, st)
+                  : ctrl2::launch_batch<fr, 4>(*d, feat, wpacked, B, h_last, ctrl_out, glimpse_maps, attn, w, ws_bytes, status_dev, xcd_offset, st);
+  });
 }

@@ -11,12 +11,13 @@
 // n_g layers [hid] * n_g + [G], ReLU on all but the last, whose softmax is the next glimpse map; the controller MLP is
 // n_c layers [hid] + [mlp] * (n_c - 1) + [nout], ReLU on all but the last); every run script uses 2 and 1.
 #include "ra_common.h"
+#include "ra_ctrl_parts.h"
 
 namespace ra {
 namespace ctrlt {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
-constexpr int kThreads = 1024;
+constexpr int kThreads = kCtrlWgThreads;
 constexpr int kWaves = kThreads / 64;
 
 constexpr int kMaxL = 4;  // layers per MLP
@@ -24,8 +25,6 @@ struct Dims {
   int G, Cf, hid, iters, nout;  // nout = 9 controller outputs
   int n_g, n_c, mlp;            // glimpse-MLP layers, controller-MLP layers, controller-MLP hidden width
 };
-
-__device__ inline float sigm(float z) { return 1.0f / (1.0f + expf(-z)); }
 
 __device__ inline float wave_sum(float v) {
 #pragma unroll
@@ -76,22 +75,6 @@ __device__ void gemv_rows(const float *v, int N, const float *__restrict__ W, in
 __host__ __device__ inline int max3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 __host__ __device__ inline int va_floats(const Dims &d) { return max3(4 * d.hid, 2 * d.hid + d.G, 2 * d.mlp); }
 
-__device__ float block_reduce(float v, bool is_max, float *red) {
-  const int t = threadIdx.x;
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) {
-    const float other = __shfl_xor(v, o);
-    v = is_max ? fmaxf(v, other) : v + other;
-  }
-  __syncthreads();
-  if ((t & 63) == 0) red[t >> 6] = v;
-  __syncthreads();
-  float r = red[0];
-  for (int w = 1; w < kWaves; ++w) r = is_max ? fmaxf(r, red[w]) : r + red[w];
-  __syncthreads();
-  return r;
-}
-
 // Saved per (image, iteration), floats:  xh [Cf + hid] | act [4 hid] (i, f, o, u after their nonlinearities) |
 // c [hid] | z [(n_g - 1) hid] (the glimpse MLP's hidden layers after their ReLUs) | gm [G] (the map this iteration READ with).
 // Per image (save_c): the controller MLP's hidden layers after their ReLUs [(n_c - 1) mlp].
@@ -131,21 +114,7 @@ __global__ __launch_bounds__(kThreads) void ctrl_fwd_kernel(const FwdArgs a) {
     float *sv = a.save + ((size_t)b * d.iters + it) * SF;
     float *sv_act = sv + (Cf + hid), *sv_c = sv_act + 4 * hid, *sv_z = sv_c + hid, *sv_gm = sv_z + (d.n_g - 1) * hid;
     for (int g = t; g < G; g += kThreads) sv_gm[g] = gm[g];
-    {  // glimpse[c] = sum_g feat[g, c] map[g]
-      const int parts = kThreads / Cf, c = t % Cf, part = t / Cf;
-      if (part < parts) {
-        float s = 0.0f;
-        for (int g = part; g < G; g += parts) s += fl[(size_t)g * Cf + c] * gm[g];
-        red[part * Cf + c] = s;
-      }
-      __syncthreads();
-      if (t < Cf) {
-        float s = 0.0f;
-        for (int p = 0; p < parts; ++p) s += red[p * Cf + t];
-        xh[t] = s;
-      }
-      __syncthreads();
-    }
+    glimpse_readout(fl, gm, G, Cf, red, xh);
     for (int e = t; e < Cf + hid; e += kThreads) sv[e] = xh[e];
     gemv_cols(xh, Cf + hid, a.Wg, 4 * hid, a.bg, va, red);
     if (t < hid) {
@@ -178,14 +147,14 @@ __global__ __launch_bounds__(kThreads) void ctrl_fwd_kernel(const FwdArgs a) {
       gemv_cols(vin, hid, a.gW[d.n_g - 1], G, a.gb[d.n_g - 1], lg, red);
       float mx = -3.0e38f;
       for (int n = t; n < G; n += kThreads) mx = fmaxf(mx, lg[n]);
-      mx = block_reduce(mx, true, red);
+      mx = block_reduce16(mx, true, red);
       float sum = 0.0f;
       for (int n = t; n < G; n += kThreads) {
         const float e = expf(lg[n] - mx);
         lg[n] = e;
         sum += e;
       }
-      sum = block_reduce(sum, false, red);
+      sum = block_reduce16(sum, false, red);
       for (int n = t; n < G; n += kThreads) gm[n] = lg[n] / sum;
       __syncthreads();
     } else {
@@ -301,7 +270,7 @@ __global__ __launch_bounds__(kThreads) void ctrl_bwd_kernel(const BwdArgs a) {
       const float *gm_next = a.save + ((size_t)b * d.iters + it + 1) * SF + (Cf + hid) + 4 * hid + hid + (d.n_g - 1) * hid;
       float dot = 0.0f;
       for (int n = t; n < G; n += kThreads) dot += gm_next[n] * dgm[n];
-      dot = block_reduce(dot, false, red);
+      dot = block_reduce16(dot, false, red);
       for (int n = t; n < G; n += kThreads) {
         const float v = gm_next[n] * (dgm[n] - dot);
         vt[n] = v;

@@ -349,14 +349,11 @@ class DecodeEngine(object):
       if self.cache_first and st0[0] == 'pair' and d['C0p'] == 4 and self.ksize['ccnn'][:2] == [3, 3] and \
           ops.first_cache_supported(4, d['ccnn_channels'][1], d['ccnn_channels'][2], d['ccnn_pool'][1], H, W):
         b['l0cache'] = ops.first_cache_alloc(Bs, H, W, device)
-      # the 16 workgroups of an image exchange through spin-waits, so ALL workgroups of every launch that
-      # can be running at the same time must be resident at once (112 KB of LDS each: one per CU).
       # `co_resident` = how many such launches may overlap (DecodePipeline: its depth)
-      if self.split_ok and Bs * 16 * max(1, self.co_resident) <= ops.cu_count() - 32:  # the C side's margin: 224 of 256
+      form = ops.ctrl_form(self.desc, Bs, self.co_resident) if self.split_ok else None
+      if form == 'split':
         b['ctrl_ws'], b['ctrl_status'] = ops.ctrl_split_workspace(self.desc, Bs, device)
-      elif (self.split_ok and ops.ctrl_batch_supported(self.desc) and
-            -(-Bs // ops.ctrl_batch_group(self.desc, Bs)) * 16 * max(1, self.co_resident) <= ops.cu_count() - 32):
-        # more than 14 images, or launches that overlap: the group-shared form (K2b, 16 workgroups per group of images)
+      elif form == 'batch':  # the group-shared form (K2b, 16 workgroups per group of images)
         b['ctrl_ws'], b['ctrl_status'] = ops.ctrl_batch_workspace(self.desc, Bs, device)
         b['ctrl_batch'] = True
         # round 6: K2b on the XCD-local exchange where every group of every launch that can run at the same time gets an XCD

@@ -189,6 +189,23 @@ def ctrl_batch_workspace(desc, B, device):
   return _exchange_workspace(desc, B, device, 'ra_ctrl_batch_workspace_bytes')
 
 
+def ctrl_form(desc, B, co_resident=1, cus=None):
+  """The controller form a launch of B images runs beside co_resident - 1 launches of its kind on a device of cus compute
+  units (default: the current device's): 'split' (16 workgroups per image), 'batch' (16 per group of ctrl_batch_group
+  images) or None (the one-workgroup kernel).  The workgroups of a team exchange through spin-waits, so ALL workgroups of
+  every launch that can be running at the same time must be resident at once (112 KB of LDS each: one per CU), with a
+  margin of 32 CUs for everything else: 224 of the MI355X's 256, the bound the C entry points check per launch."""
+  if not ctrl_split_supported(desc):
+    return None
+  room = (cu_count() if cus is None else int(cus)) - 32
+  n = 16 * max(1, int(co_resident))
+  if B * n <= room:
+    return 'split'
+  if ctrl_batch_supported(desc) and -(-B // ctrl_batch_group(desc, B)) * n <= room:
+    return 'batch'  # more than 14 images, or launches that overlap
+  return None
+
+
 def controller_batch(desc, feat, wp, h_last, ctrl_out, gmaps, attn, ws, status, xcd_offset=-1):
   """K2b: ra_controller_split_f32's recurrence with the weight slices shared by groups of ctrl_batch_group(desc, B) images.
   xcd_offset >= 0: the XCD-local exchange, group g on XCD (g + xcd_offset) % 8 (ra_controller_batch_xcd_f32: the caller keeps

@@ -1776,7 +1776,7 @@ class TrainStep(object):
       desc = ops.make_ctrl_desc(d['G'], Cf, d['hid'], d['iters'], d['n_gmlp'], d['n_cmlp'], d['mlp_dim'], d['H'], d['W'], d['Fh'],
                                 d['Fw'], d['squash'], d['fixed_var'], d['dynamic_var'], d.get('fixed_gamma', True))
       sc = self._seqc = {'B': B, 'ok': False}
-      if ops.ctrl_split_supported(desc) and B * 16 <= ops.cu_count() - 32:
+      if ops.ctrl_form(desc, B) == 'split':
         off = self.bucket.offsets
         pos = lambda k: (off[k][0] + 1 + np.arange(off[k][1], dtype=np.float64)).astype(np.float32).reshape(off[k][2])
         assert self.bucket.param.numel() < (1 << 24)  # positions are exact in float32

@@ -355,3 +355,45 @@ def test_pipeline_end_of_stream_rule(monkeypatch):
   assert not full_model.DecodePipeline(M(), depth=4, coalesce=1)._ends_soon(0)
   monkeypatch.setenv('RA_PIPE_ENDGAME', '0')
   assert not full_model.DecodePipeline(M(), depth=4, coalesce=2)._ends_soon(0)
+
+
+# make_ctrl_desc arguments (G, Cf, hid, iters, n_gmlp, n_cmlp, mlp_dim, H, W, Fh, Fw, squash, fixed_var, dynamic_var, fixed_gamma):
+# cvppp 128, cvppp 224 with squash, cvppp 512, cvppp 512 with three glimpse-MLP layers
+CTRL_DESCS = [
+    (16, 64, 256, 5, 2, 1, 256, 128, 128, 48, 48, 0, 0, 0, 1),
+    (49, 64, 256, 5, 2, 1, 256, 224, 224, 48, 48, 1, 0, 0, 1),
+    (256, 64, 256, 5, 2, 1, 256, 512, 512, 48, 48, 0, 0, 0, 1),
+    (256, 64, 256, 5, 3, 1, 256, 512, 512, 48, 48, 0, 0, 0, 1),
+]
+# Recorded from a build of commit d051046 (the parent of the commit that gave ra_ctrl_split.hip one lds_bytes() and one
+# ticket_pools()), never from the code under test: split supported, packed floats, split workspace bytes at B = 1, 8, 14, batch
+# supported, group images at B = 8, 16, batch workspace bytes at B = 5, 16
+CTRL_GEOMETRY = [
+    (1, 400969, [22152, 170048, 296816], 1, [4, 8], [190480, 379920]),
+    (1, 413257, [24072, 185408, 323696], 1, [4, 8], [205840, 410640]),
+    (1, 462601, [31752, 246848, 431216], 1, [4, 8], [267280, 533520]),
+    (1, 528393, [41992, 328768, 574576], 1, [4, 4], [349200, 697376]),
+]
+
+
+@pytest.mark.parametrize('args,want', list(zip(CTRL_DESCS, CTRL_GEOMETRY)))
+def test_ctrl_split_host_geometry(args, want):
+  r, L = C.byref(ops.make_ctrl_desc(*args)), rn.lib()
+  got = (L.ra_ctrl_split_supported(r), L.ra_ctrl_split_packed_floats(r), [L.ra_ctrl_split_workspace_bytes(r, B) for B in (1, 8, 14)],
+         L.ra_ctrl_batch_supported(r), [L.ra_ctrl_batch_group_images(r, B) for B in (8, 16)],
+         [L.ra_ctrl_batch_workspace_bytes(r, B) for B in (5, 16)])
+  assert got == want
+
+
+@pytest.mark.parametrize('B,co_resident,form', [(8, 1, 'split'), (14, 1, 'split'), (15, 1, 'batch'), (8, 4, 'batch'), (8, 16, None),
+                                                (16, 8, None)])
+def test_ctrl_form_residency_rule(B, co_resident, form):
+  """groups x 16 workgroups x launches in flight <= CUs - 32, on the cvppp-512 descriptor and 256 CUs (no device asked)."""
+  assert ops.ctrl_form(ops.make_ctrl_desc(*CTRL_DESCS[2]), B, co_resident, cus=256) == form
+
+
+def test_ctrl_form_unsupported_descriptor():
+  args = list(CTRL_DESCS[2])
+  args[2] = 250  # hid: not a multiple of the 16 slices
+  for B in (1, 8, 15, 32):
+    assert ops.ctrl_form(ops.make_ctrl_desc(*args), B, cus=256) is None

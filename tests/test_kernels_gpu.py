@@ -4,6 +4,7 @@ import numpy as np
 import pytest
 import torch
 
+import ctrl_form_cases
 import ra_oracle as ora
 import ra_ops as ops
 import ra_native as rn
@@ -227,10 +228,44 @@ def test_conv_pair(cuda, B, H, W, Ci, Ca, Cb, poolB, ups):
   assert relerr(y, ref) < 3e-5
 
 
-def _ctrl_setup(opt, seed):
-  d = ora.derive(opt)
-  P = ora.random_params(opt, seed)
-  return d, P
+class _CtrlCase(object):
+  """One controller test case, shared by the three forms: the descriptor and packed weights of make_opt(arch, H, W, 2, **flags)
+  with random_params(seed), the launch's output tensors, and the check of a launch against ora._controller / ora._decode_ctrl in
+  float64."""
+
+  def __init__(self, cuda, arch, H, W, flags, seed, split):
+    self.cuda, self.H, self.W = cuda, H, W
+    self.opt = opt = ora.make_opt(arch, H, W, 2, **flags)
+    self.d = d = ora.derive(opt)
+    P = ora.random_params(opt, seed)
+    self.P64 = {k: v.astype(np.float64) for k, v in P.items()}
+    self.Cf = d['ccnn_channels'][-1]
+    self.desc = self.make_desc(d['n_gmlp'])
+    lstm = {k[len('ctrl_lstm_'):]: v for k, v in P.items() if k.startswith('ctrl_lstm_')}
+    gmw = [(P['glimpse_mlp_w_%d' % i], P['glimpse_mlp_b_%d' % i]) for i in range(d['n_gmlp'])]
+    cmw = [(P['ctrl_mlp_w_%d' % i], P['ctrl_mlp_b_%d' % i]) for i in range(d['n_cmlp'])]
+    self.wp = dev((ops.pack_ctrl_split_weights if split else ops.pack_ctrl_weights)(self.desc, lstm, gmw, cmw), cuda)
+
+  def make_desc(self, n_gmlp):
+    d = self.d
+    return ops.make_ctrl_desc(d['G'], self.Cf, d['hid'], d['iters'], n_gmlp, d['n_cmlp'], self.opt['ctrl_mlp_dim'], self.H, self.W, 48, 48,
+                              d['squash'], d['fixed_var'], d['dynamic_var'], d['fixed_gamma'])
+
+  def feat(self, B, seed):
+    return np.maximum(np.random.RandomState(seed).randn(B, self.d['G'], self.Cf), 0).astype(np.float32)
+
+  def outputs(self, B, fill):
+    """h_last, ctrl_out, gmaps, attn"""
+    d = self.d
+    return [torch.full(s, fill, dtype=torch.float32, device=self.cuda) for s in ((B, d['hid']), (B, 9), (B, d['iters'], d['G']), (B, 16))]
+
+  def check(self, feat, h_last, ctrl_out, gmaps, attn):
+    """h_last, ctrl_out, the glimpse maps and the WHOLE attention record (entries 0..12 at their bars, 13..15 zero): every row of
+    ctrl_form_cases.errors, the one table of the controller's bars"""
+    h, co, gm = ora._controller(self.d, self.P64, feat.astype(np.float64), np.dtype(np.float64))
+    ref = (h, co, gm) + tuple(ora._decode_ctrl(self.d, co, np.dtype(np.float64)))
+    for what, err, bar in ctrl_form_cases.errors(self.d, self.H, self.W, ref, *[t.cpu().numpy() for t in (h_last, ctrl_out, gmaps, attn)]):
+      assert err < bar, (what, err, bar)
 
 
 @pytest.mark.parametrize('arch,H,W,flags', [
@@ -240,39 +275,12 @@ def _ctrl_setup(opt, seed):
     ('cvppp', 512, 512, {'fixed_var': True, 'num_ctrl_mlp_layers': 2, 'num_glimpse_mlp_layers': 3}),
 ])
 def test_controller(cuda, arch, H, W, flags):
-  opt = ora.make_opt(arch, H, W, 2, **flags)
-  d, P = _ctrl_setup(opt, 3)
-  B = 3
-  rng = np.random.RandomState(5)
-  Cf = d['ccnn_channels'][-1]
-  feat = np.maximum(rng.randn(B, d['G'], Cf), 0).astype(np.float32)
-  P64 = {k: v.astype(np.float64) for k, v in P.items()}
-  h, co, gm = ora._controller(d, P64, feat.astype(np.float64), np.dtype(np.float64))
-  cn, ls, ctr, size, lv = ora._decode_ctrl(d, co, np.dtype(np.float64))
-  desc = ops.make_ctrl_desc(d['G'], Cf, d['hid'], d['iters'], d['n_gmlp'], d['n_cmlp'],
-                            opt['ctrl_mlp_dim'], H, W, 48, 48, d['squash'], d['fixed_var'],
-                            d['dynamic_var'], d['fixed_gamma'])
-  lstm = {k[len('ctrl_lstm_'):]: v for k, v in P.items() if k.startswith('ctrl_lstm_')}
-  gmw = [(P['glimpse_mlp_w_%d' % i], P['glimpse_mlp_b_%d' % i]) for i in range(d['n_gmlp'])]
-  cmw = [(P['ctrl_mlp_w_%d' % i], P['ctrl_mlp_b_%d' % i]) for i in range(d['n_cmlp'])]
-  wp = dev(ops.pack_ctrl_weights(desc, lstm, gmw, cmw), cuda)
-  z = lambda *s: torch.zeros(s, dtype=torch.float32, device=cuda)
-  h_last, ctrl_out, gmaps, attn = z(B, d['hid']), z(B, 9), z(B, d['iters'], d['G']), z(B, 16)
-  ops.controller(desc, dev(feat, cuda), wp, h_last, ctrl_out, gmaps, attn)
+  c = _CtrlCase(cuda, arch, H, W, flags, 3, split=False)
+  feat = c.feat(3, 5)
+  out = c.outputs(3, 0.0)
+  ops.controller(c.desc, dev(feat, cuda), c.wp, *out)
   torch.cuda.synchronize()
-  assert relerr(h_last.cpu().numpy(), h) < 5e-5
-  assert np.abs(ctrl_out.cpu().numpy() - co).max() < 5e-5
-  assert np.abs(gmaps.cpu().numpy() - gm).max() < 1e-5
-  a = attn.cpu().numpy()
-  assert np.abs(a[:, 0:2] - ctr).max() < 1e-3 * max(H, W) / 100
-  assert relerr(a[:, 2:4], size) < 1e-4
-  assert np.abs(a[:, 4:6] - lv).max() < 1e-4
-  assert np.abs(a[:, 9:11] - cn).max() < 1e-4 and np.abs(a[:, 11:13] - ls).max() < 1e-4
-  if d['fixed_gamma']:
-    assert (a[:, 6] == 1.0).all() and (a[:, 8] == 2.0).all()
-  else:
-    assert relerr(a[:, 6], np.exp(co[:, 6])) < 1e-4 and np.abs(a[:, 8] - co[:, 8]).max() < 1e-4
-  assert relerr(a[:, 7], np.exp(co[:, 7])) < 1e-4
+  c.check(feat, *out)
 
 
 @pytest.mark.parametrize('arch,H,W,flags,B', [
@@ -290,35 +298,16 @@ def test_controller_split(cuda, arch, H, W, flags, B):
   """The 16-workgroup LDS-stationary controller: same maths, exchanged through tagged granules;
   launched three times on the same workspace (generation tags, as under HIP-graph replay; the XCD-local form's role
   tickets only ever count up)."""
-  opt = ora.make_opt(arch, H, W, 2, **flags)
-  d, P = _ctrl_setup(opt, 4)
-  Cf = d['ccnn_channels'][-1]
-  desc = ops.make_ctrl_desc(d['G'], Cf, d['hid'], d['iters'], d['n_gmlp'], d['n_cmlp'],
-                            opt['ctrl_mlp_dim'], H, W, 48, 48, d['squash'], d['fixed_var'],
-                            d['dynamic_var'], d['fixed_gamma'])
-  assert ops.ctrl_split_supported(desc)
-  lstm = {k[len('ctrl_lstm_'):]: v for k, v in P.items() if k.startswith('ctrl_lstm_')}
-  gmw = [(P['glimpse_mlp_w_%d' % i], P['glimpse_mlp_b_%d' % i]) for i in range(d['n_gmlp'])]
-  cmw = [(P['ctrl_mlp_w_%d' % i], P['ctrl_mlp_b_%d' % i]) for i in range(d['n_cmlp'])]
-  wp = dev(ops.pack_ctrl_split_weights(desc, lstm, gmw, cmw), cuda)
-  ws, status = ops.ctrl_split_workspace(desc, B, cuda)
-  P64 = {k: v.astype(np.float64) for k, v in P.items()}
-  z = lambda *s: torch.full(s, 7.0, dtype=torch.float32, device=cuda)
+  c = _CtrlCase(cuda, arch, H, W, flags, 4, split=True)
+  assert ops.ctrl_split_supported(c.desc)
+  ws, status = ops.ctrl_split_workspace(c.desc, B, cuda)
   for rep in range(3):
-    rng = np.random.RandomState(50 + rep)
-    feat = np.maximum(rng.randn(B, d['G'], Cf), 0).astype(np.float32)
-    h, co, gm = ora._controller(d, P64, feat.astype(np.float64), np.dtype(np.float64))
-    cn, ls, ctr, size, lv = ora._decode_ctrl(d, co, np.dtype(np.float64))
-    h_last, ctrl_out, gmaps, attn = z(B, d['hid']), z(B, 9), z(B, d['iters'], d['G']), z(B, 16)
-    ops.controller_split(desc, dev(feat, cuda), wp, h_last, ctrl_out, gmaps, attn, ws, status)
+    feat = c.feat(B, 50 + rep)
+    out = c.outputs(B, 7.0)
+    ops.controller_split(c.desc, dev(feat, cuda), c.wp, *out, ws, status)
     torch.cuda.synchronize()
     assert int(status.item()) == 0
-    assert relerr(h_last.cpu().numpy(), h) < 5e-5
-    assert np.abs(ctrl_out.cpu().numpy() - co).max() < 5e-5
-    assert np.abs(gmaps.cpu().numpy() - gm).max() < 1e-5
-    a = attn.cpu().numpy()
-    assert np.abs(a[:, 0:2] - ctr).max() < 1e-3 * max(H, W) / 100
-    assert relerr(a[:, 2:4], size) < 1e-4 and np.abs(a[:, 4:6] - lv).max() < 1e-4
+    c.check(feat, *out)
 
 
 @pytest.mark.parametrize('arch,H,W,flags,B', [
@@ -335,49 +324,29 @@ def test_controller_batch(cuda, arch, H, W, flags, B):
   """K2b, the split controller with its weight slices shared by groups of 4 images (8 for launches of more than 8): the oracle's recurrence,
   three launches on one workspace (generation tags), full and ragged groups, and agreement with the
   per-image split form."""
-  opt = ora.make_opt(arch, H, W, 2, **flags)
-  d, P = _ctrl_setup(opt, 4)
-  Cf = d['ccnn_channels'][-1]
-  desc = ops.make_ctrl_desc(d['G'], Cf, d['hid'], d['iters'], d['n_gmlp'], d['n_cmlp'],
-                            opt['ctrl_mlp_dim'], H, W, 48, 48, d['squash'], d['fixed_var'],
-                            d['dynamic_var'], d['fixed_gamma'])
-  assert ops.ctrl_batch_supported(desc)
-  assert ops.ctrl_batch_group(desc, B) == (8 if B > 8 else 4)
+  c = _CtrlCase(cuda, arch, H, W, flags, 4, split=True)
+  assert ops.ctrl_batch_supported(c.desc)
+  assert ops.ctrl_batch_group(c.desc, B) == (8 if B > 8 else 4)
   # a third glimpse-MLP layer makes the slice + a group of 8's vectors exceed 160 KB of LDS: such launches keep groups of 4
-  big = ops.make_ctrl_desc(d['G'], Cf, d['hid'], d['iters'], 3, d['n_cmlp'], opt['ctrl_mlp_dim'], H, W, 48, 48,
-                           d['squash'], d['fixed_var'], d['dynamic_var'], d['fixed_gamma'])
-  if d['G'] * 4 >= 1024:  # (with few logits per slice the larger form still fits)
+  big = c.make_desc(3)
+  if c.d['G'] * 4 >= 1024:  # (with few logits per slice the larger form still fits)
     assert ops.ctrl_split_supported(big) and ops.ctrl_batch_supported(big) and ops.ctrl_batch_group(big, 16) == 4
-  lstm = {k[len('ctrl_lstm_'):]: v for k, v in P.items() if k.startswith('ctrl_lstm_')}
-  gmw = [(P['glimpse_mlp_w_%d' % i], P['glimpse_mlp_b_%d' % i]) for i in range(d['n_gmlp'])]
-  cmw = [(P['ctrl_mlp_w_%d' % i], P['ctrl_mlp_b_%d' % i]) for i in range(d['n_cmlp'])]
-  wp = dev(ops.pack_ctrl_split_weights(desc, lstm, gmw, cmw), cuda)
-  ws, status = ops.ctrl_batch_workspace(desc, B, cuda)
-  P64 = {k: v.astype(np.float64) for k, v in P.items()}
-  z = lambda *s: torch.full(s, 7.0, dtype=torch.float32, device=cuda)
+  ws, status = ops.ctrl_batch_workspace(c.desc, B, cuda)
   for rep in range(3):
-    rng = np.random.RandomState(70 + rep)
-    feat = np.maximum(rng.randn(B, d['G'], Cf), 0).astype(np.float32)
-    h, co, gm = ora._controller(d, P64, feat.astype(np.float64), np.dtype(np.float64))
-    cn, ls, ctr, size, lv = ora._decode_ctrl(d, co, np.dtype(np.float64))
-    h_last, ctrl_out, gmaps, attn = z(B, d['hid']), z(B, 9), z(B, d['iters'], d['G']), z(B, 16)
+    feat = c.feat(B, 70 + rep)
+    out = c.outputs(B, 7.0)
     # launch 0: agent-scope exchange; launches 1, 2: the XCD-local form (round 6), group g on XCD (g + offset) % 8 — the same
     # workspace (generation tags and role tickets only ever count up)
-    ops.controller_batch(desc, dev(feat, cuda), wp, h_last, ctrl_out, gmaps, attn, ws, status, xcd_offset=(-1, 0, 5)[rep])
+    ops.controller_batch(c.desc, dev(feat, cuda), c.wp, *out, ws, status, xcd_offset=(-1, 0, 5)[rep])
     torch.cuda.synchronize()
     assert int(status.item()) == 0
-    assert relerr(h_last.cpu().numpy(), h) < 5e-5
-    assert np.abs(ctrl_out.cpu().numpy() - co).max() < 5e-5
-    assert np.abs(gmaps.cpu().numpy() - gm).max() < 1e-5
-    a = attn.cpu().numpy()
-    assert np.abs(a[:, 0:2] - ctr).max() < 1e-3 * max(H, W) / 100
-    assert relerr(a[:, 2:4], size) < 1e-4 and np.abs(a[:, 4:6] - lv).max() < 1e-4
+    c.check(feat, *out)
   if B <= 14:
-    ws2, st2 = ops.ctrl_split_workspace(desc, B, cuda)
-    h2, c2, g2, a2 = z(B, d['hid']), z(B, 9), z(B, d['iters'], d['G']), z(B, 16)
-    ops.controller_split(desc, dev(feat, cuda), wp, h2, c2, g2, a2, ws2, st2)
+    ws2, st2 = ops.ctrl_split_workspace(c.desc, B, cuda)
+    out2 = c.outputs(B, 7.0)
+    ops.controller_split(c.desc, dev(feat, cuda), c.wp, *out2, ws2, st2)
     torch.cuda.synchronize()
-    assert np.abs(c2.cpu().numpy() - ctrl_out.cpu().numpy()).max() < 2e-5
+    assert np.abs(out2[1].cpu().numpy() - out[1].cpu().numpy()).max() < 2e-5
 
 
 def _attn_rec(B, H, W, rng, big_var=False):

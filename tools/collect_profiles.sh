@@ -56,7 +56,7 @@ timeout 300 python tools/hungarian_step_probe.py 2>&1 | tail -3 > $OUT/${R3}_hun
 
 # round 5, second session: what the pipeline's slots do to each other (static tile walk / drawn tiles), per launch and as a group
 { timeout 200 python tools/contention_probe.py 16; RA_ENGINE_TICKETS=1 timeout 200 python tools/contention_probe.py 16; timeout 250 python tools/contention_by_layer.py 16; } 2>&1 | grep -v amdgpu.ids > $OUT/${R3}_contention_probes.txt
-timeout 120 python tools/ctrl_bench.py 2>&1 | grep -v amdgpu.ids > $OUT/${R3}_ctrl_bench.txt
-RA_CTRL_XCD=0 timeout 120 python tools/ctrl_bench.py 2>&1 | grep -v amdgpu.ids | sed 's/^/RA_CTRL_XCD=0  /' >> $OUT/${R3}_ctrl_bench.txt
+timeout 120 python tools/ctrl_forms.py --iters-sweep 2>&1 | grep -v amdgpu.ids > $OUT/${R3}_ctrl_bench.txt
+RA_CTRL_XCD=0 timeout 120 python tools/ctrl_forms.py --iters-sweep 2>&1 | grep -v amdgpu.ids | sed 's/^/RA_CTRL_XCD=0  /' >> $OUT/${R3}_ctrl_bench.txt
 [ -x tools/bin/mfma_rate_probe ] && timeout 60 tools/bin/mfma_rate_probe > $OUT/${R3}_mfma_rate_probe.txt 2>&1
 ls -la $OUT

@@ -7,9 +7,11 @@ filter gradients exactly when their dumps are byte-identical:
   python tools/wgrad_digest.py --lib A/librecattend.so --out a.txt      # prints the line count and sha256 of a.txt
   python tools/wgrad_digest.py --lib B/librecattend.so --out b.txt && cmp a.txt b.txt
 
-Stops at the first child that ends abnormally (nothing more is started on the device) and returns its status."""
+Stops at the first child that ends abnormally (nothing more is started on the device) and returns its status.
+tools/ctrl_digest.py runs main() over the controller's case table."""
 import argparse
 import hashlib
+import importlib
 import os
 import subprocess
 import sys
@@ -18,17 +20,18 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 
-def main():
-  ap = argparse.ArgumentParser(description=__doc__.split('\n')[0])
+def main(cases='wgrad_form_cases', env_prefix='RA_WGRAD', doc=__doc__):
+  """cases: the module under tests/ with VARIANTS, parse_line and a runner that takes --lib; env_prefix: the variables its variants set"""
+  ap = argparse.ArgumentParser(description=doc.split('\n')[0])
   ap.add_argument('--lib', help='the librecattend.so to run (default: the tree\'s own)')
   ap.add_argument('--out', required=True)
   ap.add_argument('--timeout', type=int, default=120, help='seconds per variant')
   args = ap.parse_args()
-  import wgrad_form_cases as wf
-  cmd = ['timeout', '-k', '10', str(args.timeout), sys.executable, os.path.join(ROOT, 'tests', 'wgrad_form_cases.py')]
+  wf = importlib.import_module(cases)
+  cmd = ['timeout', '-k', '10', str(args.timeout), sys.executable, os.path.join(ROOT, 'tests', cases + '.py')]
   if args.lib:
     cmd += ['--lib', os.path.abspath(args.lib)]
-  base = {k: v for k, v in os.environ.items() if not k.startswith('RA_WGRAD')}
+  base = {k: v for k, v in os.environ.items() if not k.startswith(env_prefix)}
   sha, lines = hashlib.sha256(), 0
   with open(args.out, 'wb') as out:
     for variant, env in wf.VARIANTS.items():
