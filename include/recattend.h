@@ -990,8 +990,8 @@ int ra_bn_act_pool_bwd_acc_f32(const float *u, const float *dy, const float *mea
 /* G calls of one layer (its G timesteps: per-timestep statistics and parameters, nnlib.py:121-127) stacked along the
  * batch and differentiated in one reduce / final / dx triple: u [G*B,H,W,C], dy [G*B,H/pool,W/pool,C], du like u;
  * tabs = a DEVICE table of 6 G pointers {mean, var, gamma, beta, gradient-bucket gamma, gradient-bucket beta}[G]
- * (the last two are added to); dgamma / dbeta [G,C]; ws of G * ra_bn_workspace_floats(C) floats.  C % 4 == 0 and
- * C / 4 a power of two <= 64 (RA_E_SHAPE otherwise: call the per-group entry). */
+ * (the last two are added to); dgamma / dbeta [G,C]; ws of G * ra_bn_workspace_floats(C) floats.  Where ra_bn_form
+ * reports no form for the grouped call it returns RA_E_SHAPE without a launch: call the per-group entry. */
 int ra_bn_act_pool_bwd_grouped_f32(const float *u, const float *dy, const void *const *tabs, int G, float eps,
                                    int relu, int pool, int B, int H, int W, int C, float *ws, size_t ws_floats,
                                    float *dgamma, float *dbeta, float *du, void *stream);
@@ -1007,6 +1007,19 @@ int ra_bn_act_pool_bwd_dx_f32(const float *u, const float *dy, const float *mean
                               const float *gamma, const float *beta, const float *dgamma_sum, const float *dbeta_sum,
                               double n_total, float eps, int relu, int pool, int B, int H, int W, int C, float *du,
                               void *stream);
+/* The kernel form a BatchNorm pass runs at a shape: the one host function every ra_bn_* entry point asks.  Host only, launches
+ * nothing.  pass: RA_BN_PASS_*; u [B,H,W,C] (moments: npix = B H W; pool is ignored); flags: the bf16 storage bits of the
+ * *_bf16_f32 entry points, 0 for float32 tensors; stages (per-call backward): 1 = _reduce, 2 = _dx, 3 = both in one call;
+ * G: 0 = a per-call backward, > 0 = ra_bn_act_pool_bwd_grouped_* over G groups.  Returns RA_BN_FORM_SMALL (the whole call in
+ * one workgroup), RA_BN_FORM_V4 (four channels per thread; the only form that takes bf16 storage) or RA_BN_FORM_GENERIC, or
+ * the RA_E_* code with which the entry point would refuse the call. */
+#define RA_BN_PASS_MOMENTS 0
+#define RA_BN_PASS_FORWARD 1
+#define RA_BN_PASS_BACKWARD 2
+#define RA_BN_FORM_SMALL 1
+#define RA_BN_FORM_V4 2
+#define RA_BN_FORM_GENERIC 3
+int ra_bn_form(int pass, int C, int B, int H, int W, int pool, int flags, int stages, int G);
 /* The pointwise half of the controller's LSTM cell (nnlib.py:641-646; the GEMM half is a library call):
  * pre [B][4*hid] = gate pre-activations in the order (i, f, o, u), c_prev [B][hid]:
  *   c = sigm(f) c_prev + sigm(i) tanh(u),  h = sigm(o) tanh(c);  act [B][4*hid] keeps the gate values.

@@ -169,6 +169,20 @@ struct TicketWalk {
   __device__ __forceinline__ void step() { cur = nxt; }
 };
 
+// The sum of v over a workgroup of 256 threads, in every thread: a fixed-shape LDS tree (deterministic).  red: 256 floats.
+__device__ inline float block_sum256(float v, float *red) {
+  const int tid = threadIdx.x;
+  red[tid] = v;
+  __syncthreads();
+  for (int o = 128; o > 0; o >>= 1) {
+    if (tid < o) red[tid] += red[tid + o];
+    __syncthreads();
+  }
+  const float r = red[0];
+  __syncthreads();
+  return r;
+}
+
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 

@@ -206,6 +206,19 @@ def ctrl_form(desc, B, co_resident=1, cus=None):
   return None
 
 
+_BN_PASSES = {'moments': rn.RA_BN_PASS_MOMENTS, 'forward': rn.RA_BN_PASS_FORWARD, 'backward': rn.RA_BN_PASS_BACKWARD}
+_BN_FORMS = {rn.RA_BN_FORM_SMALL: 'small', rn.RA_BN_FORM_V4: 'v4', rn.RA_BN_FORM_GENERIC: 'generic'}
+
+
+def bn_form(which, C, B, H, W, pool=1, flags=0, stages=3, G=0):
+  """The kernel form the BatchNorm pass `which` ('moments', 'forward', 'backward') runs over u [B,H,W,C]: 'small' (one
+  workgroup), 'v4' (four channels per thread: the only form with bf16 storage, flags != 0) or 'generic', or the negative
+  RA_E_* code with which the entry point refuses the call (ra_bn_form: the library's own chooser, no launch).  stages: of a
+  per-call backward (1 = reduce, 2 = dx, 3 = one call); G > 0: the grouped backward over G groups."""
+  rc = rn.lib().ra_bn_form(_BN_PASSES[which], int(C), int(B), int(H), int(W), int(pool), int(flags), int(stages), int(G))
+  return _BN_FORMS.get(rc, rc)
+
+
 def controller_batch(desc, feat, wp, h_last, ctrl_out, gmaps, attn, ws, status, xcd_offset=-1):
   """K2b: ra_controller_split_f32's recurrence with the weight slices shared by groups of ctrl_batch_group(desc, B) images.
   xcd_offset >= 0: the XCD-local exchange, group g on XCD (g + xcd_offset) % 8 (ra_controller_batch_xcd_f32: the caller keeps

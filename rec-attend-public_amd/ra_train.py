@@ -505,11 +505,11 @@ class ConvBNActPool(torch.autograd.Function):
       # float32; y also float32 where a float32 kernel reads it next: meta['y_f32']); the statistics come from the conv's
       # float32 accumulators, before the rounding.  Forward only: the stacked graph's nodes hold the backward.
       assert bf and not torch.is_grad_enabled()
-      st_ok = cout % 4 == 0 and (cout // 4) & (cout // 4 - 1) == 0 and cout // 4 <= 64 and EPILOGUE_MOMENTS['on']
+      H, W = Hs * up, Ws * up
+      st_ok = EPILOGUE_MOMENTS['on'] and ops.bn_form('forward', cout, B, H, W, pool) == 'v4' == ops.bn_form('backward', cout, B, H, W, pool, G=1)
       ud = torch.bfloat16 if st_ok else torch.float32
       yd = torch.bfloat16 if (st_ok and not meta.get('y_f32')) else torch.float32
-      u = alloc('u', (B, Hs * up, Ws * up, cout), ud)
-      H, W = u.shape[1], u.shape[2]
+      u = alloc('u', (B, H, W, cout), ud)
       xin = 1 if x.dtype == torch.bfloat16 else 0
       if cout % 4 == 0 and EPILOGUE_MOMENTS['on']:
         part = _f(rn.lib().ra_conv3x3_moments_part_floats(cout), device=dev)
@@ -868,30 +868,24 @@ class ConvStackFn(torch.autograd.Function):
     gw, gb = info['gw'], info['gb']
     dY = dY.contiguous()
     nbn = rn.lib().ra_bn_workspace_floats(cout)
-    rc = 0
+    sflags = (1 if U.dtype == torch.bfloat16 else 0) | (2 if dY.dtype == torch.bfloat16 else 0)  # the bf16 mode's storage
     if info.get('sync_world', 1) > 1:
       # whole-batch BatchNorm (--sync_bn) under the stacked backward: the T groups' 2 C sums of a layer cross the ranks in
       # ONE all_reduce (21 collectives per step; the per-timestep graph issued T times as many)
       sums = stack_bn_reduce(info, U, dY)
       allreduce_sums(sums)
       du = stack_bn_dx(info, U, dY, sums, float(info['sync_world']) * B * H * W)
+    elif sflags or ops.bn_form('backward', cout, B, H, W, pool, sflags, G=G) in ('v4', 'small'):
+      # ('small': the one-channel output layer, one workgroup per timestep of the same launch; bf16 storage exists only where
+      # the forward found both forms 'v4', so a refusal under it is an error)
+      du, dgam, dbet, ws = torch.empty_like(U), _f(G, cout, device=dev), _f(G, cout, device=dev), _f(G * nbn, device=dev)
+      check(rn.lib().ra_bn_act_pool_bwd_grouped_bf16_f32(ptr(U), ptr(dY), ptr(info['tabs']), G, _C.c_float(BN_EPS), int(relu), int(pool),
+                                                         B, H, W, cout, ptr(ws), ws.numel(), ptr(dgam), ptr(dbet), ptr(du), sflags,
+                                                         rn.stream_ptr()), 'ra_bn_act_pool_bwd_grouped_bf16_f32')
     else:
-      du, rc = torch.empty_like(U), rn.RA_E_SHAPE
-      sflags = (1 if U.dtype == torch.bfloat16 else 0) | (2 if dY.dtype == torch.bfloat16 else 0)  # the bf16 mode's storage
-      if cout % 4 == 0 or not sflags:  # (a small one-channel layer: one workgroup per timestep of the same launch)
-        dgam, dbet, ws = _f(G, cout, device=dev), _f(G, cout, device=dev), _f(G * nbn, device=dev)
-        if sflags:
-          rc = rn.lib().ra_bn_act_pool_bwd_grouped_bf16_f32(ptr(U), ptr(dY), ptr(info['tabs']), G, _C.c_float(BN_EPS), int(relu),
-                                                            int(pool), B, H, W, cout, ptr(ws), ws.numel(), ptr(dgam), ptr(dbet), ptr(du),
-                                                            sflags, rn.stream_ptr())
-        else:
-          rc = rn.lib().ra_bn_act_pool_bwd_grouped_f32(ptr(U), ptr(dY), ptr(info['tabs']), G, _C.c_float(BN_EPS), int(relu), int(pool),
-                                                       B, H, W, cout, ptr(ws), ws.numel(), ptr(dgam), ptr(dbet), ptr(du), rn.stream_ptr())
-        if rc != rn.RA_E_SHAPE or sflags:
-          check(rc, 'ra_bn_act_pool_bwd_grouped_f32')
-    if info.get('sync_world', 1) <= 1 and rc == rn.RA_E_SHAPE:
-      # a channel count the grouped float4 kernel does not take (the one-channel output layer; C / 4 not a power of two,
-      # e.g. the KITTI architecture's 96-channel layer): one call per timestep
+      # no grouped form at this channel count or size (C / 4 not a power of two, e.g. the KITTI architecture's 96-channel layer;
+      # a one-channel layer above the one-workgroup limit): one call per timestep
+      du = torch.empty_like(U)
       ws, dgam, dbet = _f(nbn, device=dev), _f(cout, device=dev), _f(cout, device=dev)
       for g, (mean, var, gamma, beta, gg, gbt) in enumerate(info['per_group']):
         sl = slice(g * B, (g + 1) * B)

@@ -397,3 +397,52 @@ def test_ctrl_form_unsupported_descriptor():
   args[2] = 250  # hid: not a multiple of the 16 slices
   for B in (1, 8, 15, 32):
     assert ops.ctrl_form(ops.make_ctrl_desc(*args), B, cus=256) is None
+
+
+# (pass, C, (B, H, W), keywords) -> form: literals read off the rules of the commit before csrc/ra_bn.hip had one chooser (its
+# ra_bn_moments_f32, bn_act_pool_impl, bn_bwd_impl and bn_bwd_grouped_impl), never from the code under test
+BN_FORMS = [
+    ('moments', 1, (8, 48, 48), {}, 'small'),
+    ('moments', 16, (2, 6, 6), {}, 'small'),
+    ('moments', 8, (2, 64, 64), {}, 'small'),       # exactly 65536 values
+    ('moments', 8, (2, 64, 66), {}, 'v4'),
+    ('moments', 128, (1, 4, 6), {}, 'v4'),          # a power of two above the one-workgroup kernels' 64
+    ('moments', 256, (1, 4, 6), {}, 'v4'),
+    ('moments', 12, (3, 6, 10), {}, 'generic'),     # C / 4 = 3
+    ('moments', 1, (2, 192, 192), {}, 'generic'),
+    ('moments', 512, (1, 2, 2), {}, rn.RA_E_SHAPE),
+    ('forward', 8, (3, 6, 10), dict(pool=2, flags=3), 'v4'),
+    ('forward', 8, (3, 6, 10), dict(flags=2), rn.RA_E_INVALID),
+    ('forward', 512, (1, 2, 2), {}, 'generic'),     # the forward has no channel limit
+    ('forward', 96, (3, 20, 20), dict(flags=1), rn.RA_E_SHAPE),
+    ('backward', 8, (3, 6, 10), {}, 'v4'),
+    ('backward', 2, (3, 10, 12), dict(stages=3), 'small'),
+    ('backward', 2, (3, 10, 12), dict(stages=1), 'generic'),
+    ('backward', 96, (3, 20, 20), {}, 'generic'),
+    ('backward', 96, (3, 20, 20), dict(flags=1), rn.RA_E_SHAPE),
+    ('backward', 512, (1, 2, 2), {}, rn.RA_E_SHAPE),
+    ('backward', 8, (3, 6, 10), dict(flags=2), rn.RA_E_INVALID),
+    ('backward', 4, (1, 2, 131073), {}, 'generic'),  # gx = 513 > 512 partial blocks: no float4 reduction ...
+    ('backward', 4, (1, 2, 131073), dict(G=3), rn.RA_E_SHAPE),
+    ('forward', 4, (1, 2, 131073), {}, 'v4'),        # ... while the forward has none to fit
+    ('backward', 1, (8, 48, 48), dict(G=3), 'small'),
+    ('backward', 1, (2, 192, 192), dict(G=3), rn.RA_E_SHAPE),
+    ('backward', 1, (8, 48, 48), dict(G=3, flags=1), rn.RA_E_SHAPE),
+    ('backward', 96, (3, 20, 20), dict(G=3), rn.RA_E_SHAPE),
+    ('backward', 64, (2, 6, 36), dict(G=3), 'v4'),
+    ('backward', 64, (2, 6, 36), dict(G=65536), rn.RA_E_SHAPE),
+    ('backward', 8, (4, 8192, 8192), {}, 'generic'),  # 2^31 values: past the float4 kernels' 32-bit indices
+    ('forward', 8, (4, 8192, 8192), dict(flags=1), rn.RA_E_SHAPE),
+]
+
+
+@pytest.mark.parametrize('which,C_,shape,kw,form', BN_FORMS)
+def test_bn_form_table(which, C_, shape, kw, form):
+  assert ops.bn_form(which, C_, *shape, **kw) == form
+
+
+def test_bn_form_refuses_bad_arguments():
+  assert ops.bn_form('forward', 8, 2, 5, 6, pool=2) == rn.RA_E_SHAPE  # odd H under the pool
+  assert ops.bn_form('forward', 8, 2, 6, 6, pool=3) == rn.RA_E_SHAPE
+  assert ops.bn_form('moments', 8, 2, 5, 6, pool=2) == 'small'        # the moments have no pool
+  assert ops.bn_form('forward', 0, 2, 6, 6) == rn.RA_E_INVALID and ops.bn_form('backward', 8, 2, 6, 6, G=-1) == rn.RA_E_INVALID

@@ -7,6 +7,7 @@ import pytest
 import torch
 
 import ra_native as rn
+from bn_form_cases import _bn_bwd_ref  # the float64 oracle of the BatchNorm backward
 
 pytestmark = pytest.mark.gpu
 
@@ -79,22 +80,6 @@ def test_small_moments_one_launch(cuda, C_, B, H, W):
   u64 = u.astype(np.float64).reshape(-1, C_)
   assert np.abs(mean.cpu().numpy() - u64.mean(axis=0)).max() < 2e-6 * 4
   assert np.abs(var.cpu().numpy() - u64.var(axis=0)).max() < 1e-5 * 4
-
-
-def _bn_bwd_ref(u, dy, mean, var, gamma, beta, relu, pool, eps=1e-3):
-  """float64: y = pool(relu(gamma * (u - mean) * rstd + beta)) with the batch statistics as functions of u."""
-  ut = torch.tensor(u, dtype=torch.float64, requires_grad=True)
-  g, b = torch.tensor(gamma, dtype=torch.float64, requires_grad=True), torch.tensor(beta, dtype=torch.float64, requires_grad=True)
-  C_ = u.shape[-1]
-  flat = ut.reshape(-1, C_)
-  mu, vv = flat.mean(0), flat.var(0, unbiased=False)
-  v = (ut - mu) / torch.sqrt(vv + eps) * g + b
-  if relu:
-    v = torch.relu(v)
-  if pool == 2:
-    v = torch.nn.functional.max_pool2d(v.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1)
-  (v * torch.tensor(dy, dtype=torch.float64)).sum().backward()
-  return ut.grad.numpy(), g.grad.numpy(), b.grad.numpy()
 
 
 @pytest.mark.parametrize('C_,pool,relu', [(1, 1, 0), (1, 1, 1), (2, 2, 1)])

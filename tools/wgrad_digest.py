@@ -8,7 +8,7 @@ filter gradients exactly when their dumps are byte-identical:
   python tools/wgrad_digest.py --lib B/librecattend.so --out b.txt && cmp a.txt b.txt
 
 Stops at the first child that ends abnormally (nothing more is started on the device) and returns its status.
-tools/ctrl_digest.py runs main() over the controller's case table."""
+tools/ctrl_digest.py and tools/bn_digest.py run main() over the controller's and the BatchNorm case tables."""
 import argparse
 import hashlib
 import importlib
@@ -21,7 +21,8 @@ sys.path.insert(0, os.path.join(ROOT, 'tests'))
 
 
 def main(cases='wgrad_form_cases', env_prefix='RA_WGRAD', doc=__doc__):
-  """cases: the module under tests/ with VARIANTS, parse_line and a runner that takes --lib; env_prefix: the variables its variants set"""
+  """cases: the module under tests/ with VARIANTS, parse_line (and digest_text, where not all of a line is compared) and a runner
+  that takes --lib; env_prefix: the variables its variants set"""
   ap = argparse.ArgumentParser(description=doc.split('\n')[0])
   ap.add_argument('--lib', help='the librecattend.so to run (default: the tree\'s own)')
   ap.add_argument('--out', required=True)
@@ -43,7 +44,7 @@ def main(cases='wgrad_form_cases', env_prefix='RA_WGRAD', doc=__doc__):
       for text in r.stdout.splitlines():
         if wf.parse_line(text) is None:
           continue
-        line = ('%s %s\n' % (variant, text)).encode()
+        line = ('%s %s\n' % (variant, getattr(wf, 'digest_text', str)(text))).encode()
         out.write(line)
         sha.update(line)
         lines += 1
