@@ -71,7 +71,7 @@ struct Geo {
 };
 
 // tools/split_probe.hip builds this file with -DRA_PROBES: wave 0 of every workgroup accumulates the shader-clock time between
-// points of the tile loop (as RA_PROBE8 in ra_conv_pair.hip) and leaves the sums in ra_probes_buf[workgroup][8]
+// points of the tile loop (as RA_PROBE8 in ra_conv_pair8.hip) and leaves the sums in ra_probes_buf[workgroup][8]
 #ifdef RA_PROBES
 __device__ long long *ra_probes_buf;
 #define RA_PHASE_PROBE_BUF ra_probes_buf

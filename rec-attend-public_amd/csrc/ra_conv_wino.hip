@@ -302,12 +302,12 @@ struct PWArgs {
 };
 
 // SPLIT (round 5): layer A — the direct 8 -> 16 conv, 54 of the kernel's 86 MFMAs per wave and tile — on the BF16 matrix pipe at
-// float32 accuracy, as in conv_pair8_mfma's SPLIT form (ra_conv_pair.hip): the staged input window is kept as three bf16
+// float32 accuracy, as in conv_pair8_mfma's SPLIT form (ra_conv_pair8.hip): the staged input window is kept as three bf16
 // tiles [pixel][8 channels] (the exact three-piece split of every float32 value, made once per staged element), a K = 32
 // block is four taps x 8 channels (three blocks for the nine taps), a lane's A operand of a block and piece is one
 // ds_read_b128, and six piece products per block replace eight float32 MFMAs.
 // tools/pairw_probe.hip builds this file with -DRA_PROBEW: wave 0 of every workgroup accumulates the shader-clock time between a
-// few points of conv_pair_wino_mfma's tile loop and leaves the sums in ra_probew_buf[workgroup][8] (as RA_PROBE8 in ra_conv_pair.hip)
+// few points of conv_pair_wino_mfma's tile loop and leaves the sums in ra_probew_buf[workgroup][8] (as RA_PROBE8 in ra_conv_pair8.hip)
 #ifdef RA_PROBEW
 __device__ long long *ra_probew_buf;
 #define RA_PHASE_PROBE_BUF ra_probew_buf

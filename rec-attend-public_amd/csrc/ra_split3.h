@@ -1,4 +1,4 @@
-// The exact three-piece bf16 split of float32 values, shared by the SPLIT forms of the conv kernels (ra_conv_pair.hip,
+// The exact three-piece bf16 split of float32 values, shared by the SPLIT forms of the conv kernels (ra_conv_pair8.hip,
 // ra_conv_wino.hip, ra_conv_split.hip), and the vector types those files share.
 #pragma once
 #include <hip/hip_runtime.h>

@@ -180,11 +180,10 @@ def test_k1_forms(cuda, kind, shape, expected):
 PAIR_ALL = [(s, p, None) for s, p in cf.PAIR_CASES] + cf.PAIR_WALK_CASES
 
 
-@pytest.mark.parametrize('shape,expected,walk', PAIR_ALL, ids=['x'.join(map(str, c[0])) for c in PAIR_ALL])
-def test_pair_forms(cuda, shape, expected, walk):
+def pair_case(shape, cuda):
+  """The seeded inputs of a pair case, on the host and packed on the device, and its float64 oracle (tests/pair_form_digest.py
+  walks the same cases with the same bytes)."""
   B, Hs, Ws, Ci, Ca, Cb, ups, pool, has_plane, cache_form = shape
-  plan = cf.pair_plan(shape)
-  assert_plan(plan, expected, walk)
   rng = np.random.RandomState(B * 1000 + Hs * 31 + Ws + Ci + Ca + Cb)
   x = rng.randn(B, Hs, Ws, Ci).astype(np.float32)
   xr = x.copy()
@@ -204,6 +203,16 @@ def test_pair_forms(cuda, shape, expected, walk):
   wpA, wpB = d(ops.pack_conv_weights(wA, transposed=bool(ups))), d(ops.pack_conv_weights(wB, transposed=bool(ups)))
   scA, shA = [d(a) for a in ops.fold_bn(bA, Ca, bnA)]
   scB, shB = [d(a) for a in ops.fold_bn(bB, Cb, bnB)]
+  return x, xr, plane, (wpA, scA, shA), (wpB, scB, shB), ref_of
+
+
+@pytest.mark.parametrize('shape,expected,walk', PAIR_ALL, ids=['x'.join(map(str, c[0])) for c in PAIR_ALL])
+def test_pair_forms(cuda, shape, expected, walk):
+  B, Hs, Ws, Ci, Ca, Cb, ups, pool, has_plane, cache_form = shape
+  plan = cf.pair_plan(shape)
+  assert_plan(plan, expected, walk)
+  x, xr, plane, (wpA, scA, shA), (wpB, scB, shB), ref_of = pair_case(shape, cuda)
+  d = lambda a: dev(a, cuda)
   out = Guarded((B, Hs * (1 + ups) // pool, Ws * (1 + ups) // pool, Cb), cuda)
   what = 'pair %r' % (shape,)
   if cache_form == 0:

@@ -1,12 +1,12 @@
 // Where the time of the first controller-CNN launch (conv_pair8_mfma<4, CACHED>: L0 + L1 at full resolution) goes:
-// builds csrc/ra_conv_pair.hip with -DRA_PROBE8 (wave 0 of every workgroup accumulates the shader-clock time between
+// builds csrc/ra_conv_pair8.hip with -DRA_PROBE8 (wave 0 of every workgroup accumulates the shader-clock time between
 // a few points of its tile loop) and prints, per phase, the share of a workgroup's time, plus the HIP-event duration
 // of the launch.  Phases: 0 = next canvas window staged to LDS + barrier, 1 = layer A's cached sums arrived, 2 = phase A
 // (3 MFMAs per group, ReLU, LDS tile), 3 = barrier, 4 = phase B (24 MFMAs per group, pool, store).
 // Without -DRA_PROBE8 it only times the launch (HIP graph of 8 copies, and eager).
 //   hipcc -O3 -std=c++17 --offload-arch=gfx950 [-DRA_PROBE8 [-DRA_P8_NOBAR]] -Iinclude -Irec-attend-public_amd/csrc \
 //         tools/pair8_probe.hip -o tools/bin/pair8_probe
-#include "../rec-attend-public_amd/csrc/ra_conv_pair.hip"
+#include "../rec-attend-public_amd/csrc/ra_conv_pair8.hip"
 
 #include <algorithm>
 #include <vector>
