@@ -1,6 +1,8 @@
 // K1 (pair form), the N-packed kernel of the first controller-CNN pair, its cache of layer A's timestep-invariant sums, and
 // their entry points.  The generic pair, ra_conv_pair_f32 (which diverts here) and the plan query are in ra_conv_pair.hip;
 // ra_conv_pair_parts.h holds what the two share.
+#include <type_traits>
+
 #include "ra_conv_pair_parts.h"
 #include "ra_split3.h"
 
@@ -15,8 +17,8 @@ namespace cpair {
 // so one MFMA row is a pixel PAIR: 12 k-steps per 32 pixels instead of 2 x 9.  W' is built in
 // registers from the standard packed filter (predicated loads), the interface does not change.
 // Tile = 16 x 32 conv pixels (8 x 16 pooled).  Row mappings:
-//   phase A (no pool): m -> (row m>>2, pair m&3), groups of 4 rows x 8 cols, 5 x 5 groups cover
-//                      the 18 x 36 (even-aligned) region layer B needs; result -> LDS tile `tmid`
+//   phase A (no pool): 21 groups of 16 (row, pixel pair) cells cover the 18 rows x 18 pairs (36 even-aligned columns) layer B
+//                      reads, each cell once (NGeo::cell); result -> LDS tile `tmid`
 //   phase B (pool 2):  m -> (pair m>>1, row m&1), groups of 2 rows x 16 cols; the pool window of a
 //                      pair is registers (2j, 2j+1) of lanes n and n^8 -> v_max + one DPP row_ror:8.
 // Both LDS tiles use odd row strides (43 / 41 pixels) so the strided operand reads are 2-way
@@ -25,13 +27,57 @@ template <int CINA>
 struct NGeo {
   static constexpr int TH = 16, TW = 32;
   static constexpr int NCGA = CINA / 4;
-  static constexpr int AGX = 5, AGY = 5, NGA = AGX * AGY, GPW = (NGA + 3) / 4;
   static constexpr int AW = 41, AHS = TH + 2;  // tmid: row stride (pixels), rows stored
-  static constexpr int LW = 43, LH = 4 * AGY + 2;  // tin: row stride, rows addressable
+  static constexpr int LW = 43, LH = 22;       // tin: row stride, rows addressable
+  // Phase A's group map.  Layer B reads rows 0..17 x pixel pairs 0..17 of the region (pair j = region columns 2j, 2j + 1): 324
+  // cells, 20.25 MFMA groups of 16.  21 groups cover them without a dead or repeated cell:
+  //   0..15   interior, 4 rows x 4 pairs: group g = rows 4 (g >> 2).., pairs 4 (g & 3)..      (m -> row m >> 2, pair m & 3)
+  //   16, 17  right strips, 8 rows x pairs 16, 17: rows 8 (g - 16)..                          (m -> row m >> 1, pair m & 1)
+  //   18, 19  bottom strips, rows 16, 17 x 8 pairs: pairs 8 (g - 18)..                        (m -> row m >> 3, pair m & 7)
+  //   20      the corner, rows 16, 17 x pairs 16, 17, in MFMA rows 0..3; rows 4..15 are spare: they repeat the cell of row
+  //           m & 3 (an address inside the staged window, finite values) and are masked at every store
+  // Every wave runs GPW = 5 slots: slot s < 4 is interior group 4 s + wave, slot 4 is strip 16 + wave.  Slot 5, the corner, is
+  // run by ONE wave per tile, wave tile & 3 (the tile's index, so the static and the ticket walk agree).
+  static constexpr int NGA = 21, GPW = 5, NSLOT = GPW + 1, AR = AHS, AP = TW / 2 + 2;  // region: AR rows x AP pairs
+  struct Cell {
+    int row, pair;
+    bool live;
+  };
+  static constexpr __host__ __device__ int group_of(int wave, int s) { return s < 4 ? 4 * s + wave : s == 4 ? 16 + wave : 20; }
+  // MFMA row m of slot s of wave `wave` (s == NSLOT - 1: any wave)
+  static constexpr __host__ __device__ Cell cell(int wave, int s, int m) {
+    if (s < 4) return Cell{4 * s + (m >> 2), 4 * wave + (m & 3), true};
+    if (s == 4) return wave < 2 ? Cell{8 * wave + (m >> 1), 16 + (m & 1), true} : Cell{16 + (m >> 3), 8 * (wave - 2) + (m & 7), true};
+    return Cell{16 + ((m >> 1) & 1), 16 + (m & 1), m < 4};
+  }
+  // the map hits each of the AR x AP cells with exactly one live MFMA row, its groups are 0 .. NGA - 1, each once, and a spare
+  // row stays inside the region (so its reads stay inside the staged window)
+  static constexpr bool map_exact() {
+    int hits[AR * AP] = {};
+    bool seen[NGA] = {};
+    for (int s = 0; s < NSLOT; ++s)
+      for (int w = 0; w < (s == GPW ? 1 : 4); ++w) {
+        const int g = group_of(w, s);
+        if (g < 0 || g >= NGA || seen[g]) return false;
+        seen[g] = true;
+        for (int m = 0; m < 16; ++m) {
+          const Cell c = cell(w, s, m);
+          if (c.row < 0 || c.row >= AR || c.pair < 0 || c.pair >= AP) return false;
+          if (c.live) ++hits[c.row * AP + c.pair];
+        }
+      }
+    for (int g = 0; g < NGA; ++g)
+      if (!seen[g]) return false;
+    for (int i = 0; i < AR * AP; ++i)
+      if (hits[i] != 1) return false;
+    return true;
+  }
+  static_assert(AR * AP == 324 && NGA * 16 - 12 == AR * AP, "18 rows x 18 pairs = 21 groups less the corner's 12 spare rows");
   // tin rows / cols actually loaded (20 x 38): every value that shares an MFMA row with a needed
   // output must be finite even where its weight is zero (pair 17 = columns 34|35 reads tin
   // columns 34..37; 0 * NaN would poison column 34)
   static constexpr int LHL = TH + 4, LWL = TW + 6;
+  static_assert(AR - 1 + 2 < LHL && 2 * (AP - 1) + 3 < LWL && LHL <= LH && LWL <= LW, "every cell's 3 x 4 window is staged");
   static constexpr int PLANE_B = AHS * AW * 16;  // bytes of one bf16 tile [AHS][AW][8] of the SPLIT form
   // the kernel's dynamic LDS, in floats: the staged input window (CACHED: the canvas alone), then the intermediate tile(s)
   template <bool CACHED>
@@ -47,6 +93,7 @@ struct NGeo {
     return tin_floats<CACHED>() + tmid_floats<SPLIT>();
   }
 };
+static_assert(NGeo<4>::map_exact() && NGeo<8>::map_exact(), "phase A's groups cover the 18 x 18 pair-rows exactly once");
 
 #ifndef RA_PAIR8_OCC
 #define RA_PAIR8_OCC 3  // workgroups per CU: 3 x 38.7 KB LDS, <= 168 VGPRs (4 spills)
@@ -112,10 +159,10 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? 3 : 4) : RA_PAIR8_OCC) void 
   const float loA = a.reluA ? 0.f : -__builtin_inff(), loB = a.reluB ? 0.f : -__builtin_inff();
   // Phase A runs its MFMAs with the operands SWAPPED (filter = A operand, pixels = B operand: the same lane contents, the other
   // argument order), so its accumulators are D^T: lane (pixel mA = lane & 15, channel block g4 = lane >> 4) holds the FOUR
-  // channels 4 g4 .. 4 g4 + 3 of column n = (p, co), i.e. channels coA0 .. coA0 + 3 of ONE pixel (row qA of the group, column
-  // 2 rA + pA).  With pixels as rows a lane held one channel of four pixels and wrote the bf16 tiles of layer B with twelve
+  // channels 4 g4 .. 4 g4 + 3 of column n = (p, co), i.e. channels coA0 .. coA0 + 3 of ONE pixel (pixel pA of the pair-row
+  // that NGeo::cell gives MFMA row mA of the group).  With pixels as rows a lane held one channel of four pixels and wrote the bf16 tiles of layer B with twelve
   // 2-byte LDS stores per group; now it is three 8-byte stores (phase A was 45 % of a workgroup's life, issue-bound on them).
-  const int qA = m >> 2, rA = m & 3, pA = ksub >> 1, coA0 = 4 * (ksub & 1);
+  const int pA = ksub >> 1, coA0 = 4 * (ksub & 1);
   f32x4 scA4, shA4;
 #pragma unroll
   for (int j = 0; j < 4; ++j) scA4[j] = a.scA[coA0 + j], shA4[j] = a.shA[coA0 + j];
@@ -271,23 +318,39 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? 3 : 4) : RA_PAIR8_OCC) void 
     }
   };
 
-  const int lane_in = CACHED ? (m >> 2) * G::LW + 2 * (m & 3) + ksub
-                             : ((m >> 2) * G::LW + 2 * (m & 3)) * CINA + ksub * NCGA;
   const __amdgpu_buffer_rsrc_t rc = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float *>(a.cache ? a.cache : a.src), 0, a.cache ? a.bytes_c : 0, 0x00020000);
   const int lane_b = ((m & 1) * G::AW + 2 * (m >> 1) + 1) * 8 + ksub * 2;
   const int pg = a.plane_chan >> 2, slot = a.plane_chan & 3;
 
-  // tile-invariant pieces of the cache / output addresses: per group slot (scalar) and per lane
-  int slot_c[G::GPW];
-#pragma unroll
-  for (int s = 0; s < G::GPW; ++s) {
-    int gi = wave + 4 * s;
-    if (gi >= G::NGA) gi = G::NGA - 1;
-    const int gr = gi / G::AGX, gc = gi - gr * G::AGX;
-    slot_c[s] = (4 * gr * a.cache_gx + gc) * 256;
-  }
-  const int lane_c = qA * a.cache_gx * 256 + rA * 64 + ksub * 16;  // cell (row, column group): [pair r][n] floats, this lane's n = 4 g4 ..
+  // What follows from a lane's cell (row, pixel pair of the region: NGeo::cell) in a group slot, all tile-invariant: the tin
+  // record its window starts at, the byte offset of its float4 in the cache ([row][column group pair >> 2][pair & 3][n], this
+  // lane's n = 4 g4 ..), and the tmid index of its pixel of the region (pixel pA of its pair).
+  struct LaneCell {
+    int in, c, pix;
+  };
+  auto lane_cell = [&](int s, int mm) {
+    const typename G::Cell c = G::cell(wave, s, mm);
+    return LaneCell{(c.row * G::LW + 2 * c.pair) * RECA + ksub * (CACHED ? 1 : NCGA),
+                    (c.row * a.cache_gx + (c.pair >> 2)) * 256 + (c.pair & 3) * 64 + ksub * 16, c.row * G::AW + 2 * c.pair + pA};
+  };
+  // ... and its pixel as row | column << 8, which only a tile on the image's border asks for (it works it out per tile, as below)
+  auto lane_rowcol = [&](int s) {
+    int mm = m;
+    asm volatile("" : "+v"(mm));
+    const typename G::Cell c = G::cell(wave, s, mm);
+    return c.row | (2 * c.pair + pA) << 8;
+  };
+  // Kept in registers for the interior slots (slot s = slot 0 moved down 4 s rows: constant and scalar offsets) and the strip
+  // slot.  The corner's is worked out by the wave that runs it, per tile, from a lane index the compiler cannot see through:
+  // hoisted out of the tile loop it would hold three more registers in every wave for one group in 21.
+  const LaneCell cell_i = lane_cell(0, m), cell_s = lane_cell(G::GPW - 1, m);
+  auto corner_cell = [&]() {
+    int mm = m;
+    asm volatile("" : "+v"(mm));
+    return lane_cell(G::GPW, mm);
+  };
+  const int rows4_c = 4 * a.cache_gx * 256;  // the cache, 4 rows down
   const __amdgpu_buffer_rsrc_t ry = __builtin_amdgcn_make_buffer_rsrc(a.y, 0, a.bytes_y, 0x00020000);
   const unsigned lane_y = co < a.CoutB ? (unsigned)(((2 * qo + p) * a.CoutB + co) * 4) : 0x80000000u;
   int g_y[4];
@@ -303,8 +366,8 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? 3 : 4) : RA_PAIR8_OCC) void 
   TC cur = split(have ? tile : 0), nxt = cur;
   if (have) fetch(cur);
   RA_PHASE_DECL;
-  // the padded groups read LDS this kernel never writes; whatever an earlier kernel left there
-  // must not be NaN/Inf (their results are discarded, but keep the arithmetic clean)
+  // no group reads LDS that a tile's staging did not write (NGeo::cell: spare rows repeat a live cell); the one-time fill keeps
+  // what an earlier kernel left in the rest of the window (tin rows 20, 21 and columns 38 .. 42, tmid column 40) defined
   for (int e = tid; e < G::template lds_floats<CACHED, SPLIT>() / 4; e += 256)
     reinterpret_cast<f32x4 *>(lds)[e] = f32x4{0.f, 0.f, 0.f, 0.f};
   __syncthreads();
@@ -319,19 +382,27 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? 3 : 4) : RA_PAIR8_OCC) void 
   const int r_per_tile = (r_chunk + 256 * my_tiles - 1) / (256 * my_tiles);
   const u32x4 r_bits = __builtin_bit_cast(u32x4, f32x4{a.rider_val, a.rider_val, a.rider_val, a.rider_val});
   bool have_n = false;
-  f32x4 cpre[CACHED ? G::GPW : 1];
-  auto load_cache = [&](const TC &tc) {
+  f32x4 cpre[CACHED ? G::NSLOT : 1];
+  LaneCell cell_c{};
+  auto load_cache = [&](const TC &tc, bool own) {
     const int tile_c0 = ((tc.b * a.cache_rows + tc.ty * G::TH) * a.cache_gx + ((tc.tx * G::TW) >> 3)) * 256;
 #pragma unroll
     for (int s = 0; s < (CACHED ? G::GPW : 1); ++s)
-      cpre[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rc, tile_c0 + slot_c[s] + lane_c, 0, 0));
+      cpre[s] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(
+                                              rc, tile_c0 + (s < 4 ? s * rows4_c + cell_i.c : cell_s.c), 0, 0));
+    if constexpr (CACHED)
+      if (own) {
+        cell_c = corner_cell();
+        cpre[G::GPW] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rc, tile_c0 + cell_c.c, 0, 0));
+      }
   };
   for (; have; tile = dyn ? (tk.step(), tk.cur) : tile + nwx, cur = nxt, have = have_n) {
     const int b = cur.b, ty0 = cur.ty * G::TH, tx0 = cur.tx * G::TW;
     // CACHED: this tile's cached sums of layer A — 32 bytes per pixel, the launch's largest read — are requested at the top of the
     // tile, one staging pass and a barrier ahead of their use (the probe's "waiting for the cached sums 14 %"; requesting them a
     // whole phase B ahead costs more in registers than the wait: DESIGN.md, the cached first pair)
-    if constexpr (CACHED) load_cache(cur);
+    const bool own = wave == (tile & 3);  // uniform: this wave runs the tile's 21st group, the corner
+    if constexpr (CACHED) load_cache(cur, own);
 
     // ---------------- stage layer A's input window (prefetched registers -> LDS) ----------------
 #pragma unroll
@@ -384,98 +455,98 @@ __global__ __launch_bounds__(256, CACHED ? (SPLIT ? 3 : 4) : RA_PAIR8_OCC) void 
     {
       const bool interior = (ty0 >= 1) & (ty0 + G::TH + 1 <= a.H) & (tx0 >= 2) & (tx0 + G::TW + 1 <= a.W);
       const int tile_c = ((b * a.cache_rows + ty0) * a.cache_gx + (tx0 >> 3)) * 256;  // (the FILL form's cache stores)
-      f32x4 acc[G::GPW];
-      int gin[G::GPW];
+      // group slots S0 .. S1 - 1 of this wave: accumulators, MFMAs, epilogue and the stores to tmid (FILL: and to the cache)
+      auto groups = [&](auto s0c, auto s1c, const LaneCell &edge, int rowcol_i, int rowcol_e) __attribute__((always_inline)) {
+        constexpr int S0 = decltype(s0c)::value, NS = decltype(s1c)::value - S0;
+        f32x4 acc[NS];
+        int gin[NS];
 #pragma unroll
-      for (int s = 0; s < G::GPW; ++s) {
-        int gi = wave + 4 * s;
-        if (gi >= G::NGA) gi = G::NGA - 1;  // duplicate work, masked at the store
-        const int gr = gi / G::AGX, gc = gi - gr * G::AGX;
-        gin[s] = (4 * gr * G::LW + 8 * gc) * RECA + lane_in;
-        if constexpr (CACHED) {
-          // this lane's 4 partial sums (columns n = 4 g4 .. + 3 of pixel mA of the group) are one float4 of the cache:
-          // [image][row ty0-1+4gr+qA (+1)][column group tx0/8+gc][pair rA][n]
-          // (byte offset = tile part + slot part + lane part; only the first changes per tile)
-          acc[s] = cpre[s] * scA4 + shA4;
-        } else {
-          acc[s] = fill ? f32x4{0.f, 0.f, 0.f, 0.f} : shA4;
-        }
-      }
-      RA_PHASE_AT(1);  // layer A's cached sums have arrived (accumulators initialised)
-      if constexpr (CACHED) {
+        for (int s = 0; s < NS; ++s) gin[s] = S0 + s < 4 ? cell_i.in + 4 * (S0 + s) * G::LW * RECA : edge.in;
 #pragma unroll
-        for (int ky = 0; ky < 3; ++ky) {
-          float av[G::GPW];
-#pragma unroll
-          for (int s = 0; s < G::GPW; ++s) av[s] = tin[gin[s] + ky * G::LW];
-#pragma unroll
-          for (int s = 0; s < G::GPW; ++s)
-            acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(bAc[ky], av[s], acc[s], 0, 0, 0);  // D^T: rows = (p, co), columns = pixels
-        }
-      } else {
-#pragma unroll
-      for (int ky = 0; ky < 3; ++ky)
-#pragma unroll
-        for (int kxp = 0; kxp < 4; ++kxp) {
-          avecA av[G::GPW];
-#pragma unroll
-          for (int s = 0; s < G::GPW; ++s)
-            av[s] = *reinterpret_cast<const avecA *>(&tin[gin[s] + (ky * G::LW + kxp) * CINA]);
-#pragma unroll
-          for (int cg = 0; cg < NCGA; ++cg)
-#pragma unroll
-            for (int s = 0; s < G::GPW; ++s)
-              acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(bA[ky * 4 + kxp][cg], av[s][cg], acc[s], 0, 0, 0);
-        }
-      }
-      if (fill) {  // uniform: raw sums -> cache, then the folded scale / shift
-#pragma unroll
-        for (int s = 0; s < G::GPW; ++s) {
-          int gi = wave + 4 * s;
-          if (gi >= G::NGA) gi = G::NGA - 1;
-          const int gr = gi / G::AGX, gc = gi - gr * G::AGX;
-          // a tile stores only cells whose four pixel pairs it computed from a complete window: its
-          // rows 0..17 (16 / 17 are computed identically by the tile below) and column groups 0..3;
-          // group 4 (pairs 2, 3 reach past the staged window) belongs to the tile on the right, except
-          // in the last tile column, where those pairs lie outside the image
-          const bool mine = (4 * gr + qA < G::AHS) & ((gc < 4) | (tx0 + G::TW >= a.W));
-          const int off = mine ? tile_c + slot_c[s] + lane_c : 0x7fffffff;
-          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, acc[s]), rc, off, 0, 0);
-          acc[s] = acc[s] * scA4 + shA4;
-        }
-      }
-#pragma unroll
-      for (int s = 0; s < G::GPW; ++s) {
-        const int gi = wave + 4 * s;
-        const int gr = gi / G::AGX, gc = gi - gr * G::AGX;
-        const bool live = (gi < G::NGA) & (4 * gr + qA < G::AHS);
-        float o[4];  // channels coA0 .. coA0 + 3 of the pixel (row 4 gr + qA, column 8 gc + 2 rA + pA) of the region
-#pragma unroll
-        for (int j = 0; j < 4; ++j) o[j] = fmaxf(acc[s][j], loA);
-        if (!interior) {  // outside the image the intermediate is layer B's SAME padding: zero
-          const int Y = ty0 - 1 + 4 * gr + qA, X = tx0 - 2 + 8 * gc + 2 * rA + pA;
-          const bool ok = (Y >= 0) & (Y < a.H) & (X >= 0) & (X < a.W);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) o[j] = ok ? o[j] : 0.f;
-        }
-        const int pix = (4 * gr + qA) * G::AW + 8 * gc + 2 * rA + pA;
-        if constexpr (SPLIT) {
-          // three bf16 tiles [pixel][channel]: the lane's four channels are 8 contiguous bytes of the pixel's record in each
-          unsigned H01, M01, L01, H23, M23, L23;
-          split3_pair(o[0], o[1], H01, M01, L01);
-          split3_pair(o[2], o[3], H23, M23, L23);
-          if (live) {
-            unsigned char *d0 = reinterpret_cast<unsigned char *>(tmid) + pix * 16 + coA0 * 2;
-            *reinterpret_cast<u32x2 *>(d0) = u32x2{H01, H23};
-            *reinterpret_cast<u32x2 *>(d0 + PLANE_B) = u32x2{M01, M23};
-            *reinterpret_cast<u32x2 *>(d0 + 2 * PLANE_B) = u32x2{L01, L23};
+        for (int s = 0; s < NS; ++s) {
+          if constexpr (CACHED) {
+            // this lane's 4 partial sums (columns n = 4 g4 .. + 3 of its pixel) are one float4 of the cache:
+            // [image][row ty0 + row][column group tx0/8 + (pair >> 2)][pair & 3][n]
+            acc[s] = cpre[S0 + s] * scA4 + shA4;
+          } else {
+            acc[s] = fill ? f32x4{0.f, 0.f, 0.f, 0.f} : shA4;
           }
-        } else if (live) {
-          // float32 tile, records [ksub][cg] (channel c at 2 (c & 3) + (c >> 2)): this lane's channels sit two floats apart
-          float *dst = tmid + pix * 8 + (ksub & 1);
-#pragma unroll
-          for (int j = 0; j < 4; ++j) dst[2 * j] = o[j];
         }
+        if constexpr (S0 == 0) RA_PHASE_AT(1);  // layer A's cached sums have arrived (accumulators initialised)
+        if constexpr (CACHED) {
+#pragma unroll
+          for (int ky = 0; ky < 3; ++ky) {
+            float av[NS];
+#pragma unroll
+            for (int s = 0; s < NS; ++s) av[s] = tin[gin[s] + ky * G::LW];
+#pragma unroll
+            for (int s = 0; s < NS; ++s)
+              acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(bAc[ky], av[s], acc[s], 0, 0, 0);  // D^T: rows = (p, co), columns = pixels
+          }
+        } else {
+#pragma unroll
+          for (int ky = 0; ky < 3; ++ky)
+#pragma unroll
+            for (int kxp = 0; kxp < 4; ++kxp) {
+              avecA av[NS];
+#pragma unroll
+              for (int s = 0; s < NS; ++s)
+                av[s] = *reinterpret_cast<const avecA *>(&tin[gin[s] + (ky * G::LW + kxp) * CINA]);
+#pragma unroll
+              for (int cg = 0; cg < NCGA; ++cg)
+#pragma unroll
+                for (int s = 0; s < NS; ++s)
+                  acc[s] = __builtin_amdgcn_mfma_f32_16x16x4f32(bA[ky * 4 + kxp][cg], av[s][cg], acc[s], 0, 0, 0);
+            }
+        }
+#pragma unroll
+        for (int s = 0; s < NS; ++s) {
+          const int S = S0 + s < 4 ? S0 + s : 0;  // (an interior slot's distance from slot 0)
+          const bool inner = S0 + s < 4;
+          const bool live = S0 + s < G::GPW || m < 4;  // the corner's spare rows (NGeo::cell)
+          if (fill) {  // uniform: raw sums -> cache, then the folded scale / shift
+            // Every live cell was computed from a complete staged window, so a tile stores all of its 18 x 18: a cell that a
+            // neighbour computes too (rows 16 / 17 are the rows 0 / 1 of the tile below, pairs 16 / 17 the pairs 0 / 1 of the
+            // tile on the right) gets the same bits from both, and the tiles' regions together cover the image
+            const int off = live ? tile_c + (inner ? S * rows4_c + cell_i.c : edge.c) : 0x7fffffff;
+            __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(__attribute__((ext_vector_type(4))) unsigned, acc[s]), rc, off, 0, 0);
+            acc[s] = acc[s] * scA4 + shA4;
+          }
+          float o[4];  // channels coA0 .. coA0 + 3 of the lane's pixel
+#pragma unroll
+          for (int j = 0; j < 4; ++j) o[j] = fmaxf(acc[s][j], loA);
+          if (!interior) {  // outside the image the intermediate is layer B's SAME padding: zero
+            const int rowcol = inner ? rowcol_i + 4 * S : rowcol_e;
+            const int Y = ty0 - 1 + (rowcol & 255), X = tx0 - 2 + (rowcol >> 8);
+            const bool ok = (Y >= 0) & (Y < a.H) & (X >= 0) & (X < a.W);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = ok ? o[j] : 0.f;
+          }
+          const int pix = inner ? cell_i.pix + 4 * S * G::AW : edge.pix;
+          if constexpr (SPLIT) {
+            // three bf16 tiles [pixel][channel]: the lane's four channels are 8 contiguous bytes of the pixel's record in each
+            unsigned H01, M01, L01, H23, M23, L23;
+            split3_pair(o[0], o[1], H01, M01, L01);
+            split3_pair(o[2], o[3], H23, M23, L23);
+            if (live) {
+              unsigned char *d0 = reinterpret_cast<unsigned char *>(tmid) + pix * 16 + coA0 * 2;
+              *reinterpret_cast<u32x2 *>(d0) = u32x2{H01, H23};
+              *reinterpret_cast<u32x2 *>(d0 + PLANE_B) = u32x2{M01, M23};
+              *reinterpret_cast<u32x2 *>(d0 + 2 * PLANE_B) = u32x2{L01, L23};
+            }
+          } else if (live) {
+            // float32 tile, records [ksub][cg] (channel c at 2 (c & 3) + (c >> 2)): this lane's channels sit two floats apart
+            float *dst = tmid + pix * 8 + (ksub & 1);
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dst[2 * j] = o[j];
+          }
+        }
+      };
+      groups(std::integral_constant<int, 0>{}, std::integral_constant<int, G::GPW>{}, cell_s, interior ? 0 : lane_rowcol(0),
+             interior ? 0 : lane_rowcol(G::GPW - 1));
+      if (own) {
+        if constexpr (!CACHED) cell_c = corner_cell();
+        groups(std::integral_constant<int, G::GPW>{}, std::integral_constant<int, G::NSLOT>{}, cell_c, 0, interior ? 0 : lane_rowcol(G::GPW));
       }
     }
     RA_PHASE_AT(2);  // phase A computed and written to the LDS tile
