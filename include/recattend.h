@@ -131,6 +131,10 @@ int ra_conv_pair_plan(int Cin, int B, int Hs, int Ws, int upsampleA, int CoutA, 
 int ra_conv_split_plan(int B, int H, int W, int Cin, int Cout, int pool, int has_plane, int *plan);
 int ra_conv_wino_plan(int B, int H, int W, int Cin, int Cout, int pool, int *plan);
 int ra_conv_pair_wino_plan(int B, int H, int W, int *plan);
+/* K1p16 (ra_conv_pair16_f32): FAMILY = PAIR with the FORM bits SPLIT | PERSIST, CK = 8, CMID = 16, NC = 1, POOL = 2, 8 x 16 tiles,
+ * SLICES = 1; GRID, XCD_MAP, TILES_MIN / TILES_MAX and TICKETS as for the Winograd pair.  The grid follows the device's CU count
+ * and the kernel's occupancy: RA_E_INVALID without a device. */
+int ra_conv_pair16_plan(int B, int H, int W, int *plan);
 /* Test aid (no reference counterpart): the launch plan of the direct paste (mode 0: ra_paste_direct_f32, ra_paste_score_direct_f32
  * without its rider workgroup) and of the attention box (mode 1: ra_attn_box_direct_f32; Cp, pc, has_canvas, has_img do not
  * count).  The paste launches one of two kernels on its shape and argument conditions; the query walks the launch's own chain
@@ -360,6 +364,17 @@ int ra_conv_pair_wino_supported(int Cin, int CoutA, int CoutB, int poolB, int H,
 int ra_conv_pair_wino_f32(const float *x, int B, int H, int W, const float *wpA, const float *scaleA,
                           const float *shiftA, int reluA, const float *wpB_wino, const float *scaleB,
                           const float *shiftB, int reluB, float *y, void *stream);
+
+/* K1p16: the same pair (8 -> 16 -> 16, poolB = 2; H, W multiples of 16: ra_conv_pair16_supported is the predicate of
+ * ra_conv_pair_wino_supported) with BOTH layers direct on the bf16 matrix pipe at float32 accuracy (three bf16 pieces per
+ * operand, six piece products per K = 32 block, as K1s): layer B reads layer A's output from LDS as bf16 pieces, a lane's four
+ * accumulator registers are one pool window, and there is no Winograd transform or exchange (csrc/ra_conv_pair16.hip).  wpA and
+ * wpB: ra_conv_pack_weights with Cin = 8 resp. 16, the packing ra_conv_pair_f32 takes.  Results differ from ra_conv_pair_wino_f32
+ * by float32 rounding only. */
+int ra_conv_pair16_supported(int Cin, int CoutA, int CoutB, int poolB, int H, int W);
+int ra_conv_pair16_f32(const float *x, int B, int H, int W, const float *wpA, const float *scaleA, const float *shiftA,
+                       int reluA, const float *wpB, const float *scaleB, const float *shiftB, int reluB, float *y,
+                       void *stream);
 
 /* The first controller-CNN pair with the image part of layer A cached.  Of layer A's input
  * concat(x, canvas) (full_model.py:640-661) only the canvas changes between timesteps

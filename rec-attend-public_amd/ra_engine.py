@@ -53,6 +53,8 @@ class DecodeEngine(object):
     # L3 Winograd 22.2 us against 41.8 us fused: no gain, one more launch -> off
     self.wino_unfuse = False
     self.pair_wino = True  # the fused L2+L3 pair with its second layer as Winograd (K1pw)
+    # ... or, first, with both layers direct on the bf16 matrix pipe (K1p16); RA_PAIR16=0: K1pw.  pair_wino = False switches both off
+    self.pair_direct16 = os.environ.get('RA_PAIR16', '1') != '0'
     self.use_wino = True  # controller-CNN layers with Cin 16 | 32, Cout % 32 == 0 as Winograd F(2x2,3x3) (K1w)
     self.cache_first = True  # image part of the first controller-CNN layer cached once per forward
     self.fill_cache_inline = True  # ... by the first timestep's own launch (else: a separate kernel)
@@ -605,6 +607,10 @@ class DecodeEngine(object):
                                    fill=fill, fill_value=1.0 / (1.0 + math.exp(5.0)))
         elif cache is not None and pl is not None:
           ops.conv_pair_cached(cache, pl, pc, wpa, sca[tt], sha[tt], wpb, scb[tt], shb[tt], cb, bufs[step[2]])
+        elif (self.pair_direct16 and self.pair_wino and layers is self.W.get('ccnn') and pl is None and
+              ops.conv_pair16_supported(src.shape[3], ca, cb, poolb, src.shape[1], src.shape[2])):
+          # K1p16: both layers direct on the bf16 matrix pipe, layer B straight from the LDS tile layer A was written to
+          ops.conv_pair16(src, wpa, sca[tt], sha[tt], wpb, scb[tt], shb[tt], out=bufs[step[2]])
         elif (self.use_wino and self.pair_wino and layers is self.W.get('ccnn') and pl is None and
               self.W['ccnn_wino'][step[2]] is not None and
               ops.conv_pair_wino_supported(src.shape[3], ca, cb, poolb, src.shape[1], src.shape[2])):

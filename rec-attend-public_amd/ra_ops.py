@@ -307,6 +307,10 @@ def conv_pair_wino_plan(B, H, W):
   return _plan('ra_conv_pair_wino_plan', B, H, W)
 
 
+def conv_pair16_plan(B, H, W):
+  return _plan('ra_conv_pair16_plan', B, H, W)
+
+
 def conv2d_fused(src0, wp, scale, shift, cout, ksize, relu=True, pool=1, src1=None, upsample=False, out=None, plane=None,
                  plane_chan=-1):
   """conv3x3 for a ksize x ksize filter, ksize in FILTER_SIZES; wp = pack_conv_weights of that filter.  ksize = 3 IS
@@ -488,6 +492,21 @@ def conv_pair_wino(x, wpA, scA, shA, wpB_wino, scB, shB, reluA=True, reluB=True,
   out = _conv_out(x, 16, 2, out=out)
   check(rn.lib().ra_conv_pair_wino_f32(ptr(x), B, H, W, ptr(wpA), ptr(scA), ptr(shA), int(reluA), ptr(wpB_wino), ptr(scB),
                                        ptr(shB), int(reluB), ptr(out), rn.stream_ptr()), 'ra_conv_pair_wino_f32')
+  return out
+
+
+def conv_pair16_supported(cin, cout_a, cout_b, pool_b, H, W):
+  return bool(rn.lib().ra_conv_pair16_supported(int(cin), int(cout_a), int(cout_b), int(pool_b), int(H), int(W)))
+
+
+def conv_pair16(x, wpA, scA, shA, wpB, scB, shB, reluA=True, reluB=True, out=None):
+  """The fused pair 8 -> 16 -> 16, pool 2, with both layers direct on the bf16 matrix pipe (ra_conv_pair16_f32).  x [B,H,W,8];
+  wpA, wpB = pack_conv_weights of the two filters."""
+  _need_cuda(x, wpA, scA, shA, wpB, scB, shB, out)
+  B, H, W, _ = x.shape
+  out = _conv_out(x, 16, 2, out=out)
+  check(rn.lib().ra_conv_pair16_f32(ptr(x), B, H, W, ptr(wpA), ptr(scA), ptr(shA), int(reluA), ptr(wpB), ptr(scB), ptr(shB),
+                                    int(reluB), ptr(out), rn.stream_ptr()), 'ra_conv_pair16_f32')
   return out
 
 

@@ -10,7 +10,7 @@ before and after it, so pass --steps large enough that the middle is pipeline) a
 """
 import csv, sys, collections
 
-ENC = ('conv_pair8_mfma', 'conv_pair_wino_mfma', 'conv_wino_mfma', 'conv_split_kernel', 'conv3x3_mfma<16, 1, 4, 2, 1, false')
+ENC = ('conv_pair8_mfma', 'conv_pair16_mfma', 'conv_pair_wino_mfma', 'conv_wino_mfma', 'conv_split_kernel', 'conv3x3_mfma<16, 1, 4, 2, 1, false')
 CTRL = ('controller_batch_kernel', 'controller_split_kernel', 'controller_kernel')
 
 
