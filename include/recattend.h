@@ -862,6 +862,56 @@ int ra_instance_overlap_f32(const float *y, const int *gt_ids, const int *ids, c
                             int *ws, size_t ws_ints, int *inter, int *pred_pixels, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The label stage in front of training and of the pre-stage's evaluation (csrc/ra_labels.hip): the ground truth the
+ * reference's setup_cityscapes.py / setup_kitti.py / setup_cvppp.py assemble (data_api/ins_seg_assembler.py:85-155,
+ * sep_labels.py, orientation.py:31-85) as ins_seg_dataset.py:158-172,216-236,257-271 reads it back, from instance-id images.
+ *
+ * ra_labels_assemble_i32 — gt_ids int32 [B,Hf,Wf] and ids, count as ra_gt_instance_catalog_i32 wrote them for it: the
+ *   catalogue of the FULL image (sep_labels takes np.unique of it), so an instance that vanishes at network size still
+ *   counts as an object.  dataset: RA_LABELS_PLAIN (cvppp.py:49-63, kitti.py:51-65) — every id != 0 is an instance, one
+ *   semantic class; RA_LABELS_CITYSCAPES (cityscapes.py:88-119) — an id is an instance iff id > 1000 and id / 1000 is one of
+ *   the labels (24, 25, 26, 27, 28, 31, 32, 33) of ra_instance_class_pick_f32, its class that label's position 0 .. 7; every
+ *   other id (stuff, ids up to 1000, caravan / trailer) is background.  Network pixel (r, c) reads full-size pixel
+ *   (min(floor(r * sy), Hf - 1), min(floor(c * sx), Wf - 1)), sy = 1.0 / ((double)H / Hf) in double and sx likewise: the
+ *   form of cv2.resize(..., INTER_NEAREST) (ins_seg_assembler.py:125,145), restated from OpenCV's source.  Outputs, each
+ *   nullable and then skipped:
+ *     num_obj int32 [B]            accepted catalogue entries
+ *     s_gt float [B,T]             1 for t < min(num_obj, T) (:267-271), also for an instance that is empty at network size
+ *     inst_id, area, sem_cls       int32 [B,T]: the id of slot t, its pixel count AT NETWORK SIZE, its class (0 under PLAIN);
+ *                                  -1 / 0 / -1 beyond num_obj
+ *     y_gt float [B,T,H,W]         slot t = the 0 / 1 mask of inst_id[b,t], zero beyond num_obj.  Slots are in descending
+ *                                  order of area (:169-172, np.argsort(area)[::-1]); equal areas: the larger catalogue
+ *                                  index (the larger id) first — a stable ascending sort read backwards, which is what
+ *                                  NumPy gives up to 16 elements; beyond that NumPy's order is not stable, so this is the
+ *                                  library's rule
+ *     d_cls uint8 [B,H,W]          orientation.get_orientation(all instances at network size, encoding='class'): over ALL
+ *                                  accepted instances, not the first T (ins_seg_assembler.py:136-139); 0 on the background.
+ *                                  Per pixel in double, in the reference's order: v = (r - cy, c - cx), centroid = sum /
+ *                                  (area + 1e-7); o = (v + 1e-8) / (sqrt(v . v) + 1e-7); a = asin(o_y) folded by the signs of
+ *                                  o_x, o_y; a += pi / 8; class = floor((a + pi) * 8 / 2 / pi) mod 8.  The centroid pixel
+ *                                  gets o = (0.1, 0.1), class 0 is shared with the background: the reference's quirks, kept
+ *     d_gt float [B,H,W,8]         d_gt[..., o] = (d_cls == o) (:257-262): channel 0 is 1 on the background
+ *     c_gt float [B,H,W,nc]        PLAIN: nc = 1, the union of the instances; CITYSCAPES: nc = 9, channel 1 + k the union of
+ *                                  class k's instances, channel 0 = 1 - max of the others (:216-236)
+ *     fg_gt_full uint8 [B,Hf,Wf]   1 where the dataset rule accepts the id (fg_model_eval.py:142-143)
+ *   Launches on one stream: the moments of the sampled positions (integer counters in LDS, workgroup partials in ws), one
+ *   workgroup per image that adds them in a fixed order, applies the rule and ranks, one fill that writes all T planes of its
+ *   pixels (16-byte stores when H * W % 4 == 0 and the outputs are 16-byte aligned), and the full-size foreground.  No
+ *   floating-point atomics, nothing indexed by an id, the same bits on every run.  An image whose catalogue status is not
+ *   0 keeps that status word for the caller to report; its outputs describe the listed ids only, the other images are
+ *   unaffected.  1 <= T <= RA_LABELS_MAX_T, 1 <= H <= Hf, 1 <= W <= Wf, Hf * Wf < 2^31, else RA_E_SHAPE before anything is
+ *   read or launched.  ws: ra_labels_workspace_bytes(B, H, W) bytes, 8-byte aligned.
+ * ---------------------------------------------------------------------------------- */
+#define RA_LABELS_PLAIN 0
+#define RA_LABELS_CITYSCAPES 1
+#define RA_LABELS_MAX_T 32
+size_t ra_labels_workspace_bytes(int B, int H, int W);
+int ra_labels_assemble_i32(const int *gt_ids, const int *ids, const int *count, int B, int Hf, int Wf, int H, int W, int T,
+                           int dataset, void *ws, size_t ws_bytes, int *num_obj, float *s_gt, int *inst_id, int *area,
+                           int *sem_cls, float *y_gt, unsigned char *d_cls, float *d_gt, float *c_gt,
+                           unsigned char *fg_gt_full, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Evaluating the pre-stage fg_model (csrc/ra_fg_eval.hip).
  *
  * ra_fg_stats_f32 — the sums behind the six statistics the reference's Evaluator logs (fg_model_train.py:131-133), replacing

@@ -37,7 +37,7 @@ def build_parser():
   for table in (cap.TRAIN_FLAGS, cap.DATA_FLAGS, cap.MODEL_FLAGS):
     cap.add_flags(p, table)
   cap.add_size_overrides(p)
-  p.add_argument('--input', default=None, help='.npz with x, y_gt, s_gt (default: synthetic batches)')
+  p.add_argument('--input', default=None, help='.npz with x and y_gt, s_gt or gt_instance_ids (default: synthetic batches)')
   p.add_argument('--seed', type=int, default=1234)
   p.add_argument('--sync_bn', action='store_true', help='BatchNorm batch moments over the whole data-parallel batch')
   return p
@@ -72,7 +72,7 @@ def main(argv=None):
       b = fmt.synthetic_batch(rng, hi - lo, H, W, T)
       return b + (dict(zip(('d_in', 'y_in'), fmt.synthetic_extras(rng, hi - lo, H, W, nsc))),) if add_d else b
     idx = (step * args.batch_size + np.arange(lo, hi)) % data['x'].shape[0]
-    b = (data['x'][idx], data['y_gt'][idx], data['s_gt'][idx])
+    b = (data['x'][idx],) + fmt.batch_labels(data, idx, H, W, T, args.dataset)
     return b + ({'d_in': data['d_in'][idx], 'y_in': data['y_in'][idx]},) if add_d else b
 
   fmt.train_loop(args, model, model_opt, folder, rank, world, make_batch)

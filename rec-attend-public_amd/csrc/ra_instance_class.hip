@@ -19,6 +19,7 @@
 #include <cstdint>
 
 #include "ra_common.h"
+#include "ra_gt_ids.h"
 
 namespace ra {
 namespace icls {
@@ -30,8 +31,6 @@ constexpr int kTile = 256;              // pixels per tile = threads per workgro
 constexpr int kWaves = kTile / kWave;   // 4
 constexpr int kTPerWave = kMaxT / kWaves;  // a wave owns the instances wave, wave + 4, ...: at most 8 (KT below: 5 up to T = 20)
 constexpr int kTargetWgs = 1024;        // four workgroups per CU: what the 127 registers of vote_kernel<9, 5> leave room for
-
-__constant__ int kLabelId[8] = {24, 25, 26, 27, 28, 31, 32, 33};  // analysis.py:203-210
 
 __device__ __forceinline__ void tap(int d, int n_src, double scale, int &i0, int &i1, float &w) {
   const double f = ((double)d + 0.5) * scale - 0.5;
@@ -158,7 +157,7 @@ __device__ __forceinline__ void pick_one(const float *vote, float conf, int C, i
       }
   }
   if (class_idx) *class_idx = idx;
-  if (label_id) *label_id = idx >= 0 && idx < 8 ? kLabelId[idx] : -1;
+  if (label_id) *label_id = idx >= 0 && idx < gtid::kCsClasses ? gtid::cs_label_id(idx) : -1;
 }
 
 // One workgroup per instance (b, t): wave w adds the nwg partials of the channels w, w + 4, ... — lane l takes the workgroups

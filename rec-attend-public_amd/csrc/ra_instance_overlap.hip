@@ -23,6 +23,7 @@
 #include <cstdint>
 
 #include "ra_common.h"
+#include "ra_gt_ids.h"
 
 namespace ra {
 namespace iov {
@@ -162,16 +163,7 @@ __global__ __launch_bounds__(256) void cat_merge_kernel(const int *part, int nwg
   }
 }
 
-// the slot of id in the sorted catalogue cat[0, n), -1 when it is not there
-__device__ __forceinline__ int find_slot(const int *cat, int n, int id) {
-  int lo = 0, hi = n;
-  while (lo < hi) {
-    const int mid = (lo + hi) >> 1;
-    if (cat[mid] < id) lo = mid + 1;
-    else hi = mid;
-  }
-  return lo < n && cat[lo] == id ? lo : -1;
-}
+using gtid::find_slot;  // the slot of an id in the sorted catalogue, -1 when it is not there
 
 // Workgroup (x, b) walks the tiles x, x + gridDim.x, ... of image b; see the head of the file.  sh: cnt[T][256], pp[32],
 // cat[256].  VEC: 16-byte loads (H * W % 4 == 0, y and gt_ids 16-byte aligned), else element loads.  Its counters go to

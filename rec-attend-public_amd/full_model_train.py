@@ -10,7 +10,9 @@ Hungarian matchings on the device, backward through the HIP kernels, one RCCL al
 flat gradient bucket when launched with torch.distributed.run (one process per GPU, every rank
 its own shard of the global --batch_size), clip + Adam, BN EMA (ra_train.TrainStep).
 
-Data: --input (an .npz with x [N,H,W,3], y_gt [N,T,H,W], s_gt [N,T]) or synthetic CVPPP-shaped
+Data: --input (an .npz with x [N,H,W,3] and either y_gt [N,T,H,W], s_gt [N,T] or gt_instance_ids
+[N,Hf,Wf]: then y_gt / s_gt of every batch are assembled on the device from the ids by the --dataset's
+rule, ra_ops.assemble_labels, eagerly in front of the captured step) or synthetic CVPPP-shaped
 batches (8..T-1 ellipses per image, sorted by area); the reference's HDF5 datasets,
 plots and CSV loggers are out of scope.  BatchNorm moments are taken over the
 rank's shard, or over the whole batch with --sync_bn.  Checkpoints (weights.npz +
@@ -36,7 +38,7 @@ def build_parser():
   cap.add_size_overrides(p)
   p.add_argument('--init_only', action='store_true',
                  help='write model_opt.yaml + initial weights and stop')
-  p.add_argument('--input', default=None, help='.npz with x, y_gt, s_gt (default: synthetic batches)')
+  p.add_argument('--input', default=None, help='.npz with x and y_gt, s_gt or gt_instance_ids (default: synthetic batches)')
   p.add_argument('--seed', type=int, default=1234)
   p.add_argument('--save_rank_weights', action='store_true',
                  help='every rank also writes weights_rank<r>.npz (its own weights, EMA shadows and per-step losses) at the end: '
@@ -77,6 +79,19 @@ def synthetic_extras(rng, B, H, W, num_semantic_classes):
   z = rng.randn(B, H, W, num_semantic_classes).astype(np.float32)
   e = np.exp(z - z.max(axis=3, keepdims=True))
   return d_in, (e / e.sum(axis=3, keepdims=True)).astype(np.float32)
+
+
+def batch_labels(data, idx, H, W, T, dataset):
+  """(y_gt, s_gt) of the images idx of an --input archive: its own planes, or — an archive that holds gt_instance_ids and no
+  y_gt — assembled on the device from the ids (ins_seg_dataset.py:158-172,267-271 on setup_*.py's output), device tensors."""
+  if 'y_gt' in data:
+    return data['y_gt'][idx], data['s_gt'][idx]
+  if 'gt_instance_ids' not in data:
+    raise KeyError('--input holds neither y_gt nor gt_instance_ids')
+  import ra_ops
+  names = [str(n) for n in data['names'][idx]] if 'names' in data else ['image %d' % i for i in idx]
+  got = ra_ops.assemble_labels(data['gt_instance_ids'][idx], H, W, T, dataset, want=('y_gt', 's_gt'), names=names)
+  return got['y_gt'], got['s_gt']
 
 
 def save_checkpoint(path, model):
@@ -205,7 +220,7 @@ def main(argv=None):
       b = synthetic_batch(rng, hi - lo, H, W, T)
       return b + (dict(zip(('d_in', 'y_in'), synthetic_extras(rng, hi - lo, H, W, nsc))),) if add_d else b
     idx = (step * args.batch_size + np.arange(lo, hi)) % data['x'].shape[0]
-    b = (data['x'][idx], data['y_gt'][idx], data['s_gt'][idx])
+    b = (data['x'][idx],) + batch_labels(data, idx, H, W, T, args.dataset)
     return b + ({'d_in': data['d_in'][idx], 'y_in': data['y_in'][idx]},) if add_d else b
 
   train_loop(args, model, model_opt, folder, rank, world, make_batch)

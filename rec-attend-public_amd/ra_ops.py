@@ -1217,6 +1217,12 @@ def gt_instance_catalog(gt_ids, check_status=True, names=None):
                                             rn.stream_ptr()), 'ra_gt_instance_catalog_i32')
   if not check_status:
     return ids, pixels, count, status
+  _raise_gt_status(status, names, 'gt_instance_catalog')
+  return ids, pixels, count
+
+
+def _raise_gt_status(status, names, who):
+  """The catalogue's status words [B] (one device-to-host copy): the first image with one set raises, named."""
   for b, st in enumerate(status.cpu().tolist()):
     if st:
       why = []
@@ -1224,8 +1230,7 @@ def gt_instance_catalog(gt_ids, check_status=True, names=None):
         why.append('an instance id outside [0, 65535]')
       if st & rn.RA_GT_STATUS_COUNT:
         why.append('more than %d distinct instance ids' % MAX_GT)
-      raise rn.RecAttendError('gt_instance_catalog: image %s has %s' % (names[b] if names is not None else b, ' and '.join(why)))
-  return ids, pixels, count
+      raise rn.RecAttendError('%s: image %s has %s' % (who, names[b] if names is not None else b, ' and '.join(why)))
 
 
 def instance_overlap(y, gt_ids, catalog):
@@ -1329,3 +1334,81 @@ def fg_sweep_counts(src, gt, thresholds):
   K = len(_sweep_thresholds(thresholds))
   return {'count_a': c[:, :K].copy(), 'sum_ab': c[:, FG_SWEEP_MAX_K:FG_SWEEP_MAX_K + K].copy(), 'sum_b': c[:, 2 * FG_SWEEP_MAX_K].copy(),
           'pixels': int(gt.shape[1] * gt.shape[2]), 'thresholds': [float(t) for t in _sweep_thresholds(thresholds)]}
+
+
+# ---------------------------------------------------------------------------- the label stage: ground truth from instance ids
+LABELS_MAX_T = rn.RA_LABELS_MAX_T
+LABEL_DATASETS = {'cvppp': rn.RA_LABELS_PLAIN, 'kitti': rn.RA_LABELS_PLAIN, 'plain': rn.RA_LABELS_PLAIN,
+                  'cityscapes': rn.RA_LABELS_CITYSCAPES}
+LABEL_OUTPUTS = ('num_obj', 's_gt', 'inst_id', 'area', 'sem_cls', 'y_gt', 'd_cls', 'd_gt', 'c_gt', 'fg_gt_full')
+
+
+def label_dataset_rule(dataset):
+  """RA_LABELS_* of a dataset name (cvppp, kitti: every id != 0 is an instance; cityscapes: labelId * 1000 + k of the eight
+  instance labels) or of the constant itself."""
+  if dataset in LABEL_DATASETS:
+    return LABEL_DATASETS[dataset]
+  if dataset in (rn.RA_LABELS_PLAIN, rn.RA_LABELS_CITYSCAPES) and not isinstance(dataset, bool):
+    return int(dataset)
+  raise rn.RecAttendError('assemble_labels: dataset %r (one of %s)' % (dataset, ', '.join(sorted(LABEL_DATASETS))))
+
+
+def assemble_labels_raw(gt_ids, catalog, H, W, T, dataset, want=LABEL_OUTPUTS):
+  """ra_labels_assemble_i32 on gt_ids int32 [B,Hf,Wf] and catalog = gt_instance_catalog(gt_ids, ...) of the same tensor:
+  {name: device tensor} over `want`; no status is looked at."""
+  _need_cuda_i32(gt_ids, 'gt_ids')
+  ids, count = catalog[0], catalog[2]
+  _need_cuda_i32(ids, 'catalog ids')
+  _need_cuda_i32(count, 'catalog count')
+  rule = label_dataset_rule(dataset)
+  unknown = [k for k in want if k not in LABEL_OUTPUTS]
+  if unknown or not want:
+    raise rn.RecAttendError('assemble_labels: want %s (any of %s)' % (list(want), ', '.join(LABEL_OUTPUTS)))
+  if gt_ids.dim() != 3 or min(gt_ids.shape) < 1:
+    raise rn.RecAttendError('assemble_labels: gt_ids must be [B,Hf,Wf], got %s' % (tuple(gt_ids.shape),))
+  B, Hf, Wf = gt_ids.shape
+  H, W, T = int(H), int(W), int(T)
+  if tuple(ids.shape) != (B, MAX_GT) or tuple(count.shape) != (B,):
+    raise rn.RecAttendError('assemble_labels: gt_ids %s, catalog ids %s, count %s do not belong together' % (
+        tuple(gt_ids.shape), tuple(ids.shape), tuple(count.shape)))
+  if not (1 <= T <= LABELS_MAX_T and 1 <= H <= Hf and 1 <= W <= Wf and Hf * Wf < 1 << 31 and B <= OVERLAP_MAX_B):
+    raise rn.RecAttendError('assemble_labels: T=%d, %d x %d -> %d x %d, B=%d (1 <= T <= %d, 1 <= H <= Hf, 1 <= W <= Wf, Hf * Wf < '
+                            '2^31, B <= %d)' % (T, Hf, Wf, H, W, B, LABELS_MAX_T, OVERLAP_MAX_B))
+  dev = gt_ids.device
+  nc = 1 + len(_cityscapes_labels()) if rule == rn.RA_LABELS_CITYSCAPES else 1
+  spec = {'num_obj': ((B,), torch.int32), 's_gt': ((B, T), torch.float32), 'inst_id': ((B, T), torch.int32),
+          'area': ((B, T), torch.int32), 'sem_cls': ((B, T), torch.int32), 'y_gt': ((B, T, H, W), torch.float32),
+          'd_cls': ((B, H, W), torch.uint8), 'd_gt': ((B, H, W, 8), torch.float32), 'c_gt': ((B, H, W, nc), torch.float32),
+          'fg_gt_full': ((B, Hf, Wf), torch.uint8)}
+  out = {k: torch.empty(spec[k][0], dtype=spec[k][1], device=dev) for k in LABEL_OUTPUTS if k in want}
+  n = rn.lib().ra_labels_workspace_bytes(B, H, W)
+  ws = torch.empty((max(n // 8, 1),), dtype=torch.int64, device=dev)
+  check(rn.lib().ra_labels_assemble_i32(ptr(gt_ids), ptr(ids), ptr(count), B, Hf, Wf, H, W, T, rule, ptr(ws), n,
+                                        *[ptr(out.get(k)) for k in LABEL_OUTPUTS], rn.stream_ptr()), 'ra_labels_assemble_i32')
+  return out
+
+
+def _cityscapes_labels():
+  import analysis
+  return analysis.CITYSCAPES_LABELS
+
+
+def assemble_labels(gt_ids, H, W, T, dataset, want=('y_gt', 's_gt'), names=None):
+  """The reference's label stage on the device (setup_*.py: ins_seg_assembler.py:85-155, read back by ins_seg_dataset.py:
+  158-172,216-236,257-271): gt_ids [B,Hf,Wf] — a torch int32 tensor or a NumPy integer array of *_instanceIds.png values —
+  -> {name: device tensor} over `want`, any of LABEL_OUTPUTS (include/recattend.h, ra_labels_assemble_i32, says what each
+  is).  dataset: 'cvppp' | 'kitti' | 'cityscapes' or RA_LABELS_*.  Runs the catalogue of the full-size image and the
+  stage's launches; an image with an id outside [0, 65535] or with more than MAX_GT distinct ids raises RecAttendError
+  naming it (names[b], else its index), from one device-to-host copy of B status words."""
+  if isinstance(gt_ids, np.ndarray):
+    if not np.issubdtype(gt_ids.dtype, np.integer):
+      raise rn.RecAttendError('assemble_labels: gt_ids must hold integers, got %s' % gt_ids.dtype)
+    if not torch.cuda.is_available():
+      raise rn.RecAttendError('recattend kernels need CUDA (HIP) tensors; no device is available. There is no CPU fallback.')
+    gt_ids = torch.as_tensor(np.ascontiguousarray(gt_ids.astype(np.int32, copy=False))).cuda()
+  label_dataset_rule(dataset)
+  _need_cuda_i32(gt_ids, 'gt_ids')
+  ids, pixels, count, status = gt_instance_catalog(gt_ids, check_status=False)
+  out = assemble_labels_raw(gt_ids, (ids, pixels, count), H, W, T, dataset, want)
+  _raise_gt_status(status, names, 'assemble_labels')
+  return out
