@@ -862,6 +862,53 @@ int ra_instance_overlap_f32(const float *y, const int *gt_ids, const int *ids, c
                             int *ws, size_t ws_ints, int *inter, int *pred_pixels, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The Cityscapes pixel-level evaluation (csrc/ra_pixel_eval.hip), cited as lines of
+ * data_api/cityscapes_scripts/evaluation/evalPixelLevelSemanticLabeling.py.  Label ids run from 0 to 33
+ * (RA_PIXEL_LABELS = 34, helpers/labels.py); the thing labels are (24, 25, 26, 27, 28, 31, 32, 33) as above, the instance
+ * categories human = {24, 25} and vehicle = {26 .. 33}, caravan and trailer included, as generateInstanceStats builds them
+ * (:182-200).  gt_ids int32 [B,H,W] are *_gtFine_instanceIds.png values, ids / count their catalogue as
+ * ra_gt_instance_catalog_i32 wrote it.  H * W < 2^31.
+ *
+ * ra_sem_labels_u8 — the label image of the pre-stage's semantic map: sem float32 [B,Hs,Ws,C] (channel 0 the background,
+ *   2 <= C <= 9) -> labels uint8 [B,H,W].  Every channel is resized to H x W with the linear resample of
+ *   ra_sem_foreground_f32 / ra_instance_class_vote_f32 (cv2.resize INTER_LINEAR, float32, the source coordinate in double);
+ *   the FIRST maximum over the channels wins; channel 0 gives label 0, channel c >= 1 the thing label (24, ..)[c - 1].  All
+ *   channels of a pixel go through the same sequence of operations, so channels equal at the four taps stay exactly equal.
+ * ra_pixel_confusion_u8 / ra_pixel_confusion_sem_f32 — evaluatePair (:532-615) for B images: the prediction is a label
+ *   image pred uint8 [B,H,W], or (_sem_f32) the label ra_sem_labels_u8 would give for sem, evaluated on the fly by the same
+ *   device function with no full-size plane written.  gt_labels uint8 [B,H,W] are the *_gtFine_labelIds.png values; NULL:
+ *   the label of a pixel is id < 1000 ? id : id / 1000, as the instance images encode it.
+ *     conf unsigned 64-bit [34,34]   conf[g][p] += the pixels with ground-truth label g and predicted label p (:566-573).
+ *                                    ADDED to what is there: a data set is many calls.
+ *     inst_tp int32 [B,RA_OVERLAP_MAX_GT]      per catalogue slot k: the pixels with gt_ids == ids[k] whose prediction
+ *                                    equals ids[k] / 1000 (:588-591)
+ *     inst_cat_tp int32 [B,RA_OVERLAP_MAX_GT]  those whose prediction lies in the instance category of ids[k] / 1000
+ *                                    (:579, :603-606); 0 where that label is in neither category.  Both are written for every
+ *                                    slot, ids <= 1000 included (the host skips them, :581), and are 0 beyond count[b].
+ *     status int32 [B]               0, or a sum of RA_PIXEL_STATUS_GT (a ground-truth label above 33 was met, :570-571) and
+ *                                    RA_PIXEL_STATUS_PRED (a predicted label above 33).  A pixel with such a label is
+ *                                    counted in no cell of conf, and nothing is indexed by an unchecked value; every other
+ *                                    pixel, of this image and of the others, is counted as usual.
+ *   A workgroup walks tiles of RA_PIXEL_TILE pixels of one image (16-byte loads of gt_ids and 4-byte loads of the label
+ *   images when H * W % 4 == 0 and the pointers are aligned so, element loads otherwise) with its counters in LDS and
+ *   leaves them in ws (ra_pixel_confusion_workspace_ints(B, H, W) ints); a finishing launch adds them, per image in int32
+ *   and over the images in 64 bits.  No global atomics: exact, the same on every run.  B <= 65535, 2 <= C <= 9, else
+ *   RA_E_SHAPE and nothing is launched.
+ * ---------------------------------------------------------------------------------- */
+#define RA_PIXEL_LABELS 34
+#define RA_PIXEL_TILE 1024
+#define RA_PIXEL_STATUS_GT 1
+#define RA_PIXEL_STATUS_PRED 2
+int ra_sem_labels_u8(const float *sem, int B, int Hs, int Ws, int C, int H, int W, unsigned char *labels, void *stream);
+size_t ra_pixel_confusion_workspace_ints(int B, int H, int W);
+int ra_pixel_confusion_u8(const unsigned char *pred, const int *gt_ids, const unsigned char *gt_labels, const int *ids,
+                          const int *count, int B, int H, int W, int *ws, size_t ws_ints, unsigned long long *conf,
+                          int *inst_tp, int *inst_cat_tp, int *status, void *stream);
+int ra_pixel_confusion_sem_f32(const float *sem, int Hs, int Ws, int C, const int *gt_ids, const unsigned char *gt_labels,
+                               const int *ids, const int *count, int B, int H, int W, int *ws, size_t ws_ints,
+                               unsigned long long *conf, int *inst_tp, int *inst_cat_tp, int *status, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * The label stage in front of training and of the pre-stage's evaluation (csrc/ra_labels.hip): the ground truth the
  * reference's setup_cityscapes.py / setup_kitti.py / setup_cvppp.py assemble (data_api/ins_seg_assembler.py:85-155,
  * sep_labels.py, orientation.py:31-85) as ins_seg_dataset.py:158-172,216-236,257-271 reads it back, from instance-id images.

@@ -400,6 +400,213 @@ class CityscapesAPAnalyzer(object):
     return result
 
 
+# ---- Cityscapes pixel-level evaluation (data_api/cityscapes_scripts/evaluation/evalPixelLevelSemanticLabeling.py) ----
+# Line numbers below are that script's.  The pixel work (evaluatePair, :532-615: the confusion matrix and the true positives of
+# every ground-truth instance) runs on the device (ops.pixel_confusion); what is left is a 34 x 34 integer matrix, two
+# integers per instance, and float64 NumPy on those.
+# helpers/labels.py as data: (id, name, category, hasInstances, ignoreInEval); its id -1 (license plate) cannot occur in an image
+PIXEL_LABEL_TABLE = (
+    (0, 'unlabeled', 'void', False, True), (1, 'ego vehicle', 'void', False, True),
+    (2, 'rectification border', 'void', False, True), (3, 'out of roi', 'void', False, True),
+    (4, 'static', 'void', False, True), (5, 'dynamic', 'void', False, True), (6, 'ground', 'void', False, True),
+    (7, 'road', 'flat', False, False), (8, 'sidewalk', 'flat', False, False), (9, 'parking', 'flat', False, True),
+    (10, 'rail track', 'flat', False, True), (11, 'building', 'construction', False, False),
+    (12, 'wall', 'construction', False, False), (13, 'fence', 'construction', False, False),
+    (14, 'guard rail', 'construction', False, True), (15, 'bridge', 'construction', False, True),
+    (16, 'tunnel', 'construction', False, True), (17, 'pole', 'object', False, False), (18, 'polegroup', 'object', False, True),
+    (19, 'traffic light', 'object', False, False), (20, 'traffic sign', 'object', False, False),
+    (21, 'vegetation', 'nature', False, False), (22, 'terrain', 'nature', False, False), (23, 'sky', 'sky', False, False),
+    (24, 'person', 'human', True, False), (25, 'rider', 'human', True, False), (26, 'car', 'vehicle', True, False),
+    (27, 'truck', 'vehicle', True, False), (28, 'bus', 'vehicle', True, False), (29, 'caravan', 'vehicle', True, True),
+    (30, 'trailer', 'vehicle', True, True), (31, 'train', 'vehicle', True, False), (32, 'motorcycle', 'vehicle', True, False),
+    (33, 'bicycle', 'vehicle', True, False))
+PIXEL_CATEGORIES = ('void', 'flat', 'construction', 'object', 'nature', 'sky', 'human', 'vehicle')  # in the table's order
+PIXEL_AVG_CLASS_SIZE = {  # :135-146
+    'bicycle': 4672.3249222261, 'caravan': 36771.8241758242, 'motorcycle': 6298.7200839748, 'rider': 3930.4788056518,
+    'bus': 35732.1511111111, 'train': 67583.7075812274, 'car': 12794.0202738185, 'person': 3462.4756337644,
+    'truck': 27855.1264367816, 'trailer': 16926.9763313609}
+_PIXEL_STAT_KEYS = ('tp', 'tpWeighted', 'fn', 'fnWeighted')
+
+
+def pixel_instance_stats():
+  """generateInstanceStats (:171-202): zeroed tp / tpWeighted / fn / fnWeighted for every label that has instances and is
+  evaluated, and for every category all of whose labels have instances (human, vehicle; 'labelIds' lists ALL its labels,
+  caravan and trailer included)."""
+  stats = {'classes': {}, 'categories': {}}
+  for _, name, _, has_inst, ignore in PIXEL_LABEL_TABLE:
+    if has_inst and not ignore:
+      stats['classes'][name] = {k: 0.0 for k in _PIXEL_STAT_KEYS}
+  for cat in PIXEL_CATEGORIES:
+    rows = [r for r in PIXEL_LABEL_TABLE if r[2] == cat]
+    if all(r[3] for r in rows):
+      stats['categories'][cat] = dict({k: 0.0 for k in _PIXEL_STAT_KEYS}, labelIds=[r[0] for r in rows])
+  return stats
+
+
+def pixel_instance_stats_add(stats, ids, pixels, inst_tp, inst_cat_tp):
+  """:581-615 for one image, from its catalogue (ids ascending, pixels) and the kernel's counts per slot: only ids > 1000 whose
+  label is evaluated count, each with weight = avgClassSize / its size; the sums grow in the toolkit's order."""
+  for inst_id, size, tp, cat_tp in zip(ids, pixels, inst_tp, inst_cat_tp):
+    inst_id, size, tp, cat_tp = int(inst_id), int(size), int(tp), int(cat_tp)
+    if inst_id <= 1000:
+      continue
+    label = inst_id // 1000
+    if label >= len(PIXEL_LABEL_TABLE):
+      raise ops.rn.RecAttendError('instance id %d: label %d is not a Cityscapes label (0 .. 33)' % (inst_id, label))
+    _, name, cat, _, ignore = PIXEL_LABEL_TABLE[label]
+    if ignore:
+      continue
+    weight = PIXEL_AVG_CLASS_SIZE[name] / float(size)
+    for rec, t in ((stats['classes'][name], tp),) + (((stats['categories'][cat], cat_tp),) if cat in stats['categories'] else ()):
+      rec['tp'] += t
+      rec['fn'] += size - t
+      rec['tpWeighted'] += float(t) * weight
+      rec['fnWeighted'] += float(size - t) * weight
+
+
+def _pixel_average(scores):
+  """getScoreAverage (:273-282): the mean over the entries that are not NaN, NaN when there is none."""
+  import math
+  vals = [v for v in scores.values() if not math.isnan(v)]
+  return sum(vals, 0.0) / len(vals) if vals else float('nan')
+
+
+def cityscapes_pixel_scores(conf, inst_stats):
+  """The scores of evalPixelLevelSemanticLabeling.py from conf [34,34] (conf[g][p] = pixels with ground-truth label g and
+  predicted label p) and inst_stats (pixel_instance_stats, filled): classScores / classInstScores per label name (:216-265)
+  and categoryScores / categoryInstScores per category (:285-338) — tp / (tp + fp + fn) in float64, where fp is the label's
+  (category's) column(s) over the rows of labels that are evaluated and not the label itself (not in the category): pixels
+  whose ground truth is ignored cost nothing; iIoU takes fp from the matrix and the weighted tp / fn from the instances.
+  NaN for an ignored label, a label without instances (iIoU), a category without evaluated labels and for 0 / 0.  Plus
+  the four averages (:273-282, :353-356) over the entries that are not NaN."""
+  import numpy as np
+  conf = np.asarray(conf).astype(np.int64)
+  n = len(PIXEL_LABEL_TABLE)
+  if conf.shape != (n, n):
+    raise ops.rn.RecAttendError('cityscapes_pixel_scores: conf must be [%d,%d], got %s' % (n, n, conf.shape))
+  nan = float('nan')
+  evaluated = [r[0] for r in PIXEL_LABEL_TABLE if not r[4]]
+  out = {k: {} for k in ('classScores', 'classInstScores', 'categoryScores', 'categoryInstScores')}
+  for label, name, _, _, ignore in PIXEL_LABEL_TABLE:
+    if ignore:
+      out['classScores'][name] = out['classInstScores'][name] = nan
+      continue
+    tp = int(conf[label, label])
+    fn = int(conf[label, :].sum()) - tp
+    fp = int(conf[[l for l in evaluated if l != label], label].sum())
+    out['classScores'][name] = float(tp) / (tp + fp + fn) if tp + fp + fn else nan
+    rec = inst_stats['classes'].get(name)
+    if rec is None:
+      out['classInstScores'][name] = nan
+    else:
+      denom = rec['tpWeighted'] + fp + rec['fnWeighted']
+      out['classInstScores'][name] = float(rec['tpWeighted']) / denom if denom != 0 else nan
+  for cat in PIXEL_CATEGORIES:
+    members = [r[0] for r in PIXEL_LABEL_TABLE if r[2] == cat and not r[4]]
+    others = [r[0] for r in PIXEL_LABEL_TABLE if r[2] != cat and not r[4]]
+    if not members:
+      out['categoryScores'][cat] = nan
+    else:
+      tp = int(conf[np.ix_(members, members)].sum())
+      fn = int(conf[members, :].sum()) - tp
+      fp = int(conf[np.ix_(others, members)].sum())
+      out['categoryScores'][cat] = float(tp) / (tp + fp + fn) if tp + fp + fn else nan
+    rec = inst_stats['categories'].get(cat)
+    if rec is None:
+      out['categoryInstScores'][cat] = nan
+    else:
+      fp = int(conf[np.ix_(others, rec['labelIds'])].sum())  # :322,330: the columns of ALL the category's labels
+      denom = rec['tpWeighted'] + fp + rec['fnWeighted']
+      out['categoryInstScores'][cat] = float(rec['tpWeighted']) / denom if denom != 0 else nan
+  out['averageScoreClasses'] = _pixel_average(out['classScores'])
+  out['averageScoreInstClasses'] = _pixel_average(out['classInstScores'])
+  out['averageScoreCategories'] = _pixel_average(out['categoryScores'])
+  out['averageScoreInstCategories'] = _pixel_average(out['categoryInstScores'])
+  return out
+
+
+def cityscapes_pixel_result(conf, inst_stats):
+  """The dict of writeJSONFile (:341-363) — confMatrix, priors, labels, the four score dicts and the four averages — plus
+  averageScorePredictedClasses: the mean class IoU over the eight thing labels of CITYSCAPES_LABELS only.  The toolkit's
+  averageScoreClasses runs over its 19 evaluated classes, of which the pre-stage predicts eight (the other eleven score 0
+  wherever they occur in the ground truth), so only the extra key says how good the model is at what it does predict."""
+  import numpy as np
+  conf = np.asarray(conf).astype(np.int64)
+  scores = cityscapes_pixel_scores(conf, inst_stats)
+  total = int(conf.sum())
+  result = {'confMatrix': conf.tolist(),
+            'priors': {r[1]: (float(int(conf[r[0], :].sum())) / total if total else float('nan')) for r in PIXEL_LABEL_TABLE},
+            'labels': {r[1]: r[0] for r in PIXEL_LABEL_TABLE}}
+  result.update(scores)
+  result['averageScorePredictedClasses'] = _pixel_average({n: scores['classScores'][n] for n, _ in CITYSCAPES_LABELS})
+  return result
+
+
+def cityscapes_pixel_table(result):
+  """printClassScores / printCategoryScores (:416-440, :496-521) without colour codes, as one string."""
+  row = lambda name, a, b: '{:<14}: '.format(name) + '{:>5.3f}'.format(a) + '    ' + '{:>5.3f}'.format(b)
+  rule = '-' * 32
+  lines = ['', 'classes          IoU      nIoU', rule]
+  lines += [row(r[1], result['classScores'][r[1]], result['classInstScores'][r[1]]) for r in PIXEL_LABEL_TABLE if not r[4]]
+  lines += [rule, row('Score Average', result['averageScoreClasses'], result['averageScoreInstClasses']), rule,
+            row('Thing classes', result['averageScorePredictedClasses'], float('nan')), rule, '',
+            'categories       IoU      nIoU', rule]
+  lines += [row(c, result['categoryScores'][c], result['categoryInstScores'][c]) for c in PIXEL_CATEGORIES if c != 'void']
+  lines += [rule, row('Score Average', result['averageScoreCategories'], result['averageScoreInstCategories']), rule, '']
+  return '\n'.join(lines)
+
+
+class CityscapesPixelAnalyzer(object):
+  """Class IoU / iIoU of the Cityscapes pixel-level evaluation, from label images or the pre-stage's semantic map while they
+  are on the device.  names: the file name of every image, indexed by results['indices'].  stage(results) takes 'gt_ids'
+  int32 [B,H,W] (the *_gtFine_instanceIds.png values), optionally 'gt_labels' uint8 [B,H,W] (else the label is derived from
+  the id), 'indices', and the prediction as 'pred' uint8 [B,H,W] or as 'sem' float32 [B,Hs,Ws,C] with 'size' = (H, W) — the
+  fused form: the arg-max labels are never written.  It is the catalogue, ONE ops.pixel_confusion call into a device matrix
+  that lives as long as the analyzer, and one small device-to-host copy (catalogue, per-instance counts, status words); the
+  instance sums grow in the toolkit's order: images as staged, instances by ascending id.  finalize(path) checks the
+  toolkit's sanity condition (the matrix sums to the pixels seen), writes the result (cityscapes_pixel_result) as JSON when
+  given a path, prints the class table and returns the dict.  One process: several ranks are not merged here."""
+
+  def __init__(self, names):
+    self.names = list(names)
+    self.conf = None  # int64 [34,34] on the device
+    self.inst_stats = pixel_instance_stats()
+    self.pixels = 0
+
+  def stage(self, results):
+    gt = results['gt_ids']
+    img_names = [str(self.names[int(i)]) for i in results['indices']]
+    fused = 'sem' in results
+    ids, pixels, count, cstatus = ops.gt_instance_catalog(gt, check_status=False)
+    out = ops.pixel_confusion(results['sem'] if fused else results['pred'], gt, results.get('gt_labels'), catalog=(ids, pixels, count),
+                              size=results['size'] if fused else None, conf=self.conf, names=img_names, check_status=False)
+    self.conf = out['conf']
+    G = ops.MAX_GT
+    host = torch.cat([ids, pixels, out['inst_tp'], out['inst_cat_tp'], count[:, None], cstatus[:, None], out['status'][:, None]],
+                     dim=1).cpu().numpy()
+    ops._raise_gt_status(torch.as_tensor(host[:, 4 * G + 1]), img_names, 'CityscapesPixelAnalyzer')
+    ops._raise_pixel_status(host[:, 4 * G + 2], img_names, 'CityscapesPixelAnalyzer')
+    for row in host:
+      n = int(row[4 * G])
+      pixel_instance_stats_add(self.inst_stats, row[:n], row[G:G + n], row[2 * G:2 * G + n], row[3 * G:3 * G + n])
+    self.pixels += int(gt.shape[0]) * int(gt.shape[1]) * int(gt.shape[2])
+
+  def finalize(self, path=None, quiet=False):
+    import json
+    import numpy as np
+    conf = self.conf.cpu().numpy() if self.conf is not None else np.zeros((len(PIXEL_LABEL_TABLE),) * 2, np.int64)
+    if int(conf.sum()) != self.pixels:  # :462-463, :472-473
+      raise ops.rn.RecAttendError('Number of analyzed pixels and entries in confusion matrix disagree: confMatrix %d, pixels %d' % (
+          int(conf.sum()), self.pixels))
+    result = cityscapes_pixel_result(conf, self.inst_stats)
+    if path is not None:
+      with open(path, 'w') as f:
+        json.dump(result, f, indent=4, sort_keys=True)
+    if not quiet:
+      print(cityscapes_pixel_table(result))
+    return result
+
+
 # ---------------------------------------------------------------------------- whole-dataset foreground / background IoU
 def _fg_counts_of(results, index):
   """(count_a, sum_ab, sum_b, pixels) of one stage() call as Python integers: from results['fg_counts'] (what

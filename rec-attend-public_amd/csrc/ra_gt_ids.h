@@ -20,6 +20,16 @@ __host__ __device__ __forceinline__ int cs_class_of(int label) {
   return cls;
 }
 
+// The label ids of helpers/labels.py run from 0 to 33 (its -1, license plate, cannot occur in an image).
+constexpr int kCsLabelIds = 34;
+// The instance category of a label as evalPixelLevelSemanticLabeling.py:182-200 builds it — a category all of whose labels
+// have instances: 1 = human {24, 25}, 2 = vehicle {26 .. 33}, caravan (29) and trailer (30) included; 0 = neither.
+__host__ __device__ __forceinline__ int cs_instance_category(int label) {
+  return label == 24 || label == 25 ? 1 : (label >= 26 && label <= 33 ? 2 : 0);
+}
+// the label of a value of *_instanceIds.png: the value itself below 1000, else value / 1000
+__host__ __device__ __forceinline__ int cs_label_of_id(int id) { return id < 1000 ? id : id / 1000; }
+
 // the slot of id in the sorted catalogue cat[0, n), -1 when it is not there
 __device__ __forceinline__ int find_slot(const int *cat, int n, int id) {
   int lo = 0, hi = n;

@@ -20,6 +20,7 @@
 
 #include "ra_common.h"
 #include "ra_gt_ids.h"
+#include "ra_resample.h"
 
 namespace ra {
 namespace icls {
@@ -32,16 +33,7 @@ constexpr int kWaves = kTile / kWave;   // 4
 constexpr int kTPerWave = kMaxT / kWaves;  // a wave owns the instances wave, wave + 4, ...: at most 8 (KT below: 5 up to T = 20)
 constexpr int kTargetWgs = 1024;        // four workgroups per CU: what the 127 registers of vote_kernel<9, 5> leave room for
 
-__device__ __forceinline__ void tap(int d, int n_src, double scale, int &i0, int &i1, float &w) {
-  const double f = ((double)d + 0.5) * scale - 0.5;
-  int i = (int)floor(f);
-  float fr = (float)(f - (double)i);
-  if (i < 0) i = 0, fr = 0.f;
-  if (i >= n_src - 1) i = n_src - 1, fr = 0.f;
-  i0 = i;
-  i1 = i + 1 < n_src ? i + 1 : i;
-  w = fr;
-}
+using resample::tap;  // one axis of the resize: the two taps and the fraction, coordinate in double
 
 // One thread per output pixel.
 __global__ __launch_bounds__(256) void sem_foreground_kernel(const float *sem, int Hs, int Ws, int C, int H, int W,

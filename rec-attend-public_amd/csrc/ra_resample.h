@@ -22,6 +22,21 @@ __device__ inline int reflect101(int i, int n) {
   return i;
 }
 
+// One axis of cv2.resize's float path with the source coordinate in DOUBLE, as cv2 evaluates it: pixel d of n_dst reads the taps
+// i0, i1 of n_src with the weights 1 - w, w (scale = n_src / n_dst in double; the fraction is rounded to float once, taps
+// clamped to the image).  A float coordinate is a few 1e-6 off at non-integer ratios; the semantic-map kernels
+// (ra_instance_class.hip, ra_pixel_eval.hip) use this one, resize_linear_at below keeps its float coordinate.
+__device__ __forceinline__ void tap(int d, int n_src, double scale, int &i0, int &i1, float &w) {
+  const double f = ((double)d + 0.5) * scale - 0.5;
+  int i = (int)floor(f);
+  float fr = (float)(f - (double)i);
+  if (i < 0) i = 0, fr = 0.f;
+  if (i >= n_src - 1) i = n_src - 1, fr = 0.f;
+  i0 = i;
+  i1 = i + 1 < n_src ? i + 1 : i;
+  w = fr;
+}
+
 // pixel (r, c) of the H x W resize of the plane p [Hs, Ws]
 __device__ inline float resize_linear_at(const float *p, int Hs, int Ws, int H, int W, int r, int c) {
   const float sy = (float)Hs / (float)H, sx = (float)Ws / (float)W;

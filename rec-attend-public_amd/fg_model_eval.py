@@ -26,6 +26,15 @@ pixels), plus 'statistics' when ground truth at network size was given; <output>
 <results>/<model_id>/output (:184-186).  --render_ori is accepted and refused: it needs the colour orientation image of
 data_api/orientation.py, and utils/png.py writes 8-bit grey only.
 
+Pixel-level class scores: when --input also holds gt_instance_ids [N,H,W] (the *_gtFine_instanceIds.png values; optionally
+gt_label_ids uint8 [N,H,W], the *_gtFine_labelIds.png values, else a pixel's label is derived from its id) and the model has
+nine semantic classes (the background and the eight labels of analysis.CITYSCAPES_LABELS), every batch's network-size y_out
+also goes through analysis.CityscapesPixelAnalyzer in its fused form — the arg-max of the resized map is taken inside the
+confusion kernel — and <output>/resultPixelLevelSemanticLabeling.json (the keys of the toolkit's
+evalPixelLevelSemanticLabeling.py, plus averageScorePredictedClasses) is written beside metrics.yaml, which gains a
+'pixel_level' entry with the averages.  A model with several semantic classes but not nine cannot be mapped to label ids: the
+script says so and goes on without.  Without gt_instance_ids nothing changes.
+
 No more than MAX_BATCH_ELEMS floats of one tensor are alive per batch; there is no CPU path: without a GPU the script raises
 RecAttendError."""
 import argparse
@@ -110,6 +119,21 @@ def main(argv=None):
   have_stats = 'y_gt' in data
   y_gt_all = data['y_gt'] if have_stats else None
   d_gt_all = data['d_gt'] if have_stats and 'd_gt' in data else None
+  pixel_an = None  # the toolkit's pixel-level class scores, when the archive has the instance-id images
+  if 'gt_instance_ids' in data:
+    nsc = int(model.opt['num_semantic_classes']) if 'num_semantic_classes' in model.opt else 1
+    ids_all = data['gt_instance_ids']
+    lab_all = data['gt_label_ids'] if 'gt_label_ids' in data else None
+    if tuple(ids_all.shape) != (N, H, W) or not np.issubdtype(ids_all.dtype, np.integer):
+      raise RecAttendError('--input: gt_instance_ids is %s %s, expected integers [%d,%d,%d]' % (ids_all.dtype, tuple(ids_all.shape), N, H, W))
+    if lab_all is not None and (tuple(lab_all.shape) != (N, H, W) or lab_all.dtype != np.uint8):
+      raise RecAttendError('--input: gt_label_ids is %s %s, expected uint8 [%d,%d,%d]' % (lab_all.dtype, tuple(lab_all.shape), N, H, W))
+    if nsc == 1 + len(analysis.CITYSCAPES_LABELS):
+      pixel_an = analysis.CityscapesPixelAnalyzer(names)
+    elif nsc > 1:
+      print('pixel-level class scores are left out: the model has %d semantic classes, and only %d (the background and the '
+            'labels %s) map to Cityscapes label ids' % (nsc, 1 + len(analysis.CITYSCAPES_LABELS),
+                                                        ', '.join(n for n, _ in analysis.CITYSCAPES_LABELS)))
   fg_an = [analysis.ForegroundIOUAnalyzer('fg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]  # :62-69
   bg_an = [analysis.BackgroundIOUAnalyzer('bg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]
   totals = [{'count_a': 0, 'sum_ab': 0, 'sum_b': 0, 'pixels': 0} for _ in thresholds]
@@ -123,7 +147,14 @@ def main(argv=None):
     b1 = min(N, b0 + bs)
     x = up(x_all[b0:b1])
     gt = torch.as_tensor(np.ascontiguousarray(gt_all[b0:b1])).to(dev)
-    soft = foreground_plane(model.run('y_out', {'x': x, 'phase_train': False}))
+    y_out = model.run('y_out', {'x': x, 'phase_train': False})
+    soft = foreground_plane(y_out)
+    if pixel_an is not None:
+      res_px = {'sem': y_out.contiguous(), 'size': (H, W), 'indices': list(range(b0, b1)),
+                'gt_ids': torch.as_tensor(np.ascontiguousarray(ids_all[b0:b1].astype(np.int32, copy=False))).to(dev)}
+      if lab_all is not None:
+        res_px['gt_labels'] = torch.as_tensor(np.ascontiguousarray(lab_all[b0:b1])).to(dev)
+      pixel_an.stage(res_px)
     counts = ops.fg_sweep_counts(soft, gt, thresholds)
     res = {'fg_counts': counts, 'indices': list(range(b0, b1))}
     for k in range(len(thresholds)):
@@ -149,6 +180,9 @@ def main(argv=None):
     summary['statistics'] = {n: float(np.mean([s[n] for s in stats])) for n in STAT_NAMES if n in stats[0]}
     for n, v in summary['statistics'].items():
       print('{:17s}{:7.4f}'.format(n, v))
+  if pixel_an is not None:
+    px = pixel_an.finalize(os.path.join(out_dir, 'resultPixelLevelSemanticLabeling.json'))
+    summary['pixel_level'] = {k: float(px[k]) for k in sorted(px) if k.startswith('averageScore')}
   with open(os.path.join(out_dir, 'metrics.yaml'), 'w') as f:
     yaml.safe_dump(summary, f)
   print('%d images -> %s' % (N, out_dir))

@@ -1262,6 +1262,127 @@ def instance_overlap(y, gt_ids, catalog):
   return inter, pred
 
 
+# ---------------------------------------------------------------------------- Cityscapes pixel-level evaluation
+PIXEL_LABELS = rn.RA_PIXEL_LABELS  # label ids 0 .. 33
+PIXEL_TILE = rn.RA_PIXEL_TILE      # pixels per tile of the confusion kernel; one workgroup per tile up to 2048 / B tiles per image
+SEM_MIN_C, SEM_MAX_C = 2, 9        # channels of a semantic map the arg-max takes: background + up to the eight thing labels
+
+
+def _need_dev(t, dtype, what):
+  if not isinstance(t, torch.Tensor) or not t.is_cuda:
+    raise rn.RecAttendError('recattend kernels need CUDA (HIP) tensors; got a CPU tensor for %s. There is no CPU fallback.' % what)
+  if t.dtype != dtype:
+    raise rn.RecAttendError('%s must be a %s tensor, got %s' % (what, str(dtype).replace('torch.', ''), t.dtype))
+  if not t.is_contiguous():
+    raise rn.RecAttendError('%s must be contiguous, got strides %s for shape %s' % (what, tuple(t.stride()), tuple(t.shape)))
+
+
+def _check_sem(who, sem, size):
+  _need_dev(sem, torch.float32, 'sem')
+  if size is None or len(size) != 2:
+    raise rn.RecAttendError('%s: a semantic map needs size=(H, W), got %r' % (who, size))
+  H, W = int(size[0]), int(size[1])
+  if sem.dim() != 4 or min(sem.shape) < 1 or not SEM_MIN_C <= sem.shape[3] <= SEM_MAX_C:
+    raise rn.RecAttendError('%s: sem must be [B,Hs,Ws,C] with %d <= C <= %d, got %s' % (who, SEM_MIN_C, SEM_MAX_C, tuple(sem.shape)))
+  B, Hs, Ws, _ = sem.shape
+  if H < 1 or W < 1 or H * W >= 1 << 31 or Hs * Ws >= 1 << 31 or B > OVERLAP_MAX_B:
+    raise rn.RecAttendError('%s: B=%d, %d x %d -> %d x %d (B <= %d, planes of 1 .. 2^31 - 1 pixels)' % (who, B, Hs, Ws, H, W, OVERLAP_MAX_B))
+  return H, W
+
+
+def sem_labels(sem, size):
+  """The label image of the pre-stage's semantic map (ra_sem_labels_u8): sem float32 [B,Hs,Ws,C] (channel 0 the background,
+  2 <= C <= 9), size = (H, W) -> uint8 [B,H,W].  Every channel is resized with the linear resample of sem_foreground /
+  instance_class_vote, the first maximum wins, channel 0 -> label 0, channel c >= 1 -> the id of CITYSCAPES_LABELS[c - 1]."""
+  H, W = _check_sem('sem_labels', sem, size)
+  B, Hs, Ws, Cc = sem.shape
+  labels = torch.empty((B, H, W), dtype=torch.uint8, device=sem.device)
+  check(rn.lib().ra_sem_labels_u8(ptr(sem), B, Hs, Ws, Cc, H, W, ptr(labels), rn.stream_ptr()), 'ra_sem_labels_u8')
+  return labels
+
+
+def pixel_confusion(pred, gt_ids, gt_labels=None, catalog=None, size=None, conf=None, names=None, check_status=True):
+  """evaluatePair of evalPixelLevelSemanticLabeling.py (:532-615) for B images (ra_pixel_confusion_u8 / _sem_f32).  pred: a
+  uint8 label tensor [B,H,W], or a float32 semantic map [B,Hs,Ws,C] together with size = (H, W) — then the prediction is
+  what sem_labels(pred, size) gives, evaluated inside the kernel.  gt_ids int32 [B,H,W]: *_gtFine_instanceIds.png values;
+  gt_labels uint8 [B,H,W]: *_gtFine_labelIds.png values, or None: id < 1000 ? id : id // 1000.  catalog: what
+  gt_instance_catalog(gt_ids) returned, built here when None.  conf: an int64 [34,34] device tensor that is ADDED to (a
+  fresh zero one when None).  Returns {'conf': that tensor, 'inst_tp', 'inst_cat_tp': int32 [B,MAX_GT] per catalogue slot,
+  'catalog'}.  An image with a ground-truth or predicted label above 33 raises RecAttendError naming it (names[b], else its
+  index), from one device-to-host copy of B status words; with check_status=False the words come back as 'status'
+  instead, and the pixels with such a label are in no cell of conf."""
+  who = 'pixel_confusion'
+  fused = isinstance(pred, torch.Tensor) and pred.dtype == torch.float32
+  if fused:
+    H, W = _check_sem(who, pred, size)
+  else:
+    _need_dev(pred, torch.uint8, 'pred (a uint8 label image, or a float32 semantic map with size=)')
+    if pred.dim() != 3 or min(pred.shape) < 1:
+      raise rn.RecAttendError('%s: pred must be [B,H,W], got %s' % (who, tuple(pred.shape)))
+    H, W = pred.shape[1:]
+    if size is not None and (int(size[0]), int(size[1])) != (H, W):
+      raise rn.RecAttendError('%s: size %r does not match the label image %s' % (who, tuple(size), tuple(pred.shape)))
+  B = pred.shape[0]
+  _need_cuda_i32(gt_ids, 'gt_ids')
+  if gt_labels is not None:
+    _need_dev(gt_labels, torch.uint8, 'gt_labels')
+  if tuple(gt_ids.shape) != (B, H, W) or (gt_labels is not None and tuple(gt_labels.shape) != (B, H, W)):
+    raise rn.RecAttendError('%s: pred %s (size %d x %d), gt_ids %s, gt_labels %s do not belong together' % (
+        who, tuple(pred.shape), H, W, tuple(gt_ids.shape), None if gt_labels is None else tuple(gt_labels.shape)))
+  if H * W >= 1 << 31 or B > OVERLAP_MAX_B:
+    raise rn.RecAttendError('%s: B=%d, H * W = %d (B <= %d, H * W < 2^31)' % (who, B, H * W, OVERLAP_MAX_B))
+  if conf is not None:
+    _need_dev(conf, torch.int64, 'conf')
+    if tuple(conf.shape) != (PIXEL_LABELS, PIXEL_LABELS):
+      raise rn.RecAttendError('%s: conf must be [%d,%d], got %s' % (who, PIXEL_LABELS, PIXEL_LABELS, tuple(conf.shape)))
+  if names is not None and len(names) != B:
+    raise rn.RecAttendError('%s: %d names for %d images' % (who, len(names), B))
+  if catalog is not None:
+    ids, count = catalog[0], catalog[2]
+    _need_cuda_i32(ids, 'catalog ids')
+    _need_cuda_i32(count, 'catalog count')
+    if tuple(ids.shape) != (B, MAX_GT) or tuple(count.shape) != (B,):
+      raise rn.RecAttendError('%s: gt_ids %s, catalog ids %s, count %s do not belong together' % (
+          who, tuple(gt_ids.shape), tuple(ids.shape), tuple(count.shape)))
+  else:
+    catalog = gt_instance_catalog(gt_ids, names=names)
+    ids, count = catalog[0], catalog[2]
+  dev = gt_ids.device
+  if conf is None:
+    conf = torch.zeros((PIXEL_LABELS, PIXEL_LABELS), dtype=torch.int64, device=dev)
+  n = rn.lib().ra_pixel_confusion_workspace_ints(B, H, W)
+  ws = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+  inst_tp = torch.empty((B, MAX_GT), dtype=torch.int32, device=dev)
+  inst_cat_tp = torch.empty((B, MAX_GT), dtype=torch.int32, device=dev)
+  status = torch.empty((B,), dtype=torch.int32, device=dev)
+  tail = (ptr(gt_ids), ptr(gt_labels), ptr(ids), ptr(count), B, H, W, ptr(ws), n, ptr(conf), ptr(inst_tp), ptr(inst_cat_tp),
+          ptr(status), rn.stream_ptr())
+  if fused:
+    _, Hs, Ws, Cc = pred.shape
+    check(rn.lib().ra_pixel_confusion_sem_f32(ptr(pred), Hs, Ws, Cc, *tail), 'ra_pixel_confusion_sem_f32')
+  else:
+    check(rn.lib().ra_pixel_confusion_u8(ptr(pred), *tail), 'ra_pixel_confusion_u8')
+  out = {'conf': conf, 'inst_tp': inst_tp, 'inst_cat_tp': inst_cat_tp, 'catalog': catalog}
+  if not check_status:
+    out['status'] = status
+    return out
+  _raise_pixel_status(status, names, who)
+  return out
+
+
+def _raise_pixel_status(status, names, who):
+  """The confusion kernel's status words [B] (a tensor: one device-to-host copy; or host values): the first image with one
+  set raises, named."""
+  for b, st in enumerate(status.cpu().tolist() if isinstance(status, torch.Tensor) else [int(v) for v in status]):
+    if st:
+      why = []
+      if st & rn.RA_PIXEL_STATUS_GT:
+        why.append('a ground-truth label above %d' % (PIXEL_LABELS - 1))
+      if st & rn.RA_PIXEL_STATUS_PRED:
+        why.append('a predicted label above %d' % (PIXEL_LABELS - 1))
+      raise rn.RecAttendError('%s: image %s has %s' % (who, names[b] if names is not None else b, ' and '.join(why)))
+
+
 # ---------------------------------------------------------------------------- evaluating the pre-stage fg_model
 FG_STAT_NAMES = ('inter_soft', 'sum_soft', 'sum_gt', 'inter_hard', 'sum_hard', 'seg_ce', 'ori_ce', 'ori_correct', 'mask')  # RA_FG_STAT_*
 FG_SWEEP_MAX_K = rn.RA_FG_SWEEP_MAX_K
