@@ -74,6 +74,12 @@ __device__ void gemv_rows(const float *v, int N, const float *__restrict__ W, in
 
 __host__ __device__ inline int max3(int a, int b, int c) { return a > b ? (a > c ? a : c) : (b > c ? b : c); }
 __host__ __device__ inline int va_floats(const Dims &d) { return max3(4 * d.hid, 2 * d.hid + d.G, 2 * d.mlp); }
+// The forward's reduction scratch serves two users: gemv_cols (at most 16 parts of N <= 4 hid partial sums) and
+// glimpse_readout (kThreads / Cf parts of Cf).  Below hid = 16 the read-out is the larger; from there on this is 16 * 4 hid.
+__host__ __device__ inline int red_floats(const Dims &d) {
+  const int gemv = 16 * 4 * d.hid, readout = (kThreads / d.Cf) * d.Cf;
+  return gemv > readout ? gemv : readout;
+}
 
 // Saved per (image, iteration), floats:  xh [Cf + hid] | act [4 hid] (i, f, o, u after their nonlinearities) |
 // c [hid] | z [(n_g - 1) hid] (the glimpse MLP's hidden layers after their ReLUs) | gm [G] (the map this iteration READ with).
@@ -95,8 +101,8 @@ __global__ __launch_bounds__(kThreads) void ctrl_fwd_kernel(const FwdArgs a) {
   extern __shared__ __attribute__((aligned(16))) float smem[];
   const Dims d = a.d;
   const int t = threadIdx.x, b = blockIdx.x, G = d.G, Cf = d.Cf, hid = d.hid;
-  float *red = smem;                         // 16 * 4 hid
-  float *xh = red + 16 * 4 * hid;            // [Cf + hid]
+  float *red = smem;                         // [red_floats]
+  float *xh = red + red_floats(d);           // [Cf + hid]
   float *cst = xh + Cf + hid;                // [hid]
   float *va = cst + hid;                     // [va_floats]: the gates; the MLPs' ping-pong buffers and logits
   float *gm = va + va_floats(d);             // [G]
@@ -351,7 +357,7 @@ using namespace ra;
 namespace {
 using ra::ctrlt::Dims;
 size_t fwd_lds_floats(const Dims &d) {
-  return (size_t)16 * 4 * d.hid + (d.Cf + d.hid) + d.hid + ra::ctrlt::va_floats(d) + d.G + (size_t)d.G * d.Cf;
+  return (size_t)ra::ctrlt::red_floats(d) + (d.Cf + d.hid) + d.hid + ra::ctrlt::va_floats(d) + d.G + (size_t)d.G * d.Cf;
 }
 size_t bwd_lds_floats(const Dims &d) {
   return (size_t)64 + 2 * d.hid + 4 * d.hid + (d.Cf + d.hid) + d.G + ra::ctrlt::max3(d.hid, d.G, d.mlp) + (d.hid > d.mlp ? d.hid : d.mlp) +

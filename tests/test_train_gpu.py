@@ -682,6 +682,115 @@ def test_attention_head_and_knob_vs_torch_autograd(cuda, flags):
   assert np.abs(gb.cpu().numpy() - 1.0 - bl.grad.numpy()).max() < 1e-4
 
 
+@pytest.mark.parametrize('B', [65, 130])
+def test_attention_head_and_knob_beyond_one_workgroup(cuda, B):
+  """AttnHead and KnobMix index images as blockIdx.x * 64 + threadIdx.x and the stacked step hands them T * B rows (128 at
+  cfg4): the construction of test_attention_head_and_knob_vs_torch_autograd at 65 and 130 images (a last workgroup of 1 and
+  of 2), for all 16 flag values, on a controller output of row stride 12 and a knob column of a [B, 3] tensor, with two
+  log-size inputs above 20 (softplus's linear branch under squash), one in the first workgroup and one past it, and each
+  upstream gradient absent in turn.  Scored per entry of every image at the bars of that test: 2e-5 forward, 5e-4 for d co."""
+  import ra_train
+  T, H, W, Fh, Fw = 4, 64, 96, 16, 16
+  g = torch.Generator().manual_seed(100 + B)
+  co_full = (torch.randn(B, 12, generator=g) * 0.7).double()
+  co_full[3, 2], co_full[B - 1, 3] = 25.0, 22.0
+  ctr_gt, size_gt = torch.rand(B, T, 2, generator=g).double() * 60, 10 + torch.rand(B, T, 2, generator=g).double() * 30
+  match = torch.nn.functional.one_hot(torch.randint(0, T, (B,), generator=g), T).double()
+  knob = (torch.rand(B, 3, generator=g) > 0.5).double()
+  assert 0 < knob[64:, 1].sum() < B - 64 or B == 65
+  dims, fdim = torch.tensor([H, W], dtype=torch.float64), torch.tensor([Fh, Fw], dtype=torch.float64)
+  names = ['cn', 'ls', 'ctr', 'size', 'lv', 'ag', 'bg', 'ylg', 'c2', 's2']
+  wts = {k: torch.randn(*((B,) if k in ('ag', 'bg', 'ylg') else (B, 2)), generator=g).double() for k in names}
+  f = lambda t: t.detach().float().to(cuda)
+  wts32 = {k: f(v) for k, v in wts.items()}
+  # the whole graph, then without each of the head's eight outputs (the knob left out of the loss: its backward would hand the
+  # head zeros for ctr and size, not an absent gradient), then the knob with one of its two upstream gradients
+  losses = [names] + [[k for k in names[:8] if k != drop] for drop in names[:8]] + [names[:8] + ['c2'], names[:8] + ['s2']]
+  worst = lambda a, b: ((a - b).abs() / b.abs().clamp(min=1.0)).max().item()  # every entry of every image on its own scale
+
+  for flags in range(16):
+    squash, fixed_var, dynamic_var, fixed_gamma = bool(flags & 1), bool(flags & 2), bool(flags & 4), bool(flags & 8)
+    cof = co_full.clone().requires_grad_(True)
+    co = cof[:, :9]
+    cn, ls = co[:, 0:2], co[:, 2:4]
+    if squash:
+      cn, ls = torch.tanh(cn), -torch.nn.functional.softplus(ls)
+    ctr, size = (cn + 1.0) * dims / 2.0, torch.exp(ls) * dims
+    lv = torch.zeros_like(ctr) if fixed_var else torch.log(size) - torch.log(fdim)
+    if dynamic_var:
+      lv = co[:, 4:6]
+    ag = torch.ones(B, dtype=torch.float64) if fixed_gamma else torch.exp(co[:, 6])
+    ylg = torch.full((B,), 2.0, dtype=torch.float64) if fixed_gamma else co[:, 8]
+    bg = torch.exp(co[:, 7])
+    kb = knob[:, 1:2]
+    ctr2 = kb * (match[:, :, None] * ctr_gt).sum(dim=1) + (1 - kb) * ctr
+    size2 = kb * (match[:, :, None] * size_gt).sum(dim=1) + (1 - kb) * size
+    ref = dict(zip(names, (cn, ls, ctr, size, lv, ag, bg, ylg, ctr2, size2)))
+
+    cof32 = f(co_full).requires_grad_(True)
+    co32 = cof32[:, :9]
+    assert co32.stride() == (12, 1)
+    out = ra_train.AttnHead.apply(co32, H, W, Fh, Fw, flags)
+    arec = out[8]
+    c2, s2, arec2 = ra_train.KnobMix.apply(out[2], out[3], f(match), f(ctr_gt), f(size_gt), f(knob)[:, 1], arec)
+    got = dict(zip(names, out[:8] + (c2, s2)))
+    with torch.no_grad():
+      want = ra_train.attn_record(got['ctr'], got['size'], got['lv'], attn_gamma=got['ag'], box_gamma=got['bg'], y_lg_gamma=got['ylg'])
+      assert torch.equal(arec, want) and torch.equal(arec2, ra_train.attn_record(c2, s2, got['lv'], attn_gamma=got['ag'], box_gamma=got['bg'],
+                                                                              y_lg_gamma=got['ylg']))
+    for k in names:
+      e = worst(got[k].detach().cpu().double(), ref[k].detach())
+      assert e < 2e-5, (flags, k, e)
+    for terms in losses:
+      gr, = torch.autograd.grad(sum((ref[k] * wts[k]).sum() for k in terms if ref[k].requires_grad), cof, retain_graph=True)
+      gd, = torch.autograd.grad(sum((got[k] * wts32[k]).sum() for k in terms), cof32, retain_graph=True)
+      assert (gd[:, 9:] == 0).all()
+      e = worst(gd.cpu().double(), gr)
+      assert e < 5e-4, (flags, sorted(set(names) - set(terms)), e)
+
+
+def test_pointwise_kernels_ragged_last_workgroup(cuda):
+  """LSTMCell at B * hid = 257 and 771 (one element, and three, past a 256-thread workgroup) and gaussian_filter at L * F = 333:
+  the references and bars of test_fused_pointwise_kernels_vs_torch_autograd, per image."""
+  import math
+  import ra_train
+  g = torch.Generator().manual_seed(14)
+  for B, hid in ((1, 257), (3, 257)):
+    pre = torch.randn(B, 4 * hid, generator=g).double().requires_grad_(True)
+    c0 = torch.randn(B, hid, generator=g).double().requires_grad_(True)
+    gi, gf, go, gu = [pre[:, k * hid:(k + 1) * hid] for k in range(4)]
+    c1 = torch.sigmoid(gf) * c0 + torch.sigmoid(gi) * torch.tanh(gu)
+    h1 = torch.sigmoid(go) * torch.tanh(c1)
+    wh, wc = torch.randn(B, hid, generator=g).double(), torch.randn(B, hid, generator=g).double()
+    p32, c32 = [t.detach().float().to(cuda).requires_grad_(True) for t in (pre, c0)]
+    h, c = ra_train.LSTMCell.apply(p32, c32)
+    assert np.abs(h.detach().cpu().numpy() - h1.detach().numpy()).max() < 1e-6
+    assert np.abs(c.detach().cpu().numpy() - c1.detach().numpy()).max() < 1e-6
+    for with_c in (True, False):  # c's gradient absent: the last glimpse of a timestep
+      ref = torch.autograd.grad((h1 * wh).sum() + ((c1 * wc).sum() if with_c else 0.0), (pre, c0), retain_graph=True)
+      got = torch.autograd.grad((h * wh.float().to(cuda)).sum() + ((c * wc.float().to(cuda)).sum() if with_c else 0.0), (p32, c32), retain_graph=True)
+      for a, b in zip(got, ref):
+        assert np.abs(a.cpu().numpy() - b.numpy()).max() < 1e-5, (B, with_c)
+  B, L, F = 3, 37, 9
+  ctr = (torch.rand(B, generator=g) * L).double().requires_grad_(True)
+  size = (5 + 20 * torch.rand(B, generator=g)).double().requires_grad_(True)
+  lgv = (torch.randn(B, generator=g) * 0.5).double().requires_grad_(True)
+  j = torch.arange(F, dtype=torch.float64)
+  mu = ctr[:, None] + ((size[:, None] + 1.0) / F) * (j[None, :] - (F - 1) / 2.0)
+  dd = torch.arange(L, dtype=torch.float64)[None, :, None] - mu[:, None, :]
+  var = torch.exp(lgv)[:, None, None]
+  ref = torch.exp(-0.5 * dd * dd / var) / (torch.sqrt(var) * math.sqrt(2 * math.pi))
+  wgt = torch.randn(B, L, F, generator=g).double()
+  (ref * wgt).sum().backward()
+  c32, s32, v32 = [t.detach().float().to(cuda).requires_grad_(True) for t in (ctr, size, lgv)]
+  out = ra_train.gaussian_filter(c32, s32, v32, L, F)
+  (out * wgt.float().to(cuda)).sum().backward()
+  assert np.abs(out.detach().cpu().numpy() - ref.detach().numpy()).max() < 1e-6
+  for a, b in ((c32, ctr), (s32, size), (v32, lgv)):
+    err = np.abs(a.grad.cpu().numpy() - b.grad.numpy()) / np.maximum(1.0, np.abs(b.grad.numpy()))
+    assert err.max() < 2e-4, err
+
+
 def test_training_graph_applies_the_augmentation(cuda):
   """full_model.py:203-232: img.random_transformation(x, padding, phase_train, ..., y=y_gt) sits in front of the
   training graph.  With the step's draws given (crop offset, flips, transpose), the product's loss equals the
@@ -959,13 +1068,16 @@ def test_fused_controller_equals_library_path(cuda, knob):
     assert np.abs(got - g).max() < 1e-3 * max(np.abs(g).max(), 1e-4 * scale), (k, np.abs(got - g).max(), np.abs(g).max())
 
 
-@pytest.mark.parametrize('n_g,n_c', [(2, 1), (1, 1), (3, 2), (4, 3)])
-def test_controller_fn_unit_vs_library(cuda, n_g, n_c):
+@pytest.mark.parametrize('n_g,n_c,hw', [(2, 1, 64), (1, 1, 64), (3, 2, 64), (4, 3, 64), (2, 1, 128)],
+                         ids=['2-1', '1-1', '3-2', '4-3', '2-1-128x128'])
+def test_controller_fn_unit_vs_library(cuda, n_g, n_c, hw):
   """ControllerFn alone: one timestep's controller on a random feature map, forward outputs and — for random upstream
   gradients of h and ctrl_out — d feat and every controller parameter's gradient, against the library-GEMM path; at the
-  run scripts' depths (2 glimpse-MLP layers, 1 controller-MLP layer) and at others (full_model.py:350-352,382-384)."""
+  run scripts' depths (2 glimpse-MLP layers, 1 controller-MLP layer) and at others (full_model.py:350-352,382-384).
+  At 128 x 128 (G = 16; 4 everywhere else) the parameter gradients are formed both ways _CtrlStepBuffers knows: the
+  project's short-K GEMM and the library's products."""
   import full_model
-  opt, P, x, y_gt, s_gt = _case(T=2, wmul=1.0, num_glimpse_mlp_layers=n_g, num_ctrl_mlp_layers=n_c, ctrl_mlp_dim=48)
+  opt, P, x, y_gt, s_gt = _case(H=hw, W=hw, T=2, wmul=1.0, num_glimpse_mlp_layers=n_g, num_ctrl_mlp_layers=n_c, ctrl_mlp_dim=48)
   rng = np.random.RandomState(2)
   for k in P:  # livelier controller weights than the 0.01 init: the softmax must not stay uniform
     if k.startswith(('ctrl_lstm_w', 'glimpse_mlp_w', 'ctrl_mlp_w')):
@@ -974,12 +1086,13 @@ def test_controller_fn_unit_vs_library(cuda, n_g, n_c):
       P[k] = (rng.randn(*P[k].shape) * 0.1).astype(np.float32)
   B = 3
   res = {}
-  for fused in (False, True):
+  for fused, own_gemm in [(False, True), (True, True)] + ([(True, False)] if hw == 128 else []):
     m = full_model.get_model(opt).load_weights(P)
     ts = ra_train.TrainStep(m)
-    ts.fuse_controller = fused
+    ts.fuse_controller, ts.own_gemm = fused, own_gemm
     d = ts.d
     assert (d['n_gmlp'], d['n_cmlp']) == (n_g, n_c) and (ts._ctrl_buffers(B, 64) is not None) == fused
+    assert d['G'] == (hw // 32) ** 2
     feat = torch.tensor(np.random.RandomState(4).rand(B, d['G'], 64).astype(np.float32), device=cuda, requires_grad=True)
     wh = torch.tensor(np.random.RandomState(5).randn(B, d['hid']).astype(np.float32), device=cuda)
     wc = torch.tensor(np.random.RandomState(6).randn(B, 9).astype(np.float32), device=cuda)
@@ -988,13 +1101,14 @@ def test_controller_fn_unit_vs_library(cuda, n_g, n_c):
     h, co = ts._controller(feat, 1)
     ((h * wh).sum() + (co * wc).sum()).backward()
     names = [k for k in ts.bucket.names if k.startswith(('ctrl_lstm', 'glimpse_mlp', 'ctrl_mlp'))]
-    res[fused] = (h.detach().cpu().numpy(), co.detach().cpu().numpy(), feat.grad.cpu().numpy(),
-                  {k: ts.bucket.grad_of[k].cpu().numpy().copy() for k in names})
-  (h0, c0, f0, g0), (h1, c1, f1, g1) = res[False], res[True]
-  assert np.abs(h1 - h0).max() < 2e-6 and np.abs(c1 - c0).max() < 2e-6 * max(1.0, np.abs(c0).max())
-  assert np.abs(f1 - f0).max() < 1e-5 * max(1.0, np.abs(f0).max()), np.abs(f1 - f0).max()
-  for k in g0:
-    assert np.abs(g1[k] - g0[k]).max() < 2e-5 * max(1.0, np.abs(g0[k]).max()), (k, np.abs(g1[k] - g0[k]).max(), np.abs(g0[k]).max())
+    res[fused, own_gemm] = (h.detach().cpu().numpy(), co.detach().cpu().numpy(), feat.grad.cpu().numpy(),
+                            {k: ts.bucket.grad_of[k].cpu().numpy().copy() for k in names})
+  h0, c0, f0, g0 = res.pop((False, True))
+  for h1, c1, f1, g1 in res.values():
+    assert np.abs(h1 - h0).max() < 2e-6 and np.abs(c1 - c0).max() < 2e-6 * max(1.0, np.abs(c0).max())
+    assert np.abs(f1 - f0).max() < 1e-5 * max(1.0, np.abs(f0).max()), np.abs(f1 - f0).max()
+    for k in g0:
+      assert np.abs(g1[k] - g0[k]).max() < 2e-5 * max(1.0, np.abs(g0[k]).max()), (k, np.abs(g1[k] - g0[k]).max(), np.abs(g0[k]).max())
 
 
 @pytest.mark.parametrize('dtype', ['float32', 'bf16'])
