@@ -1005,6 +1005,34 @@ int ra_fg_sweep_counts_f32(const float *src, const unsigned char *gt, int N, int
                            const float *thresholds, int K, unsigned long long *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Training the pre-stage fg_model (csrc/ra_fg_loss.hip).
+ *
+ * ra_fg_loss_bwd_f32 — the gradient of the loss head of fg_model.py:196-248 with respect to the logits [npix, nsc + no]; the
+ *   forward value is ra_fg_stats_f32.  y_gt [npix, nsc], d_gt [npix, no] (NULL when no == 0), nsc 1 .. 16, no 0 | 8,
+ *   segm_loss_fn 0 = iou (loss = -I / U over the whole batch, modellib.py:171-181) | 1 = bce (f_bce for nsc == 1, f_ce over all
+ *   channels otherwise, divided by npix; :221-233).  sums: the RA_FG_STAT_COUNT device doubles ra_fg_stats_f32 wrote for the
+ *   same tensors, read on the device (no host synchronisation).  upstream: dL/dloss.  With p = sigmoid(z) (nsc == 1) or
+ *   softmax(z[0:nsc]), evaluated with the expressions of ra_fg_head_f32, and eps = 1e-5 kept inside the logarithms
+ *   (modellib.py:418-427), so that the derivative is of log(p + eps):
+ *     bce   q = (-g / (p + eps) + (1 - g) / (1 - p + eps)) / npix        (nsc == 1);  q_c = -g_c / (p_c + eps) / npix  (nsc > 1)
+ *     iou   q = -(g U - I (1 - g)) / U^2, U = sum p + sum g - I + 1e-5; for nsc > 1 over the channels c >= 1, q_0 = 0 (:215)
+ *     dz = q p (1 - p)  (nsc == 1);   dz_c = p_c (q_c - sum_j p_j q_j)  (nsc > 1)
+ *   and for no == 8, with m = g (nsc == 1) or max over c >= 1 of g_c (:201-206), d = softmax(z[nsc:]), MASK = sum m:
+ *     q_k = -d_gt_k m / (d_k + eps) / MASK, then the same softmax adjoint (:235-240).
+ *   orientation_acc and the hard IoU carry no gradient.  When no == 8 and MASK == 0 the reference divides 0 by 0 and trains on
+ *   NaN; here the orientation logits' gradient is written as 0 and status[0] = 1 (else status[0] = 0), for the guarded
+ *   optimizer entries to skip the step.  dlogits [npix, nsc + no]; no floating-point atomics: the same bits on every run.
+ * ra_momentum_step_guarded_f32 — tf.train.MomentumOptimizer(lr, momentum) on one flat float32 bucket of n parameters
+ *   (fg_model.py:262-263): g = grads * grad_scale + wd_coef * params (wd_coef nullable), accum = momentum * accum + g,
+ *   params -= lr * accum; applied ONLY IF none of the n_status device words is non-zero (status nullable with n_status 0), the
+ *   contract of ra_adam_step_guarded_f32's n_other words.
+ * ---------------------------------------------------------------------------------- */
+int ra_fg_loss_bwd_f32(const float *logits, const float *y_gt, const float *d_gt, size_t npix, int nsc, int no,
+                       int segm_loss_fn, const double *sums, float upstream, float *dlogits, int *status, void *stream);
+int ra_momentum_step_guarded_f32(float *params, const float *grads, float *accum, const float *wd_coef, size_t n, float lr,
+                                 float momentum, float grad_scale, const int *status, int n_status, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Training step (full_model.py:1039-1057).
  * ra_adam_step_f32 — gradient clip + Adam on one flat float32 bucket of n parameters:
  *   g = clip(grads * grad_scale + wd_coef * params, -clip, clip)   (wd_coef nullable; the

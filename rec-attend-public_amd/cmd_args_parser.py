@@ -82,6 +82,33 @@ FG_EVAL_FLAGS = [  # EvalArgsParser + FGEvalArgsParser, cmd_args_parser.py:143-1
     ('model_id', _S, None), ('batch_size', _I, 32), ('results', _S, './results'), ('output', _S, None),
     ('split', _S, 'valid'), ('prefetch', _B, False), ('queue_size', _I, 50), ('num_worker', _I, 4),
 ]
+FG_MODEL_FLAGS = [  # FGModelArgsParser.add_args, fg_model_train.py:425-448 (the lists stay strings: make_fg_model_opt splits them)
+    ('cnn_filter_size', _S, '3,3,3,3,3,3,3,3,3,3'), ('cnn_depth', _S, '8,8,16,16,32,32,64,64,128,128'),
+    ('cnn_pool', _S, '1,2,1,2,1,2,1,2,1,2'), ('dcnn_filter_size', _S, '3,3,3,3,3,3,3,3,3,3,3'),
+    ('dcnn_depth', _S, '128,128,64,64,32,32,16,16,8,8,1'), ('dcnn_pool', _S, '2,1,2,1,2,1,2,1,2,1,1'),
+    ('add_skip_conn', _B, False), ('cnn_skip_mask', _S, '1,0,0,0,0,0,1,0,1,0'), ('dcnn_skip_mask', _S, '0,1,0,1,0,0,0,0,0,1'),
+    ('segm_loss_fn', _S, 'iou'), ('add_orientation', _B, False), ('num_orientation_classes', _I, 8),
+    ('num_semantic_classes', _I, 1), ('base_learn_rate', _F, 1e-3), ('learn_rate_decay', _F, 0.96),
+    ('steps_per_learn_rate_decay', _I, 5000), ('rnd_colour', _B, False), ('padding', _I, 16), ('optimizer', _S, 'adam'),
+]
+
+
+def make_fg_model_opt(args):
+  """args -> the model_opt dict of FGModelArgsParser.make_opt (fg_model_train.py:450-500): same keys, same quirks — the cnn
+  and dcnn filter sizes are 3 whatever the flags say, the flips and the transpose are off, weight_decay is 5e-5."""
+  ints = lambda s: [int(v) for v in s.split(',')]
+  mask = lambda s: [v == '1' for v in s.split(',')]
+  h, w, _ = INP_DIM[args.dataset]
+  cnn_depth, dcnn_depth = ints(args.cnn_depth), ints(args.dcnn_depth)
+  return {'inp_height': h, 'inp_width': w, 'inp_depth': 3, 'padding': args.padding,
+          'cnn_filter_size': [3] * len(cnn_depth), 'cnn_depth': cnn_depth, 'cnn_pool': ints(args.cnn_pool),
+          'cnn_skip_mask': mask(args.cnn_skip_mask), 'dcnn_filter_size': [3] * len(dcnn_depth), 'dcnn_depth': dcnn_depth,
+          'dcnn_pool': ints(args.dcnn_pool), 'dcnn_skip_mask': mask(args.dcnn_skip_mask), 'weight_decay': 5e-5, 'use_bn': True,
+          'segm_loss_fn': args.segm_loss_fn, 'rnd_hflip': False, 'rnd_vflip': False, 'rnd_transpose': False,
+          'rnd_colour': args.rnd_colour, 'add_skip_conn': args.add_skip_conn, 'base_learn_rate': args.base_learn_rate,
+          'learn_rate_decay': args.learn_rate_decay, 'steps_per_learn_rate_decay': args.steps_per_learn_rate_decay,
+          'add_orientation': args.add_orientation, 'num_orientation_classes': args.num_orientation_classes,
+          'num_semantic_classes': args.num_semantic_classes, 'optimizer': args.optimizer}
 
 
 def add_flags(parser, table):

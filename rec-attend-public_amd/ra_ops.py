@@ -1394,6 +1394,12 @@ def fg_statistics(logits, y_gt, d_gt, nsc, no):
   float64.  The hard quantities are taken on the logits ([logit > 0]; [logit == max logit], every maximum; the first maximum
   of the orientation logits), not on the rounded probabilities: the two agree in exact arithmetic, and float32 rounding of a
   softmax must not invent ties.  One device-to-host copy of nine doubles."""
+  return dict(zip(FG_STAT_NAMES, fg_stat_sums(logits, y_gt, d_gt, nsc, no).cpu().tolist()))
+
+
+def fg_stat_sums(logits, y_gt, d_gt, nsc, no):
+  """fg_statistics without the copy to the host: the RA_FG_STAT_COUNT sums as a float64 device tensor, in the order of
+  FG_STAT_NAMES (what ra_fg_loss_bwd_f32 reads)."""
   nsc, no = int(nsc), int(no)
   if not 1 <= nsc <= 16 or no not in (0, 8):
     raise rn.RecAttendError('fg_statistics: nsc %d (1 .. 16), no %d (0 | 8)' % (nsc, no))
@@ -1413,7 +1419,45 @@ def fg_statistics(logits, y_gt, d_gt, nsc, no):
   sums = torch.empty((len(FG_STAT_NAMES),), dtype=torch.float64, device=dev)
   check(rn.lib().ra_fg_stats_f32(ptr(logits), ptr(y_gt), ptr(d_gt), npix, nsc, no, ptr(ws), n, ptr(sums), rn.stream_ptr()),
         'ra_fg_stats_f32')
-  return dict(zip(FG_STAT_NAMES, sums.cpu().tolist()))
+  return sums
+
+
+FG_SEGM_LOSS_FN = {'iou': 0, 'bce': 1}  # segm_loss_fn of ra_fg_loss_bwd_f32 (fg_model.py:228-231)
+
+
+def fg_loss_backward(logits, y_gt, d_gt, nsc, no, segm_loss_fn, sums, upstream=1.0, status=None):
+  """dL/dlogits of the loss head of fg_model.py:196-248 (ra_fg_loss_bwd_f32): logits [..., nsc + no], y_gt [..., nsc] (or
+  [...] for nsc == 1), d_gt [..., 8] or None, segm_loss_fn 'iou' | 'bce', sums: the float64 device tensor fg_stat_sums gave for
+  the same tensors (read on the device).  Returns (dlogits, status): status is an int32 device tensor of one word, 1 when the
+  batch has orientation classes and no foreground pixel (the orientation gradient is then 0 and the guarded optimizer
+  entries skip the step), else 0; pass `status` to have it written in place."""
+  nsc, no = int(nsc), int(no)
+  if segm_loss_fn not in FG_SEGM_LOSS_FN:
+    raise rn.RecAttendError('fg_loss_backward: segm_loss_fn %r (iou | bce)' % (segm_loss_fn,))
+  if not 1 <= nsc <= 16 or no not in (0, 8):
+    raise rn.RecAttendError('fg_loss_backward: nsc %d (1 .. 16), no %d (0 | 8)' % (nsc, no))
+  if (d_gt is not None) != bool(no):
+    raise rn.RecAttendError('fg_loss_backward: d_gt goes with no = 8 and only with it (no = %d, d_gt %s)' % (
+        no, 'given' if d_gt is not None else 'missing'))
+  _need_cuda(logits, y_gt, d_gt)
+  if not sums.is_cuda:
+    raise rn.RecAttendError('fg_loss_backward: sums must stay on the device (fg_stat_sums); there is no CPU path')
+  if logits.dim() < 1 or logits.shape[-1] != nsc + no or logits.numel() == 0:
+    raise rn.RecAttendError('fg_loss_backward: logits %s for nsc %d + no %d channels' % (tuple(logits.shape), nsc, no))
+  npix = logits.numel() // (nsc + no)
+  if y_gt.numel() != npix * nsc or (no and d_gt.numel() != npix * no):
+    raise rn.RecAttendError('fg_loss_backward: logits %s, y_gt %s, d_gt %s do not belong together' % (
+        tuple(logits.shape), tuple(y_gt.shape), None if d_gt is None else tuple(d_gt.shape)))
+  if sums.dtype != torch.float64 or sums.numel() != len(FG_STAT_NAMES) or not sums.is_contiguous():
+    raise rn.RecAttendError('fg_loss_backward: sums must be the %d float64 values of fg_stat_sums' % len(FG_STAT_NAMES))
+  if status is None:
+    status = torch.empty((1,), dtype=torch.int32, device=logits.device)
+  elif status.dtype != torch.int32 or status.numel() < 1 or not status.is_cuda:
+    raise rn.RecAttendError('fg_loss_backward: status must be an int32 device tensor')
+  dlogits = torch.empty_like(logits)
+  check(rn.lib().ra_fg_loss_bwd_f32(ptr(logits), ptr(y_gt), ptr(d_gt), npix, nsc, no, FG_SEGM_LOSS_FN[segm_loss_fn], ptr(sums),
+                                    C.c_float(float(upstream)), ptr(dlogits), ptr(status), rn.stream_ptr()), 'ra_fg_loss_bwd_f32')
+  return dlogits, status
 
 
 def _sweep_thresholds(thresholds):
