@@ -1160,6 +1160,57 @@ int ra_bn_act_pool_bwd_dx_f32(const float *u, const float *dy, const float *mean
 #define RA_BN_FORM_V4 2
 #define RA_BN_FORM_GENERIC 3
 int ra_bn_form(int pass, int C, int B, int H, int W, int pool, int flags, int stages, int G);
+/* Training the WIDE layers of fg_model (fg_model.py:112-160 trained by :249-265; nnlib.cnn nnlib.py:229-253 and nnlib.dcnn
+ * nnlib.py:362-400 with phase_train = True): the train-mode pieces above for the channel counts K1-wide runs, Cout 129 .. 512
+ * (a multiple of 16) and Cin <= 1024 (a multiple of 4) = ra_conv_wide_supported(Cin, Cout).  Float32 storage only.  The
+ * forward is ra_conv3x3_wide_f32 with scale = 1, shift = bias, no ReLU, no pool; its data gradient is the same kernel on the
+ * flipped, in/out-swapped packing.  New entries beside the narrow ones: none of those changes what it answers.
+ *   ra_conv_wide_pack_weights_dev  ra_conv_wide_pack_weights on DEVICE pointers (weights change every step), restricted to the
+ *                                  output channels [co_first, co_first + co_count) of the filter: out = the host pack of that
+ *                                  slice, bit for bit, ra_conv_wide_packed_floats(Cin, co_count) floats; co_count obeys
+ *                                  the wide range.  A data gradient of more than 512 channels is two ranges.  chan_map: device,
+ *                                  nullable; an entry outside [0, Cin_w) packs zeros.
+ *   ra_conv3x3_wgrad_wide_acc_f32  ra_conv3x3_wgrad_acc_f32 for the wide range (csrc/ra_wgrad_wide.hip): gw += dW in the reference
+ *                                  layout of the filter that ran, gb += db (nullable), one writer per element, no atomics,
+ *                                  fixed order.  Output-stationary on v_mfma_f32_16x16x4_f32, the pixels (K) split over
+ *                                  workgroups and summed by a second pass.  ws: ra_conv3x3_wgrad_wide_workspace_floats(Cin,
+ *                                  Cout, B, H, W) floats, H, W = the conv's map (twice x's with upsample).
+ *   ra_conv3x3_wgrad_wide_plan     the one chooser's answer for x [B,H,W,Cin] (host only, launches nothing): rec receives
+ *                                  RA_WGW_PLAN_INTS ints, indexed by RA_WGW_PLAN_*: the workgroup's ci x co block and pixel tile
+ *                                  side, taps per workgroup, grid (ci blocks, co blocks, K split), pixel tiles per part and in
+ *                                  all, static LDS bytes, workspace floats.  RA_E_SHAPE where the launch would refuse.
+ *   ra_bn_wide_*                   nnlib.py:98-119,250-253 as ra_bn_moments_f32 / ra_bn_act_pool_f32 /
+ *                                  ra_bn_act_pool_bwd_acc_f32 with the same arithmetic, for any C % 4 == 0, C <= 512
+ *                                  (csrc/ra_bn_wide.hip: a thread owns a channel quad of one pooling window, C / 4 need not be
+ *                                  a power of two); ws: ra_bn_wide_workspace_floats(C) floats.  Else RA_E_SHAPE, no launch. */
+#define RA_WGW_PLAN_INTS 12
+#define RA_WGW_PLAN_TILE_CI 0
+#define RA_WGW_PLAN_TILE_CO 1
+#define RA_WGW_PLAN_TILE_PIX 2
+#define RA_WGW_PLAN_TAPS 3
+#define RA_WGW_PLAN_GRID_CI 4
+#define RA_WGW_PLAN_GRID_CO 5
+#define RA_WGW_PLAN_SPLIT 6
+#define RA_WGW_PLAN_TILES_PER_PART 7
+#define RA_WGW_PLAN_NTILES 8
+#define RA_WGW_PLAN_LDS 9
+#define RA_WGW_PLAN_WS_FLOATS 10
+int ra_conv_wide_pack_weights_dev(const float *w, int Cin_w, int Cout, int Cin, const int *chan_map, int flags, int co_first,
+                                  int co_count, float *out, void *stream);
+size_t ra_conv3x3_wgrad_wide_workspace_floats(int Cin, int Cout, int B, int H, int W);
+int ra_conv3x3_wgrad_wide_acc_f32(const float *x, int Cin, int B, int Hs, int Ws, int upsample, const float *du, int Cout,
+                                  float *ws, size_t ws_floats, const int *chan_map, int cin_w, int transposed, float *gw,
+                                  float *gb, void *stream);
+int ra_conv3x3_wgrad_wide_plan(int Cin, int Cout, int B, int H, int W, int upsample, int *rec);
+size_t ra_bn_wide_workspace_floats(int C);
+int ra_bn_wide_moments_f32(const float *u, size_t npix, int C, float *ws, size_t ws_floats, float *mean, float *var,
+                           void *stream);
+int ra_bn_wide_act_pool_f32(const float *u, const float *mean, const float *var, const float *gamma, const float *beta,
+                            float eps, int relu, int pool, int B, int H, int W, int C, float *y, void *stream);
+int ra_bn_wide_act_pool_bwd_acc_f32(const float *u, const float *dy, const float *mean, const float *var, const float *gamma,
+                                    const float *beta, float eps, int relu, int pool, int B, int H, int W, int C, float *ws,
+                                    size_t ws_floats, float *dgamma, float *dbeta, float *du, float *acc_gamma,
+                                    float *acc_beta, void *stream);
 /* The pointwise half of the controller's LSTM cell (nnlib.py:641-646; the GEMM half is a library call):
  * pre [B][4*hid] = gate pre-activations in the order (i, f, o, u), c_prev [B][hid]:
  *   c = sigm(f) c_prev + sigm(i) tanh(u),  h = sigm(o) tanh(c);  act [B][4*hid] keeps the gate values.

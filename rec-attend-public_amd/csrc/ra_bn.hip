@@ -12,10 +12,10 @@
 #include <type_traits>
 
 #include "ra_common.h"
+#include "ra_bn_parts.h"
 
 namespace ra {
 namespace train {
-typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int kRedBlocks = 512;  // partial sums per channel that a reduction leaves for its finishing launch, at most
 constexpr int kMaxC = 256;       // channels of the moments and of the per-call backward (a finishing workgroup per channel)
@@ -29,9 +29,6 @@ constexpr size_t kSmallElems = 65536;  // per group
 // once per pixel, the per-channel constants hoisted (the grid stride is a multiple of C / 4, so a
 // thread's channel group never changes).  The generic kernels below moved 0.5 TB/s.
 // Summation order is fixed (no atomics): bit-reproducible.
-struct BnConst {
-  f32x4 mu, g, be, rstd;
-};
 // Storage of a channel quad: float32 (16 bytes) or, in the bf16 mode's tensors between the conv layers' passes
 // (model_opt['compute_dtype'] = 'bf16'), bf16 (8 bytes; loads are exact, stores round to nearest even as v_cvt_pk_bf16_f32).
 typedef unsigned u32x2q __attribute__((ext_vector_type(2)));
@@ -56,19 +53,6 @@ struct Q4<true> {
                   __builtin_bit_cast(unsigned, __builtin_convertvector(f32x2{v.z, v.w}, bf16x2))};
   }
 };
-__device__ inline BnConst bn_const(const float *mean, const float *var, const float *gamma, const float *beta, float eps,
-                                   int c0) {
-  BnConst k;
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    const float rstd = var ? rsqrtf(var[c0 + i] + eps) : 1.f;
-    k.rstd[i] = rstd;
-    k.g[i] = (gamma ? gamma[c0 + i] : 1.f) * rstd;
-    k.mu[i] = mean ? mean[c0 + i] : 0.f;
-    k.be[i] = beta ? beta[c0 + i] : 0.f;
-  }
-  return k;
-}
 // sum over the threads of a workgroup that share (tid % C4); valid in threads tid < C4.  C4 = 1 << lg <= 64.
 __device__ inline float sum_by_group(float v, int C4, float *red) {
   for (int off = 32; off >= C4; off >>= 1) v += __shfl_xor(v, off, 64);
@@ -147,30 +131,6 @@ __global__ __launch_bounds__(256) void bn_act_pool_v4_kernel(const typename Q4<U
         }
         Q4<YB>::st(y, ((row0 + r) * Wo + xo) * C4 + cg, best);
       }
-  }
-}
-
-// dv of every pixel of the window (dy routed to the FIRST maximum, masked by the ReLU) and xhat
-template <int POOL>
-__device__ inline void window_grad(const f32x4 (&w)[POOL * POOL], const f32x4 dyv, const BnConst &k, float lo, int relu,
-                                   f32x4 (&dv)[POOL * POOL], f32x4 (&xh)[POOL * POOL]) {
-#pragma unroll
-  for (int i = 0; i < 4; ++i) {
-    float best = -__builtin_inff();
-    int arg = 0;
-    float v[POOL * POOL];
-#pragma unroll
-    for (int q = 0; q < POOL * POOL; ++q) {
-      xh[q][i] = (w[q][i] - k.mu[i]) * k.rstd[i];
-      v[q] = (w[q][i] - k.mu[i]) * k.g[i] + k.be[i];
-      const float a = fmaxf(v[q], lo);
-      if (a > best) {
-        best = a;
-        arg = q;
-      }
-    }
-#pragma unroll
-    for (int q = 0; q < POOL * POOL; ++q) dv[q][i] = (q == arg && !(relu && v[q] <= 0.f)) ? dyv[i] : 0.f;
   }
 }
 

@@ -251,6 +251,30 @@ __global__ __launch_bounds__(256) void fg_head(const HeadArgs a) {
   }
 }
 
+// ra_conv_wide_pack_weights on the device, for the output channels [co_first, co_first + co_count) of the filter: one thread per
+// packed float, the host loop's index arithmetic.  nslice / nchunk are those of the packed slice (Cin, co_count).
+__global__ __launch_bounds__(256) void pack_wide_kernel(const float *w, int Cin_w, int Cout, int Cin, const int *chan_map, int tr,
+                                                        int co_first, int co_count, int nchunk, size_t total, float *out) {
+  const size_t e = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (e >= total) return;
+  size_t r = e;
+  const int cg = r & 3;
+  r >>= 2;
+  const int n = r % NS;
+  r /= NS;
+  const int ksub = r & 3;
+  r >>= 2;
+  const int tap = r % 9;
+  r /= 9;
+  const int ch = r % nchunk, s = (int)(r / nchunk);
+  const int c = ch * CK + 4 * cg + ksub, col = s * NS + n, co = co_first + col, ky = tap / 3, kx = tap % 3;
+  float v = 0.f;
+  const int src_c = c < Cin ? (chan_map ? chan_map[c] : c) : -1;
+  if (col < co_count && src_c >= 0 && src_c < Cin_w)
+    v = tr ? w[(((size_t)(2 - ky) * 3 + (2 - kx)) * Cout + co) * Cin_w + src_c] : w[(((size_t)ky * 3 + kx) * Cin_w + src_c) * Cout + co];
+  out[e] = v;
+}
+
 }  // namespace convw
 }  // namespace ra
 
@@ -293,6 +317,20 @@ extern "C" int ra_conv_wide_pack_weights(const float *w, int Cin_w, int Cout, in
               out[(((((size_t)s * nchunk + ch) * 9 + tap) * 4 + ksub) * convw::NS + n) * 4 + cg] = v;
             }
   return 0;
+}
+
+extern "C" int ra_conv_wide_pack_weights_dev(const float *w, int Cin_w, int Cout, int Cin, const int *chan_map, int flags, int co_first,
+                                             int co_count, float *out, void *stream) {
+  if (!w || !out || Cin_w <= 0 || Cout <= 0 || co_first < 0 || co_count <= 0)
+    return fail(RA_E_INVALID, "ra_conv_wide_pack_weights_dev: bad argument");
+  if (!ra_conv_wide_supported(Cin, co_count))
+    return fail(RA_E_SHAPE, "ra_conv_wide_pack_weights_dev: Cin %d (%% 4, <= 1024) or co_count %d (129 .. 512, %% 16)", Cin, co_count);
+  if (co_first + co_count > Cout) return fail(RA_E_SHAPE, "ra_conv_wide_pack_weights_dev: channels [%d, %d) of %d", co_first, co_first + co_count, Cout);
+  if (!chan_map && Cin_w != Cin) return fail(RA_E_SHAPE, "ra_conv_wide_pack_weights_dev: Cin_w != Cin without map");
+  const size_t total = ra_conv_wide_packed_floats(Cin, co_count);
+  hipLaunchKernelGGL(convw::pack_wide_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, as_stream(stream), w, Cin_w, Cout, Cin,
+                     chan_map, (flags & RA_CONV_TRANSPOSED) ? 1 : 0, co_first, co_count, ceil_div(Cin, convw::CK), total, out);
+  return launch_status("ra_conv_wide_pack_weights_dev");
 }
 
 extern "C" int ra_conv3x3_wide_f32(const float *src0, int C0, const float *src1, int C1, int B, int Hs, int Ws, int upsample,

@@ -1,7 +1,11 @@
 #!/usr/bin/env python
 """Entry point with the flag surface of the reference's fg_model_train.py (:425-448 + TrainArgsParser + DataArgsParser):
 trains the pre-stage fg_model — step two of run_kitti.sh / run_cityscapes.sh, between the label stage and fg_model_pack.py —
-for nets whose layers have up to 128 output channels (ra_fg_train.FgTrainStep; wider nets are refused by name).
+by default for nets whose layers have up to 128 output channels (ra_fg_train.FgTrainStep; wider nets are refused by name).
+--train_wide opts into the wide path (layers of up to 512 output channels, inputs of up to 1024: the nets of run_kitti.sh and
+run_cityscapes.sh); the flag is saved in model_opt.yaml as train_wide, so that --restore continues on the same path, and
+fg_model_pack.py / fg_model_eval.py ignore it.  It is a flag and not the default because the suite pins the default's refusals
+(ra_fg_train's docstring).
 
 --input is an .npz with x [N,h,w,3], y_gt [N,h,w] or [N,h,w,nsc] and, with --add_orientation, d_gt [N,h,w,8]: exactly what
 `setup_labels.py --target fg_model` writes.  Batch k takes the images (k * batch_size + i) % N.  --valid_input (optional, the
@@ -33,12 +37,16 @@ def build_parser():
   p.add_argument('--input', default=None, help='.npz with x, y_gt (+ d_gt with --add_orientation)')
   p.add_argument('--valid_input', default=None, help='.npz of the same layout, scored every --steps_per_valid steps')
   p.add_argument('--seed', type=int, default=1234)
+  p.add_argument('--train_wide', action='store_true', help='train layers of more than 128 channels (float32, uncaptured; '
+                 'ra_fg_train.FgTrainStep(model, wide=True))')
   return p
 
 
 def make_opt(args):
   opt = cap.make_fg_model_opt(args)
   opt['seed'] = int(args.seed)
+  if getattr(args, 'train_wide', False):  # only when asked for: without the flag model_opt.yaml is what it was
+    opt['train_wide'] = True
   return opt
 
 
@@ -99,7 +107,7 @@ def main(argv=None):
   model = fg_model.get_model(model_opt)
   if restore:
     model.load_weights(dict(np.load(os.path.join(restore, 'weights.npz'))))
-  trainer = ra_fg_train.FgTrainStep(model)  # refuses what is not built, and a machine without a device, before any data is read
+  trainer = ra_fg_train.FgTrainStep(model, wide=bool(model_opt.get('train_wide', False)))  # refuses what is not built, and a machine without a device, before any data is read
   if restore:
     trainer.load_state_dict(dict(np.load(os.path.join(restore, 'optimizer.npz'))))
     print('restored %s at global_step %d' % (restore, trainer.bucket.global_step))

@@ -181,7 +181,7 @@ def _check_train_filter_sizes(f, what):
                          (what, list(f), ops.FILTER_SIZES))
 
 
-WIDE_COUT = 128  # K1 serves up to 128 output channels; wider 3x3 layers run the wide kernel (ops.conv_wide), eval only
+WIDE_COUT = 128  # K1 serves up to 128 output channels; wider 3x3 layers run the wide kernel (ops.conv_wide): at eval here, in training through ra_fg_train.FgTrainStep(model, wide=True)
 
 
 def _check_wide_layers(f, ch, what):

@@ -1,5 +1,7 @@
-"""Training the pre-stage fg_model (fg_model.py:94-266 of the reference) for nets whose layers have up to 128 output
-channels: `FgTrainStep(model)` is to `fg_model.Model` what `ra_train.TrainStep(model)` is to `full_model`.
+"""Training the pre-stage fg_model (fg_model.py:94-266 of the reference): `FgTrainStep(model)` is to `fg_model.Model` what
+`ra_train.TrainStep(model)` is to `full_model`.  By default for nets whose layers have up to 128 output channels; with
+`FgTrainStep(model, wide=True)` also the nets the reference's run scripts train, layers of up to 512 output channels and
+inputs (previous map + skip) of up to 1024.
 
   model = fg_model.get_model(opt)
   step = FgTrainStep(model)                 # parameters become views of one flat bucket
@@ -16,9 +18,21 @@ momentum 0.9 (:262-263) on the bucket.  The weight-decay terms wd * l2_loss(w) o
 The stack does not go through the nnlib.cnn / nnlib.dcnn closures: fg_model.get_model builds them for eval, and they hold
 the weight tensors they were created with.  sync_model() copies the bucket's values into those tensors.
 
-Not built, refused by name in the constructor: a layer of more than 128 output channels (the wide filter-gradient kernel and
-BatchNorm forms for 129 - 512 channels), a dcnn layer whose input (previous map + skip) has more than 128 channels (its data
-gradient is a conv of that many outputs), dcnn filter sizes other than 3, the step as one captured HIP graph, several ranks.
+The wide path is OPT-IN, and the flag is not a tuning knob: the suite pins the default trainer's refusals of wide nets
+(tests/test_fg_train.py), so without `wide=True` every check answers as it did before the wide kernels existed.  With it a layer
+of more than 128 output channels, or of more than 128 input channels, runs as a WideConvBNActPool node: K1-wide forward
+(ra_conv3x3_wide_f32, previous map and skip as two sources, no concat), ra_bn_wide_* BatchNorm, the output-stationary filter
+gradient ra_conv3x3_wgrad_wide_acc_f32, and a data gradient per source through K1-wide on a device pack of that source's
+output-channel range (ra_conv_wide_pack_weights_dev).  The wide path is float32 and uncaptured, and has been measured on
+synthetic data only.
+
+Not built, refused by name in the constructor: without wide=True, a layer of more than 128 output channels or a dcnn layer
+whose input (previous map + skip) has more than 128 channels; with it, a wide layer with a filter size other than 3, more than
+128 output channels that are no multiple of 16 or exceed 512, a source of a wide layer that is no multiple of 4 channels, a
+source of more than 128 channels that K1-wide cannot produce as a data gradient (no multiple of 16, or more than 512),
+compute_dtype = 'bf16'; always: dcnn filter sizes other than 3, the step as one captured HIP graph, several ranks.  Stride-2
+wide layers run the full-resolution conv of the zero-stuffed map and ra_subsample_odd_f32, as the narrow ones do: the
+sub-pixel form is not built.
 """
 import ctypes as C
 import math
@@ -98,12 +112,17 @@ def _layers(d):
   return out
 
 
-def check_options(opt, d):
+WIDE_HINT = '; FgTrainStep(model, wide=True) / fg_model_train.py --train_wide takes the opt-in wide path'
+
+
+def check_options(opt, d, wide=False):
   """The constructor's refusals that need no device and no library: raised before anything else happens."""
-  wide = [c for c in d['cnn_channels'][1:] + d['dcnn_channels'][1:] if c > nn.WIDE_COUT]
-  if wide:
+  over = [c for c in d['cnn_channels'][1:] + d['dcnn_channels'][1:] if c > nn.WIDE_COUT]
+  if over and not wide:
     raise rn.RecAttendError('fg_model: training with layers of %s output channels is not built (up to %d; eval decodes 3x3 '
-                            'layers of up to 512)' % (wide, nn.WIDE_COUT))
+                            'layers of up to 512)%s' % (over, nn.WIDE_COUT, WIDE_HINT))
+  if wide and opt.get('compute_dtype', 'float32') == 'bf16':
+    raise rn.RecAttendError("fg_model: the wide training path is float32; compute_dtype = 'bf16' is not built for it")
   if any(f != 3 for f in d['dcnn_filter_size']):
     raise rn.RecAttendError('fg_model: training with dcnn_filter_size %s is not built (3x3 only; eval decodes any of %s)' %
                             (list(d['dcnn_filter_size']), ops.FILTER_SIZES))
@@ -124,14 +143,68 @@ def check_options(opt, d):
                             'not built)' % world)
 
 
-def check_kernel_forms(d):
+def _layer_sources(d, scope, i):
+  """Channels of the layer's sources: [previous map] or [previous map, skip map]."""
+  if scope == 'cnn':
+    return [d['cnn_channels'][i]]
+  sk = d['dcnn_skip_ch'][i] if d['dcnn_skip_ch'] else 0
+  return [d['dcnn_channels'][i]] + ([sk] if sk else [])
+
+
+def _runs_wide(cin_w, cout):
+  """With wide=True a layer runs as a WideConvBNActPool node when its output or its input is beyond K1's 128 channels."""
+  return cout > nn.WIDE_COUT or cin_w > nn.WIDE_COUT
+
+
+def _check_wide_layer(lib, d, scope, i, cin_w, cout, what):
+  """check_kernel_forms for a layer that runs as a WideConvBNActPool node: the new plan / support queries instead of a refusal."""
+  pad4 = lambda c: -(-c // 4) * 4
+  sources = _layer_sources(d, scope, i)
+  ups = int(scope == 'dcnn' and d['dcnn_pool'][i] == 2)
+  fs = d['%s_filter_size' % scope][i]
+  if fs != 3:
+    raise rn.RecAttendError('%s: filter size %d: layers of more than %d input or output channels are trained with 3x3 filters only' %
+                            (what, fs, nn.WIDE_COUT))
+  cx = sum(pad4(c) for c in sources)
+  if cout > nn.WIDE_COUT:
+    if cout % 16 or cout > 512:
+      raise rn.RecAttendError('%s: a layer of more than %d output channels needs a multiple of 16, up to 512' % (what, nn.WIDE_COUT))
+    if any(c % 4 for c in sources):
+      raise rn.RecAttendError('%s: the sources of a wide layer (%s channels) must be multiples of 4' % (what, sources))
+    if not lib.ra_conv_wide_supported(cx, cout):
+      raise rn.RecAttendError('%s: the wide conv takes inputs of up to 1024 channels, got %d' % (what, cx))
+    rec = (C.c_int * rn.RA_WGW_PLAN_INTS)()
+    for c in sources:
+      if lib.ra_conv3x3_wgrad_wide_plan(c, cout, 1, 16, 16, ups, rec) != 0:
+        raise rn.RecAttendError('%s: the wide filter gradient refuses the shape: %s' % (what, (lib.ra_last_error_string() or b'').decode()))
+  else:  # a narrow layer behind a wide input: K1 and the narrow filter gradient, as without the flag
+    if not lib.ra_conv_cout_padded(cout) or not lib.ra_conv_packed_floats(cx, cout):
+      raise rn.RecAttendError('%s: no conv / filter-gradient kernel form for these channel counts' % what)
+    rec = (C.c_int * rn.RA_PLAN_INTS)()
+    if lib.ra_conv3x3_plan(cx, 0, 1, 16, 16, ups, 3, cout, 1, 0, 0, 0, 0, rec) == rn.RA_E_SHAPE:
+      raise rn.RecAttendError('%s: the forward conv refuses the shape: %s' % (what, (lib.ra_last_error_string() or b'').decode()))
+  if not (scope == 'cnn' and i == 0):  # the data gradient: one conv per source, of that source's channels
+    for c in sources:
+      ok = lib.ra_conv_wide_supported(pad4(cout), c) if c > nn.WIDE_COUT else lib.ra_conv_packed_floats(pad4(cout), c)
+      if not ok:
+        raise rn.RecAttendError('%s: the data gradient towards a source of %d channels is a conv of that many output channels: '
+                                'beyond %d they must be a multiple of 16, up to 512' % (what, c, nn.WIDE_COUT))
+
+
+def check_kernel_forms(d, wide=False):
   """Every layer's channel counts against the kernels' own host-side argument checks (forward conv, data gradient, filter
-  gradient, BatchNorm), on a nominal 16 x 16 map: a count a kernel form refuses is named here, not in the middle of a step."""
+  gradient, BatchNorm), on a nominal 16 x 16 map: a count a kernel form refuses is named here, not in the middle of a step.
+  wide: the opt-in wide path (the module docstring says why it is a flag) admits up to 512 output and 1024 input channels."""
   lib = rn.lib()
   rec = (C.c_int * rn.RA_PLAN_INTS)()
   pad4 = lambda c: -(-c // 4) * 4
   for scope, i, cin_w, cout, bn in _layers(d):
     what = 'fg_model: %s layer %d (%d -> %d channels)' % (scope, i, cin_w, cout)
+    if wide and _runs_wide(cin_w, cout):
+      _check_wide_layer(lib, d, scope, i, cin_w, cout, what)
+      if cout <= nn.WIDE_COUT:  # a narrow layer behind a wide input keeps the narrow BatchNorm kernels; ra_bn_wide_* take any wide count
+        _check_bn_forms(lib, d, scope, i, cout, what)
+      continue
     cx = pad4(cin_w) if scope == 'cnn' else _dcnn_packed_width(d, i)
     ups = int(scope == 'dcnn' and d['dcnn_pool'][i] == 2)
     mom = int(bn and cout % 4 == 0)
@@ -143,11 +216,16 @@ def check_kernel_forms(d):
       if not lib.ra_conv_packed_floats(pad4(cout), cin_w) or \
           lib.ra_conv3x3_plan(pad4(cout), 0, 1, 16, 16, 0, 3, cin_w, 1, 0, 0, 0, 0, rec) == rn.RA_E_SHAPE:
         raise rn.RecAttendError('%s: training a layer whose input — the previous map plus its skip — has %d channels is not '
-                                'built: its data gradient is a conv of that many output channels (up to %d)' % (what, cin_w, nn.WIDE_COUT))
-    pool = d['cnn_pool'][i] if scope == 'cnn' else 1
-    for ps in (rn.RA_BN_PASS_MOMENTS, rn.RA_BN_PASS_FORWARD, rn.RA_BN_PASS_BACKWARD):
-      if lib.ra_bn_form(ps, cout, 1, 16, 16, pool, 0, 3, 0) < 0:
-        raise rn.RecAttendError('%s: no BatchNorm kernel form for %d channels' % (what, cout))
+                                'built: its data gradient is a conv of that many output channels (up to %d)%s' %
+                                (what, cin_w, nn.WIDE_COUT, WIDE_HINT))
+    _check_bn_forms(lib, d, scope, i, cout, what)
+
+
+def _check_bn_forms(lib, d, scope, i, cout, what):
+  pool = d['cnn_pool'][i] if scope == 'cnn' else 1
+  for ps in (rn.RA_BN_PASS_MOMENTS, rn.RA_BN_PASS_FORWARD, rn.RA_BN_PASS_BACKWARD):
+    if lib.ra_bn_form(ps, cout, 1, 16, 16, pool, 0, 3, 0) < 0:
+      raise rn.RecAttendError('%s: no BatchNorm kernel form for %d channels' % (what, cout))
 
 
 def _dcnn_packed_width(d, i):
@@ -157,19 +235,191 @@ def _dcnn_packed_width(d, i):
   return pad4(d['dcnn_channels'][i]) + (pad4(sk) if sk else 0)
 
 
+def _source_maps(c0, C0, c1, C1, dev):
+  """Kernel channel -> filter row for a layer whose kernel input is [x0 (C0 channels, c0 real) | x1 (C1, c1 real)] and whose
+  filter has c0 + c1 input rows: (the whole input's map, x0's, x1's) as int32 device tensors; None where the kernels' default
+  (channel c is row c) says the same."""
+  m0 = list(range(c0)) + [-1] * (C0 - c0)
+  m1 = [c0 + m for m in range(c1)] + [-1] * (C1 - c1)
+  t = lambda m: rt._const('cmap', tuple(m), dev, lambda: torch.tensor(m, dtype=torch.int32, device=dev))
+  whole = None if (C0 == c0 and C1 == c1) else t(m0 + m1)
+  return whole, (None if (C0 == c0 and not C1) else t(m0)), (t(m1) if C1 else None)
+
+
+def _ones_zeros(n, dev):
+  return (rt._const('ones', n, dev, lambda: torch.ones(n, dtype=torch.float32, device=dev)),
+          rt._const('zeros', n, dev, lambda: torch.zeros(n, dtype=torch.float32, device=dev)))
+
+
+def _source_dgrad(duc, w, tr, stride, first, n, x_shape, cout, cache):
+  """The data gradient towards ONE source of a layer: the conv kernel on the flipped, in/out-swapped packing of the filter's
+  input rows [first, first + n) — K1-wide on a device pack of that output-channel range beyond 128 channels, K1 up to there —
+  then, for a stride-2 layer, the odd positions of the full-resolution result.  duc [B,H,W,cd]: du, channels padded to % 4."""
+  B, Hs, Ws, Cs = x_shape
+  dev, cd = duc.device, duc.shape[3]
+  pm = rt._pad_map(cout, cd, dev)
+  wd = w.detach()
+  if n > nn.WIDE_COUT:
+    key = ('wide-dgrad', w.data_ptr(), w._version, first, n)
+    hit = cache.get(key)
+    if hit is None:  # the filter read with rows and columns swapped: cout input rows, the source's n of the cin_w output columns
+      hit = cache[key] = (w, ops.pack_wide_weights_dev(wd, cin_kernel=cd, chan_map=pm, transposed=not tr, co_first=first, co_count=n))
+    ones, zeros = _ones_zeros(n, dev)
+    dxr = ops.conv_wide(duc, hit[1], ones, zeros, n, relu=False, pool=1)
+  else:
+    whole = first == 0 and n == (w.shape[3] if tr else w.shape[2])
+    ws = wd if whole else (wd[:, :, :, first:first + n] if tr else wd[:, :, first:first + n, :]).contiguous()
+    ones, zeros = _ones_zeros(ops.cout_padded(n), dev)
+    dxr = ops.conv3x3(duc, rt._pack_dev(ws, cout, n, cd, pm, not tr, cache), ones, zeros, n, relu=False, pool=1)
+  if stride == 2:
+    sub = rt._f(B, Hs, Ws, n, device=dev)
+    check(rn.lib().ra_subsample_odd_f32(ptr(dxr), B, Hs, Ws, n, ptr(sub), rn.stream_ptr()), 'ra_subsample_odd_f32')
+    dxr = sub
+  if Cs != n:  # padding channels of the source
+    dx = torch.zeros((B, Hs, Ws, Cs), dtype=torch.float32, device=dev)
+    dx[..., :n] = dxr
+    return dx
+  return dxr
+
+
+class WideConvBNActPool(torch.autograd.Function):
+  """ra_train.ConvBNActPool's contract for a layer of nnlib.cnn (nnlib.py:229-253) or nnlib.dcnn (nnlib.py:362-400) beyond K1's
+  128 channels, on either side, in training mode.  float32.
+
+  x0 [B,Hs,Ws,C0] the previous map and x1 [B,Hs,Ws,C1] the skip map or None (each % 4; concat(x0, x1) is never formed), w in the
+  reference layout ([3,3,Cin,Cout]; transposed: [3,3,Cout,Cin]) whose input rows are meta['c0'] of x0's channels followed by
+  meta['c1'] of x1's, b [Cout], gamma / beta [Cout] or None.  meta: transposed, stride, pool, relu, c0, c1, cache, and grads =
+  (gw, gb, ggamma, gbeta) views of a gradient bucket, which then receive the parameter gradients inside the kernels.
+  Returns (y, batch mean, batch var); backward returns a gradient per source.  A constant number of launches per layer:
+    Cout > 128   K1-wide, ra_bn_wide_*, ra_conv3x3_wgrad_wide_acc_f32 (once per source, through a channel map)
+    Cout <= 128  K1, ra_bn_*, ra_conv3x3_wgrad_acc_f32 (likewise): only the data gradient is wide
+  and the data gradient per source by _source_dgrad."""
+
+  @staticmethod
+  def forward(ctx, x0, x1, w, b, gamma, beta, meta):
+    ctx.set_materialize_grads(False)
+    dev = x0.device
+    x0 = x0.contiguous()
+    x1 = None if x1 is None else x1.contiguous()
+    B, Hs, Ws, C0 = x0.shape
+    C1 = 0 if x1 is None else x1.shape[3]
+    tr, stride, pool, relu = meta['transposed'], meta['stride'], meta['pool'], meta['relu']
+    cout, cin_w = (w.shape[2], w.shape[3]) if tr else (w.shape[3], w.shape[2])
+    c0, c1 = meta['c0'], meta.get('c1', 0)
+    if c0 + c1 != cin_w or c0 > C0 or c1 > C1 or tuple(w.shape[:2]) != (3, 3):
+      raise rn.RecAttendError('WideConvBNActPool: a 3x3 filter of %d input rows for sources of %d (of %d) + %d (of %d) channels' %
+                              (cin_w, c0, C0, c1, C1))
+    cache = meta.get('cache')
+    cache = rt._PACK if cache is None else cache
+    whole, _, _ = _source_maps(c0, C0, c1, C1, dev)
+    use_bn = gamma is not None
+    lib = rn.lib()
+    mean = var = None
+    if cout > nn.WIDE_COUT:
+      key = ('wide', w.data_ptr(), w._version, C0, C1, bool(tr))
+      hit = cache.get(key)
+      if hit is None:
+        hit = cache[key] = (w, ops.pack_wide_weights_dev(w.detach().contiguous(), cin_kernel=C0 + C1, chan_map=whole, transposed=tr))
+      ones, _ = _ones_zeros(cout, dev)
+      u = ops.conv_wide(x0, hit[1], ones, b.detach(), cout, relu=False, pool=1, src1=x1, upsample=(stride == 2))
+      if use_bn:
+        mean, var = ops.bn_wide_moments(u)
+      y = ops.bn_wide_act_pool(u, mean, var, gamma, beta, relu=relu, pool=pool)
+    else:
+      cp = ops.cout_padded(cout)
+      ones, _ = _ones_zeros(cp, dev)
+      shift = b.detach() if cp == cout else torch.nn.functional.pad(b.detach(), (0, cp - cout))
+      wp = rt._pack_dev(w.contiguous(), cin_w, cout, C0 + C1, whole, tr, cache)
+      u = ops.conv3x3(x0, wp, ones, shift, cout, relu=False, pool=1, src1=x1, upsample=(stride == 2))
+      _, H, W, _ = u.shape
+      if use_bn:
+        mean, var = rt._f(cout, device=dev), rt._f(cout, device=dev)
+        ws = rt._f(lib.ra_bn_workspace_floats(cout), device=dev)
+        check(lib.ra_bn_moments_f32(ptr(u), B * H * W, cout, ptr(ws), ws.numel(), ptr(mean), ptr(var), rn.stream_ptr()), 'ra_bn_moments_f32')
+      y = rt._f(B, H // pool, W // pool, cout, device=dev)
+      check(lib.ra_bn_act_pool_f32(ptr(u), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(ops.BN_EPS), int(relu), int(pool), B, H, W,
+                                   cout, ptr(y), rn.stream_ptr()), 'ra_bn_act_pool_f32')
+    ctx.meta, ctx.cache = meta, cache
+    ctx.save_for_backward(x0, x1, w, u, mean, var, gamma, beta)
+    if use_bn:
+      ctx.mark_non_differentiable(mean, var)
+      return y, mean, var
+    z = torch.zeros(0, device=dev)
+    ctx.mark_non_differentiable(z)
+    return y, z, z
+
+  @staticmethod
+  def backward(ctx, dy, _dm, _dv):
+    if dy is None:
+      return None, None, None, None, None, None, None
+    x0, x1, w, u, mean, var, gamma, beta = ctx.saved_tensors
+    meta, cache = ctx.meta, ctx.cache
+    dev = x0.device
+    tr, stride, pool, relu = meta['transposed'], meta['stride'], meta['pool'], meta['relu']
+    B, Hs, Ws, C0 = x0.shape
+    C1 = 0 if x1 is None else x1.shape[3]
+    _, H, W, cout = u.shape
+    cin_w = w.shape[3] if tr else w.shape[2]
+    c0, c1 = meta['c0'], meta.get('c1', 0)
+    _, m0, m1 = _source_maps(c0, C0, c1, C1, dev)
+    dy = dy.contiguous()
+    lib = rn.lib()
+    grads = meta.get('grads')  # views of the flat gradient bucket: the kernels add to them; else fresh tensors are returned
+    if grads is not None:
+      gw, gb, gg, gbt = grads
+    else:
+      gw, gb, gg, gbt = torch.zeros_like(w), torch.zeros(cout, dtype=torch.float32, device=dev), None, None
+    wide = cout > nn.WIDE_COUT
+    ups = int(stride == 2)
+    # ---- BatchNorm / ReLU / pool, then the filter gradient of the SAME conv that ran, source by source (gb once)
+    if wide:
+      du, dgamma, dbeta = ops.bn_wide_act_pool_bwd(u, dy, mean, var, gamma, beta, relu=relu, pool=pool, acc_gamma=gg, acc_beta=gbt)
+      wws = None
+      for xs, ms in ((x0, m0), (x1, m1)):
+        if xs is not None:
+          n = lib.ra_conv3x3_wgrad_wide_workspace_floats(xs.shape[3], cout, B, H, W)
+          wws = wws if wws is not None and wws.numel() >= n else rt._f(n, device=dev)
+          ops.wgrad_wide_acc(xs, du, gw, gb if xs is x0 else None, chan_map=ms, transposed=tr, upsample=bool(ups), ws=wws)
+    else:
+      du, dgamma, dbeta = torch.empty_like(u), rt._f(cout, device=dev), rt._f(cout, device=dev)
+      ws = rt._f(lib.ra_bn_workspace_floats(cout), device=dev)
+      check(lib.ra_bn_act_pool_bwd_acc_f32(ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(ops.BN_EPS), int(relu),
+                                           int(pool), B, H, W, cout, ptr(ws), ws.numel(), ptr(dgamma), ptr(dbeta), ptr(du), ptr(gg), ptr(gbt),
+                                           rn.stream_ptr()), 'ra_bn_act_pool_bwd_acc_f32')
+      for xs, ms in ((x0, m0), (x1, m1)):
+        if xs is not None:
+          nws = lib.ra_conv3x3_wgrad_workspace_floats(xs.shape[3], cout, B, H, W)
+          wws = rt._f(nws, device=dev)
+          check(lib.ra_conv3x3_wgrad_acc_f32(ptr(xs), xs.shape[3], B, Hs, Ws, ups, ptr(du), cout, ptr(wws), nws, ptr(ms), int(cin_w), int(tr),
+                                             ptr(gw), ptr(gb if xs is x0 else None), rn.stream_ptr()), 'ra_conv3x3_wgrad_acc_f32')
+    # ---- the data gradient, one conv per source
+    dx = [None, None]
+    if any(ctx.needs_input_grad[:2]):
+      duc = rt._pad_channels(du)
+      for s, (xs, first, n) in enumerate(((x0, 0, c0), (x1, c0, c1))):
+        if xs is not None and ctx.needs_input_grad[s]:
+          dx[s] = _source_dgrad(duc, w, tr, stride, first, n, tuple(xs.shape), cout, cache)
+    use_bn = gamma is not None
+    if grads is not None:
+      return dx[0], dx[1], None, None, None, None, None
+    return dx[0], dx[1], gw, gb, (dgamma if use_bn else None), (dbeta if use_bn else None), None
+
+
 class FgTrainStep(object):
   """model.run(['loss', 'train_step'], feed{x, y_gt, d_gt, phase_train=True}) of the reference's fg trainer
   (fg_model_train.py:101-108)."""
 
-  def __init__(self, model):
+  def __init__(self, model, wide=False):
+    """wide: the opt-in path for layers of more than 128 output or input channels (the module docstring)."""
     self.model, self.opt, self.d = model, model.opt, model.dims
+    self.wide = bool(wide)
     d = self.d
-    check_options(self.opt, d)
+    check_options(self.opt, d, wide=self.wide)
     import torch.distributed as dist
     if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
       raise rn.RecAttendError('fg_model: the trainer runs in a single process; WORLD_SIZE = %d (data-parallel fg training is '
                               'not built)' % dist.get_world_size())
-    check_kernel_forms(d)
+    check_kernel_forms(d, wide=self.wide)
     if not torch.cuda.is_available():
       raise rn.RecAttendError('fg_model: the training step needs an MI355X (HIP device); there is no CPU fallback')
     self.nsc, self.no = d['nsc'], d['no']
@@ -246,15 +496,19 @@ class FgTrainStep(object):
     f32 = lambda t: t.to(dtype=torch.float32).contiguous()
     return f32(x), f32(y_gt).reshape(B, H, W, nsc), f32(d_gt) if no else None
 
-  def _layer(self, x, scope, i, bn, meta, stats):
+  def _layer(self, x, scope, i, bn, meta, stats, skip=None):
+    """skip: the layer runs as a WideConvBNActPool node on (x, skip), two sources, instead of ConvBNActPool on one packed input."""
     P = self.leaves
     key = '%s_%d_0' % (scope, i)
     g = self.bucket.grad_of
     if bn and torch.is_grad_enabled():  # the layer's parameter gradients accumulate in the bucket inside the kernels
       meta['grads'] = (g['%s_w_%d' % (scope, i)], g['%s_b_%d' % (scope, i)], g[key + '_gamma'], g[key + '_beta'])
     meta['cache'] = self._pack
-    y, mean, var = rt.ConvBNActPool.apply(x, P['%s_w_%d' % (scope, i)], P['%s_b_%d' % (scope, i)],
-                                          P[key + '_gamma'] if bn else None, P[key + '_beta'] if bn else None, meta)
+    params = (P['%s_w_%d' % (scope, i)], P['%s_b_%d' % (scope, i)], P[key + '_gamma'] if bn else None, P[key + '_beta'] if bn else None)
+    if 'c0' in meta:
+      y, mean, var = WideConvBNActPool.apply(x, skip, *params, meta)
+    else:
+      y, mean, var = rt.ConvBNActPool.apply(x, *params, meta)
     if bn:
       stats[key] = (mean, var)
     return y
@@ -266,11 +520,20 @@ class FgTrainStep(object):
     maps, h = [x], x
     for i in range(len(d['cnn_filter_size'])):
       meta = dict(transposed=False, stride=1, pool=d['cnn_pool'][i], relu=True, chan_map=None)
+      if self.wide and _runs_wide(d['cnn_channels'][i], d['cnn_channels'][i + 1]):
+        meta.update(c0=h.shape[3], c1=0)
       h = self._layer(rt._pad_channels(h), 'cnn', i, d['use_bn'], meta, stats)
       maps.append(h)
     nd = len(d['dcnn_filter_size'])
     for i in range(nd):
       cmap, src = None, d['skip_src'][i]
+      last = i == nd - 1  # no BatchNorm and no activation on the last layer (fg_model.py:130,155)
+      if self.wide and _runs_wide(d['dcnn_in_ch'][i], d['dcnn_channels'][i + 1]):  # previous map and skip as two sources
+        sk = maps[src] if src is not None else None
+        meta = dict(transposed=True, stride=d['dcnn_pool'][i], pool=1, relu=not last, c0=h.shape[3], c1=sk.shape[3] if sk is not None else 0)
+        h = self._layer(rt._pad_channels(h), 'dcnn', i, d['use_bn'] and not last, meta, stats,
+                        skip=rt._pad_channels(sk) if sk is not None else None)
+        continue
       if src is not None:  # concat(prev, skip) (nnlib.py:365) as one packed input; chan_map sends each packed channel to its filter row
         sk, prev_c = maps[src], h.shape[3]
         hp, skp = rt._pad_channels(h), rt._pad_channels(sk)
@@ -279,7 +542,6 @@ class FgTrainStep(object):
         if cmap == list(range(len(cmap))):
           cmap = None
         h = torch.cat([hp, skp], dim=3)
-      last = i == nd - 1  # no BatchNorm and no activation on the last layer (fg_model.py:130,155)
       meta = dict(transposed=True, stride=d['dcnn_pool'][i], pool=1, relu=not last, chan_map=cmap)
       h = self._layer(rt._pad_channels(h), 'dcnn', i, d['use_bn'] and not last, meta, stats)
     return h

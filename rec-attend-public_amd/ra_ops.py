@@ -370,6 +370,113 @@ def conv_wide(src0, wp, scale, shift, cout, relu=True, pool=1, src1=None, upsamp
   return out
 
 
+# ---- training the wide layers (csrc/ra_wgrad_wide.hip, ra_bn_wide.hip; ra_fg_train.WideConvBNActPool)
+
+
+def pack_wide_weights_dev(w, cin_kernel=None, chan_map=None, transposed=False, co_first=0, co_count=None):
+  """pack_wide_weights on the device (the weights change every step), for the output channels [co_first, co_first + co_count)
+  of the filter: w [3,3,Ci,Co] (transposed: [3,3,Co,Ci]) a device tensor, chan_map an int32 device tensor or None -> the
+  packed slice, bit-equal to the host pack of w's slice.  With `transposed` toggled and Ci / Co swapped by the caller it is the
+  data gradient's packing."""
+  _need_cuda(w)
+  if w.dim() != 4 or tuple(w.shape[:2]) != (3, 3):
+    raise rn.RecAttendError('filter of shape %r: wide layers are built for 3x3 filters only' % (tuple(w.shape),))
+  cin_w, cout = (w.shape[3], w.shape[2]) if transposed else (w.shape[2], w.shape[3])
+  cin = cin_w if cin_kernel is None else int(cin_kernel)
+  co_count = cout - co_first if co_count is None else int(co_count)
+  if chan_map is None and cin != cin_w:
+    raise rn.RecAttendError('pack_wide_weights_dev: a kernel input of %d channels for %d filter rows needs a chan_map' % (cin, cin_w))
+  if chan_map is not None and not (chan_map.is_cuda and chan_map.dtype == torch.int32 and chan_map.numel() == cin):
+    raise rn.RecAttendError('pack_wide_weights_dev: chan_map must be an int32 device tensor of %d entries' % cin)
+  n = rn.lib().ra_conv_wide_packed_floats(cin, co_count)
+  if n == 0:
+    raise rn.RecAttendError('unsupported wide conv shape Cin=%d Cout=%d (Cin %% 4, <= 1024; Cout 129 .. 512, %% 16)' % (cin, co_count))
+  out = torch.empty(n, dtype=torch.float32, device=w.device)
+  check(rn.lib().ra_conv_wide_pack_weights_dev(ptr(w), int(cin_w), int(cout), cin, ptr(chan_map), rn.RA_CONV_TRANSPOSED if transposed else 0,
+                                               int(co_first), co_count, ptr(out), rn.stream_ptr()), 'ra_conv_wide_pack_weights_dev')
+  return out
+
+
+_WGW_FIELDS = sorted((v, k[len('RA_WGW_PLAN_'):].lower()) for k, v in rn.CONSTANTS.items() if k.startswith('RA_WGW_PLAN_') and k != 'RA_WGW_PLAN_INTS')
+
+
+def wgrad_wide_plan(cin, cout, B, Hs, Ws, upsample=False):
+  """The launch the wide filter gradient takes for x [B,Hs,Ws,cin] and cout output channels (ra_conv3x3_wgrad_wide_plan: host
+  only): {'tile_ci', 'tile_co', 'tile_pix', 'taps', 'grid_ci', 'grid_co', 'split', 'tiles_per_part', 'ntiles', 'lds', 'ws_floats'}."""
+  rec = (C.c_int * rn.RA_WGW_PLAN_INTS)()
+  check(rn.lib().ra_conv3x3_wgrad_wide_plan(int(cin), int(cout), int(B), int(Hs), int(Ws), int(bool(upsample)), rec), 'ra_conv3x3_wgrad_wide_plan')
+  return {name: rec[i] for i, name in _WGW_FIELDS}
+
+
+def wgrad_wide_acc(x, du, gw, gb=None, chan_map=None, transposed=False, upsample=False, ws=None):
+  """gw += the filter gradient of the wide 3x3 conv that ran on x [B,Hs,Ws,Cin] and produced du's tensor [B,H,W,Cout], gb += the
+  bias gradient (None: not wanted).  gw in the reference layout: [3,3,cin_w,Cout], transposed: [3,3,Cout,cin_w] with flipped
+  taps; chan_map (int32 device tensor, or None) sends kernel channel c to filter row chan_map[c], -1 = padding.  ws: a
+  workspace to reuse (at least ra_conv3x3_wgrad_wide_workspace_floats floats)."""
+  _need_cuda(x, du, gw, gb, ws)
+  B, Hs, Ws, cin = x.shape
+  H, W, cout = du.shape[1:]
+  up = 2 if upsample else 1
+  if tuple(du.shape[:3]) != (B, Hs * up, Ws * up):
+    raise rn.RecAttendError('wgrad_wide_acc: x of %r and du of %r' % (tuple(x.shape), tuple(du.shape)))
+  cin_w = gw.shape[3] if transposed else gw.shape[2]
+  if tuple(gw.shape) != ((3, 3, cout, cin_w) if transposed else (3, 3, cin_w, cout)) or (gb is not None and gb.numel() != cout):
+    raise rn.RecAttendError('wgrad_wide_acc: gw of %r / gb for %d output channels' % (tuple(gw.shape), cout))
+  if chan_map is not None and not (chan_map.is_cuda and chan_map.dtype == torch.int32 and chan_map.numel() == cin):
+    raise rn.RecAttendError('wgrad_wide_acc: chan_map must be an int32 device tensor of %d entries' % cin)
+  n = rn.lib().ra_conv3x3_wgrad_wide_workspace_floats(cin, cout, B, H, W)
+  if n == 0:
+    raise rn.RecAttendError('wgrad_wide_acc: unsupported shape Cin=%d Cout=%d (Cin %% 4, <= 1024; Cout 129 .. 512, %% 16)' % (cin, cout))
+  if ws is None or ws.numel() < n:
+    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+  check(rn.lib().ra_conv3x3_wgrad_wide_acc_f32(ptr(x), cin, B, Hs, Ws, int(bool(upsample)), ptr(du), cout, ptr(ws), ws.numel(), ptr(chan_map),
+                                               int(cin_w), int(bool(transposed)), ptr(gw), ptr(gb), rn.stream_ptr()),
+        'ra_conv3x3_wgrad_wide_acc_f32')
+  return gw
+
+
+def _bn_wide_ws(C_, device, ws):
+  n = rn.lib().ra_bn_wide_workspace_floats(int(C_))
+  return ws if ws is not None and ws.numel() >= n else torch.empty(n, dtype=torch.float32, device=device)
+
+
+def bn_wide_moments(u, ws=None):
+  """(mean, var) [C] of u [..., C] over every other axis, biased (tf.nn.moments, nnlib.py:98): any C % 4 == 0 up to 512."""
+  _need_cuda(u, ws)
+  C_ = u.shape[-1]
+  mean, var = (torch.empty(C_, dtype=torch.float32, device=u.device) for _ in range(2))
+  ws = _bn_wide_ws(C_, u.device, ws)
+  check(rn.lib().ra_bn_wide_moments_f32(ptr(u), u.numel() // C_, C_, ptr(ws), ws.numel(), ptr(mean), ptr(var), rn.stream_ptr()),
+        'ra_bn_wide_moments_f32')
+  return mean, var
+
+
+def bn_wide_act_pool(u, mean, var, gamma, beta, relu=True, pool=1, out=None):
+  """y = max_pool(relu?(gamma (u - mean) rsqrt(var + 1e-3) + beta)) for u [B,H,W,C], C % 4 == 0 up to 512; mean / var / gamma /
+  beta None together: y = pool(relu?(u))."""
+  _need_cuda(u, mean, var, gamma, beta, out)
+  B, H, W, C_ = u.shape
+  if out is None:
+    out = torch.empty((B, H // pool, W // pool, C_), dtype=torch.float32, device=u.device)
+  check(rn.lib().ra_bn_wide_act_pool_f32(ptr(u), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(BN_EPS), int(relu), int(pool), B, H, W,
+                                         C_, ptr(out), rn.stream_ptr()), 'ra_bn_wide_act_pool_f32')
+  return out
+
+
+def bn_wide_act_pool_bwd(u, dy, mean, var, gamma, beta, relu=True, pool=1, acc_gamma=None, acc_beta=None, ws=None):
+  """The backward of bn_wide_act_pool with the batch statistics differentiated through -> (du, dgamma, dbeta); acc_gamma /
+  acc_beta (views of a gradient bucket, or None) receive += dgamma / dbeta in the kernel."""
+  _need_cuda(u, dy, mean, var, gamma, beta, acc_gamma, acc_beta, ws)
+  B, H, W, C_ = u.shape
+  du = torch.empty_like(u)
+  dgamma, dbeta = (torch.empty(C_, dtype=torch.float32, device=u.device) for _ in range(2))
+  ws = _bn_wide_ws(C_, u.device, ws)
+  check(rn.lib().ra_bn_wide_act_pool_bwd_acc_f32(ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(BN_EPS), int(relu),
+                                                 int(pool), B, H, W, C_, ptr(ws), ws.numel(), ptr(dgamma), ptr(dbeta), ptr(du),
+                                                 ptr(acc_gamma), ptr(acc_beta), rn.stream_ptr()), 'ra_bn_wide_act_pool_bwd_acc_f32')
+  return du, dgamma, dbeta
+
+
 def fg_head(logits, nsc, no, quantise=False, y_out=None, d_out=None, x=None, packed=None, canvas_plane=None):
   """The head of fg_model: logits [B,H,W,nsc+no] -> (y_out [B,H,W,nsc], d_out [B,H,W,no] or None); quantise: the 8-bit
   round trip floor(v * 255) / 255.  packed [B,H,W,Cp] (with x [B,H,W,D]): the decode engine's packed input image is
