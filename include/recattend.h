@@ -39,7 +39,7 @@ extern "C" {
  * bump it).  101 = round 3's removal of the table-form attention entry points and the phase-fused patch net; 102-113 =
  * rounds 3-5 (signature changes of the controller / conv entry points as the kernels were rebuilt; `git log -p
  * include/recattend.h` has each).  ra_native.py refuses a library whose version differs from the header it was written against. */
-#define RA_ABI_VERSION 113
+#define RA_ABI_VERSION 114
 int ra_version(void);
 /* Human-readable description of the last non-zero return on this thread. */
 const char *ra_last_error_string(void);
@@ -1123,6 +1123,41 @@ int ra_conv3x3_wgrad_multi_acc_f32(const void *const *xtab, const void *const *d
                                    int Hs, int Ws, int upsample, int Cout, float *ws, size_t ws_floats,
                                    const int *chan_map, int cin_w, int transposed, float *gw, float *gb,
                                    int bf16_operands, void *stream);
+/* Training nnlib.cnn / nnlib.dcnn layers of filter size KF in {1, 5, 7} (nnlib.py:131-257, :260-404; csrc/ra_wgrad_kxk.hip).
+ * ra_convkxk_wgrad_f32 / _acc_f32: ra_conv3x3_wgrad_f32 / _acc_f32 with KF taps, for the SAME conv ra_convkxk_f32 ran:
+ *   dW[ky][kx][ci][co] = sum_{b,y,x} X[b,y+ky-p,x+kx-p,ci] dU[b,y,x,co], db[co] = sum dU; X zero-padded, p = KF / 2; with
+ *   upsample X is the zero-stuffed image of the stride-2 transposed conv under the forward's window for that KF.  dw
+ *   [KF,KF,Cin,Cout]; the accumulate entry adds to gw in the reference layout ([KF,KF,Cin_w,Cout], or transposed: taps
+ *   flipped, [KF,KF,Cout,Cin_w]; chan_map: device, nullable) and to gb (nullable).  f32 MFMA, the taps' rows split over the
+ *   grid, per-workgroup partial records and a fixed-order finishing launch: no atomics, two runs give the same bits.  The
+ *   caller owns ws (ra_convkxk_wgrad_workspace_floats(KF, Cin, Cout, B, H, W) floats, H, W = the conv's map: twice x's with
+ *   upsample); nothing is allocated or synchronised.  KF = 3 forwards to the 3x3 entries; another KF, Cin % 4 != 0 or
+ *   Cout > 128 return RA_E_SHAPE (the workspace query: 0) without a launch.
+ * ra_convkxk_wgrad_plan: the chooser's answer for KF in {1, 5, 7} (host only, launches nothing): rec receives
+ *   RA_WGK_PLAN_INTS ints indexed by RA_WGK_PLAN_*.  The one variable of the launch form is NT, the 16-channel tiles of Cout
+ *   per workgroup: 1 for Cout <= 16, else 2.
+ * ra_conv_pack_weights_k_dev: ra_conv_pack_weights_k on device pointers (weights change every step).
+ * ra_subsample_even_f32: y[b,i,j,:] = x[b,2i,2j,:], x [B,2H,2W,C]: the data gradient of a stride-2 transposed layer of
+ *   filter size 1 (dx[i] = du[2i] w; the centred windows of KF = 3, 5, 7 sit on 2i + 1: ra_subsample_odd_f32). */
+#define RA_WGK_PLAN_INTS 8
+#define RA_WGK_PLAN_NT 0
+#define RA_WGK_PLAN_GRID_X 1
+#define RA_WGK_PLAN_GRID_Y 2
+#define RA_WGK_PLAN_GRID_Z 3
+#define RA_WGK_PLAN_LDS_BYTES 4
+#define RA_WGK_PLAN_RECORD_FLOATS 5
+#define RA_WGK_PLAN_NTILES 6
+#define RA_WGK_PLAN_ACC_TILES 7
+size_t ra_convkxk_wgrad_workspace_floats(int KF, int Cin, int Cout, int B, int H, int W);
+int ra_convkxk_wgrad_plan(int KF, int Cin, int Cout, int B, int H, int W, int *rec);
+int ra_convkxk_wgrad_f32(const float *x, int Cin, int B, int Hs, int Ws, int upsample, const float *du, int Cout, int KF,
+                         float *ws, size_t ws_floats, float *dw, float *db, void *stream);
+int ra_convkxk_wgrad_acc_f32(const float *x, int Cin, int B, int Hs, int Ws, int upsample, const float *du, int Cout, int KF,
+                             float *ws, size_t ws_floats, const int *chan_map, int Cin_w, int transposed, float *gw, float *gb,
+                             void *stream);
+int ra_conv_pack_weights_k_dev(const float *w, int KF, int Cin_w, int Cout, int Cin, const int *chan_map, int flags, float *out,
+                               void *stream);
+int ra_subsample_even_f32(const float *x, int B, int H, int W, int C, float *y, void *stream);
 int ra_bn_act_pool_bwd_acc_f32(const float *u, const float *dy, const float *mean, const float *var,
                                const float *gamma, const float *beta, float eps, int relu, int pool,
                                int B, int H, int W, int C, float *ws, size_t ws_floats, float *dgamma,

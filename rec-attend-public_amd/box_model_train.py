@@ -40,18 +40,29 @@ def build_parser():
   p.add_argument('--input', default=None, help='.npz with x and y_gt, s_gt or gt_instance_ids (default: synthetic batches)')
   p.add_argument('--seed', type=int, default=1234)
   p.add_argument('--sync_bn', action='store_true', help='BatchNorm batch moments over the whole data-parallel batch')
+  p.add_argument('--train_any_filter', action='store_true',
+                 help='train layers of filter size 1, 5 and 7 too (float32, per-timestep graph; saved as train_any_filter in '
+                      'model_opt.yaml, so that --restore continues on the same path); without it only 3x3 filters train')
   return p
 
 
-def main(argv=None):
-  import torch
-  args = build_parser().parse_args(argv)
+def make_opt(args):
+  """model_opt of a run (box_model_train.py:397-451 of the reference) plus this trainer's own keys."""
   full = cap.make_model_opt(args, args.inp_height, args.inp_width, args.timespan)
   model_opt = {k: full[k] for k in BOX_KEYS if k in full}
   model_opt['attn_box_padding_ratio'], model_opt['weight_decay'], model_opt['use_bn'] = 0.2, 5e-5, True  # :421-423
   # 'fixed_var' is args.fixed_var as the reference writes it (box_model_train.py:442; False unless the flag is given), so
   # that the controller is pre-trained with the variance parameterisation full_model then continues with
   model_opt['sync_bn'], model_opt['seed'] = bool(args.sync_bn), int(args.seed)
+  if getattr(args, 'train_any_filter', False):  # only when asked for: without the flag model_opt.yaml is what it was
+    model_opt['train_any_filter'] = True
+  return model_opt
+
+
+def main(argv=None):
+  import torch
+  args = build_parser().parse_args(argv)
+  model_opt = make_opt(args)
   rank, world, local_rank = ra_dist.init()
   if torch.cuda.is_available():
     torch.cuda.set_device(local_rank)

@@ -652,7 +652,7 @@ def _register_controller(model, opt, d, pt_ctrl=None):
   ccnn = nn.cnn(d['ccnn_filters'], d['ccnn_channels'], d['ccnn_pool'],
                 [relu] * d['ccnn_nlayers'], [d['use_bn']] * d['ccnn_nlayers'],
                 phase_train=model.get('phase_train'), wd=opt['weight_decay'], scope='ctrl_cnn',
-                model=model, init_weights=pt_ctrl and pt_ctrl.get('ccnn'))
+                model=model, init_weights=pt_ctrl and pt_ctrl.get('ccnn'), train_any_filter=bool(opt.get('train_any_filter', False)))
   ccnn.declare_copies(T)
   Cf = d['ccnn_channels'][-1]
   cell = nn.lstm(Cf, d['hid'], wd=opt['weight_decay'], scope='ctrl_lstm', model=model,
@@ -733,14 +733,14 @@ def get_model(opt, is_training=True):
   acnn = nn.cnn(d['acnn_filters'], d['acnn_channels'], d['acnn_pool'],
                 [relu] * d['acnn_nlayers'], [d['use_bn']] * d['acnn_nlayers'],
                 phase_train=model['phase_train'], wd=wd, scope='attn_cnn', model=model,
-                init_weights=pt_attn and pt_attn['acnn'])
+                init_weights=pt_attn and pt_attn['acnn'], train_any_filter=bool(opt.get('train_any_filter', False)))
   acnn.declare_copies(d['T'])
   smlp = nn.mlp([d['hid'] + d['core_dim'], 1], [nn.sigmoid], wd=wd, scope='score_mlp',
                 model=model, init_weights=pt_score and pt_score.get('smlp'))
   adcnn = nn.dcnn(d['adcnn_filters'], d['adcnn_channels'], d['adcnn_unpool'],
                   [relu] * d['adcnn_nlayers'], use_bn=[d['use_bn']] * d['adcnn_nlayers'],
                   skip_ch=d['skip_ch'], phase_train=model['phase_train'], wd=wd, model=model,
-                  init_weights=pt_attn and pt_attn['adcnn'], scope='attn_dcnn')
+                  init_weights=pt_attn and pt_attn['adcnn'], scope='attn_dcnn', train_any_filter=bool(opt.get('train_any_filter', False)))
   adcnn.declare_copies(d['T'])
   model.closures = dict(ccnn=ccnn, crnn_cell=cell, gmlp=gmlp, cmlp=cmlp, acnn=acnn, smlp=smlp,
                         adcnn=adcnn)

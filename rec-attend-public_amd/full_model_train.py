@@ -45,7 +45,19 @@ def build_parser():
                       'the data-parallel ranks must hold ONE model — tests/test_distributed_gpu.py checks they do')
   p.add_argument('--sync_bn', action='store_true',
                  help='data parallel: BatchNorm batch moments over the WHOLE batch (nnlib.py:98), one small collective per BN call')
+  p.add_argument('--train_any_filter', action='store_true',
+                 help='train layers of filter size 1, 5 and 7 too (float32, per-timestep graph; saved as train_any_filter in '
+                      'model_opt.yaml, so that --restore continues on the same path); without it only 3x3 filters train')
   return p
+
+
+def make_opt(args):
+  """model_opt of a run (full_model_train.py:460-668 of the reference) plus this trainer's own keys."""
+  model_opt = cap.make_model_opt(args, args.inp_height, args.inp_width, args.timespan)
+  model_opt['sync_bn'], model_opt['seed'] = bool(args.sync_bn), int(args.seed)
+  if getattr(args, 'train_any_filter', False):  # only when asked for: without the flag model_opt.yaml is what it was
+    model_opt['train_any_filter'] = True
+  return model_opt
 
 
 def synthetic_batch(rng, B, H, W, T):
@@ -198,8 +210,7 @@ def train_loop(args, model, model_opt, folder, rank, world, make_batch):
 def main(argv=None):
   import torch
   args = build_parser().parse_args(argv)
-  model_opt = cap.make_model_opt(args, args.inp_height, args.inp_width, args.timespan)
-  model_opt['sync_bn'], model_opt['seed'] = bool(args.sync_bn), int(args.seed)
+  model_opt = make_opt(args)
   rank, world, local_rank = ra_dist.init()
   if torch.cuda.is_available():
     torch.cuda.set_device(local_rank)

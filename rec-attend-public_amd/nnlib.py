@@ -177,8 +177,8 @@ def _check_filter_sizes(f, what):
 def _check_train_filter_sizes(f, what):
   """Training (the backward kernels) is built for 3x3 filters only: refuse before any kernel runs."""
   if any(fi != 3 for fi in f):
-    raise RecAttendError('%s: training with filter sizes %s is not built (3x3 only; eval decodes any of %s)' %
-                         (what, list(f), ops.FILTER_SIZES))
+    raise RecAttendError('%s: training with filter sizes %s is not built (3x3 only; eval decodes any of %s; '
+                         'train_any_filter=True trains them in float32)' % (what, list(f), ops.FILTER_SIZES))
 
 
 WIDE_COUT = 128  # K1 serves up to 128 output channels; wider 3x3 layers run the wide kernel (ops.conv_wide): at eval here, in training through ra_fg_train.FgTrainStep(model, wide=True)
@@ -201,11 +201,11 @@ def _check_train_wide(ch, what):
 
 
 def cnn(f, ch, pool, act, use_bn, phase_train=None, wd=None, scope='cnn', model=None,
-        init_weights=None, frozen=None, shared_weights=None):
+        init_weights=None, frozen=None, shared_weights=None, train_any_filter=False):
   """nnlib.py:131-257.  Returns run_cnn(x) -> list of the N layer outputs.
 
   Each layer is ONE fused kernel: conv f x f + bias + BN(copy) + ReLU + max-pool.  `act[i]`
-  must be relu (or None); `f[i]` in ops.FILTER_SIZES (training: 3).  A 3x3 layer of more than 128 output channels (up to 512;
+  must be relu (or None); `f[i]` in ops.FILTER_SIZES (training: 3, or any of them with train_any_filter=True, in float32).  A 3x3 layer of more than 128 output channels (up to 512;
   fg_model's inner layers) runs the wide kernel (ops.conv_wide) at eval; training refuses it.  BN parameters are separate per call ("copy"),
   like the reference's copy counter (nnlib.py:212,254); run_cnn.reset_copy() rewinds it for
   the next forward pass, run_cnn(x, copy=t) addresses a copy explicitly."""
@@ -267,7 +267,8 @@ def cnn(f, ch, pool, act, use_bn, phase_train=None, wd=None, scope='cnn', model=
     """phase_train = True: per layer conv + b -> BN on the batch moments -> ReLU -> max-pool as one autograd node on the
     training step's kernels; the copy's EMA shadows move (nnlib.py:229-253 with :98-112)."""
     import ra_train as rt
-    _check_train_filter_sizes(f, 'cnn')
+    if not train_any_filter:
+      _check_train_filter_sizes(f, 'cnn')
     _check_train_wide(ch, 'cnn')
     h = [None] * nlayers
     prev = x
@@ -322,12 +323,13 @@ def cnn(f, ch, pool, act, use_bn, phase_train=None, wd=None, scope='cnn', model=
 
 
 def dcnn(f, ch, pool, act, use_bn, skip_ch=None, phase_train=None, wd=None, scope='dcnn',
-         model=None, init_weights=None, frozen=None):
+         model=None, init_weights=None, frozen=None, train_any_filter=False):
   """nnlib.py:260-404.  Returns run_dcnn(x, skip=None) -> list of the N layer outputs.
 
   Layer = [concat(prev, skip[i])] -> conv2d_transpose(w[f,f,out,in], stride pool[i], SAME) + b
   -> BN(copy) -> ReLU, as ONE fused kernel (the concat is two source pointers, the stride-2
-  transpose is a conv over the zero-stuffed input with flipped taps).  Wide layers (more than 128 output channels) as in cnn."""
+  transpose is a conv over the zero-stuffed input with flipped taps).  Training: filter size 3, or any of ops.FILTER_SIZES with
+  train_any_filter=True (float32).  Wide layers (more than 128 output channels) as in cnn."""
   nlayers = len(f)
   w = [None] * nlayers
   b = [None] * nlayers
@@ -388,7 +390,8 @@ def dcnn(f, ch, pool, act, use_bn, skip_ch=None, phase_train=None, wd=None, scop
     node per layer on the training step's kernels (nnlib.py:362-400 with :98-112).  The concat is ONE packed kernel
     input whose chan_map sends every packed channel to its row of the [3,3,out,in] filter."""
     import ra_train as rt
-    _check_train_filter_sizes(f, 'dcnn')
+    if not train_any_filter:
+      _check_train_filter_sizes(f, 'dcnn')
     _check_train_wide(ch, 'dcnn')
     h = [None] * nlayers
     prev = x

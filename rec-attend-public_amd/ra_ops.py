@@ -332,6 +332,84 @@ def conv2d_fused(src0, wp, scale, shift, cout, ksize, relu=True, pool=1, src1=No
   return out
 
 
+# ---- training layers of filter size 1, 5 and 7 (csrc/ra_wgrad_kxk.hip; ra_train.ConvBNActPool)
+
+_WGK_FIELDS = sorted((v, k[len('RA_WGK_PLAN_'):].lower()) for k, v in rn.CONSTANTS.items() if k.startswith('RA_WGK_PLAN_') and k != 'RA_WGK_PLAN_INTS')
+
+
+def wgrad_kxk_plan(ksize, cin, cout, B, H, W):
+  """The launch the k x k filter gradient (ksize in 1, 5, 7) takes for a conv map [B,H,W,cout] of cin kernel channels
+  (ra_convkxk_wgrad_plan: host only): {'nt', 'grid_x', 'grid_y', 'grid_z', 'lds_bytes', 'record_floats', 'ntiles', 'acc_tiles'}."""
+  rec = (C.c_int * rn.RA_WGK_PLAN_INTS)()
+  check(rn.lib().ra_convkxk_wgrad_plan(int(ksize), int(cin), int(cout), int(B), int(H), int(W), rec), 'ra_convkxk_wgrad_plan')
+  return {name: rec[i] for i, name in _WGK_FIELDS}
+
+
+def pack_conv_weights_dev(w, ksize, cin_kernel=None, chan_map=None, transposed=False):
+  """pack_conv_weights of a ksize x ksize filter on the device (the weights change every step): w [k,k,Ci,Co] (transposed:
+  [k,k,Co,Ci]) a device tensor, chan_map an int32 device tensor or None -> the input of conv2d_fused(..., ksize=k)."""
+  _need_cuda(w)
+  if w.dim() != 4 or tuple(w.shape[:2]) != (ksize, ksize):
+    raise rn.RecAttendError('filter of shape %r is not %d x %d' % (tuple(w.shape), ksize, ksize))
+  cin_w, cout = (w.shape[3], w.shape[2]) if transposed else (w.shape[2], w.shape[3])
+  cin = cin_w if cin_kernel is None else int(cin_kernel)
+  if chan_map is not None and not (chan_map.is_cuda and chan_map.dtype == torch.int32 and chan_map.numel() == cin):
+    raise rn.RecAttendError('pack_conv_weights_dev: chan_map must be an int32 device tensor of %d entries' % cin)
+  n = rn.lib().ra_conv_packed_floats_k(int(ksize), cin, int(cout))
+  if n == 0:
+    raise rn.RecAttendError('unsupported conv shape k=%d Cin=%d Cout=%d (k in 1, 3, 5, 7; Cin %% 4; Cout <= 128)' % (ksize, cin, cout))
+  out = torch.empty(n, dtype=torch.float32, device=w.device)
+  check(rn.lib().ra_conv_pack_weights_k_dev(ptr(w), int(ksize), int(cin_w), int(cout), cin, ptr(chan_map),
+                                            rn.RA_CONV_TRANSPOSED if transposed else 0, ptr(out), rn.stream_ptr()), 'ra_conv_pack_weights_k_dev')
+  return out
+
+
+def _wgrad_kxk_args(who, x, du, ksize, upsample, ws):
+  _need_cuda(x, du, ws)
+  B, Hs, Ws, cin = x.shape
+  H, W, cout = du.shape[1:]
+  up = 2 if upsample else 1
+  if tuple(du.shape[:3]) != (B, Hs * up, Ws * up) or not (x.is_contiguous() and du.is_contiguous()):
+    raise rn.RecAttendError('%s: contiguous x of %r and du of %r' % (who, tuple(x.shape), tuple(du.shape)))
+  n = rn.lib().ra_convkxk_wgrad_workspace_floats(int(ksize), cin, cout, B, H, W)
+  if n == 0:
+    raise rn.RecAttendError('%s: unsupported shape k=%d Cin=%d Cout=%d (k in 1, 3, 5, 7; Cin %% 4; Cout <= 128)' % (who, ksize, cin, cout))
+  if ws is None or ws.numel() < n:
+    ws = torch.empty(n, dtype=torch.float32, device=x.device)
+  return B, Hs, Ws, cin, cout, ws
+
+
+def wgrad_kxk(x, du, ksize, upsample=False, ws=None, dw=None, db=None):
+  """(dw [k,k,Cin,Cout], db [Cout]) of the ksize x ksize conv that ran on x [B,Hs,Ws,Cin] (Cin % 4 == 0) and produced du's
+  tensor [B,H,W,Cout], Cout <= 128; upsample: the stride-2 transposed form.  ksize = 3 is the 3x3 kernel.  ws: a workspace
+  to reuse (ra_convkxk_wgrad_workspace_floats floats)."""
+  B, Hs, Ws, cin, cout, ws = _wgrad_kxk_args('wgrad_kxk', x, du, ksize, upsample, ws)
+  dw = torch.empty((ksize, ksize, cin, cout), dtype=torch.float32, device=x.device) if dw is None else dw
+  db = torch.empty(cout, dtype=torch.float32, device=x.device) if db is None else db
+  _need_cuda(dw, db)
+  check(rn.lib().ra_convkxk_wgrad_f32(ptr(x), cin, B, Hs, Ws, int(bool(upsample)), ptr(du), cout, int(ksize), ptr(ws), ws.numel(), ptr(dw),
+                                      ptr(db), rn.stream_ptr()), 'ra_convkxk_wgrad_f32')
+  return dw, db
+
+
+def wgrad_kxk_acc(x, du, ksize, gw, gb=None, chan_map=None, transposed=False, upsample=False, ws=None):
+  """gw += the filter gradient of wgrad_kxk in the reference layout of the filter that ran ([k,k,cin_w,Cout]; transposed:
+  [k,k,Cout,cin_w] with flipped taps), gb += the bias gradient (None: not wanted).  chan_map (int32 device tensor, or None)
+  sends kernel channel c to filter row chan_map[c], -1 = padding."""
+  B, Hs, Ws, cin, cout, ws = _wgrad_kxk_args('wgrad_kxk_acc', x, du, ksize, upsample, ws)
+  _need_cuda(gw, gb)
+  cin_w = gw.shape[3] if transposed else gw.shape[2]
+  if tuple(gw.shape) != ((ksize, ksize, cout, cin_w) if transposed else (ksize, ksize, cin_w, cout)) or not gw.is_contiguous() or \
+      (gb is not None and gb.numel() != cout):
+    raise rn.RecAttendError('wgrad_kxk_acc: gw of %r / gb for %d output channels' % (tuple(gw.shape), cout))
+  if chan_map is not None and not (chan_map.is_cuda and chan_map.dtype == torch.int32 and chan_map.numel() == cin):
+    raise rn.RecAttendError('wgrad_kxk_acc: chan_map must be an int32 device tensor of %d entries' % cin)
+  check(rn.lib().ra_convkxk_wgrad_acc_f32(ptr(x), cin, B, Hs, Ws, int(bool(upsample)), ptr(du), cout, int(ksize), ptr(ws), ws.numel(),
+                                          ptr(chan_map), int(cin_w), int(bool(transposed)), ptr(gw), ptr(gb), rn.stream_ptr()),
+        'ra_convkxk_wgrad_acc_f32')
+  return gw
+
+
 def conv_wide_supported(cin, cout):
   """The wide 3x3 layer takes Cout 129 .. 512 (a multiple of 16) and cin = C0 + C1 <= 1024 (a multiple of 4)."""
   return bool(rn.lib().ra_conv_wide_supported(int(cin), int(cout)))

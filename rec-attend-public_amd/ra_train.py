@@ -365,23 +365,27 @@ class _PackCache(dict):
       self.filled = self.tr._pack_epoch
 
 
-def _pack_dev(w, cin_w, cout, cin, cmap_t, transposed, cache=None):
+def _pack_dev(w, cin_w, cout, cin, cmap_t, transposed, cache=None, ksize=3):
   cache = _PACK if cache is None else cache
   key = (w.data_ptr(), w._version, int(cin_w), int(cout), int(cin), 0 if cmap_t is None else cmap_t.data_ptr(), bool(transposed))
+  if ksize != 3:
+    key += (int(ksize),)
   hit = cache.get(key)
   if hit is not None:
     return hit[1]
   if isinstance(cache, _PackCache):
-    pre = cache.lookup(('w',) + key[2:], w, lambda pos: _pack_dev_now(pos, cin_w, cout, cin, cmap_t, transposed))
+    pre = cache.lookup(('w',) + key[2:], w, lambda pos: _pack_dev_now(pos, cin_w, cout, cin, cmap_t, transposed, ksize))
     if pre is not None:
       cache[key] = (w, pre)
       return pre
-  out = _pack_dev_now(w, cin_w, cout, cin, cmap_t, transposed)
+  out = _pack_dev_now(w, cin_w, cout, cin, cmap_t, transposed, ksize)
   cache[key] = (w, out)
   return out
 
 
-def _pack_dev_now(w, cin_w, cout, cin, cmap_t, transposed):
+def _pack_dev_now(w, cin_w, cout, cin, cmap_t, transposed, ksize=3):
+  if ksize != 3:  # a filter of size 1, 5 or 7 (ra_convkxk_f32's packing)
+    return ops.pack_conv_weights_dev(w, ksize, cin_kernel=cin, chan_map=cmap_t, transposed=transposed)
   n = rn.lib().ra_conv_packed_floats(cin, cout)
   if n == 0:
     raise rn.RecAttendError('unsupported conv shape Cin=%d Cout=%d' % (cin, cout))
@@ -465,7 +469,9 @@ class ConvBNActPool(torch.autograd.Function):
   """One layer of nnlib.cnn (nnlib.py:229-253) or nnlib.dcnn (nnlib.py:362-400) in training mode.
 
   x [B,Hs,Ws,Cx] (Cx % 4 == 0), w in the reference layout ([3,3,Cin,Cout]; transposed:
-  [3,3,Cout,Cin]), b [Cout], gamma / beta [Cout] or None.  Returns (y, batch mean, batch var)."""
+  [3,3,Cout,Cin]), b [Cout], gamma / beta [Cout] or None.  Returns (y, batch mean, batch var).
+  A filter of size 1, 5 or 7 (meta['ksize'], default w.shape[0]) runs in float32 on ra_convkxk_f32, the two-pass batch moments
+  and ra_convkxk_wgrad_f32 / _acc_f32 (csrc/ra_wgrad_kxk.hip); its filter gradient is never deferred."""
 
   @staticmethod
   def forward(ctx, x, w, b, gamma, beta, meta):
@@ -481,7 +487,13 @@ class ConvBNActPool(torch.autograd.Function):
     cp = ops.cout_padded(cout)
     cache = meta.get('cache')
     cache = _PACK if cache is None else cache
-    wp = _pack_dev(w.contiguous(), cin_w, cout, Cx, cmap_t, tr, cache)
+    f = int(meta.get('ksize') or w.shape[0])  # the filter size: 3, or (train_any_filter) 1, 5, 7 on the float32 k x k kernels
+    if f != 3:
+      if meta.get('bf16') or meta.get('bf16_store'):
+        raise rn.RecAttendError("a layer of filter size %d trains in float32 only (compute_dtype = 'bf16' is built for 3x3 filters)" % f)
+      if cout > 128 or cp == 0:
+        raise rn.RecAttendError('a layer of filter size %d trains with up to 128 output channels, not %d' % (f, cout))
+    wp = _pack_dev(w.contiguous(), cin_w, cout, Cx, cmap_t, tr, cache, ksize=f)
     scale = _const('ones', cp, dev, lambda: torch.ones(cp, dtype=torch.float32, device=dev))
     shift = b.detach()
     if cp != cout:  # padded once per step (the layer's bias is shared by all timesteps), not once per use
@@ -530,7 +542,7 @@ class ConvBNActPool(torch.autograd.Function):
                                              B, H, W, cout, ptr(y), (1 if st_ok else 0) | (2 if yd == torch.bfloat16 else 0),
                                              rn.stream_ptr()), 'ra_bn_act_pool_bf16_f32')
       return y, mean, var
-    if use_bn and cout % 4 == 0 and EPILOGUE_MOMENTS['on']:
+    if use_bn and cout % 4 == 0 and EPILOGUE_MOMENTS['on'] and f == 3:
       # the batch moments ride on the conv epilogue: per-wave channel sums, then one small finishing launch
       u = place('u', B, Hs * up, Ws * up, cout)
       part = _f(rn.lib().ra_conv3x3_moments_part_floats(cout), device=dev)
@@ -542,8 +554,12 @@ class ConvBNActPool(torch.autograd.Function):
             'ra_bn_moments_from_partials_f32')
       H, W = u.shape[1], u.shape[2]
     else:
-      u = ops.conv3x3(x, wp, scale, shift, cout, relu=False, pool=1, upsample=(stride == 2), bf16=bf,
-                      out=place('u', B, Hs * up, Ws * up, cout))
+      if f == 3:
+        u = ops.conv3x3(x, wp, scale, shift, cout, relu=False, pool=1, upsample=(stride == 2), bf16=bf,
+                        out=place('u', B, Hs * up, Ws * up, cout))
+      else:  # ra_convkxk_f32, then the two-pass moments: its epilogue carries none
+        u = ops.conv2d_fused(x, wp, scale, shift, cout, f, relu=False, pool=1, upsample=(stride == 2),
+                             out=place('u', B, Hs * up, Ws * up, cout))
       H, W = u.shape[1], u.shape[2]
       if use_bn:
         ws = _f(rn.lib().ra_bn_workspace_floats(cout), device=dev)
@@ -555,7 +571,7 @@ class ConvBNActPool(torch.autograd.Function):
     y = place('y', B, H // pool, W // pool, cout)
     check(rn.lib().ra_bn_act_pool_f32(ptr(u), ptr(mean), ptr(var), ptr(gamma), ptr(beta), _C.c_float(BN_EPS), int(relu),
                                       int(pool), B, H, W, cout, ptr(y), rn.stream_ptr()), 'ra_bn_act_pool_f32')
-    ctx.meta, ctx.cmap, ctx.cache = meta, cmap, cache
+    ctx.meta, ctx.cmap, ctx.cache, ctx.ksize = meta, cmap, cache, f
     if not use_bn:
       ctx.n_total = 0.0
     ctx.save_for_backward(x, w, u, mean, var, gamma, beta)
@@ -581,8 +597,10 @@ class ConvBNActPool(torch.autograd.Function):
     ws = _f(rn.lib().ra_bn_workspace_floats(cout), device=dev)
     dgamma, dbeta, du = _f(cout, device=dev), _f(cout, device=dev), torch.empty_like(u)
     grads = meta.get('grads')  # (gw, gb, ggamma, gbeta): views of the flat gradient bucket -> accumulate in-kernel
-    deferred = grads is not None and meta.get('wgrad_defer') is not None  # the filter gradient waits for the end of backward
-    nws = 0 if deferred else rn.lib().ra_conv3x3_wgrad_workspace_floats(Cx, cout, B, H, W)
+    f = ctx.ksize
+    # the filter gradient waits for the end of backward (3x3 only: the pointer-table form; another size accumulates per call)
+    deferred = grads is not None and meta.get('wgrad_defer') is not None and f == 3
+    nws = 0 if deferred else rn.lib().ra_convkxk_wgrad_workspace_floats(f, Cx, cout, B, H, W)
     wws = None if deferred else _f(nws, device=dev)
     synced = ctx.n_total > 0.0 and ctx.n_total != float(B * H * W)
     bf = bool(meta.get('bf16'))  # compute_dtype = 'bf16': bf16 operands on the bf16 MFMA, float32 sums and tensors
@@ -624,7 +642,7 @@ class ConvBNActPool(torch.autograd.Function):
       if cmap is not None:
         real = [j for j in cmap if j >= 0]
         assert len(set(real)) == len(real), 'chan_map must be injective (one writer per gradient element)'
-      defer = meta.get('wgrad_defer')
+      defer = meta.get('wgrad_defer') if deferred else None
       if defer is not None:
         # the filter is shared by the step's timesteps: this call only adds its per-workgroup partial sums to the
         # layer's buffer; the end-of-backward callback (_DeferredWgrads) reduces each layer ONCE
@@ -638,6 +656,10 @@ class ConvBNActPool(torch.autograd.Function):
         assert slot.setdefault('shape', shape) == shape, 'a deferred filter gradient needs one shape per layer'
         slot['calls'].append((x, du))  # nothing is launched here
         slot.update(cmap_t=cmap_t, gw=gw, gb=gb)
+      elif f != 3:
+        check(rn.lib().ra_convkxk_wgrad_acc_f32(ptr(x), Cx, B, Hs, Ws, int(stride == 2), ptr(du), cout, f, ptr(wws), nws,
+                                                ptr(cmap_t), int(cin_w), int(tr), ptr(gw), ptr(gb), rn.stream_ptr()),
+              'ra_convkxk_wgrad_acc_f32')
       else:
         check(wgrad_acc(ptr(x), Cx, B, Hs, Ws, int(stride == 2), ptr(du), cout, ptr(wws), nws,
                         ptr(cmap_t), int(cin_w), int(tr), ptr(gw), ptr(gb), rn.stream_ptr()), 'ra_conv3x3_wgrad_acc_f32')
@@ -646,11 +668,15 @@ class ConvBNActPool(torch.autograd.Function):
     else:
       dgamma, dbeta = bn_backward(None, None)
       # ---- backward-weight (of the SAME conv that ran) + bias
-      dWf, db = _f(3, 3, Cx, cout, device=dev), _f(cout, device=dev)
-      check(wgrad_out(ptr(x), Cx, B, Hs, Ws, int(stride == 2), ptr(du), cout, ptr(wws), nws,
-                      ptr(dWf), ptr(db), rn.stream_ptr()), 'ra_conv3x3_wgrad_f32')
+      dWf, db = _f(f, f, Cx, cout, device=dev), _f(cout, device=dev)
+      if f != 3:
+        check(rn.lib().ra_convkxk_wgrad_f32(ptr(x), Cx, B, Hs, Ws, int(stride == 2), ptr(du), cout, f, ptr(wws), nws,
+                                            ptr(dWf), ptr(db), rn.stream_ptr()), 'ra_convkxk_wgrad_f32')
+      else:
+        check(wgrad_out(ptr(x), Cx, B, Hs, Ws, int(stride == 2), ptr(du), cout, ptr(wws), nws,
+                        ptr(dWf), ptr(db), rn.stream_ptr()), 'ra_conv3x3_wgrad_f32')
       if cmap is not None:  # packed kernel channels -> the filter's own input channels
-        real = torch.zeros((3, 3, cin_w, cout), dtype=torch.float32, device=dev)
+        real = torch.zeros((f, f, cin_w, cout), dtype=torch.float32, device=dev)
         for c, j in enumerate(cmap):
           if j >= 0:
             real[:, :, j, :] += dWf[:, :, c, :]
@@ -666,12 +692,20 @@ class ConvBNActPool(torch.autograd.Function):
       cpb = ops.cout_padded(cin_w)
       ones = _const('ones', cpb, dev, lambda: torch.ones(cpb, dtype=torch.float32, device=dev))
       zeros = _const('zeros', cpb, dev, lambda: torch.zeros(cpb, dtype=torch.float32, device=dev))
-      wpb = _pack_dev(w.contiguous(), cout, cin_w, cd, _pad_map(cout, cd, dev), not tr, ctx.cache)
-      dxr = ops.conv3x3(duc, wpb, ones, zeros, cin_w, relu=False, pool=1, bf16=bf)
+      wpb = _pack_dev(w.contiguous(), cout, cin_w, cd, _pad_map(cout, cd, dev), not tr, ctx.cache, ksize=f)
+      if f == 3:
+        dxr = ops.conv3x3(duc, wpb, ones, zeros, cin_w, relu=False, pool=1, bf16=bf)
+      else:
+        dxr = ops.conv2d_fused(duc, wpb, ones, zeros, cin_w, f, relu=False, pool=1)
       if stride == 2:
+        # the stride-2 transposed conv reads x[i] at dx[i] = sum_k du[2i + k - pad_lo] w[k], pad_lo = max(f - 2, 0) // 2: a centred
+        # window at the ODD position 2i + 1 for f = 3, 5, 7, the EVEN position 2i itself for f = 1
         sub = _f(B, Hs, Ws, cin_w, device=dev)
-        check(rn.lib().ra_subsample_odd_f32(ptr(dxr), B, Hs, Ws, cin_w, ptr(sub), rn.stream_ptr()),
-              'ra_subsample_odd_f32')
+        if f == 1:
+          check(rn.lib().ra_subsample_even_f32(ptr(dxr), B, Hs, Ws, cin_w, ptr(sub), rn.stream_ptr()), 'ra_subsample_even_f32')
+        else:
+          check(rn.lib().ra_subsample_odd_f32(ptr(dxr), B, Hs, Ws, cin_w, ptr(sub), rn.stream_ptr()),
+                'ra_subsample_odd_f32')
         dxr = sub
       if cmap is not None:
         dx = torch.zeros_like(x)
@@ -1472,7 +1506,34 @@ def _check_3x3(d, keys):
   another filter size decodes (ra_convkxk_f32) but refuses to train, before any kernel runs."""
   bad = ['%s %s' % (k, d[k]) for k in keys if k in d and any(f != 3 for f in d[k])]
   if bad:
-    raise rn.RecAttendError('training is built for 3x3 filters only; this model has filter sizes %s' % ', '.join(bad))
+    raise rn.RecAttendError("training is built for 3x3 filters only; this model has filter sizes %s (model_opt['train_any_filter'] / "
+                            '--train_any_filter trains sizes 1, 5 and 7 in float32)' % ', '.join(bad))
+
+
+_FILTER_CHANNELS = {'ccnn_filters': 'ccnn_channels', 'acnn_filters': 'acnn_channels', 'adcnn_filters': 'adcnn_channels'}
+
+
+def _check_filter_sizes(d, opt, keys):
+  """The guard of the trainers.  Without model_opt['train_any_filter'] it is _check_3x3.  With it, layers of filter size 1, 5
+  and 7 train on the float32 k x k kernels (ra_convkxk_f32, ra_convkxk_wgrad_f32); still refused by name, before any kernel:
+  compute_dtype = 'bf16' together with such a layer, and such a layer with more than 128 channels.  True when a layer differs from 3."""
+  if not opt.get('train_any_filter', False):
+    _check_3x3(d, keys)
+    return False
+  other = False
+  for k in keys:
+    ch = d.get(_FILTER_CHANNELS[k])
+    for i, f in enumerate(d.get(k, ())):
+      if f == 3:
+        continue
+      other = True
+      if ch is not None and max(ch[i], ch[i + 1]) > 128:
+        raise rn.RecAttendError('train_any_filter: %s layer %d has filter size %d and %d -> %d channels: sizes other than 3 train with '
+                                'up to 128 channels' % (k, i, f, ch[i], ch[i + 1]))
+  if other and str(opt.get('compute_dtype', 'float32')).lower() in ('bf16', 'bfloat16'):
+    raise rn.RecAttendError("train_any_filter: compute_dtype = 'bf16' is built for 3x3 filters only; layers of filter size 1, 5 or 7 "
+                            'train in float32')
+  return other
 
 
 class TrainStep(object):
@@ -1482,7 +1543,7 @@ class TrainStep(object):
     import full_model  # noqa: F401  (the Model class)
     self.model, self.opt, self.d = model, model.opt, model.dims
     d = self.d
-    _check_3x3(d, ('ccnn_filters', 'acnn_filters', 'adcnn_filters'))
+    self.any_filter = _check_filter_sizes(d, self.opt, ('ccnn_filters', 'acnn_filters', 'adcnn_filters'))
     if not torch.cuda.is_available():
       raise rn.RecAttendError('the training step needs an MI355X (HIP device); there is no CPU fallback')
     if self.opt.get('box_loss_fn', 'iou') not in ('iou', 'mse', 'huber') or \
@@ -1639,6 +1700,8 @@ class TrainStep(object):
     kernels' packed tensors) and the controller fits the fused kernels (ra_ctrl_train.hip: up to 4 layers per MLP)."""
     d, opt = self.d, self.opt
     c4 = lambda cs: all(c % 4 == 0 for c in cs)
+    if self.any_filter:  # the stacked step's layer nodes (ConvStackFn) are 3x3: another filter size takes the per-timestep graph
+      return False
     return bool(self.batched_backward and torch.is_grad_enabled() and d['use_bn'] and self.fuse_param_grads and
                 self.fuse_controller and bool(opt.get('stop_canvas_grad', True)) and  # a canvas gradient couples the timesteps
                 c4(self.model.dims['ccnn_channels'][1:]) and c4(opt['attn_cnn_depth']) and c4(opt['attn_dcnn_depth'][:-1]) and
@@ -2472,7 +2535,7 @@ class BoxTrainStep(TrainStep):
 
   def __init__(self, model, world=1):
     self.model, self.opt, self.d = model, model.opt, model.dims
-    _check_3x3(self.d, ('ccnn_filters',))
+    self.any_filter = _check_filter_sizes(self.d, self.opt, ('ccnn_filters',))
     if not torch.cuda.is_available():
       raise rn.RecAttendError('the training step needs an MI355X (HIP device); there is no CPU fallback')
     if self.opt.get('box_loss_fn', 'iou') not in ('iou', 'mse', 'huber'):
