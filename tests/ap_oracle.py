@@ -2,7 +2,9 @@
 data_api/cityscapes_scripts/evaluation/evalInstanceLevelSemanticLabeling.py, cited as :line; instances2dict.py, instance.py):
 the ground-truth instances of an image, the assignment of predictions to them (:260-353), the matching per class and overlap
 threshold (:356-551) and the averages (:553-579), restated loop by loop on pixel arrays — one count_nonzero per prediction
-and ground-truth instance, one np.append per example — and slow on purpose.  It shares no code with analysis.py.  `COUNTERS`
+and ground-truth instance, one np.append per example — and slow on purpose.  It shares no code with analysis.py.  The script
+itself runs once translated to Python 3: oracle/toolkit_fixtures.py recorded its result files on seven scenes as
+tests/golden/toolkit_instance.{npz,json}, and tests/test_toolkit_fixtures.py holds run() to them (observed difference: 0).  `COUNTERS`
 records which branches a run took, so that a test can assert that its scene reached them.  Also here: a seeded scene generator
 and a 16-bit PNG writer for the ground truth of the file-route tests."""
 import collections
@@ -21,6 +23,12 @@ OVERLAPS = np.arange(0.5, 1., 0.05)   # :134
 MIN_REGION = 100                      # :136, first entry (no distances: :386-389)
 
 COUNTERS = collections.Counter()
+# the branches a set of scenes has to take before its AP says anything about the evaluation (keys of COUNTERS)
+BRANCHES = ('pred_on_void', 'void_ignored',                      # void pixels under a prediction, enough of them to ignore it
+            'matched_a_group', 'group_pixels_ignored',
+            'matched_a_small_instance', 'small_instance_pixels_ignored',
+            'hard_false_negative', 'duplicate_match', 'false_positive', 'class_with_gt_only', 'class_with_neither',
+            'pred_label_not_evaluated', 'pred_empty', 'equal_score_true_and_false')
 
 
 def gt_instances(gt):

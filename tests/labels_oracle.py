@@ -2,12 +2,15 @@
 full-size masks, each resized on its own, the orientation over the stack, the sort by area — not the kernels' (sample the
 id image, compare ids): data_api/sep_labels.py, data_api/cvppp.py:49-63 / kitti.py:51-65 / cityscapes.py:88-119,
 data_api/ins_seg_assembler.py:120-151, data_api/orientation.py:31-85, data_api/ins_seg_dataset.py:158-172,216-236,257-271,
-fg_model_eval.py:142-143.  The test helper of test_labels*.py and the host stand-in tools/labels_bench.py times; the
-reference itself (Python 2, cv2, h5py) cannot be run here.
+fg_model_eval.py:142-143.  The test helper of test_labels*.py and the host stand-in tools/labels_bench.py times.  Two of the
+reference's modules run once translated to Python 3, orientation.py and sep_labels.py: oracle/toolkit_fixtures.py recorded
+get_orientation ('class' and 'one_hot') and get_separate_labels on ellipse images and on hand-made edge masks as
+tests/golden/toolkit_orientation.npz, and tests/test_toolkit_fixtures.py holds get_orientation / separate_labels here to
+them (every class equal).  The rest of the stage (the dataset classes, the assembler: cv2, h5py) still cannot be run.
 
-Two statements are this project's and not checked against the reference's libraries: the nearest-neighbour rule is OpenCV's
-resizeNN restated from its source (cv2 is not part of this stack), and equal areas are ordered as a stable ascending sort read
-backwards (NumPy's default argsort is stable only up to 16 elements)."""
+Two statements are this project's and REMAIN UNCHECKED against the reference's libraries, cv2 being absent: the nearest-neighbour
+rule is OpenCV's resizeNN restated from its source, and equal areas are ordered as a stable ascending sort read backwards
+(NumPy's default argsort is stable only up to 16 elements)."""
 import numpy as np
 
 from cs_oracle import LABELS  # [(name, label id)]: the eight Cityscapes labels with instances, in trainId order

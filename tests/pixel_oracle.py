@@ -1,7 +1,10 @@
 """NumPy restatement of the Cityscapes pixel-level evaluation (data_api/cityscapes_scripts/evaluation/
 evalPixelLevelSemanticLabeling.py: evaluatePair :532-615, the score functions :216-338, getScoreAverage :273-282,
 generateInstanceStats :171-202), written from those lines with plain loops over np.unique and a [34,34] matrix; the test
-helper of test_pixel_eval*.py.  The label table (helpers/labels.py) and avgClassSize (:135-146) are data."""
+helper of test_pixel_eval*.py.  The label table (helpers/labels.py) and avgClassSize (:135-146) are data.  The script itself
+runs once translated to Python 3 (its pure-Python pair loop): oracle/toolkit_fixtures.py recorded its result files on four
+scenes as tests/golden/toolkit_pixel.{npz,json}, and tests/test_toolkit_fixtures.py holds evaluate() to them — matrix equal,
+scores within same_scores (observed difference: 0)."""
 import math
 import struct
 import zlib

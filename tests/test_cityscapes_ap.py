@@ -44,11 +44,8 @@ def _scene_and_oracle(seed):
 def test_scene_takes_every_branch():
   sc, ap, avg, n = _scene_and_oracle(0)
   assert sc['gt_ids'].shape == (3, 96, 160) and (sc['gt_ids'][0] == 26).sum() == 1500          # a group of an evaluated class
-  for key in ('pred_on_void', 'void_ignored',                      # void pixels under a prediction, enough of them to ignore it
-              'matched_a_group', 'group_pixels_ignored',
-              'matched_a_small_instance', 'small_instance_pixels_ignored',  # the 80-pixel person: covered, ignored ...
-              'hard_false_negative', 'duplicate_match', 'false_positive', 'class_with_gt_only', 'class_with_neither',
-              'pred_label_not_evaluated', 'pred_empty', 'equal_score_true_and_false'):
+  assert len(ao.BRANCHES) == 14
+  for key in ao.BRANCHES:  # among them the 80-pixel person: covered, ignored ...
     assert n.get(key, 0) > 0, key
   person = [nm for nm, _ in ao.INST_LABELS].index('person')
   # ... and not a false positive: at overlap 0.5 the person class has the one false positive of image 1 only
