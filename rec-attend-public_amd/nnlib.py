@@ -8,9 +8,9 @@ the reference (`'{scope}_w_{i}'`, `'{scope}_{i}_{copy}_{beta,gamma,ema_mean,ema_
 
 `phase_train=False`: the decode loop's fused eval kernels (EMA statistics folded into the conv
 epilogue).  `phase_train=True` (round 5): the training step's kernels behind the same closures —
-each cnn / dcnn layer is one `ra_train.ConvBNActPool` node (conv with the batch moments in its
+each cnn / dcnn layer is one `ra_layer_train.ConvBNActPool` node (conv with the batch moments in its
 epilogue, BN + ReLU + pool on the batch statistics, MFMA backward-data / backward-weight, the
-statistics differentiated through), `batch_norm` is `ra_train.BatchNormTrain`, and every call
+statistics differentiated through), `batch_norm` is `ra_layer_train.BatchNormTrain`, and every call
 moves the copy's EMA shadows by `shadow = decay shadow + (1 - decay) value`, `decay = 1 - 0.1
 phase_train` (nnlib.py:103-110).  Gradients are torch autograd's: mark the registered tensors
 (`model[...]`) with `requires_grad_()` and differentiate the closures' outputs — the counterpart
@@ -140,8 +140,8 @@ def batch_norm(x, n_out, phase_train, scope='bn', scope2='bn', affine=True, init
   over (B,H,W) (biased variance, differentiated through), and the EMA shadows updated (nnlib.py:98-112)."""
   beta, gamma, mean, var = _bn_register(model, scope2, n_out, init_beta, init_gamma)
   if _is_train(phase_train):
-    import ra_train as rt
-    y, bmean, bvar = rt.BatchNormTrain.apply(x, gamma, beta)
+    import ra_layer_train as lt
+    y, bmean, bvar = lt.BatchNormTrain.apply(x, gamma, beta)
     _ema_update(mean, var, bmean, bvar)
     return y
   sc, sh = ops.fold_bn(None, n_out, (beta, gamma, mean, var))
@@ -266,7 +266,7 @@ def cnn(f, ch, pool, act, use_bn, phase_train=None, wd=None, scope='cnn', model=
   def run_cnn_train(x, cp):
     """phase_train = True: per layer conv + b -> BN on the batch moments -> ReLU -> max-pool as one autograd node on the
     training step's kernels; the copy's EMA shadows move (nnlib.py:229-253 with :98-112)."""
-    import ra_train as rt
+    import ra_layer_train as lt
     if not train_any_filter:
       _check_train_filter_sizes(f, 'cnn')
     _check_train_wide(ch, 'cnn')
@@ -279,7 +279,7 @@ def cnn(f, ch, pool, act, use_bn, phase_train=None, wd=None, scope='cnn', model=
       meta = dict(transposed=False, stride=1, pool=pool[ii] if pool[ii] > 1 else 1, relu=act[ii] is not None,
                   chan_map=None)
       bn = _bn(ii, cp) if use_bn[ii] else None
-      y, mean, var = rt.ConvBNActPool.apply(rt._pad_channels(prev), w[ii], b[ii], bn[1] if bn else None,
+      y, mean, var = lt.ConvBNActPool.apply(lt._pad_channels(prev), w[ii], b[ii], bn[1] if bn else None,
                                             bn[0] if bn else None, meta)
       if bn:
         _ema_update(bn[2], bn[3], mean, var)
@@ -389,7 +389,7 @@ def dcnn(f, ch, pool, act, use_bn, skip_ch=None, phase_train=None, wd=None, scop
     """phase_train = True: [concat(prev, skip)] -> conv2d_transpose + b -> BN on the batch moments -> ReLU, one autograd
     node per layer on the training step's kernels (nnlib.py:362-400 with :98-112).  The concat is ONE packed kernel
     input whose chan_map sends every packed channel to its row of the [3,3,out,in] filter."""
-    import ra_train as rt
+    import ra_layer_train as lt
     if not train_any_filter:
       _check_train_filter_sizes(f, 'dcnn')
     _check_train_wide(ch, 'dcnn')
@@ -402,16 +402,10 @@ def dcnn(f, ch, pool, act, use_bn, skip_ch=None, phase_train=None, wd=None, scop
       sk = skip[ii] if skip is not None else None
       cmap = None
       if sk is not None:
-        n_prev, n_skip = prev.shape[3], sk.shape[3]
-        xp, skp = rt._pad_channels(prev), rt._pad_channels(sk)
-        cmap = list(range(n_prev)) + [-1] * (xp.shape[3] - n_prev) + [n_prev + k for k in range(n_skip)] + \
-            [-1] * (skp.shape[3] - n_skip)
-        if cmap == list(range(len(cmap))):
-          cmap = None
-        prev = torch.cat([xp, skp], dim=3)
+        prev, cmap = lt.concat_skip(prev, sk)
       meta = dict(transposed=True, stride=pool[ii], pool=1, relu=act[ii] is not None, chan_map=cmap)
       bn = _bn(ii, cp) if use_bn[ii] else None
-      y, mean, var = rt.ConvBNActPool.apply(rt._pad_channels(prev), w[ii], b[ii], bn[1] if bn else None,
+      y, mean, var = lt.ConvBNActPool.apply(lt._pad_channels(prev), w[ii], b[ii], bn[1] if bn else None,
                                             bn[0] if bn else None, meta)
       if bn:
         _ema_update(bn[2], bn[3], mean, var)

@@ -2,7 +2,8 @@
 'nccl' = RCCL on ROCm, 'gloo' on CPU for tests).  The path shards over independent images
 (SURVEY.md §8e): rank r decodes images [r*B/N, (r+1)*B/N) with NO data-path collective;
 torch.distributed is used only for the barrier, the max-over-ranks timing and an optional
-host-side gather of the small score tensor."""
+host-side gather of the small score tensor.  Training adds the collectives of a synchronised
+BatchNorm (sync_moments, allreduce_sums; ra_layer_train calls them, ra_train re-exports them)."""
 import os
 
 import torch
@@ -72,3 +73,44 @@ def gather_scores(s_local, world):
   torch.distributed.all_gather(out, s_local.contiguous()) if len(set(sizes)) == 1 else \
       torch.distributed.all_gather_object(out, s_local.cpu())
   return out
+
+
+# ---- data-parallel training: whole-batch BatchNorm (model_opt['sync_bn'])
+
+
+def combine_moments(count, mean, var):
+  """Whole-batch moments from per-shard ones: count [R], mean / var [R,C] (biased variance, as tf.nn.moments) ->
+  (total count, mean [C], var [C]) by Chan's pairwise update (no E[x^2] - E[x]^2 cancellation)."""
+  count = count.to(mean.dtype)
+  n = count.sum()
+  w = (count / n)[:, None]
+  m = (w * mean).sum(dim=0)
+  v = (w * (var + (mean - m[None, :]) ** 2)).sum(dim=0)
+  return n, m, v
+
+
+def sync_moments(mean, var, n_local):
+  """BatchNorm batch moments over the GLOBAL batch (nnlib.py:98 normalises over the whole batch): every rank
+  contributes (count, mean, var) of its shard in ONE all_gather of 2C+1 floats; mean / var are overwritten with
+  the whole-batch moments.  Returns the global element count (n_local for world 1)."""
+  import torch.distributed as dist
+  if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
+    return float(n_local)
+  C = mean.numel()
+  mine = torch.empty(2 * C + 1, dtype=torch.float32, device=mean.device)
+  mine[:C], mine[C:2 * C], mine[2 * C] = mean, var, float(n_local)
+  parts = [torch.empty_like(mine) for _ in range(dist.get_world_size())]
+  dist.all_gather(parts, mine)
+  allp = torch.stack(parts)
+  n, m, v = combine_moments(allp[:, 2 * C], allp[:, :C], allp[:, C:2 * C])
+  mean.copy_(m)
+  var.copy_(v)
+  return float(n_local) * dist.get_world_size()  # equal shards (the trainers require batch_size % world == 0): no host sync
+
+
+def allreduce_sums(t):
+  """Sum of a small tensor over the ranks (the 2C per-channel sums of a synchronised BatchNorm backward)."""
+  import torch.distributed as dist
+  if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
+    dist.all_reduce(t, op=dist.ReduceOp.SUM)
+  return t

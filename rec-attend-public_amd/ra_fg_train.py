@@ -9,7 +9,7 @@ inputs (previous map + skip) of up to 1024.
   step.sync_model()                         # before model.run / model.statistics / model.prestage see the new weights
 
 One step is image_ops.random_transformation on (x, d_gt, y_gt) -> the cnn / dcnn stack, layer by layer, as
-ra_train.ConvBNActPool nodes on the batch moments (the conv, BatchNorm, pool and filter-gradient kernels of the full model's
+ra_layer_train.ConvBNActPool nodes on the batch moments (the conv, BatchNorm, pool and filter-gradient kernels of the full model's
 training step; parameter gradients accumulate in the bucket inside the kernels) -> ra_fg_stats_f32 for the value of the loss
 and its pieces -> FgLoss.backward = ra_fg_loss_bwd_f32 -> Adam (epsilon 1e-7, no gradient clip: fg_model.py:260-261) or
 momentum 0.9 (:262-263) on the bucket.  The weight-decay terms wd * l2_loss(w) of nnlib.weight_variable belong to total_loss
@@ -22,9 +22,9 @@ The wide path is OPT-IN, and the flag is not a tuning knob: the suite pins the d
 (tests/test_fg_train.py), so without `wide=True` every check answers as it did before the wide kernels existed.  With it a layer
 of more than 128 output channels, or of more than 128 input channels, runs as a WideConvBNActPool node: K1-wide forward
 (ra_conv3x3_wide_f32, previous map and skip as two sources, no concat), ra_bn_wide_* BatchNorm, the output-stationary filter
-gradient ra_conv3x3_wgrad_wide_acc_f32, and a data gradient per source through K1-wide on a device pack of that source's
-output-channel range (ra_conv_wide_pack_weights_dev).  The wide path is float32 and uncaptured, and has been measured on
-synthetic data only.
+gradient ra_conv3x3_wgrad_wide_acc_f32, and a data gradient per source (ra_layer_train.conv_dgrad on that source's rows of the
+filter: K1-wide on a device pack of that output-channel range, ra_conv_wide_pack_weights_dev).  Both nodes live in
+ra_layer_train.  The wide path is float32 and uncaptured, and has been measured on synthetic data only.
 
 Not built, refused by name in the constructor: without wide=True, a layer of more than 128 output channels or a dcnn layer
 whose input (previous map + skip) has more than 128 channels; with it, a wide layer with a filter size other than 3, more than
@@ -46,6 +46,7 @@ import nnlib as nn
 import ra_native as rn
 import ra_ops as ops
 import ra_train as rt
+from ra_layer_train import ConvBNActPool, WideConvBNActPool, _pad_channels, _source_maps, concat_skip, pad4  # noqa: F401
 from ra_native import check, ptr
 
 BETA1, BETA2, ADAM_EPS = 0.9, 0.999, 1e-7  # tf.train.AdamOptimizer(learn_rate, epsilon=1e-7), fg_model.py:258-261
@@ -158,7 +159,6 @@ def _runs_wide(cin_w, cout):
 
 def _check_wide_layer(lib, d, scope, i, cin_w, cout, what):
   """check_kernel_forms for a layer that runs as a WideConvBNActPool node: the new plan / support queries instead of a refusal."""
-  pad4 = lambda c: -(-c // 4) * 4
   sources = _layer_sources(d, scope, i)
   ups = int(scope == 'dcnn' and d['dcnn_pool'][i] == 2)
   fs = d['%s_filter_size' % scope][i]
@@ -197,7 +197,6 @@ def check_kernel_forms(d, wide=False):
   wide: the opt-in wide path (the module docstring says why it is a flag) admits up to 512 output and 1024 input channels."""
   lib = rn.lib()
   rec = (C.c_int * rn.RA_PLAN_INTS)()
-  pad4 = lambda c: -(-c // 4) * 4
   for scope, i, cin_w, cout, bn in _layers(d):
     what = 'fg_model: %s layer %d (%d -> %d channels)' % (scope, i, cin_w, cout)
     if wide and _runs_wide(cin_w, cout):
@@ -230,179 +229,8 @@ def _check_bn_forms(lib, d, scope, i, cout, what):
 
 def _dcnn_packed_width(d, i):
   """Channels of dcnn layer i's kernel input: the previous map and the skip map, each padded to a multiple of 4."""
-  pad4 = lambda c: -(-c // 4) * 4
   sk = d['dcnn_skip_ch'][i] if d['dcnn_skip_ch'] else 0
   return pad4(d['dcnn_channels'][i]) + (pad4(sk) if sk else 0)
-
-
-def _source_maps(c0, C0, c1, C1, dev):
-  """Kernel channel -> filter row for a layer whose kernel input is [x0 (C0 channels, c0 real) | x1 (C1, c1 real)] and whose
-  filter has c0 + c1 input rows: (the whole input's map, x0's, x1's) as int32 device tensors; None where the kernels' default
-  (channel c is row c) says the same."""
-  m0 = list(range(c0)) + [-1] * (C0 - c0)
-  m1 = [c0 + m for m in range(c1)] + [-1] * (C1 - c1)
-  t = lambda m: rt._const('cmap', tuple(m), dev, lambda: torch.tensor(m, dtype=torch.int32, device=dev))
-  whole = None if (C0 == c0 and C1 == c1) else t(m0 + m1)
-  return whole, (None if (C0 == c0 and not C1) else t(m0)), (t(m1) if C1 else None)
-
-
-def _ones_zeros(n, dev):
-  return (rt._const('ones', n, dev, lambda: torch.ones(n, dtype=torch.float32, device=dev)),
-          rt._const('zeros', n, dev, lambda: torch.zeros(n, dtype=torch.float32, device=dev)))
-
-
-def _source_dgrad(duc, w, tr, stride, first, n, x_shape, cout, cache):
-  """The data gradient towards ONE source of a layer: the conv kernel on the flipped, in/out-swapped packing of the filter's
-  input rows [first, first + n) — K1-wide on a device pack of that output-channel range beyond 128 channels, K1 up to there —
-  then, for a stride-2 layer, the odd positions of the full-resolution result.  duc [B,H,W,cd]: du, channels padded to % 4."""
-  B, Hs, Ws, Cs = x_shape
-  dev, cd = duc.device, duc.shape[3]
-  pm = rt._pad_map(cout, cd, dev)
-  wd = w.detach()
-  if n > nn.WIDE_COUT:
-    key = ('wide-dgrad', w.data_ptr(), w._version, first, n)
-    hit = cache.get(key)
-    if hit is None:  # the filter read with rows and columns swapped: cout input rows, the source's n of the cin_w output columns
-      hit = cache[key] = (w, ops.pack_wide_weights_dev(wd, cin_kernel=cd, chan_map=pm, transposed=not tr, co_first=first, co_count=n))
-    ones, zeros = _ones_zeros(n, dev)
-    dxr = ops.conv_wide(duc, hit[1], ones, zeros, n, relu=False, pool=1)
-  else:
-    whole = first == 0 and n == (w.shape[3] if tr else w.shape[2])
-    ws = wd if whole else (wd[:, :, :, first:first + n] if tr else wd[:, :, first:first + n, :]).contiguous()
-    ones, zeros = _ones_zeros(ops.cout_padded(n), dev)
-    dxr = ops.conv3x3(duc, rt._pack_dev(ws, cout, n, cd, pm, not tr, cache), ones, zeros, n, relu=False, pool=1)
-  if stride == 2:
-    sub = rt._f(B, Hs, Ws, n, device=dev)
-    check(rn.lib().ra_subsample_odd_f32(ptr(dxr), B, Hs, Ws, n, ptr(sub), rn.stream_ptr()), 'ra_subsample_odd_f32')
-    dxr = sub
-  if Cs != n:  # padding channels of the source
-    dx = torch.zeros((B, Hs, Ws, Cs), dtype=torch.float32, device=dev)
-    dx[..., :n] = dxr
-    return dx
-  return dxr
-
-
-class WideConvBNActPool(torch.autograd.Function):
-  """ra_train.ConvBNActPool's contract for a layer of nnlib.cnn (nnlib.py:229-253) or nnlib.dcnn (nnlib.py:362-400) beyond K1's
-  128 channels, on either side, in training mode.  float32.
-
-  x0 [B,Hs,Ws,C0] the previous map and x1 [B,Hs,Ws,C1] the skip map or None (each % 4; concat(x0, x1) is never formed), w in the
-  reference layout ([3,3,Cin,Cout]; transposed: [3,3,Cout,Cin]) whose input rows are meta['c0'] of x0's channels followed by
-  meta['c1'] of x1's, b [Cout], gamma / beta [Cout] or None.  meta: transposed, stride, pool, relu, c0, c1, cache, and grads =
-  (gw, gb, ggamma, gbeta) views of a gradient bucket, which then receive the parameter gradients inside the kernels.
-  Returns (y, batch mean, batch var); backward returns a gradient per source.  A constant number of launches per layer:
-    Cout > 128   K1-wide, ra_bn_wide_*, ra_conv3x3_wgrad_wide_acc_f32 (once per source, through a channel map)
-    Cout <= 128  K1, ra_bn_*, ra_conv3x3_wgrad_acc_f32 (likewise): only the data gradient is wide
-  and the data gradient per source by _source_dgrad."""
-
-  @staticmethod
-  def forward(ctx, x0, x1, w, b, gamma, beta, meta):
-    ctx.set_materialize_grads(False)
-    dev = x0.device
-    x0 = x0.contiguous()
-    x1 = None if x1 is None else x1.contiguous()
-    B, Hs, Ws, C0 = x0.shape
-    C1 = 0 if x1 is None else x1.shape[3]
-    tr, stride, pool, relu = meta['transposed'], meta['stride'], meta['pool'], meta['relu']
-    cout, cin_w = (w.shape[2], w.shape[3]) if tr else (w.shape[3], w.shape[2])
-    c0, c1 = meta['c0'], meta.get('c1', 0)
-    if c0 + c1 != cin_w or c0 > C0 or c1 > C1 or tuple(w.shape[:2]) != (3, 3):
-      raise rn.RecAttendError('WideConvBNActPool: a 3x3 filter of %d input rows for sources of %d (of %d) + %d (of %d) channels' %
-                              (cin_w, c0, C0, c1, C1))
-    cache = meta.get('cache')
-    cache = rt._PACK if cache is None else cache
-    whole, _, _ = _source_maps(c0, C0, c1, C1, dev)
-    use_bn = gamma is not None
-    lib = rn.lib()
-    mean = var = None
-    if cout > nn.WIDE_COUT:
-      key = ('wide', w.data_ptr(), w._version, C0, C1, bool(tr))
-      hit = cache.get(key)
-      if hit is None:
-        hit = cache[key] = (w, ops.pack_wide_weights_dev(w.detach().contiguous(), cin_kernel=C0 + C1, chan_map=whole, transposed=tr))
-      ones, _ = _ones_zeros(cout, dev)
-      u = ops.conv_wide(x0, hit[1], ones, b.detach(), cout, relu=False, pool=1, src1=x1, upsample=(stride == 2))
-      if use_bn:
-        mean, var = ops.bn_wide_moments(u)
-      y = ops.bn_wide_act_pool(u, mean, var, gamma, beta, relu=relu, pool=pool)
-    else:
-      cp = ops.cout_padded(cout)
-      ones, _ = _ones_zeros(cp, dev)
-      shift = b.detach() if cp == cout else torch.nn.functional.pad(b.detach(), (0, cp - cout))
-      wp = rt._pack_dev(w.contiguous(), cin_w, cout, C0 + C1, whole, tr, cache)
-      u = ops.conv3x3(x0, wp, ones, shift, cout, relu=False, pool=1, src1=x1, upsample=(stride == 2))
-      _, H, W, _ = u.shape
-      if use_bn:
-        mean, var = rt._f(cout, device=dev), rt._f(cout, device=dev)
-        ws = rt._f(lib.ra_bn_workspace_floats(cout), device=dev)
-        check(lib.ra_bn_moments_f32(ptr(u), B * H * W, cout, ptr(ws), ws.numel(), ptr(mean), ptr(var), rn.stream_ptr()), 'ra_bn_moments_f32')
-      y = rt._f(B, H // pool, W // pool, cout, device=dev)
-      check(lib.ra_bn_act_pool_f32(ptr(u), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(ops.BN_EPS), int(relu), int(pool), B, H, W,
-                                   cout, ptr(y), rn.stream_ptr()), 'ra_bn_act_pool_f32')
-    ctx.meta, ctx.cache = meta, cache
-    ctx.save_for_backward(x0, x1, w, u, mean, var, gamma, beta)
-    if use_bn:
-      ctx.mark_non_differentiable(mean, var)
-      return y, mean, var
-    z = torch.zeros(0, device=dev)
-    ctx.mark_non_differentiable(z)
-    return y, z, z
-
-  @staticmethod
-  def backward(ctx, dy, _dm, _dv):
-    if dy is None:
-      return None, None, None, None, None, None, None
-    x0, x1, w, u, mean, var, gamma, beta = ctx.saved_tensors
-    meta, cache = ctx.meta, ctx.cache
-    dev = x0.device
-    tr, stride, pool, relu = meta['transposed'], meta['stride'], meta['pool'], meta['relu']
-    B, Hs, Ws, C0 = x0.shape
-    C1 = 0 if x1 is None else x1.shape[3]
-    _, H, W, cout = u.shape
-    cin_w = w.shape[3] if tr else w.shape[2]
-    c0, c1 = meta['c0'], meta.get('c1', 0)
-    _, m0, m1 = _source_maps(c0, C0, c1, C1, dev)
-    dy = dy.contiguous()
-    lib = rn.lib()
-    grads = meta.get('grads')  # views of the flat gradient bucket: the kernels add to them; else fresh tensors are returned
-    if grads is not None:
-      gw, gb, gg, gbt = grads
-    else:
-      gw, gb, gg, gbt = torch.zeros_like(w), torch.zeros(cout, dtype=torch.float32, device=dev), None, None
-    wide = cout > nn.WIDE_COUT
-    ups = int(stride == 2)
-    # ---- BatchNorm / ReLU / pool, then the filter gradient of the SAME conv that ran, source by source (gb once)
-    if wide:
-      du, dgamma, dbeta = ops.bn_wide_act_pool_bwd(u, dy, mean, var, gamma, beta, relu=relu, pool=pool, acc_gamma=gg, acc_beta=gbt)
-      wws = None
-      for xs, ms in ((x0, m0), (x1, m1)):
-        if xs is not None:
-          n = lib.ra_conv3x3_wgrad_wide_workspace_floats(xs.shape[3], cout, B, H, W)
-          wws = wws if wws is not None and wws.numel() >= n else rt._f(n, device=dev)
-          ops.wgrad_wide_acc(xs, du, gw, gb if xs is x0 else None, chan_map=ms, transposed=tr, upsample=bool(ups), ws=wws)
-    else:
-      du, dgamma, dbeta = torch.empty_like(u), rt._f(cout, device=dev), rt._f(cout, device=dev)
-      ws = rt._f(lib.ra_bn_workspace_floats(cout), device=dev)
-      check(lib.ra_bn_act_pool_bwd_acc_f32(ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(ops.BN_EPS), int(relu),
-                                           int(pool), B, H, W, cout, ptr(ws), ws.numel(), ptr(dgamma), ptr(dbeta), ptr(du), ptr(gg), ptr(gbt),
-                                           rn.stream_ptr()), 'ra_bn_act_pool_bwd_acc_f32')
-      for xs, ms in ((x0, m0), (x1, m1)):
-        if xs is not None:
-          nws = lib.ra_conv3x3_wgrad_workspace_floats(xs.shape[3], cout, B, H, W)
-          wws = rt._f(nws, device=dev)
-          check(lib.ra_conv3x3_wgrad_acc_f32(ptr(xs), xs.shape[3], B, Hs, Ws, ups, ptr(du), cout, ptr(wws), nws, ptr(ms), int(cin_w), int(tr),
-                                             ptr(gw), ptr(gb if xs is x0 else None), rn.stream_ptr()), 'ra_conv3x3_wgrad_acc_f32')
-    # ---- the data gradient, one conv per source
-    dx = [None, None]
-    if any(ctx.needs_input_grad[:2]):
-      duc = rt._pad_channels(du)
-      for s, (xs, first, n) in enumerate(((x0, 0, c0), (x1, c0, c1))):
-        if xs is not None and ctx.needs_input_grad[s]:
-          dx[s] = _source_dgrad(duc, w, tr, stride, first, n, tuple(xs.shape), cout, cache)
-    use_bn = gamma is not None
-    if grads is not None:
-      return dx[0], dx[1], None, None, None, None, None
-    return dx[0], dx[1], gw, gb, (dgamma if use_bn else None), (dbeta if use_bn else None), None
 
 
 class FgTrainStep(object):
@@ -508,7 +336,7 @@ class FgTrainStep(object):
     if 'c0' in meta:
       y, mean, var = WideConvBNActPool.apply(x, skip, *params, meta)
     else:
-      y, mean, var = rt.ConvBNActPool.apply(x, *params, meta)
+      y, mean, var = ConvBNActPool.apply(x, *params, meta)
     if bn:
       stats[key] = (mean, var)
     return y
@@ -522,7 +350,7 @@ class FgTrainStep(object):
       meta = dict(transposed=False, stride=1, pool=d['cnn_pool'][i], relu=True, chan_map=None)
       if self.wide and _runs_wide(d['cnn_channels'][i], d['cnn_channels'][i + 1]):
         meta.update(c0=h.shape[3], c1=0)
-      h = self._layer(rt._pad_channels(h), 'cnn', i, d['use_bn'], meta, stats)
+      h = self._layer(_pad_channels(h), 'cnn', i, d['use_bn'], meta, stats)
       maps.append(h)
     nd = len(d['dcnn_filter_size'])
     for i in range(nd):
@@ -531,19 +359,13 @@ class FgTrainStep(object):
       if self.wide and _runs_wide(d['dcnn_in_ch'][i], d['dcnn_channels'][i + 1]):  # previous map and skip as two sources
         sk = maps[src] if src is not None else None
         meta = dict(transposed=True, stride=d['dcnn_pool'][i], pool=1, relu=not last, c0=h.shape[3], c1=sk.shape[3] if sk is not None else 0)
-        h = self._layer(rt._pad_channels(h), 'dcnn', i, d['use_bn'] and not last, meta, stats,
-                        skip=rt._pad_channels(sk) if sk is not None else None)
+        h = self._layer(_pad_channels(h), 'dcnn', i, d['use_bn'] and not last, meta, stats,
+                        skip=_pad_channels(sk) if sk is not None else None)
         continue
       if src is not None:  # concat(prev, skip) (nnlib.py:365) as one packed input; chan_map sends each packed channel to its filter row
-        sk, prev_c = maps[src], h.shape[3]
-        hp, skp = rt._pad_channels(h), rt._pad_channels(sk)
-        cmap = list(range(prev_c)) + [-1] * (hp.shape[3] - prev_c) + [prev_c + m for m in range(sk.shape[3])] + \
-            [-1] * (skp.shape[3] - sk.shape[3])
-        if cmap == list(range(len(cmap))):
-          cmap = None
-        h = torch.cat([hp, skp], dim=3)
+        h, cmap = concat_skip(h, maps[src])
       meta = dict(transposed=True, stride=d['dcnn_pool'][i], pool=1, relu=not last, chan_map=cmap)
-      h = self._layer(rt._pad_channels(h), 'dcnn', i, d['use_bn'] and not last, meta, stats)
+      h = self._layer(_pad_channels(h), 'dcnn', i, d['use_bn'] and not last, meta, stats)
     return h
 
   def forward_loss(self, x, y_gt, d_gt=None, draws=None, generator=None):

@@ -6,6 +6,7 @@ calling with CPU tensors raises.  Host-side weight repacking (ra_conv_pack_weigh
 ra_conv_fold_bn, ra_ctrl_pack_weights) runs in the library's C++ and works without a GPU.
 """
 import ctypes as C
+import os
 
 import numpy as np
 import torch
@@ -16,12 +17,13 @@ from ra_native import check, ptr
 BN_EPS = 1e-3  # nnlib.py:119
 
 
-def _need_cuda(*ts):
+def _need_cuda(*ts, f32=True):
+  """f32=False: tensors that may be stored as bf16 (checked for device and contiguity only)."""
   for t in ts:
     if t is not None and not t.is_cuda:
       raise rn.RecAttendError('recattend kernels need CUDA (HIP) tensors; got a CPU tensor. '
                               'There is no CPU fallback.')
-    if t is not None and (t.dtype != torch.float32 or not t.is_contiguous()):
+    if t is not None and ((f32 and t.dtype != torch.float32) or not t.is_contiguous()):
       raise rn.RecAttendError('recattend kernels need contiguous float32 tensors')
 
 
@@ -332,7 +334,7 @@ def conv2d_fused(src0, wp, scale, shift, cout, ksize, relu=True, pool=1, src1=No
   return out
 
 
-# ---- training layers of filter size 1, 5 and 7 (csrc/ra_wgrad_kxk.hip; ra_train.ConvBNActPool)
+# ---- training layers of filter size 1, 5 and 7 (csrc/ra_wgrad_kxk.hip; ra_layer_train.ConvBNActPool)
 
 _WGK_FIELDS = sorted((v, k[len('RA_WGK_PLAN_'):].lower()) for k, v in rn.CONSTANTS.items() if k.startswith('RA_WGK_PLAN_') and k != 'RA_WGK_PLAN_INTS')
 
@@ -448,7 +450,7 @@ def conv_wide(src0, wp, scale, shift, cout, relu=True, pool=1, src1=None, upsamp
   return out
 
 
-# ---- training the wide layers (csrc/ra_wgrad_wide.hip, ra_bn_wide.hip; ra_fg_train.WideConvBNActPool)
+# ---- training the wide layers (csrc/ra_wgrad_wide.hip, ra_bn_wide.hip; ra_layer_train.WideConvBNActPool)
 
 
 def pack_wide_weights_dev(w, cin_kernel=None, chan_map=None, transposed=False, co_first=0, co_count=None):
@@ -513,46 +515,212 @@ def wgrad_wide_acc(x, du, gw, gb=None, chan_map=None, transposed=False, upsample
   return gw
 
 
-def _bn_wide_ws(C_, device, ws):
-  n = rn.lib().ra_bn_wide_workspace_floats(int(C_))
-  return ws if ws is not None and ws.numel() >= n else torch.empty(n, dtype=torch.float32, device=device)
+# ---- BatchNorm / filter gradient / subsample of the training layers (csrc/ra_bn.hip, ra_bn_wide.hip, ra_wgrad.hip; ra_layer_train).
+# wide: the ra_bn_wide_* kernels (C % 4 == 0 up to 512).
+
+_POISON = os.environ.get('RA_POISON')  # a debugging aid: every scratch tensor starts as this value (e.g. "nan") instead of stale memory
 
 
-def bn_wide_moments(u, ws=None):
-  """(mean, var) [C] of u [..., C] over every other axis, biased (tf.nn.moments, nnlib.py:98): any C % 4 == 0 up to 512."""
+def _f(*shape, device):
+  if _POISON:
+    return torch.full(shape, float(_POISON), dtype=torch.float32, device=device)
+  return torch.empty(shape, dtype=torch.float32, device=device)
+
+
+def bn_workspace(C_, like, ws=None, groups=1, wide=False):
+  """ws if it is large enough for `groups` BatchNorm passes over C_ channels, else a new workspace of the library's size."""
+  n = groups * (rn.lib().ra_bn_wide_workspace_floats if wide else rn.lib().ra_bn_workspace_floats)(int(C_))
+  return ws if ws is not None and ws.numel() >= n else _f(n, device=like.device)
+
+
+def bn_moments(u, ws=None, out=None, wide=False):
+  """(mean, var) [C] of u [..., C] over every other axis, biased (tf.nn.moments, nnlib.py:98); out = (mean, var) to fill."""
   _need_cuda(u, ws)
   C_ = u.shape[-1]
-  mean, var = (torch.empty(C_, dtype=torch.float32, device=u.device) for _ in range(2))
-  ws = _bn_wide_ws(C_, u.device, ws)
-  check(rn.lib().ra_bn_wide_moments_f32(ptr(u), u.numel() // C_, C_, ptr(ws), ws.numel(), ptr(mean), ptr(var), rn.stream_ptr()),
-        'ra_bn_wide_moments_f32')
+  mean, var = out if out is not None else (_f(C_, device=u.device), _f(C_, device=u.device))
+  ws = bn_workspace(C_, u, ws, wide=wide)
+  name = 'ra_bn_wide_moments_f32' if wide else 'ra_bn_moments_f32'
+  check(getattr(rn.lib(), name)(ptr(u), u.numel() // C_, C_, ptr(ws), ws.numel(), ptr(mean), ptr(var), rn.stream_ptr()), name)
   return mean, var
 
 
-def bn_wide_act_pool(u, mean, var, gamma, beta, relu=True, pool=1, out=None):
-  """y = max_pool(relu?(gamma (u - mean) rsqrt(var + 1e-3) + beta)) for u [B,H,W,C], C % 4 == 0 up to 512; mean / var / gamma /
-  beta None together: y = pool(relu?(u))."""
-  _need_cuda(u, mean, var, gamma, beta, out)
+def conv3x3_train(x, wp, scale, shift, cout, upsample=False, bf16=False, out=None, store_flags=None, moments=True):
+  """The training forward's conv3x3 (no ReLU, no pool) -> (u, part, nparts); moments: nparts per-wave channel sums in part, for
+  bn_moments_from_partials.  store_flags (bit 0: x is bf16, bit 1: out is bf16): ra_conv3x3_bf16_f32; None: ra_conv3x3_moments_f32."""
+  _need_cuda(x, wp, scale, shift, out, f32=False)
+  B, Hs, Ws, cin = x.shape
+  u = _conv_out(x, cout, 1, upsample, out)
+  part = _f(rn.lib().ra_conv3x3_moments_part_floats(int(cout)), device=x.device) if moments else None
+  nparts = C.c_int(0)
+  head = (ptr(x), cin, None, 0, B, Hs, Ws, int(bool(upsample)), ptr(wp), ptr(scale), ptr(shift), int(cout), 0)
+  tail = (ptr(part), part.numel(), C.byref(nparts)) if moments else (None, 0, None)
+  if store_flags is None:
+    check(rn.lib().ra_conv3x3_moments_f32(*head, int(bool(bf16)), ptr(u), *tail, rn.stream_ptr()), 'ra_conv3x3_moments_f32')
+  else:
+    check(rn.lib().ra_conv3x3_bf16_f32(*head, 1, ptr(u), *tail, int(store_flags), rn.stream_ptr()), 'ra_conv3x3_bf16_f32')
+  return u, part, nparts.value
+
+
+def bn_moments_from_partials(part, nparts, C_, out=None):
+  """(mean, var) [C] from the nparts per-wave channel sums a conv epilogue left (conv3x3_train)."""
+  _need_cuda(part)
+  mean, var = out if out is not None else (_f(C_, device=part.device), _f(C_, device=part.device))
+  check(rn.lib().ra_bn_moments_from_partials_f32(ptr(part), int(nparts), int(C_), ptr(mean), ptr(var), rn.stream_ptr()),
+        'ra_bn_moments_from_partials_f32')
+  return mean, var
+
+
+def bn_act_pool(u, mean, var, gamma, beta, relu=True, pool=1, out=None, store_flags=None, wide=False):
+  """y = max_pool(relu?(gamma (u - mean) rsqrt(var + 1e-3) + beta)) for u [B,H,W,C]; the four None together: y = pool(relu?(u)).
+  store_flags (bit 0: u stored as bf16, bit 1: out, then required, written as bf16): the bf16-storage form (narrow kernels only)."""
+  _need_cuda(u, out, f32=False)
+  _need_cuda(mean, var, gamma, beta)
   B, H, W, C_ = u.shape
   if out is None:
     out = torch.empty((B, H // pool, W // pool, C_), dtype=torch.float32, device=u.device)
-  check(rn.lib().ra_bn_wide_act_pool_f32(ptr(u), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(BN_EPS), int(relu), int(pool), B, H, W,
-                                         C_, ptr(out), rn.stream_ptr()), 'ra_bn_wide_act_pool_f32')
+  head = (ptr(u), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(BN_EPS), int(relu), int(pool), B, H, W, C_, ptr(out))
+  if store_flags is not None:
+    assert not wide
+    check(rn.lib().ra_bn_act_pool_bf16_f32(*head, int(store_flags), rn.stream_ptr()), 'ra_bn_act_pool_bf16_f32')
+  else:
+    name = 'ra_bn_wide_act_pool_f32' if wide else 'ra_bn_act_pool_f32'
+    check(getattr(rn.lib(), name)(*head, rn.stream_ptr()), name)
   return out
 
 
-def bn_wide_act_pool_bwd(u, dy, mean, var, gamma, beta, relu=True, pool=1, acc_gamma=None, acc_beta=None, ws=None):
-  """The backward of bn_wide_act_pool with the batch statistics differentiated through -> (du, dgamma, dbeta); acc_gamma /
-  acc_beta (views of a gradient bucket, or None) receive += dgamma / dbeta in the kernel."""
-  _need_cuda(u, dy, mean, var, gamma, beta, acc_gamma, acc_beta, ws)
-  B, H, W, C_ = u.shape
-  du = torch.empty_like(u)
-  dgamma, dbeta = (torch.empty(C_, dtype=torch.float32, device=u.device) for _ in range(2))
-  ws = _bn_wide_ws(C_, u.device, ws)
-  check(rn.lib().ra_bn_wide_act_pool_bwd_acc_f32(ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(BN_EPS), int(relu),
-                                                 int(pool), B, H, W, C_, ptr(ws), ws.numel(), ptr(dgamma), ptr(dbeta), ptr(du),
-                                                 ptr(acc_gamma), ptr(acc_beta), rn.stream_ptr()), 'ra_bn_wide_act_pool_bwd_acc_f32')
+def bn_act_pool_bwd(u, dy, mean, var, gamma, beta, relu=True, pool=1, acc=None, ws=None, du=None, wide=False):
+  """The backward of bn_act_pool with the batch statistics differentiated through -> (du, dgamma, dbeta).  acc = (acc_gamma,
+  acc_beta), views of a gradient bucket or None: the entry point whose kernel adds dgamma / dbeta there; acc None: the plain one."""
+  acc = (None, None) if wide and acc is None else acc  # the wide kernels have the accumulating entry point only
+  _need_cuda(u, dy, mean, var, gamma, beta, ws, du, *(acc or ()))
+  C_ = u.shape[3]
+  du = torch.empty_like(u) if du is None else du
+  dgamma, dbeta = _f(C_, device=u.device), _f(C_, device=u.device)
+  ws = bn_workspace(C_, u, ws, wide=wide)
+  head = (ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(BN_EPS), int(relu), int(pool), *u.shape, ptr(ws), ws.numel(),
+          ptr(dgamma), ptr(dbeta), ptr(du))
+  if acc is None:
+    check(rn.lib().ra_bn_act_pool_bwd_f32(*head, rn.stream_ptr()), 'ra_bn_act_pool_bwd_f32')
+  else:
+    name = 'ra_bn_wide_act_pool_bwd_acc_f32' if wide else 'ra_bn_act_pool_bwd_acc_f32'
+    check(getattr(rn.lib(), name)(*head, ptr(acc[0]), ptr(acc[1]), rn.stream_ptr()), name)
   return du, dgamma, dbeta
+
+
+def bn_wide_moments(u, ws=None):
+  """bn_moments on the wide kernels (any C % 4 == 0 up to 512)."""
+  return bn_moments(u, ws=ws, wide=True)
+
+
+def bn_wide_act_pool(u, mean, var, gamma, beta, relu=True, pool=1, out=None):
+  """bn_act_pool on the wide kernels, float32 storage."""
+  return bn_act_pool(u, mean, var, gamma, beta, relu=relu, pool=pool, out=out, wide=True)
+
+
+def bn_wide_act_pool_bwd(u, dy, mean, var, gamma, beta, relu=True, pool=1, acc_gamma=None, acc_beta=None, ws=None):
+  """bn_act_pool_bwd on the wide kernels; acc_gamma / acc_beta (views of a gradient bucket, or None) receive += in the kernel."""
+  return bn_act_pool_bwd(u, dy, mean, var, gamma, beta, relu=relu, pool=pool, acc=(acc_gamma, acc_beta), ws=ws, wide=True)
+
+
+def bn_act_pool_bwd_reduce(u, dy, mean, var, gamma, beta, relu=True, pool=1, acc=(None, None), ws=None, out=None):
+  """First half of the backward on WHOLE-batch statistics: this rank's sums (dgamma, dbeta) into out, also added to acc."""
+  _need_cuda(u, dy, mean, var, gamma, beta, ws, *acc)
+  C_ = u.shape[3]
+  dgamma, dbeta = out if out is not None else (_f(C_, device=u.device), _f(C_, device=u.device))
+  ws = bn_workspace(C_, u, ws)
+  check(rn.lib().ra_bn_act_pool_bwd_reduce_f32(ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta), C.c_float(BN_EPS), int(relu), int(pool),
+                                               *u.shape, ptr(ws), ws.numel(), ptr(dgamma), ptr(dbeta), ptr(acc[0]), ptr(acc[1]), rn.stream_ptr()),
+        'ra_bn_act_pool_bwd_reduce_f32')
+  return dgamma, dbeta
+
+
+def bn_act_pool_bwd_dx(u, dy, mean, var, gamma, beta, dgamma_sum, dbeta_sum, n_total, relu=True, pool=1, du=None):
+  """Second half: du from the sums of the whole data-parallel batch of n_total elements per channel."""
+  _need_cuda(u, dy, mean, var, gamma, beta, du)
+  du = torch.empty_like(u) if du is None else du
+  check(rn.lib().ra_bn_act_pool_bwd_dx_f32(ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta), ptr(dgamma_sum), ptr(dbeta_sum),
+                                           C.c_double(n_total), C.c_float(BN_EPS), int(relu), int(pool), *u.shape, ptr(du), rn.stream_ptr()),
+        'ra_bn_act_pool_bwd_dx_f32')
+  return du
+
+
+def bn_act_pool_bwd_grouped(U, dY, tabs, G, relu=True, pool=1, store_flags=0, ws=None):
+  """The backward of G stacked calls of one layer, U [G * B,H,W,C], in one launch -> (du, dgamma [G,C], dbeta [G,C]).  tabs: device
+  table of 6 G pointers {mean, var, gamma, beta, gradient gamma, gradient beta}[G] (the last two receive +=); store_flags as the kernel's."""
+  _need_cuda(U, dY, tabs, ws, f32=False)
+  N, H, W, C_ = U.shape
+  du = torch.empty_like(U)
+  dgamma, dbeta = _f(G, C_, device=U.device), _f(G, C_, device=U.device)
+  ws = bn_workspace(C_, U, ws, groups=G)
+  check(rn.lib().ra_bn_act_pool_bwd_grouped_bf16_f32(ptr(U), ptr(dY), ptr(tabs), int(G), C.c_float(BN_EPS), int(relu), int(pool), N // G, H, W,
+                                                     C_, ptr(ws), ws.numel(), ptr(dgamma), ptr(dbeta), ptr(du), int(store_flags),
+                                                     rn.stream_ptr()), 'ra_bn_act_pool_bwd_grouped_bf16_f32')
+  return du, dgamma, dbeta
+
+
+def wgrad3x3_workspace_floats(cin, cout, B, H, W):
+  return rn.lib().ra_conv3x3_wgrad_workspace_floats(int(cin), int(cout), int(B), int(H), int(W))
+
+
+def _wgrad3x3_ws(x, du, ws):
+  n = wgrad3x3_workspace_floats(x.shape[3], du.shape[3], *du.shape[:3])
+  return ws if ws is not None and ws.numel() >= n else _f(n, device=x.device)
+
+
+def wgrad3x3(x, du, upsample=False, bf16=False, ws=None):
+  """(dw [3,3,Cin,Cout], db [Cout]) of the 3x3 conv that ran on x [B,Hs,Ws,Cin] and produced du's tensor [B,H,W,Cout]; upsample: the
+  stride-2 transposed form; bf16: bf16 operands, float32 sums."""
+  _need_cuda(x, du, ws)
+  B, Hs, Ws, cin = x.shape
+  cout = du.shape[3]
+  dw, db = _f(3, 3, cin, cout, device=x.device), _f(cout, device=x.device)
+  ws = _wgrad3x3_ws(x, du, ws)
+  name = 'ra_conv3x3_wgrad_bf16ops_f32' if bf16 else 'ra_conv3x3_wgrad_f32'
+  check(getattr(rn.lib(), name)(ptr(x), cin, B, Hs, Ws, int(bool(upsample)), ptr(du), cout, ptr(ws), ws.numel(), ptr(dw), ptr(db),
+                                rn.stream_ptr()), name)
+  return dw, db
+
+
+def wgrad3x3_acc(x, du, gw, gb=None, chan_map=None, transposed=False, upsample=False, bf16=False, ws=None):
+  """gw += wgrad3x3's filter gradient in the reference layout of the filter that ran ([3,3,cin_w,Cout]; transposed: [3,3,Cout,cin_w],
+  taps flipped), gb += the bias gradient (None: not wanted).  chan_map (int32 device tensor or None): kernel channel c -> filter row
+  chan_map[c], -1 = padding.  x and / or du stored as bf16: the bf16-storage form (bf16 operands)."""
+  _need_cuda(x, du, f32=False)
+  _need_cuda(gw, gb, ws)
+  B, Hs, Ws, cin = x.shape
+  ws = _wgrad3x3_ws(x, du, ws)
+  head = (ptr(x), cin, B, Hs, Ws, int(bool(upsample)), ptr(du), du.shape[3], ptr(ws), ws.numel(), ptr(chan_map),
+          int(gw.shape[3] if transposed else gw.shape[2]), int(bool(transposed)), ptr(gw), ptr(gb))
+  fmt = (1 if x.dtype == torch.bfloat16 else 0) | (2 if du.dtype == torch.bfloat16 else 0)
+  if fmt:
+    check(rn.lib().ra_conv3x3_wgrad_acc_bf16_f32(*head, fmt, rn.stream_ptr()), 'ra_conv3x3_wgrad_acc_bf16_f32')
+  else:
+    name = 'ra_conv3x3_wgrad_acc_bf16ops_f32' if bf16 else 'ra_conv3x3_wgrad_acc_f32'
+    check(getattr(rn.lib(), name)(*head, rn.stream_ptr()), name)
+  return gw
+
+
+def wgrad3x3_multi_acc(tab, n, seg_shape, cout, ws, gw, gb, chan_map=None, cin_w=None, transposed=False, upsample=False, bf16=False):
+  """wgrad3x3_acc summed over n calls of one layer in one pass: tab (int64 device tensor, 128 slots) holds the calls' x pointers
+  in [0, 64) and du pointers in [64, 128); seg_shape = (B,Hs,Ws,Cin) of every x; ws: wgrad3x3_workspace_floats(Cin, cout, n * B, H, W) floats."""
+  _need_cuda(ws, gw, gb)
+  B, Hs, Ws, cin = seg_shape
+  check(rn.lib().ra_conv3x3_wgrad_multi_acc_f32(tab.data_ptr(), tab.data_ptr() + 8 * 64, int(n), cin, B, Hs, Ws, int(bool(upsample)), int(cout),
+                                                ptr(ws), ws.numel(), ptr(chan_map), int(cin_w), int(bool(transposed)), ptr(gw), ptr(gb),
+                                                int(bf16), rn.stream_ptr()), 'ra_conv3x3_wgrad_multi_acc_f32')
+  return gw
+
+
+def subsample(x, even=False, out=None):
+  """Every second pixel of x [B,2 Hs,2 Ws,C] in both directions -> [B,Hs,Ws,C]: the odd positions (2 i + 1), or the even ones."""
+  _need_cuda(x, out)
+  B, H, W, C_ = x.shape
+  out = _f(B, H // 2, W // 2, C_, device=x.device) if out is None else out
+  if tuple(out.shape) != (B, H // 2, W // 2, C_):
+    raise rn.RecAttendError('subsample: out of shape %r for x of %r' % (tuple(out.shape), tuple(x.shape)))
+  name = 'ra_subsample_even_f32' if even else 'ra_subsample_odd_f32'
+  check(getattr(rn.lib(), name)(ptr(x), B, H // 2, W // 2, C_, ptr(out), rn.stream_ptr()), name)
+  return out
 
 
 def fg_head(logits, nsc, no, quantise=False, y_out=None, d_out=None, x=None, packed=None, canvas_plane=None):

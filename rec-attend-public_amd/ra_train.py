@@ -13,7 +13,7 @@ over the ranks and the optimizer kernel scales it by 1 / world (equal shards: ba
 required by the trainers).  BatchNorm batch moments (nnlib.py:98) are taken over the rank's shard by
 default; with model_opt['sync_bn'] every BN call gathers the ranks' (count, mean, M2) and its backward
 all-reduces the two per-channel sums, so that normalisation and gradient equal the single-process ones
-(sync_moments below).  Initial weights, Adam moments, EMA shadows and global_step are
+(ra_dist.sync_moments).  Initial weights, Adam moments, EMA shadows and global_step are
 broadcast from rank 0 when a trainer is built (broadcast_state), so ranks start from ONE model whatever
 their random seeds were.
 """
@@ -177,50 +177,13 @@ class GradBucket(object):
     return lr
 
 
-def combine_moments(count, mean, var):
-  """Whole-batch moments from per-shard ones: count [R], mean / var [R,C] (biased variance, as tf.nn.moments) ->
-  (total count, mean [C], var [C]) by Chan's pairwise update (no E[x^2] - E[x]^2 cancellation)."""
-  count = count.to(mean.dtype)
-  n = count.sum()
-  w = (count / n)[:, None]
-  m = (w * mean).sum(dim=0)
-  v = (w * (var + (mean - m[None, :]) ** 2)).sum(dim=0)
-  return n, m, v
-
-
-def sync_moments(mean, var, n_local):
-  """BatchNorm batch moments over the GLOBAL batch (nnlib.py:98 normalises over the whole batch): every rank
-  contributes (count, mean, var) of its shard in ONE all_gather of 2C+1 floats; mean / var are overwritten with
-  the whole-batch moments.  Returns the global element count (n_local for world 1)."""
-  import torch.distributed as dist
-  if not (dist.is_available() and dist.is_initialized()) or dist.get_world_size() == 1:
-    return float(n_local)
-  C = mean.numel()
-  mine = torch.empty(2 * C + 1, dtype=torch.float32, device=mean.device)
-  mine[:C], mine[C:2 * C], mine[2 * C] = mean, var, float(n_local)
-  parts = [torch.empty_like(mine) for _ in range(dist.get_world_size())]
-  dist.all_gather(parts, mine)
-  allp = torch.stack(parts)
-  n, m, v = combine_moments(allp[:, 2 * C], allp[:, :C], allp[:, C:2 * C])
-  mean.copy_(m)
-  var.copy_(v)
-  return float(n_local) * dist.get_world_size()  # equal shards (the trainers require batch_size % world == 0): no host sync
-
-
-def allreduce_sums(t):
-  """Sum of a small tensor over the ranks (the 2C per-channel sums of a synchronised BatchNorm backward)."""
-  import torch.distributed as dist
-  if dist.is_available() and dist.is_initialized() and dist.get_world_size() > 1:
-    dist.all_reduce(t, op=dist.ReduceOp.SUM)
-  return t
-
-
 # =====================================================================================================
 # The training graph (full_model.py:638-1057, phase_train = True) as a torch.autograd tape over
 # HIP kernels.  torch is the tape and the memory; what runs on the GPU:
 #   * every conv layer of the three CNNs — forward (MFMA conv, BN batch moments, normalise + ReLU +
 #     pool) and backward (BN / pool / ReLU adjoint, backward-data on the MFMA conv kernel with the
-#     flipped packing, backward-weight on MFMA) — ConvBNActPool, csrc/ra_train.hip + ra_wgrad.hip + ra_conv.hip;
+#     flipped packing, backward-weight on MFMA) — ra_layer_train.ConvBNActPool / ConvStackFn, csrc/ra_train.hip + ra_bn.hip +
+#     ra_wgrad.hip + ra_conv.hip;
 #   * the pairwise soft IoU of the two losses and its adjoint — PairIoU, csrc/ra_loss.hip;
 #   * the ground-truth boxes and both Hungarian matchings (device solver), clip + Adam;
 #   * the attention resample — box, read, write — forward on the decode loop's banded kernels and backward
@@ -237,13 +200,13 @@ BN_EPS = ops.BN_EPS
 EMA_DECAY = 0.9  # 1 - 0.1 * phase_train (nnlib.py:103-104)
 
 
-_POISON = os.environ.get('RA_POISON')  # a debugging aid: every scratch tensor starts as this value (e.g. "nan") instead of stale memory
-
-
-def _f(*shape, device):
-  if _POISON:
-    return torch.full(shape, float(_POISON), dtype=torch.float32, device=device)
-  return torch.empty(shape, dtype=torch.float32, device=device)
+import ra_layer_train as _layers
+from ra_dist import allreduce_sums, combine_moments, sync_moments  # noqa: F401
+from ra_layer_train import (EPILOGUE_MOMENTS, SPLIT_DGRAD, BatchNormTrain, ConvBNActPool, ConvStackFn, _DeferredWgrads,  # noqa: F401
+                            _LatestVersionPack, _PACK, _PackCache, _const, _f, _pack_dev, _pad_channels, _pad_map, concat_skip,
+                            conv_dgrad, stack_bn_dx, stack_bn_reduce)
+# TrainStep resolves the nodes, and the nodes the collectives, through THIS module's globals: a tool or a test can replace them here
+_layers.COLLECTIVES.update(sync_moments=lambda *a: sync_moments(*a), allreduce_sums=lambda t: allreduce_sums(t))
 
 
 _SIDE = {}
@@ -255,693 +218,6 @@ def _side_stream(device, which=0):
     _SIDE[k] = torch.cuda.Stream(device=device)
   return _SIDE[k]
 
-
-class _LatestVersionPack(dict):
-  """The pack cache of callers OUTSIDE a TrainStep (the train-mode nnlib closures, tests, one-off layer calls).  Keys carry the
-  source tensor's data pointer AND version — (ptr, version, geometry...), ('shift', ptr, version, cp), ('split', ptr, version,
-  transposed) — so an in-place optimizer step makes every entry of that weight stale; a plain dict kept them all and an
-  ordinary training loop over the closures grew by one set of packed filters per layer, direction and step (~1 MB
-  per step at the CVPPP arch).  Here a new version of the same (tensor, geometry) REPLACES the old entry, and the whole cache
-  is capped (oldest first) for callers that keep creating tensors."""
-  CAP = 2048
-
-  def __init__(self):
-    super().__init__()
-    self._latest = {}
-
-  @staticmethod
-  def _identity(key):
-    return (key[0], key[1]) + tuple(key[3:]) if isinstance(key[0], str) else (key[0],) + tuple(key[2:])
-
-  def __setitem__(self, key, value):
-    ident = self._identity(key)
-    old = self._latest.get(ident)
-    if old is not None and old != key:
-      super().pop(old, None)
-    self._latest[ident] = key
-    super().__setitem__(key, value)
-    while len(self) > self.CAP:
-      k0 = next(iter(self))
-      super().pop(k0)
-      self._latest.pop(self._identity(k0), None)
-
-  def clear(self):
-    super().clear()
-    self._latest.clear()
-
-
-_PACK = _LatestVersionPack()
-# A TrainStep owns its own cache
-# (TrainStep._pack, handed to the layer functions through meta['cache']): per step, (weight storage, geometry) -> packed
-# filter — the filters are shared by the T timesteps.  forward_loss() clears the trainer's dict (the optimizer writes the
-# weights through raw pointers); an entry keeps its source tensor alive and carries the tensor's version, so a caller
-# cannot be handed the pack of a freed tensor whose address was reused, nor one that predates an in-place update.
-
-
-class _PackCache(dict):
-  """A TrainStep's per-step cache of packed filters (cleared by every forward_loss), plus the step's PRE-PACKED filters:
-  the device packer only moves values, so packing an array of flat-bucket POSITIONS once per (layer, geometry) gives an
-  index map, and every later step packs all of its filters and pads all of its biases with ONE gather launch over the
-  parameter bucket (ra_gather_f32) instead of one pack launch (+ a fill and a copy for a padded bias) per layer and
-  direction.  A geometry seen for the first time takes the per-layer launch and joins the map for the next step."""
-
-  def __init__(self, trainer):
-    super().__init__()
-    self.tr = trainer
-    self.entries, self.pending = {}, []   # key -> (start, n) in self.wp; [(key, index map)] waiting for the next refresh
-    self.imap = self.wp = None
-    self.filled = -1                        # the pack epoch self.wp holds
-
-  def _where(self, t):
-    """Offset (in floats) of a contiguous float32 parameter inside the bucket, or None."""
-    par = self.tr.bucket.param
-    off = t.data_ptr() - par.data_ptr()
-    if t.dtype != torch.float32 or not t.is_contiguous() or off < 0 or off % 4 or off // 4 + t.numel() > par.numel():
-      return None
-    return off // 4
-
-  def _positions(self, t, off):
-    assert self.tr.bucket.param.numel() < (1 << 24)  # positions (+1; 0 = "no source") are exact in float32
-    return (torch.arange(t.numel(), device=t.device, dtype=torch.float32) + float(off + 1)).reshape(t.shape)
-
-  def lookup(self, key, t, make_map):
-    """key: the packing's geometry; t: the parameter; make_map(positions) -> packed positions.  The packed values of
-    this step, or None (first sight of the geometry, or a tensor outside the bucket: the caller packs as before)."""
-    off = self._where(t)
-    if off is None or not getattr(self.tr, 'prepack', True):
-      return None
-    key = (off, t.numel()) + key
-    hit = self.entries.get(key)
-    if hit is not None:
-      return self.wp[hit[0]:hit[0] + hit[1]] if self.filled == self.tr._pack_epoch else None
-    if all(k != key for k, _ in self.pending) and not torch.cuda.is_current_stream_capturing():
-      with torch.no_grad():
-        self.pending.append((key, (make_map(self._positions(t, off)).reshape(-1) - 1.0).to(torch.int32)))
-    return None
-
-  def merge(self):
-    """Take in the geometries met since the last merge.  Never inside a stream capture: the index map is built by eager
-    launches from tensors that are freed here (a captured copy of those launches would re-read freed memory at every
-    replay); TrainStep._graphed merges before it captures."""
-    if self.pending and not torch.cuda.is_current_stream_capturing():
-      self.tr._drop_captured_steps()  # the buffers below move
-      n0 = 0 if self.imap is None else self.imap.numel()
-      maps = ([self.imap] if n0 else [])
-      for key, m in self.pending:
-        pad = (-m.numel()) % 4       # 16-byte aligned views
-        self.entries[key] = (n0, m.numel())
-        maps.append(torch.nn.functional.pad(m, (0, pad), value=-1))
-        n0 += m.numel() + pad
-      self.imap = torch.cat(maps)
-      self.wp = torch.empty(n0, dtype=torch.float32, device=self.imap.device)
-      self.pending = []
-
-  def refresh(self):
-    """Once per optimisation step, after the epoch moved: this step's packed filters and padded biases, one gather."""
-    self.merge()
-    if self.imap is not None and getattr(self.tr, 'prepack', True):
-      check(rn.lib().ra_gather_f32(ptr(self.tr.bucket.param), ptr(self.imap), self.imap.numel(), ptr(self.wp), rn.stream_ptr()),
-            'ra_gather_f32')
-      self.filled = self.tr._pack_epoch
-
-
-def _pack_dev(w, cin_w, cout, cin, cmap_t, transposed, cache=None, ksize=3):
-  cache = _PACK if cache is None else cache
-  key = (w.data_ptr(), w._version, int(cin_w), int(cout), int(cin), 0 if cmap_t is None else cmap_t.data_ptr(), bool(transposed))
-  if ksize != 3:
-    key += (int(ksize),)
-  hit = cache.get(key)
-  if hit is not None:
-    return hit[1]
-  if isinstance(cache, _PackCache):
-    pre = cache.lookup(('w',) + key[2:], w, lambda pos: _pack_dev_now(pos, cin_w, cout, cin, cmap_t, transposed, ksize))
-    if pre is not None:
-      cache[key] = (w, pre)
-      return pre
-  out = _pack_dev_now(w, cin_w, cout, cin, cmap_t, transposed, ksize)
-  cache[key] = (w, out)
-  return out
-
-
-def _pack_dev_now(w, cin_w, cout, cin, cmap_t, transposed, ksize=3):
-  if ksize != 3:  # a filter of size 1, 5 or 7 (ra_convkxk_f32's packing)
-    return ops.pack_conv_weights_dev(w, ksize, cin_kernel=cin, chan_map=cmap_t, transposed=transposed)
-  n = rn.lib().ra_conv_packed_floats(cin, cout)
-  if n == 0:
-    raise rn.RecAttendError('unsupported conv shape Cin=%d Cout=%d' % (cin, cout))
-  out = _f(n, device=w.device)
-  check(rn.lib().ra_conv_pack_weights_dev(ptr(w), int(cin_w), int(cout), int(cin), ptr(cmap_t),
-                                          rn.RA_CONV_TRANSPOSED if transposed else 0, ptr(out), rn.stream_ptr()),
-        'ra_conv_pack_weights_dev')
-  return out
-
-
-_CONST = {}
-
-
-def _const(kind, key, device, make):
-  """Small constant device tensors (unit scales, zero shifts, channel maps) are built once: a training
-  step runs ~1300 layer calls and each host->device upload costs more than the kernel it feeds."""
-  k = (kind, key, str(device))
-  t = _CONST.get(k)
-  if t is None:
-    t = _CONST[k] = make()
-  return t
-
-
-def _pad_map(n_real, n_kernel, device):
-  """chan_map for a kernel input of n_kernel channels whose first n_real are real."""
-  if n_real == n_kernel:
-    return None
-  return _const('padmap', (n_real, n_kernel), device, lambda: torch.tensor(
-      list(range(n_real)) + [-1] * (n_kernel - n_real), dtype=torch.int32, device=device))
-
-
-def _pad_channels(t, mult=4):
-  c = t.shape[-1]
-  cp = -(-c // mult) * mult
-  if cp == c:
-    return t.contiguous()
-  out = torch.zeros(t.shape[:-1] + (cp,), dtype=t.dtype, device=t.device)
-  out[..., :c] = t
-  return out
-
-
-EPILOGUE_MOMENTS = {'on': os.environ.get('RA_EPI_MOMENTS', '1') != '0'}  # tuning aid: 0 = the two-pass moments kernels
-
-
-class _DeferredWgrads(dict):
-  """(scope, layer) -> the (x, du) pairs of the layer's calls in the running backward pass.  A filter shared by the
-  step's T timesteps (every nnlib.cnn / dcnn layer of full_model, full_model.py:455-535) sums T filter gradients; as
-  the end-of-backward callback this object forms each layer's sum in ONE pass over the images of all its calls
-  (ra_conv3x3_wgrad_multi_acc_f32 through two pointer tables): 4 launches per layer and step instead of 2 T, and the
-  patch-sized layers' fixed costs (launch, cross-wave reduction, partial sums) are paid once, not T times."""
-  armed = False
-
-  def reset(self):
-    """A new forward pass: nothing of an interrupted backward pass may be added to."""
-    self.armed = False
-    for slot in self.values():
-      slot['calls'] = []
-
-  def __call__(self):
-    self.armed = False
-    for slot in self.values():
-      calls, slot['calls'] = slot['calls'], []
-      Cx, cout, B, Hs, Ws, H, W, ups, _, cin_w, tr, bf = slot['shape']
-      for k in range(0, len(calls), 64):
-        part = calls[k:k + 64]
-        n = len(part)
-        nws = rn.lib().ra_conv3x3_wgrad_workspace_floats(Cx, cout, n * B, H, W)
-        if slot['ws'] is None or slot['ws'].numel() < nws:
-          slot['ws'] = _f(nws, device=slot['tab'].device)
-        tab = slot['tab']
-        for off, col in ((0, 0), (64, 1)):
-          host = (_C.c_void_p * n)(*[c[col].data_ptr() for c in part])
-          check(rn.lib().ra_ptr_table(host, n, tab.data_ptr() + 8 * off, rn.stream_ptr()), 'ra_ptr_table')
-        check(rn.lib().ra_conv3x3_wgrad_multi_acc_f32(tab.data_ptr(), tab.data_ptr() + 8 * 64, n, Cx, B, Hs, Ws, ups, cout,
-                                                      ptr(slot['ws']), slot['ws'].numel(), ptr(slot['cmap_t']), cin_w, tr,
-                                                      ptr(slot['gw']), ptr(slot['gb']), int(bf), rn.stream_ptr()),
-              'ra_conv3x3_wgrad_multi_acc_f32')
-
-
-class ConvBNActPool(torch.autograd.Function):
-  """One layer of nnlib.cnn (nnlib.py:229-253) or nnlib.dcnn (nnlib.py:362-400) in training mode.
-
-  x [B,Hs,Ws,Cx] (Cx % 4 == 0), w in the reference layout ([3,3,Cin,Cout]; transposed:
-  [3,3,Cout,Cin]), b [Cout], gamma / beta [Cout] or None.  Returns (y, batch mean, batch var).
-  A filter of size 1, 5 or 7 (meta['ksize'], default w.shape[0]) runs in float32 on ra_convkxk_f32, the two-pass batch moments
-  and ra_convkxk_wgrad_f32 / _acc_f32 (csrc/ra_wgrad_kxk.hip); its filter gradient is never deferred."""
-
-  @staticmethod
-  def forward(ctx, x, w, b, gamma, beta, meta):
-    ctx.set_materialize_grads(False)  # nothing differentiates mean / var: no zero tensors for their gradients
-    dev = x.device
-    x = x.contiguous()
-    B, Hs, Ws, Cx = x.shape
-    tr, stride, pool, relu = meta['transposed'], meta['stride'], meta['pool'], meta['relu']
-    cout, cin_w = (w.shape[2], w.shape[3]) if tr else (w.shape[3], w.shape[2])
-    cmap = meta.get('chan_map')
-    cmap_t = _const('cmap', tuple(cmap), dev, lambda: torch.tensor(cmap, dtype=torch.int32, device=dev)) \
-        if cmap is not None else _pad_map(cin_w, Cx, dev)
-    cp = ops.cout_padded(cout)
-    cache = meta.get('cache')
-    cache = _PACK if cache is None else cache
-    f = int(meta.get('ksize') or w.shape[0])  # the filter size: 3, or (train_any_filter) 1, 5, 7 on the float32 k x k kernels
-    if f != 3:
-      if meta.get('bf16') or meta.get('bf16_store'):
-        raise rn.RecAttendError("a layer of filter size %d trains in float32 only (compute_dtype = 'bf16' is built for 3x3 filters)" % f)
-      if cout > 128 or cp == 0:
-        raise rn.RecAttendError('a layer of filter size %d trains with up to 128 output channels, not %d' % (f, cout))
-    wp = _pack_dev(w.contiguous(), cin_w, cout, Cx, cmap_t, tr, cache, ksize=f)
-    scale = _const('ones', cp, dev, lambda: torch.ones(cp, dtype=torch.float32, device=dev))
-    shift = b.detach()
-    if cp != cout:  # padded once per step (the layer's bias is shared by all timesteps), not once per use
-      key = ('shift', b.data_ptr(), b._version, cp)
-      hit = cache.get(key)
-      if hit is None:
-        pre = cache.lookup(('b', cp), b.detach(), lambda pos: torch.nn.functional.pad(pos, (0, cp - cout))) \
-            if isinstance(cache, _PackCache) else None
-        hit = cache[key] = (b, pre if pre is not None else torch.nn.functional.pad(b.detach(), (0, cp - cout)))
-      shift = hit[1]
-    use_bn = gamma is not None
-    bf = bool(meta.get('bf16'))
-    mean = var = None
-    if use_bn:
-      mean, var = meta['stat_out'] if meta.get('stat_out') is not None else (_f(cout, device=dev), _f(cout, device=dev))
-    alloc = meta.get('alloc')  # the batched-backward step keeps u / y of a layer's T calls in one [T, ...] slab
-    place = (lambda kind, *shape: alloc(kind, shape)) if alloc is not None else (lambda kind, *shape: _f(*shape, device=dev))
-    up = 2 if stride == 2 else 1
-    if meta.get('bf16_store') and alloc is not None and use_bn and not meta.get('sync_bn'):
-      # bf16 mode, stacked step: u and y live in HBM as bf16 where the float4 BatchNorm kernels take the channel count (else
-      # float32; y also float32 where a float32 kernel reads it next: meta['y_f32']); the statistics come from the conv's
-      # float32 accumulators, before the rounding.  Forward only: the stacked graph's nodes hold the backward.
-      assert bf and not torch.is_grad_enabled()
-      H, W = Hs * up, Ws * up
-      st_ok = EPILOGUE_MOMENTS['on'] and ops.bn_form('forward', cout, B, H, W, pool) == 'v4' == ops.bn_form('backward', cout, B, H, W, pool, G=1)
-      ud = torch.bfloat16 if st_ok else torch.float32
-      yd = torch.bfloat16 if (st_ok and not meta.get('y_f32')) else torch.float32
-      u = alloc('u', (B, H, W, cout), ud)
-      xin = 1 if x.dtype == torch.bfloat16 else 0
-      if cout % 4 == 0 and EPILOGUE_MOMENTS['on']:
-        part = _f(rn.lib().ra_conv3x3_moments_part_floats(cout), device=dev)
-        nparts = _C.c_int(0)
-        check(rn.lib().ra_conv3x3_bf16_f32(ptr(x), Cx, None, 0, B, Hs, Ws, int(stride == 2), ptr(wp), ptr(scale), ptr(shift), cout, 0, 1,
-                                           ptr(u), ptr(part), part.numel(), _C.byref(nparts), xin | (2 if st_ok else 0),
-                                           rn.stream_ptr()), 'ra_conv3x3_bf16_f32')
-        check(rn.lib().ra_bn_moments_from_partials_f32(ptr(part), nparts.value, cout, ptr(mean), ptr(var), rn.stream_ptr()),
-              'ra_bn_moments_from_partials_f32')
-      else:  # a channel count without epilogue moments (the one-channel output layer): float32 u, two-pass moments
-        check(rn.lib().ra_conv3x3_bf16_f32(ptr(x), Cx, None, 0, B, Hs, Ws, int(stride == 2), ptr(wp), ptr(scale), ptr(shift), cout, 0, 1,
-                                           ptr(u), None, 0, None, xin, rn.stream_ptr()), 'ra_conv3x3_bf16_f32')
-        ws = _f(rn.lib().ra_bn_workspace_floats(cout), device=dev)
-        check(rn.lib().ra_bn_moments_f32(ptr(u), B * H * W, cout, ptr(ws), ws.numel(), ptr(mean), ptr(var), rn.stream_ptr()),
-              'ra_bn_moments_f32')
-      y = alloc('y', (B, H // pool, W // pool, cout), yd)
-      check(rn.lib().ra_bn_act_pool_bf16_f32(ptr(u), ptr(mean), ptr(var), ptr(gamma), ptr(beta), _C.c_float(BN_EPS), int(relu), int(pool),
-                                             B, H, W, cout, ptr(y), (1 if st_ok else 0) | (2 if yd == torch.bfloat16 else 0),
-                                             rn.stream_ptr()), 'ra_bn_act_pool_bf16_f32')
-      return y, mean, var
-    if use_bn and cout % 4 == 0 and EPILOGUE_MOMENTS['on'] and f == 3:
-      # the batch moments ride on the conv epilogue: per-wave channel sums, then one small finishing launch
-      u = place('u', B, Hs * up, Ws * up, cout)
-      part = _f(rn.lib().ra_conv3x3_moments_part_floats(cout), device=dev)
-      nparts = _C.c_int(0)
-      check(rn.lib().ra_conv3x3_moments_f32(ptr(x), Cx, None, 0, B, Hs, Ws, int(stride == 2), ptr(wp), ptr(scale), ptr(shift),
-                                            cout, 0, int(bf), ptr(u), ptr(part), part.numel(), _C.byref(nparts),
-                                            rn.stream_ptr()), 'ra_conv3x3_moments_f32')
-      check(rn.lib().ra_bn_moments_from_partials_f32(ptr(part), nparts.value, cout, ptr(mean), ptr(var), rn.stream_ptr()),
-            'ra_bn_moments_from_partials_f32')
-      H, W = u.shape[1], u.shape[2]
-    else:
-      if f == 3:
-        u = ops.conv3x3(x, wp, scale, shift, cout, relu=False, pool=1, upsample=(stride == 2), bf16=bf,
-                        out=place('u', B, Hs * up, Ws * up, cout))
-      else:  # ra_convkxk_f32, then the two-pass moments: its epilogue carries none
-        u = ops.conv2d_fused(x, wp, scale, shift, cout, f, relu=False, pool=1, upsample=(stride == 2),
-                             out=place('u', B, Hs * up, Ws * up, cout))
-      H, W = u.shape[1], u.shape[2]
-      if use_bn:
-        ws = _f(rn.lib().ra_bn_workspace_floats(cout), device=dev)
-        check(rn.lib().ra_bn_moments_f32(ptr(u), B * H * W, cout, ptr(ws), ws.numel(), ptr(mean), ptr(var),
-                                         rn.stream_ptr()), 'ra_bn_moments_f32')
-    if use_bn:
-      # whole-batch statistics under data parallelism (nnlib.py:98): one all_gather of (count, mean, var)
-      ctx.n_total = sync_moments(mean, var, B * H * W) if meta.get('sync_bn') else 0.0
-    y = place('y', B, H // pool, W // pool, cout)
-    check(rn.lib().ra_bn_act_pool_f32(ptr(u), ptr(mean), ptr(var), ptr(gamma), ptr(beta), _C.c_float(BN_EPS), int(relu),
-                                      int(pool), B, H, W, cout, ptr(y), rn.stream_ptr()), 'ra_bn_act_pool_f32')
-    ctx.meta, ctx.cmap, ctx.cache, ctx.ksize = meta, cmap, cache, f
-    if not use_bn:
-      ctx.n_total = 0.0
-    ctx.save_for_backward(x, w, u, mean, var, gamma, beta)
-    if use_bn:
-      ctx.mark_non_differentiable(mean, var)
-      return y, mean, var
-    z = torch.zeros(0, device=dev)
-    ctx.mark_non_differentiable(z)
-    return y, z, z
-
-  @staticmethod
-  def backward(ctx, dy, _dm, _dv):
-    if dy is None:
-      return None, None, None, None, None, None
-    x, w, u, mean, var, gamma, beta = ctx.saved_tensors
-    meta, cmap = ctx.meta, ctx.cmap
-    dev = x.device
-    tr, stride, pool, relu = meta['transposed'], meta['stride'], meta['pool'], meta['relu']
-    B, Hs, Ws, Cx = x.shape
-    _, H, W, cout = u.shape
-    cin_w = w.shape[3] if tr else w.shape[2]
-    dy = dy.contiguous()
-    ws = _f(rn.lib().ra_bn_workspace_floats(cout), device=dev)
-    dgamma, dbeta, du = _f(cout, device=dev), _f(cout, device=dev), torch.empty_like(u)
-    grads = meta.get('grads')  # (gw, gb, ggamma, gbeta): views of the flat gradient bucket -> accumulate in-kernel
-    f = ctx.ksize
-    # the filter gradient waits for the end of backward (3x3 only: the pointer-table form; another size accumulates per call)
-    deferred = grads is not None and meta.get('wgrad_defer') is not None and f == 3
-    nws = 0 if deferred else rn.lib().ra_convkxk_wgrad_workspace_floats(f, Cx, cout, B, H, W)
-    wws = None if deferred else _f(nws, device=dev)
-    synced = ctx.n_total > 0.0 and ctx.n_total != float(B * H * W)
-    bf = bool(meta.get('bf16'))  # compute_dtype = 'bf16': bf16 operands on the bf16 MFMA, float32 sums and tensors
-    wgrad_acc = rn.lib().ra_conv3x3_wgrad_acc_bf16ops_f32 if bf else rn.lib().ra_conv3x3_wgrad_acc_f32
-    wgrad_out = rn.lib().ra_conv3x3_wgrad_bf16ops_f32 if bf else rn.lib().ra_conv3x3_wgrad_f32
-
-    def bn_backward(acc_g, acc_b):
-      """dgamma / dbeta / du; with whole-batch statistics the two per-channel sums are all-reduced between the
-      reduction and the du pass (the bucket still receives this rank's own sums: it is summed over the ranks later)."""
-      if not synced:
-        if acc_g is not None:
-          check(rn.lib().ra_bn_act_pool_bwd_acc_f32(ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta),
-                                                    _C.c_float(BN_EPS), int(relu), int(pool), B, H, W, cout, ptr(ws), ws.numel(),
-                                                    ptr(dgamma), ptr(dbeta), ptr(du), ptr(acc_g), ptr(acc_b), rn.stream_ptr()),
-                'ra_bn_act_pool_bwd_acc_f32')
-        else:
-          check(rn.lib().ra_bn_act_pool_bwd_f32(ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta),
-                                                _C.c_float(BN_EPS), int(relu), int(pool), B, H, W, cout, ptr(ws), ws.numel(),
-                                                ptr(dgamma), ptr(dbeta), ptr(du), rn.stream_ptr()), 'ra_bn_act_pool_bwd_f32')
-        return dgamma, dbeta
-      both = _f(2 * cout, device=dev)
-      dgl, dbl = both[:cout], both[cout:]
-      check(rn.lib().ra_bn_act_pool_bwd_reduce_f32(ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta),
-                                                   _C.c_float(BN_EPS), int(relu), int(pool), B, H, W, cout, ptr(ws), ws.numel(),
-                                                   ptr(dgl), ptr(dbl), ptr(acc_g), ptr(acc_b), rn.stream_ptr()),
-            'ra_bn_act_pool_bwd_reduce_f32')
-      mine = both.clone()
-      allreduce_sums(both)
-      check(rn.lib().ra_bn_act_pool_bwd_dx_f32(ptr(u), ptr(dy), ptr(mean), ptr(var), ptr(gamma), ptr(beta), ptr(dgl), ptr(dbl),
-                                               _C.c_double(ctx.n_total), _C.c_float(BN_EPS), int(relu), int(pool), B, H, W, cout,
-                                               ptr(du), rn.stream_ptr()), 'ra_bn_act_pool_bwd_dx_f32')
-      return mine[:cout], mine[cout:]  # the parameter gradients of THIS rank's shard (the bucket all-reduce sums them)
-
-    if grads is not None:
-      gw, gb, gg, gbt = grads
-      bn_backward(gg, gbt)
-      cmap_t = _const('cmap', tuple(cmap), dev, lambda: torch.tensor(cmap, dtype=torch.int32, device=dev)) \
-          if cmap is not None else None
-      if cmap is not None:
-        real = [j for j in cmap if j >= 0]
-        assert len(set(real)) == len(real), 'chan_map must be injective (one writer per gradient element)'
-      defer = meta.get('wgrad_defer') if deferred else None
-      if defer is not None:
-        # the filter is shared by the step's timesteps: this call only adds its per-workgroup partial sums to the
-        # layer's buffer; the end-of-backward callback (_DeferredWgrads) reduces each layer ONCE
-        if not defer.armed:
-          defer.armed = True
-          torch.autograd.Variable._execution_engine.queue_callback(defer)
-        slot = defer.get(meta['wgrad_key'])
-        if slot is None:
-          slot = defer[meta['wgrad_key']] = dict(calls=[], tab=torch.zeros(128, dtype=torch.int64, device=dev), ws=None)
-        shape = (Cx, cout, B, Hs, Ws, H, W, int(stride == 2), tuple(cmap) if cmap is not None else None, int(cin_w), int(tr), bf)
-        assert slot.setdefault('shape', shape) == shape, 'a deferred filter gradient needs one shape per layer'
-        slot['calls'].append((x, du))  # nothing is launched here
-        slot.update(cmap_t=cmap_t, gw=gw, gb=gb)
-      elif f != 3:
-        check(rn.lib().ra_convkxk_wgrad_acc_f32(ptr(x), Cx, B, Hs, Ws, int(stride == 2), ptr(du), cout, f, ptr(wws), nws,
-                                                ptr(cmap_t), int(cin_w), int(tr), ptr(gw), ptr(gb), rn.stream_ptr()),
-              'ra_convkxk_wgrad_acc_f32')
-      else:
-        check(wgrad_acc(ptr(x), Cx, B, Hs, Ws, int(stride == 2), ptr(du), cout, ptr(wws), nws,
-                        ptr(cmap_t), int(cin_w), int(tr), ptr(gw), ptr(gb), rn.stream_ptr()), 'ra_conv3x3_wgrad_acc_f32')
-      dw = db = None
-      dgamma = dbeta = None
-    else:
-      dgamma, dbeta = bn_backward(None, None)
-      # ---- backward-weight (of the SAME conv that ran) + bias
-      dWf, db = _f(f, f, Cx, cout, device=dev), _f(cout, device=dev)
-      if f != 3:
-        check(rn.lib().ra_convkxk_wgrad_f32(ptr(x), Cx, B, Hs, Ws, int(stride == 2), ptr(du), cout, f, ptr(wws), nws,
-                                            ptr(dWf), ptr(db), rn.stream_ptr()), 'ra_convkxk_wgrad_f32')
-      else:
-        check(wgrad_out(ptr(x), Cx, B, Hs, Ws, int(stride == 2), ptr(du), cout, ptr(wws), nws,
-                        ptr(dWf), ptr(db), rn.stream_ptr()), 'ra_conv3x3_wgrad_f32')
-      if cmap is not None:  # packed kernel channels -> the filter's own input channels
-        real = torch.zeros((f, f, cin_w, cout), dtype=torch.float32, device=dev)
-        for c, j in enumerate(cmap):
-          if j >= 0:
-            real[:, :, j, :] += dWf[:, :, c, :]
-        dWf = real
-      elif Cx != cin_w:
-        dWf = dWf[:, :, :cin_w, :]
-      dw = dWf.flip(0, 1).permute(0, 1, 3, 2).contiguous() if tr else dWf.contiguous()
-    # ---- backward-data: the same MFMA conv kernel on the flipped / in-out-swapped packing
-    dx = None
-    if ctx.needs_input_grad[0]:
-      duc = _pad_channels(du)
-      cd = duc.shape[3]
-      cpb = ops.cout_padded(cin_w)
-      ones = _const('ones', cpb, dev, lambda: torch.ones(cpb, dtype=torch.float32, device=dev))
-      zeros = _const('zeros', cpb, dev, lambda: torch.zeros(cpb, dtype=torch.float32, device=dev))
-      wpb = _pack_dev(w.contiguous(), cout, cin_w, cd, _pad_map(cout, cd, dev), not tr, ctx.cache, ksize=f)
-      if f == 3:
-        dxr = ops.conv3x3(duc, wpb, ones, zeros, cin_w, relu=False, pool=1, bf16=bf)
-      else:
-        dxr = ops.conv2d_fused(duc, wpb, ones, zeros, cin_w, f, relu=False, pool=1)
-      if stride == 2:
-        # the stride-2 transposed conv reads x[i] at dx[i] = sum_k du[2i + k - pad_lo] w[k], pad_lo = max(f - 2, 0) // 2: a centred
-        # window at the ODD position 2i + 1 for f = 3, 5, 7, the EVEN position 2i itself for f = 1
-        sub = _f(B, Hs, Ws, cin_w, device=dev)
-        if f == 1:
-          check(rn.lib().ra_subsample_even_f32(ptr(dxr), B, Hs, Ws, cin_w, ptr(sub), rn.stream_ptr()), 'ra_subsample_even_f32')
-        else:
-          check(rn.lib().ra_subsample_odd_f32(ptr(dxr), B, Hs, Ws, cin_w, ptr(sub), rn.stream_ptr()),
-                'ra_subsample_odd_f32')
-        dxr = sub
-      if cmap is not None:
-        dx = torch.zeros_like(x)
-        for c, j in enumerate(cmap):
-          if j >= 0:
-            dx[..., c] = dxr[..., j]
-      elif Cx != cin_w:
-        dx = torch.zeros_like(x)
-        dx[..., :cin_w] = dxr
-      else:
-        dx = dxr
-    use_bn = gamma is not None
-    return dx, dw, db, (dgamma if use_bn else None), (dbeta if use_bn else None), None
-
-
-class BatchNormTrain(torch.autograd.Function):
-  """nnlib.batch_norm with phase_train = True as an operator of its own (nnlib.py:98-119): tf.nn.moments over (B, H, W),
-  gamma (x - mean) rsqrt(var + 1e-3) + beta, the batch statistics differentiated through.  x [B,H,W,C] float32.
-  Returns (normed, batch mean, batch var); inside nnlib.cnn / dcnn the same kernels run fused behind the conv
-  (ConvBNActPool)."""
-
-  @staticmethod
-  def forward(ctx, x, gamma, beta):
-    ctx.set_materialize_grads(False)
-    x = x.contiguous()
-    B, H, W, C = x.shape
-    dev = x.device
-    mean, var = _f(C, device=dev), _f(C, device=dev)
-    ws = _f(rn.lib().ra_bn_workspace_floats(C), device=dev)
-    check(rn.lib().ra_bn_moments_f32(ptr(x), B * H * W, C, ptr(ws), ws.numel(), ptr(mean), ptr(var), rn.stream_ptr()),
-          'ra_bn_moments_f32')
-    y = torch.empty_like(x)
-    check(rn.lib().ra_bn_act_pool_f32(ptr(x), ptr(mean), ptr(var), ptr(gamma), ptr(beta), _C.c_float(BN_EPS), 0, 1, B, H, W, C,
-                                      ptr(y), rn.stream_ptr()), 'ra_bn_act_pool_f32')
-    ctx.save_for_backward(x, mean, var, gamma, beta)
-    ctx.mark_non_differentiable(mean, var)
-    return y, mean, var
-
-  @staticmethod
-  def backward(ctx, dy, _dm, _dv):
-    if dy is None:
-      return None, None, None
-    x, mean, var, gamma, beta = ctx.saved_tensors
-    B, H, W, C = x.shape
-    dev = x.device
-    ws = _f(rn.lib().ra_bn_workspace_floats(C), device=dev)
-    dgamma, dbeta, dx = _f(C, device=dev), _f(C, device=dev), torch.empty_like(x)
-    check(rn.lib().ra_bn_act_pool_bwd_f32(ptr(x), ptr(dy.contiguous()), ptr(mean), ptr(var), ptr(gamma), ptr(beta),
-                                          _C.c_float(BN_EPS), 0, 1, B, H, W, C, ptr(ws), ws.numel(), ptr(dgamma), ptr(dbeta),
-                                          ptr(dx), rn.stream_ptr()), 'ra_bn_act_pool_bwd_f32')
-    return dx, dgamma, dbeta
-
-
-SPLIT_DGRAD = {'on': os.environ.get('RA_SPLIT_DGRAD', '1') != '0'}  # tuning aid: 0 = every float32 data gradient on K1
-
-
-def _conv_dgrad(du, w, tr, stride, cmap, x_shape, cin_w, cache, bf, out_dtype=torch.float32):
-  """Backward-data of ConvBNActPool's conv: the same MFMA conv kernel on the flipped / in-out-swapped packing.  In the bf16
-  mode's stacked step du may be stored as bf16 and the result takes the input tensor's storage type (out_dtype)."""
-  dev = du.device
-  if du.dtype == torch.bfloat16 or out_dtype == torch.bfloat16:
-    return _conv_dgrad_bf16(du, w, tr, stride, cmap, x_shape, cin_w, cache, out_dtype)
-  B, Hs, Ws, Cx = x_shape
-  cout = du.shape[3]
-  cpb = ops.cout_padded(cin_w)
-  ones = _const('ones', cpb, dev, lambda: torch.ones(cpb, dtype=torch.float32, device=dev))
-  zeros = _const('zeros', cpb, dev, lambda: torch.zeros(cpb, dtype=torch.float32, device=dev))
-  if (SPLIT_DGRAD['on'] and not bf and stride == 1 and cmap is None and Cx == cin_w and cout == 32 and  # (16 channels: conv16_kernel is as fast; 64: K1s's 8-row form is the decode loop's, not measured here)
-      ops.conv_split_supported(cout, cin_w, 1, du.shape[1], du.shape[2]) and du.numel() * 4 < (1 << 31)):
-    # round 5: the float32 data gradient of a 16- / 32-channel layer on the bf16 matrix pipe at float32 accuracy (K1s,
-    # csrc/ra_conv_split.hip: every operand the exact sum of three bf16 pieces, six piece products) — 32 -> 32 at 128 x 128 x
-    # 128 images: 2 x 292 -> 193 us in the cfg4 step.  The filter's pieces are packed on the device once per step (cache: per pack epoch).
-    key = ('split', w.data_ptr(), w._version, bool(tr))
-    hit = cache.get(key)
-    if hit is None:
-      hit = cache[key] = (w, ops.pack_split_weights_dev(w.detach(), cout, cin_w, transposed=not tr))
-    return ops.conv_split(du.contiguous(), hit[1], ones, zeros, cin_w, relu=False, pool=1)
-  duc = _pad_channels(du)
-  cd = duc.shape[3]
-  wpb = _pack_dev(w.contiguous(), cout, cin_w, cd, _pad_map(cout, cd, dev), not tr, cache)
-  dxr = ops.conv3x3(duc, wpb, ones, zeros, cin_w, relu=False, pool=1, bf16=bf)
-  if stride == 2:
-    sub = _f(B, Hs, Ws, cin_w, device=dev)
-    check(rn.lib().ra_subsample_odd_f32(ptr(dxr), B, Hs, Ws, cin_w, ptr(sub), rn.stream_ptr()), 'ra_subsample_odd_f32')
-    dxr = sub
-  if cmap is not None:
-    dx = torch.zeros((B, Hs, Ws, Cx), dtype=torch.float32, device=dev)
-    for c, j in enumerate(cmap):
-      if j >= 0:
-        dx[..., c] = dxr[..., j]
-    return dx
-  if Cx != cin_w:
-    dx = torch.zeros((B, Hs, Ws, Cx), dtype=torch.float32, device=dev)
-    dx[..., :cin_w] = dxr
-    return dx
-  return dxr
-
-
-def _conv_dgrad_bf16(du, w, tr, stride, cmap, x_shape, cin_w, cache, out_dtype):
-  dev = du.device
-  B, Hs, Ws, Cx = x_shape
-  cout = du.shape[3]
-  assert cout % 4 == 0 or du.dtype == torch.float32  # bf16 du exists only behind the float4 BatchNorm kernels
-  duc = _pad_channels(du)
-  cd = duc.shape[3]
-  cpb = ops.cout_padded(cin_w)
-  ones = _const('ones', cpb, dev, lambda: torch.ones(cpb, dtype=torch.float32, device=dev))
-  zeros = _const('zeros', cpb, dev, lambda: torch.zeros(cpb, dtype=torch.float32, device=dev))
-  wpb = _pack_dev(w.contiguous(), cout, cin_w, cd, _pad_map(cout, cd, dev), not tr, cache)
-  H, W = du.shape[1], du.shape[2]
-  dxr = torch.empty((B, H, W, cin_w), dtype=out_dtype, device=dev)
-  flags = (1 if du.dtype == torch.bfloat16 else 0) | (2 if out_dtype == torch.bfloat16 else 0)
-  check(rn.lib().ra_conv3x3_bf16_f32(ptr(duc), cd, None, 0, B, H, W, 0, ptr(wpb), ptr(ones), ptr(zeros), cin_w, 0, 1, ptr(dxr), None, 0,
-                                     None, flags, rn.stream_ptr()), 'ra_conv3x3_bf16_f32')
-  if stride == 2:  # the transposed conv's stride: keep the odd positions (whole pixels: the element type does not matter)
-    sub = torch.empty((B, Hs, Ws, cin_w), dtype=out_dtype, device=dev)
-    if out_dtype == torch.bfloat16:
-      assert cin_w % 2 == 0
-      check(rn.lib().ra_subsample_odd_f32(ptr(dxr), B, Hs, Ws, cin_w // 2, ptr(sub), rn.stream_ptr()), 'ra_subsample_odd_f32')
-    else:
-      check(rn.lib().ra_subsample_odd_f32(ptr(dxr), B, Hs, Ws, cin_w, ptr(sub), rn.stream_ptr()), 'ra_subsample_odd_f32')
-    dxr = sub
-  if cmap is not None:
-    dx = torch.zeros((B, Hs, Ws, Cx), dtype=out_dtype, device=dev)
-    for c, j in enumerate(cmap):
-      if j >= 0:
-        dx[..., c] = dxr[..., j]
-    return dx
-  if Cx != cin_w:
-    dx = torch.zeros((B, Hs, Ws, Cx), dtype=out_dtype, device=dev)
-    dx[..., :cin_w] = dxr
-    return dx
-  return dxr
-
-
-def stack_bn_reduce(info, U, dY):
-  """Synchronised BatchNorm under the stacked backward, first half: the per-channel sums (sum dv, sum dv * xhat) of every
-  timestep group of this rank's shard -> [G, 2 cout]; this rank's own sums also go to the gradient bucket (gamma / beta:
-  the bucket all-reduce sums them over the ranks later)."""
-  G, B, dev = info['G'], info['B'], U.device
-  _, H, W, cout = U.shape
-  ws = _f(rn.lib().ra_bn_workspace_floats(cout), device=dev)
-  sums = _f(G, 2 * cout, device=dev)
-  for g, (mean, var, gamma, beta, gg, gbt) in enumerate(info['per_group']):
-    sl = slice(g * B, (g + 1) * B)
-    check(rn.lib().ra_bn_act_pool_bwd_reduce_f32(ptr(U[sl]), ptr(dY[sl]), ptr(mean), ptr(var), ptr(gamma), ptr(beta),
-                                                 _C.c_float(BN_EPS), int(info['relu']), int(info['pool']), B, H, W, cout, ptr(ws),
-                                                 ws.numel(), ptr(sums[g, :cout]), ptr(sums[g, cout:]), ptr(gg), ptr(gbt),
-                                                 rn.stream_ptr()), 'ra_bn_act_pool_bwd_reduce_f32')
-  return sums
-
-
-def stack_bn_dx(info, U, dY, sums, n_total):
-  """... second half: du of every group from the sums of the WHOLE data-parallel batch (n_total elements per channel)."""
-  G, B = info['G'], info['B']
-  _, H, W, cout = U.shape
-  du = torch.empty_like(U)
-  for g, (mean, var, gamma, beta, _, _) in enumerate(info['per_group']):
-    sl = slice(g * B, (g + 1) * B)
-    check(rn.lib().ra_bn_act_pool_bwd_dx_f32(ptr(U[sl]), ptr(dY[sl]), ptr(mean), ptr(var), ptr(gamma), ptr(beta), ptr(sums[g, :cout]),
-                                             ptr(sums[g, cout:]), _C.c_double(n_total), _C.c_float(BN_EPS), int(info['relu']),
-                                             int(info['pool']), B, H, W, cout, ptr(du[sl]), rn.stream_ptr()), 'ra_bn_act_pool_bwd_dx_f32')
-  return du
-
-
-class ConvStackFn(torch.autograd.Function):
-  """The T calls of one conv + BatchNorm + ReLU + pool layer of a training step (its T timesteps: shared filter,
-  per-timestep statistics and BatchNorm parameters, nnlib.py:121-127) as ONE node of the autograd graph.
-
-  The timesteps of full_model are coupled only through the canvas, whose gradient is stopped (full_model.py:843-848),
-  and the controller state starts from zero in each: once the sequential forward has filled the layer's [T, ...] slabs
-  (x, u, y, statistics), the backward passes of the T timesteps are independent and run here stacked along the batch —
-  one grouped BatchNorm backward (ra_bn_act_pool_bwd_grouped_f32), one filter gradient and one data gradient over
-  T * B images instead of T of each.  forward() returns the precomputed y slab."""
-
-  @staticmethod
-  def forward(ctx, X, w, b, info):
-    ctx.set_materialize_grads(False)
-    ctx.info = info
-    ctx.save_for_backward(X, w)
-    return info['Y']
-
-  @staticmethod
-  def backward(ctx, dY):
-    if dY is None:
-      return None, None, None, None
-    X, w = ctx.saved_tensors
-    info = ctx.info
-    G, B, U, dev = info['G'], info['B'], info['U'], X.device
-    tr, stride, pool, relu, cmap, bf = info['transposed'], info['stride'], info['pool'], info['relu'], info['chan_map'], info['bf16']
-    N, Hs, Ws, Cx = X.shape
-    _, H, W, cout = U.shape
-    cin_w = w.shape[3] if tr else w.shape[2]
-    gw, gb = info['gw'], info['gb']
-    dY = dY.contiguous()
-    nbn = rn.lib().ra_bn_workspace_floats(cout)
-    sflags = (1 if U.dtype == torch.bfloat16 else 0) | (2 if dY.dtype == torch.bfloat16 else 0)  # the bf16 mode's storage
-    if info.get('sync_world', 1) > 1:
-      # whole-batch BatchNorm (--sync_bn) under the stacked backward: the T groups' 2 C sums of a layer cross the ranks in
-      # ONE all_reduce (21 collectives per step; the per-timestep graph issued T times as many)
-      sums = stack_bn_reduce(info, U, dY)
-      allreduce_sums(sums)
-      du = stack_bn_dx(info, U, dY, sums, float(info['sync_world']) * B * H * W)
-    elif sflags or ops.bn_form('backward', cout, B, H, W, pool, sflags, G=G) in ('v4', 'small'):
-      # ('small': the one-channel output layer, one workgroup per timestep of the same launch; bf16 storage exists only where
-      # the forward found both forms 'v4', so a refusal under it is an error)
-      du, dgam, dbet, ws = torch.empty_like(U), _f(G, cout, device=dev), _f(G, cout, device=dev), _f(G * nbn, device=dev)
-      check(rn.lib().ra_bn_act_pool_bwd_grouped_bf16_f32(ptr(U), ptr(dY), ptr(info['tabs']), G, _C.c_float(BN_EPS), int(relu), int(pool),
-                                                         B, H, W, cout, ptr(ws), ws.numel(), ptr(dgam), ptr(dbet), ptr(du), sflags,
-                                                         rn.stream_ptr()), 'ra_bn_act_pool_bwd_grouped_bf16_f32')
-    else:
-      # no grouped form at this channel count or size (C / 4 not a power of two, e.g. the KITTI architecture's 96-channel layer;
-      # a one-channel layer above the one-workgroup limit): one call per timestep
-      du = torch.empty_like(U)
-      ws, dgam, dbet = _f(nbn, device=dev), _f(cout, device=dev), _f(cout, device=dev)
-      for g, (mean, var, gamma, beta, gg, gbt) in enumerate(info['per_group']):
-        sl = slice(g * B, (g + 1) * B)
-        check(rn.lib().ra_bn_act_pool_bwd_acc_f32(ptr(U[sl]), ptr(dY[sl]), ptr(mean), ptr(var), ptr(gamma), ptr(beta),
-                                                  _C.c_float(BN_EPS), int(relu), int(pool), B, H, W, cout, ptr(ws), ws.numel(),
-                                                  ptr(dgam), ptr(dbet), ptr(du[sl]), ptr(gg), ptr(gbt), rn.stream_ptr()),
-              'ra_bn_act_pool_bwd_acc_f32')
-    cmap_t = _const('cmap', tuple(cmap), dev, lambda: torch.tensor(cmap, dtype=torch.int32, device=dev)) if cmap is not None else None
-    nws = rn.lib().ra_conv3x3_wgrad_workspace_floats(Cx, cout, N, H, W)
-    wws = info['cache'].get(('wgrad_ws', nws))
-    if wws is None:
-      wws = info['cache'][('wgrad_ws', nws)] = _f(nws, device=dev)
-    wfmt = (1 if X.dtype == torch.bfloat16 else 0) | (2 if du.dtype == torch.bfloat16 else 0)
-    if wfmt:
-      check(rn.lib().ra_conv3x3_wgrad_acc_bf16_f32(ptr(X), Cx, N, Hs, Ws, int(stride == 2), ptr(du), cout, ptr(wws), nws, ptr(cmap_t),
-                                                   int(cin_w), int(tr), ptr(gw), ptr(gb), wfmt, rn.stream_ptr()), 'ra_conv3x3_wgrad_acc_bf16_f32')
-    else:
-      wgrad = rn.lib().ra_conv3x3_wgrad_acc_bf16ops_f32 if bf else rn.lib().ra_conv3x3_wgrad_acc_f32
-      check(wgrad(ptr(X), Cx, N, Hs, Ws, int(stride == 2), ptr(du), cout, ptr(wws), nws, ptr(cmap_t), int(cin_w), int(tr), ptr(gw),
-                  ptr(gb), rn.stream_ptr()), 'ra_conv3x3_wgrad_acc_f32')
-    dx = _conv_dgrad(du, w, tr, stride, cmap, X.shape, cin_w, info['cache'], bf, X.dtype) if ctx.needs_input_grad[0] else None
-    return dx, None, None, None
 
 
 class PairIoU(torch.autograd.Function):
@@ -1631,20 +907,24 @@ class TrainStep(object):
   match_side_stream = os.environ.get('RA_MATCH_SIDE', '1') != '0'  # the box matching under the mask matching (one fork / join)
   match_merged = os.environ.get('RA_MATCH_MERGED', '1') != '0'  # otherwise: both matchings as one launch of 2 B problems
 
+  def _layer(self, x, scope, i, n, tt, stats, tr, stride, pool, cmap):
+    """One ConvBNActPool call, layer (scope, i) of n at timestep tt, on its kernel input x."""
+    P, bn, key = self.leaves, self.d['use_bn'], '%s_%d_%d' % (scope, i, tt)
+    meta = dict(transposed=tr, stride=stride, pool=pool, relu=True, chan_map=cmap, stat_out=self._stat_views.get(key),
+                bf16_store=self.bf16_store, y_f32=(i == n - 1),  # the net's last output feeds float32 kernels (controller, score, dcnn)
+                grads=self._grad_views(scope, i, key, bn), cache=self._pack, sync_bn=self.sync_bn, bf16=self.bf16,
+                wgrad_defer=self._wgrad_parts if self.defer_wgrad else None, wgrad_key=(scope, i),
+                alloc=self._tape_alloc(scope, i, tt, meta_of=(tr, stride, pool, cmap)))
+    y, mean, var = ConvBNActPool.apply(x, P['%s_w_%d' % (scope, i)], P['%s_b_%d' % (scope, i)], P[key + '_gamma'] if bn else None,
+                                       P[key + '_beta'] if bn else None, meta)
+    if bn:
+      stats[key] = (mean, var)
+    return y
+
   def _cnn(self, x, scope, n, pools, tt, cmap0, stats):
-    P, hs = self.leaves, []
+    hs = []
     for i in range(n):
-      bn = self.d['use_bn']
-      key = '%s_%d_%d' % (scope, i, tt)
-      meta = dict(transposed=False, stride=1, pool=pools[i], relu=True, chan_map=cmap0 if i == 0 else None,
-                  bf16_store=self.bf16_store, y_f32=(i == n - 1),  # the net's last output feeds float32 kernels (controller, score, dcnn)
-                  stat_out=self._stat_views.get(key), grads=self._grad_views(scope, i, key, bn), cache=self._pack,
-                  sync_bn=self.sync_bn, bf16=self.bf16, wgrad_defer=self._wgrad_parts if self.defer_wgrad else None,
-                  wgrad_key=(scope, i), alloc=self._tape_alloc(scope, i, tt, meta_of=(False, 1, pools[i], cmap0 if i == 0 else None)))
-      x, mean, var = ConvBNActPool.apply(_pad_channels(x) if i else x, P['%s_w_%d' % (scope, i)], P['%s_b_%d' % (scope, i)],
-                                         P[key + '_gamma'] if bn else None, P[key + '_beta'] if bn else None, meta)
-      if bn:
-        stats[key] = (mean, var)
+      x = self._layer(_pad_channels(x) if i else x, scope, i, n, tt, stats, False, 1, pools[i], cmap0 if i == 0 else None)
       hs.append(x)
     return hs
 
@@ -1652,28 +932,11 @@ class TrainStep(object):
     """nnlib.dcnn (nnlib.py:362-400).  skips[i] = (tensor, real channel map or None) is concatenated
     behind the previous layer's output (concat(prev, skip), :365): one packed kernel input whose
     chan_map sends every packed channel to its row of the [3,3,out,in] filter."""
-    P = self.leaves
     for i in range(n):
-      bn = self.d['use_bn']
-      key = '%s_%d_%d' % (scope, i, tt)
       cmap = None
       if skips is not None and skips[i] is not None:
-        sk, smap = skips[i]
-        prev_c = x.shape[3]
-        xp, skp = _pad_channels(x), _pad_channels(sk if sk.dtype == x.dtype else sk.to(x.dtype))
-        smap = list(range(sk.shape[3])) if smap is None else smap
-        cmap = list(range(prev_c)) + [-1] * (xp.shape[3] - prev_c) + [prev_c + m if m >= 0 else -1 for m in smap] + \
-            [-1] * (skp.shape[3] - len(smap))
-        x = torch.cat([xp, skp], dim=3)
-      meta = dict(transposed=True, stride=unpool[i], pool=1, relu=True, chan_map=cmap, stat_out=self._stat_views.get(key),
-                  bf16_store=self.bf16_store, y_f32=(i == n - 1),
-                  grads=self._grad_views(scope, i, key, bn), cache=self._pack, sync_bn=self.sync_bn, bf16=self.bf16,
-                  wgrad_defer=self._wgrad_parts if self.defer_wgrad else None, wgrad_key=(scope, i),
-                  alloc=self._tape_alloc(scope, i, tt, meta_of=(True, unpool[i], 1, cmap)))
-      x, mean, var = ConvBNActPool.apply(_pad_channels(x), P['%s_w_%d' % (scope, i)], P['%s_b_%d' % (scope, i)],
-                                         P[key + '_gamma'] if bn else None, P[key + '_beta'] if bn else None, meta)
-      if bn:
-        stats[key] = (mean, var)
+        x, cmap = concat_skip(x, *skips[i], keep_identity=True)  # the map, identity or not, is part of this trainer's pack-cache keys
+      x = self._layer(_pad_channels(x), scope, i, n, tt, stats, True, unpool[i], 1, cmap)
     return x
 
   def _linear(self, x, wname, bname):
@@ -1755,8 +1018,7 @@ class TrainStep(object):
     for i in range(n):
       tr, stride, pool, cmap = self._tape['layers'][(scope, i)]
       if skips is not None and skips[i] is not None:
-        sk = skips[i] if skips[i].dtype == X.dtype else skips[i].to(X.dtype)
-        X = torch.cat([_pad_channels(X), _pad_channels(sk)], dim=3)  # the channel map of the sequential phase applies
+        X = concat_skip(X, skips[i])[0]  # the channel map of the sequential phase applies
       U, Y = self._slabs['%s_%d_u' % (scope, i)], self._slabs['%s_%d_y' % (scope, i)]
       tab, per_group = self._bn_tables(scope, i)
       gw, gb = self.bucket.grad_of['%s_w_%d' % (scope, i)], self.bucket.grad_of['%s_b_%d' % (scope, i)]

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Which host-side ops launch the training step's small kernels?  One EAGER step (TrainStep.use_graph off)
-under torch.profiler with Python stacks; prints aten ops by call count with the ra_train.py line that issued them."""
+under torch.profiler with Python stacks; prints aten ops by call count with the ra_train.py / ra_layer_train.py line that issued them."""
 import collections, os, sys
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..', 'rec-attend-public_amd'))
@@ -34,7 +34,7 @@ class Census(TorchDispatchMode):
     site = 'autograd engine (no Python frame)'
     for fr in reversed(traceback.extract_stack(limit=40)):
       fn = os.path.basename(fr.filename)
-      if fn in ('ra_train.py', 'ra_ops.py', 'modellib.py', 'nnlib.py', 'full_model.py'):
+      if fn in ('ra_train.py', 'ra_layer_train.py', 'ra_ops.py', 'modellib.py', 'nnlib.py', 'full_model.py'):
         site = '%s:%d %s' % (fn, fr.lineno, (fr.line or '').strip()[:80])
         break
     by[(str(func).replace('aten.', ''), site)] += 1
