@@ -137,9 +137,9 @@ int ra_conv_pair_wino_plan(int B, int H, int W, int *plan);
 int ra_conv_pair16_plan(int B, int H, int W, int *plan);
 /* Test aid (no reference counterpart): the launch plan of the direct paste (mode 0: ra_paste_direct_f32, ra_paste_score_direct_f32
  * without its rider workgroup) and of the attention box (mode 1: ra_attn_box_direct_f32; Cp, pc, has_canvas, has_img do not
- * count).  The paste launches one of two kernels on its shape and argument conditions; the query walks the launch's own chain
- * of choices (one code path: the launch is that chain with plan == NULL) and fills plan[RA_PASTE_PLAN_INTS] instead of
- * launching.  has_canvas / has_img: a canvas plane / a packed image is given; aligned16: y_out, canvas and patch are all
+ * count).  The paste launches one of two kernels on its shape and argument conditions; the query asks the launch's own
+ * chooser (one host function takes these facts and returns the record the launch is made from) and fills
+ * plan[RA_PASTE_PLAN_INTS] instead of launching.  has_canvas / has_img: a canvas plane / a packed image is given; aligned16: y_out, canvas and patch are all
  * 16-byte aligned.  No device is needed; RA_PASTE_GEO counts as it does for a launch.  Fields: KERNEL RA_PASTE_KERNEL_GENERAL
  * (paste_direct_kernel) or RA_PASTE_KERNEL_WINDOW (paste_win_kernel), ROWS image rows per workgroup, GRID_X (the last
  * workgroup holds H % ROWS rows where that is not 0), THREADS, LDS dynamic shared bytes.  Returns what the launch's argument

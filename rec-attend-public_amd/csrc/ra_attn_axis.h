@@ -32,6 +32,20 @@ struct Axis {  // one axis of one example's filter bank
     lo = (int)a;
     hi = (int)c > lo ? (int)c : lo;
   }
+  // pixel span [lo, hi) of the whole window: from the first pixel of tap 0's band to the last of tap F - 1's
+  __device__ inline void span(int &lo, int &hi) const {
+    int tmp;
+    band(0, lo, tmp);
+    band(F - 1, tmp, hi);
+  }
+  // the span widened to whole float4 column groups inside the image (the paste kernels' window columns); never hi < lo
+  __device__ inline void span4(int &lo, int &hi) const {
+    span(lo, hi);
+    lo &= ~3;
+    hi = (hi + 3) & ~3;
+    hi = hi < L ? hi : L;
+    hi = hi < lo ? lo : hi;
+  }
   // tap range [jlo, jhi) whose band contains pixel l (widened by one tap each side: extra terms
   // are harmless, missing ones are not)
   __device__ inline void taps(int l, int &jlo, int &jhi) const {

@@ -9,7 +9,7 @@
 // Same banding rule as ra_attn.hip: taps whose weight is below exp(-30) of the peak are skipped.
 #include <cstdlib>
 
-#include "ra_attn_axis.h"
+#include "ra_attn_parts.h"
 #include "ra_common.h"
 
 namespace ra {
@@ -29,43 +29,76 @@ __device__ long long *ra_probe_buf;
 #endif
 
 // ---- extract, row-parallel form ---------------------------------------------------------------------
-// Workgroup = (one tap j, channel group cg, image b).  The tap's row band (2R+1 rows) x the window's
-// columns is read in rounds of 16 rows: lane = image column (a wave reads 1 KB runs), wave w takes rows
-// w, w+4, ... and every thread keeps KR x 4 independent 16-byte buffer loads in flight (rows / columns
-// outside the tile are not issued), so the dependent chain is  record -> load round(s) -> LDS reduce ->
-// store  and a launch is Fh x Cp/4 x B workgroups (384 at cfg2's B = 8; round 2's whole-band form: 96).
+// The band walk of ra_attn_parts.h with 16-byte image loads: the dependent chain is  record -> load round(s) -> LDS reduce
+// -> store  and a launch is Fh x Cp/4 x B workgroups (384 at cfg2's B = 8; round 2's whole-band form: 96).
 // What tools/attn_probe.hip (wall-clock stamps inside the kernel) says bounds it at cfg2: the bytes the CUs
 // pull from L2 — a tap spacing of (size+1)/F against a band of 2R+1 rows means every image row is read by
 // ~8 taps' workgroups, 50 MB per launch at ~75 GB/s per CU — and the 2.5 us of a dependent launch; 2-D
 // tiles (TJ taps x NI outputs per workgroup) cut the bytes to 20 MB but pay it back in multiply-adds per
 // loaded row and a longer reduction, and measured no faster.
-// The row filter's weights of a round are evaluated once per wave, one per lane, and handed to the
-// multiply-adds through v_readlane (a v_exp costs 16 cycles of a SIMD that holds one or two waves).
-// Work items are dealt to the 8 XCDs in contiguous chunks (workgroup id % 8 = XCD): the taps of one
-// image share almost all their rows, and those re-reads then hit ONE L2.
-template <int KR>
+//
+// ND = 1: the decode loop's extract, any Cp / 4 channel groups.
+// ND = 3: extract + the first attention-CNN layer in ONE launch (round 5).  The decode loop's tail is a chain of dependent
+// launches (extract -> 6 conv -> 7 transposed conv -> paste), each ~2.5 us of launch floor.  The first conv layer (nnlib.cnn
+// layer 0 of the attention CNN: 3x3 SAME on the 48 x 48 patch, BN + ReLU, no pooling; full_model.py:792-795, nnlib.py:229-253)
+// needs, for output row j, the patch rows j-1, j, j+1 — and the three taps' row bands overlap almost completely (band 2R+1 = 31
+// rows against a tap spacing of 3.7 rows at cfg2: the union is 38 rows).  So workgroup (tap j, image b) reduces its rows ONCE
+// with three row-filter weights per row, contracts the three row sums with the column filter, keeps the three patch rows in LDS
+// and evaluates the conv's output row j from them: no second launch and no cross-workgroup hand-over (the neighbours' rows are
+// recomputed, not waited for).  Writes x_patch row j (the model's output; dcnn skip source) and h_acnn[0] row j.
+// Shapes: one packed channel group (Cp = 4: the CVPPP input), Fw <= 64 (parts = 4), Cout <= 16.
+struct Conv0Args {  // ND = 3 only
+  const float *w, *scale, *shift;  // w [3,3,4,Cout], BN folded into scale / shift [Cout]
+  int Cout, relu;
+  float *y0;  // [B,Fh,Fw,Cout]
+};
+
+template <int ND, int KR>
 __global__ __launch_bounds__(256) void extract_rows_kernel(const float *__restrict__ img, int Ci, int chan0,
                                                             const float *__restrict__ canvas, int canvas_chan,
                                                             const float *__restrict__ attn, int H, int W, int Fh, int Fw,
-                                                            int Cp, int use_gamma, float *__restrict__ patch,
-                                                            int n_items, int chunk, int prio) {
-  raise_prio(prio);
-  __shared__ f32x4 red[4][256];
+                                                            int Cp_arg, int use_gamma, float *__restrict__ patch,
+                                                            const Conv0Args c0, int n_items, int chunk, int prio) {
+  static_assert(ND == 1 || ND == 3, "taps a workgroup reduces");
+  if constexpr (ND == 1) raise_prio(prio);
+  __shared__ f32x4 red[ND][4][256];
+  __shared__ f32x4 p3[3][66];  // ND = 3: patch rows j-1, j, j+1 with one zero column each side (SAME padding)
+  __shared__ float w0s[9 * 4 * 16];
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int slot = blockIdx.x >> 3;
-  const int item = (blockIdx.x & 7) * chunk + slot;
-  if (slot >= chunk || item >= n_items) return;
+  int item;
+  if (!band_item(n_items, chunk, item)) return;
   RA_PROBE_AT(0);
-  const int ncg = Cp >> 2;
+  const int Cp = ND == 1 ? Cp_arg : 4, ncg = Cp >> 2;
   const int b = item / (Fh * ncg), rem = item - b * Fh * ncg;
   const int j = rem / ncg, cg = rem - j * ncg;
   const float *rec = attn + (size_t)b * RA_ATTN_STRIDE;
   const Axis Ay = make_axis(rec, 0, H, Fh), Ax = make_axis(rec, 1, W, Fw);
-  int l0, l1, w0, w1, tmp;
-  Ay.band(j, l0, l1);
-  Ax.band(0, w0, tmp);
-  Ax.band(Fw - 1, tmp, w1);
+  // the row bands of taps j - ND/2 .. j + ND/2 (empty beyond the patch) and their union [l0, l1)
+  int l0d[ND], l1d[ND], l0, l1, w0, w1;
+  if constexpr (ND == 1) {
+    Ay.band(j, l0d[0], l1d[0]);
+    l0 = l0d[0];
+    l1 = l1d[0];
+  } else {
+    l0 = H;
+    l1 = 0;
+#pragma unroll
+    for (int d = 0; d < ND; ++d) {
+      const int jd = j - ND / 2 + d;
+      l0d[d] = l1d[d] = 0;
+      if (jd >= 0 && jd < Fh) {
+        Ay.band(jd, l0d[d], l1d[d]);
+        l0 = l0d[d] < l0 ? l0d[d] : l0;
+        l1 = l1d[d] > l1 ? l1d[d] : l1;
+      }
+    }
+  }
+  Ax.span(w0, w1);
   if (w1 > -1000000) RA_PROBE_AT(1);  // the record has arrived
+  if constexpr (ND == 3) {
+    for (int e = t; e < 36 * c0.Cout; e += 256) w0s[e] = c0.w[e];
+    if (t < 6) p3[t >> 1][(t & 1) ? Fw + 1 : 0] = f32x4{0, 0, 0, 0};
+  }
   const int ch0 = chan0 + 4 * cg;
   const bool use_canvas = canvas != nullptr && (canvas_chan >= ch0) && (canvas_chan < ch0 + 4);
   const int cslot = canvas_chan - ch0;
@@ -74,53 +107,45 @@ __global__ __launch_bounds__(256) void extract_rows_kernel(const float *__restri
       0x00020000);
   const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float *>(use_canvas ? canvas + (size_t)b * H * W : img), 0, use_canvas ? H * W * 4 : 0, 0x00020000);
-  constexpr int kOOB = 0x7fffffff;
 
-  // stage-2 role: output column oi, its band's columns dealt to `parts` neighbouring lanes
-  const int parts = (Fw * 4 <= 256) ? 4 : (Fw * 2 <= 256) ? 2 : 1;
-  const int oi = t / parts, part = t - oi * parts;
-  const bool owner = oi < Fw;
-  int bi_lo = 0, bi_hi = 0;
-  if (owner) Ax.band(oi, bi_lo, bi_hi);
-  f32x4 P = f32x4{0, 0, 0, 0};
-  constexpr int kPre = 8;
+  const Role ro = stage2_role<ND == 1 ? 0 : 4>(Ax, t);
+  f32x4 P[ND];
+#pragma unroll
+  for (int d = 0; d < ND; ++d) P[d] = f32x4{0, 0, 0, 0};
   float fpre[kPre];
 #pragma unroll
   for (int u = 0; u < kPre; ++u) fpre[u] = 0.0f;
 
   for (int cp = w0; cp < w1; cp += 256) {
-    f32x4 acc[4];
+    f32x4 acc[ND][4];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) acc[p] = f32x4{0, 0, 0, 0};
+    for (int d = 0; d < ND; ++d)
+#pragma unroll
+      for (int p = 0; p < 4; ++p) acc[d][p] = f32x4{0, 0, 0, 0};
     for (int rb = l0; rb < l1; rb += 4 * KR) {
       f32x4 xv[KR][4];
       float cv[KR][4];
 #pragma unroll
-      for (int k = 0; k < KR; ++k) {
-        const int row = rb + 4 * k + wv;
+      for (int k = 0; k < KR; ++k)
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-          const int col = cp + 64 * p + lane;
-          const int pix = (row < l1 && col < w1) ? row * W + col : -1;
-          xv[k][p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsI, pix >= 0 ? pix * Ci * 4 : kOOB, 0, 0));
-          cv[k][p] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsC, pix >= 0 ? pix * 4 : kOOB, 0, 0));
+          const int pix = round_pix(rb, k, wv, cp, p, lane, l1, w1, W);
+          xv[k][p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsI, pix_off(pix, Ci * 4), 0, 0));
+          cv[k][p] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsC, pix_off(pix, 4), 0, 0));
         }
-      }
-      // this thread's first 8 column-filter weights (terms bi_lo + part + u * parts) depend on the record only:
-      // evaluated here, under the loads' latency, instead of behind their wait
-#pragma unroll
-      for (int u = 0; u < kPre; ++u) {
-        const int ww = bi_lo + part + u * parts;
-        fpre[u] = (owner && ww < bi_hi) ? Ax.w((float)ww, oi) : 0.0f;
-      }
-      // the row filter of this wave's KR rows: lane k evaluates row rb + 4k + wv
+      col_weights(Ax, ro, fpre);
       const int rowl = rb + 4 * lane + wv;
-      const float fyv = (lane < KR && rowl < l1) ? Ay.w((float)rowl, j) : 0.0f;
+      float fyv[ND];
+#pragma unroll
+      for (int d = 0; d < ND; ++d)
+        fyv[d] = (ND == 1 || rowl >= l0d[d]) ? row_weight<KR>(Ay, j - ND / 2 + d, rowl, lane, l1d[d]) : 0.0f;
       // straight-line on purpose: a branch per row makes the compiler sink every load to its use (one
       // round trip per row); rows beyond the band were not loaded (0) and carry zero weights
 #pragma unroll
       for (int k = 0; k < KR; ++k) {
-        const float wy = readlane_f(fyv, k);
+        float wy[ND];
+#pragma unroll
+        for (int d = 0; d < ND; ++d) wy[d] = readlane_f(fyv[d], k);
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
           f32x4 x = xv[k][p];
@@ -130,243 +155,90 @@ __global__ __launch_bounds__(256) void extract_rows_kernel(const float *__restri
             x.z = cslot == 2 ? cv[k][p] : x.z;
             x.w = cslot == 3 ? cv[k][p] : x.w;
           }
-          acc[p] += wy * x;
+#pragma unroll
+          for (int d = 0; d < ND; ++d) acc[d][p] += wy[d] * x;
         }
       }
     }
-    __syncthreads();  // the previous column group's stage 2 is done with `red`
-#pragma unroll
-    for (int p = 0; p < 4; ++p) red[wv][64 * p + lane] = acc[p];
-    __syncthreads();
+    reduce_waves(red, acc, t, wv, lane);
     if (cp == w0) RA_PROBE_AT(2);  // all rows loaded and reduced
-    red[0][t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);  // column t of this group, all four row slots
-    __syncthreads();
-    if (owner) {
+    // stage 2: P[d] += sum over the output column's band inside this page of fx(w, oi) red[d][0][w - cp]  (written out here,
+    // its only user: ra_attn_parts.h says what it cost as a function)
+    if (ro.owner) {
       const int cend = (cp + 256 < w1) ? cp + 256 : w1;
-      const int a = bi_lo > cp ? bi_lo : cp, c = bi_hi < cend ? bi_hi : cend;
-      if (bi_lo >= cp && bi_hi <= cend && bi_hi - bi_lo <= kPre * parts) {  // the usual case: the pre-computed weights
-        f32x4 sv[kPre];
+      const int a = ro.bi_lo > cp ? ro.bi_lo : cp, c = ro.bi_hi < cend ? ro.bi_hi : cend;
+      if (ro.bi_lo >= cp && ro.bi_hi <= cend && ro.bi_hi - ro.bi_lo <= kPre * ro.parts) {  // the usual case: the pre-computed weights
+        f32x4 sv[kPre][ND];
 #pragma unroll
         for (int u = 0; u < kPre; ++u) {
-          const int ww = bi_lo + part + u * parts;
-          const int wi = (ww < bi_hi ? ww : bi_hi - 1) - cp;
-          sv[u] = red[0][wi > 0 ? wi : 0];
+          const int ww = ro.bi_lo + ro.part + u * ro.parts;
+          const int wi = (ww < ro.bi_hi ? ww : ro.bi_hi - 1) - cp;
+#pragma unroll
+          for (int d = 0; d < ND; ++d) sv[u][d] = red[d][0][wi > 0 ? wi : 0];
         }
 #pragma unroll
-        for (int u = 0; u < kPre; ++u) P += fpre[u] * sv[u];
+        for (int u = 0; u < kPre; ++u)
+#pragma unroll
+          for (int d = 0; d < ND; ++d) P[d] += fpre[u] * sv[u][d];
       } else {
-        for (int wb = a; wb < c; wb += 4 * parts) {  // batches of 4 terms: independent exps and LDS reads
+        for (int wb = a; wb < c; wb += 4 * ro.parts) {  // batches of 4 terms: independent exps and LDS reads
           float f[4];
-          f32x4 sv[4];
+          f32x4 sv[4][ND];
 #pragma unroll
           for (int u = 0; u < 4; ++u) {
-            const int ww = wb + u * parts + part;
+            const int ww = wb + u * ro.parts + ro.part;
             const int wc = ww < c ? ww : c - 1;
-            f[u] = (ww < c) ? Ax.w((float)wc, oi) : 0.0f;
-            sv[u] = red[0][wc - cp];
+            f[u] = (ww < c) ? Ax.w((float)wc, ro.oi) : 0.0f;
+#pragma unroll
+            for (int d = 0; d < ND; ++d) sv[u][d] = red[d][0][wc - cp];
           }
 #pragma unroll
-          for (int u = 0; u < 4; ++u) P += f[u] * sv[u];
+          for (int u = 0; u < 4; ++u)
+#pragma unroll
+            for (int d = 0; d < ND; ++d) P[d] += f[u] * sv[u][d];
         }
       }
     }
   }
-  if (parts >= 2) {
 #pragma unroll
-    for (int c = 0; c < 4; ++c) P[c] += __shfl_xor(P[c], 1);
-  }
-  if (parts >= 4) {
-#pragma unroll
-    for (int c = 0; c < 4; ++c) P[c] += __shfl_xor(P[c], 2);
-  }
-  if (owner && part == 0) {
+  for (int d = 0; d < ND; ++d) P[d] = parts_sum(P[d], ro.parts);
+  if (ro.owner && ro.part == 0) {
     const float gamma = use_gamma ? rec[6] : 1.0f;
-    *reinterpret_cast<f32x4 *>(patch + (((size_t)b * Fh + j) * Fw + oi) * Cp + 4 * cg) = gamma * P;
+    if constexpr (ND == 3) {
+#pragma unroll
+      for (int d = 0; d < ND; ++d) p3[d][ro.oi + 1] = gamma * P[d];
+    }
+    *reinterpret_cast<f32x4 *>(patch + (((size_t)b * Fh + j) * Fw + ro.oi) * Cp + 4 * cg) = gamma * P[ND / 2];
   }
   RA_PROBE_AT(3);
-}
-
-// ---- extract + the first attention-CNN layer in ONE launch (round 5) --------------------------------------
-// The decode loop's tail is a chain of dependent launches (extract -> 6 conv -> 7 transposed conv -> paste), each
-// ~2.5 us of launch floor.  The first conv layer (nnlib.cnn layer 0 of the attention CNN: 3x3 SAME on the 48 x 48 patch,
-// BN + ReLU, no pooling; full_model.py:792-795, nnlib.py:229-253) needs, for output row j, the patch rows j-1, j, j+1 —
-// and the three taps' row bands overlap almost completely (band 2R+1 = 31 rows against a tap spacing of 3.7 rows at
-// cfg2: the union is 38 rows).  So workgroup (tap j, image b) reduces its rows ONCE with three row-filter weights per
-// row, contracts the three row sums with the column filter, keeps the three patch rows in LDS and evaluates the
-// conv's output row j from them: no second launch and no cross-workgroup hand-over (the neighbours' rows are
-// recomputed, not waited for).  Writes x_patch row j (the model's output; dcnn skip source) and h_acnn[0] row j.
-// Shapes: one packed channel group (Cp = 4: the CVPPP input), Fw <= 64, Cout <= 16.
-template <int KR>
-__global__ __launch_bounds__(256) void extract_conv0_kernel(const float *__restrict__ img, int Ci, int chan0,
-                                                             const float *__restrict__ canvas, int canvas_chan,
-                                                             const float *__restrict__ attn, int H, int W, int Fh, int Fw,
-                                                             int use_gamma, float *__restrict__ patch,
-                                                             const float *__restrict__ w0, const float *__restrict__ scale,
-                                                             const float *__restrict__ shift, int Cout, int relu,
-                                                             float *__restrict__ y0, int n_items, int chunk) {
-  __shared__ f32x4 red[3][4][256];
-  __shared__ f32x4 p3[3][66];       // patch rows j-1, j, j+1 with one zero column each side (SAME padding)
-  __shared__ float w0s[9 * 4 * 16];
-  const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int slot = blockIdx.x >> 3;
-  const int item = (blockIdx.x & 7) * chunk + slot;
-  if (slot >= chunk || item >= n_items) return;
-  const int b = item / Fh, j = item - b * Fh;
-  const float *rec = attn + (size_t)b * RA_ATTN_STRIDE;
-  const Axis Ay = make_axis(rec, 0, H, Fh), Ax = make_axis(rec, 1, W, Fw);
-  int l0d[3], l1d[3], l0u = H, l1u = 0, w0c, w1c, tmp;
-#pragma unroll
-  for (int d = 0; d < 3; ++d) {
-    const int jd = j - 1 + d;
-    l0d[d] = l1d[d] = 0;
-    if (jd >= 0 && jd < Fh) {
-      Ay.band(jd, l0d[d], l1d[d]);
-      l0u = l0d[d] < l0u ? l0d[d] : l0u;
-      l1u = l1d[d] > l1u ? l1d[d] : l1u;
-    }
-  }
-  Ax.band(0, w0c, tmp);
-  Ax.band(Fw - 1, tmp, w1c);
-  for (int e = t; e < 36 * Cout; e += 256) w0s[e] = w0[e];
-  if (t < 6) p3[t >> 1][(t & 1) ? Fw + 1 : 0] = f32x4{0, 0, 0, 0};
-  const bool use_canvas = canvas != nullptr && (canvas_chan >= chan0) && (canvas_chan < chan0 + 4);
-  const int cslot = canvas_chan - chan0;
-  const __amdgpu_buffer_rsrc_t rsI = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(img + (size_t)b * H * W * Ci + chan0), 0, (int)((size_t)H * W * Ci * 4 - (size_t)chan0 * 4), 0x00020000);
-  const __amdgpu_buffer_rsrc_t rsC = __builtin_amdgcn_make_buffer_rsrc(
-      const_cast<float *>(use_canvas ? canvas + (size_t)b * H * W : img), 0, use_canvas ? H * W * 4 : 0, 0x00020000);
-  constexpr int kOOB = 0x7fffffff;
-
-  const int oi = t >> 2, part = t & 3;  // stage 2: output column oi, its band's columns dealt to 4 neighbouring lanes
-  const bool owner = oi < Fw;
-  int bi_lo = 0, bi_hi = 0;
-  if (owner) Ax.band(oi, bi_lo, bi_hi);
-  f32x4 P[3];
-#pragma unroll
-  for (int d = 0; d < 3; ++d) P[d] = f32x4{0, 0, 0, 0};
-  constexpr int kPre = 8;
-  float fpre[kPre];
-#pragma unroll
-  for (int u = 0; u < kPre; ++u) fpre[u] = 0.0f;
-
-  for (int cp = w0c; cp < w1c; cp += 256) {
-    f32x4 acc[3][4];
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-      for (int p = 0; p < 4; ++p) acc[d][p] = f32x4{0, 0, 0, 0};
-    for (int rb = l0u; rb < l1u; rb += 4 * KR) {
-      f32x4 xv[KR][4];
-      float cv[KR][4];
-#pragma unroll
-      for (int k = 0; k < KR; ++k) {
-        const int row = rb + 4 * k + wv;
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          const int col = cp + 64 * p + lane;
-          const int pix = (row < l1u && col < w1c) ? row * W + col : -1;
-          xv[k][p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsI, pix >= 0 ? pix * Ci * 4 : kOOB, 0, 0));
-          cv[k][p] = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsC, pix >= 0 ? pix * 4 : kOOB, 0, 0));
-        }
-      }
-#pragma unroll
-      for (int u = 0; u < kPre; ++u) {  // under the loads' latency: this thread's first 8 column-filter weights
-        const int ww = bi_lo + part + u * 4;
-        fpre[u] = (owner && ww < bi_hi) ? Ax.w((float)ww, oi) : 0.0f;
-      }
-      // the three taps' row-filter weights of this wave's KR rows: lane k evaluates row rb + 4k + wv (zero outside a tap's band)
-      const int rowl = rb + 4 * lane + wv;
-      float fyv[3];
-#pragma unroll
-      for (int d = 0; d < 3; ++d) fyv[d] = (lane < KR && rowl >= l0d[d] && rowl < l1d[d]) ? Ay.w((float)rowl, j - 1 + d) : 0.0f;
-#pragma unroll
-      for (int k = 0; k < KR; ++k) {
-        const float wy0 = readlane_f(fyv[0], k), wy1 = readlane_f(fyv[1], k), wy2 = readlane_f(fyv[2], k);
-#pragma unroll
-        for (int p = 0; p < 4; ++p) {
-          f32x4 x = xv[k][p];
-          if (use_canvas) {
-            x.x = cslot == 0 ? cv[k][p] : x.x;
-            x.y = cslot == 1 ? cv[k][p] : x.y;
-            x.z = cslot == 2 ? cv[k][p] : x.z;
-            x.w = cslot == 3 ? cv[k][p] : x.w;
-          }
-          acc[0][p] += wy0 * x;
-          acc[1][p] += wy1 * x;
-          acc[2][p] += wy2 * x;
-        }
-      }
-    }
-    __syncthreads();  // the previous column group's stage 2 is done with `red`
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-      for (int p = 0; p < 4; ++p) red[d][wv][64 * p + lane] = acc[d][p];
+  if constexpr (ND == 3) {
     __syncthreads();
+    // the conv layer's output row j: u[i, co] = sum_{d, kx, c} w[d][kx][c][co] * P[j - 1 + d][i + kx - 1][c], BN (folded) + ReLU
+    const int Cout = c0.Cout;
+    const float lo = c0.relu ? 0.f : -__builtin_inff();
+    for (int e = t; e < Fw * Cout; e += 256) {
+      const int i = e / Cout, co = e - i * Cout;
+      float u = 0.f;
 #pragma unroll
-    for (int d = 0; d < 3; ++d) red[d][0][t] = (red[d][0][t] + red[d][1][t]) + (red[d][2][t] + red[d][3][t]);
-    __syncthreads();
-    if (owner) {
-      const int cend = (cp + 256 < w1c) ? cp + 256 : w1c;
-      const int a = bi_lo > cp ? bi_lo : cp, c = bi_hi < cend ? bi_hi : cend;
-      if (bi_lo >= cp && bi_hi <= cend && bi_hi - bi_lo <= kPre * 4) {  // the usual case: the pre-computed weights
+      for (int d = 0; d < 3; ++d)
 #pragma unroll
-        for (int u = 0; u < kPre; ++u) {
-          const int ww = bi_lo + part + u * 4;
-          const int wi = (ww < bi_hi ? ww : bi_hi - 1) - cp;
-          const int wj = wi > 0 ? wi : 0;
-#pragma unroll
-          for (int d = 0; d < 3; ++d) P[d] += fpre[u] * red[d][0][wj];
+        for (int kx = 0; kx < 3; ++kx) {
+          const f32x4 pv = p3[d][i + kx];
+          const float *wr = w0s + ((d * 3 + kx) * 4) * Cout + co;
+          u += wr[0] * pv.x;
+          u += wr[Cout] * pv.y;
+          u += wr[2 * Cout] * pv.z;
+          u += wr[3 * Cout] * pv.w;
         }
-      } else {
-        for (int wb = a; wb < c; wb += 16) {
-#pragma unroll
-          for (int u = 0; u < 4; ++u) {
-            const int ww = wb + u * 4 + part;
-            const int wc = ww < c ? ww : c - 1;
-            const float f = (ww < c) ? Ax.w((float)wc, oi) : 0.0f;
-#pragma unroll
-            for (int d = 0; d < 3; ++d) P[d] += f * red[d][0][wc - cp];
-          }
-        }
-      }
+      c0.y0[(((size_t)b * Fh + j) * Fw + i) * Cout + co] = fmaxf(u * c0.scale[co] + c0.shift[co], lo);
     }
-  }
-#pragma unroll
-  for (int d = 0; d < 3; ++d)
-#pragma unroll
-    for (int c = 0; c < 4; ++c) {
-      P[d][c] += __shfl_xor(P[d][c], 1);
-      P[d][c] += __shfl_xor(P[d][c], 2);
-    }
-  if (owner && part == 0) {
-    const float gamma = use_gamma ? rec[6] : 1.0f;
-#pragma unroll
-    for (int d = 0; d < 3; ++d) p3[d][oi + 1] = gamma * P[d];
-    *reinterpret_cast<f32x4 *>(patch + (((size_t)b * Fh + j) * Fw + oi) * 4) = gamma * P[1];
-  }
-  __syncthreads();
-  // the conv layer's output row j: u[i, co] = sum_{d, kx, c} w0[d][kx][c][co] * P[j - 1 + d][i + kx - 1][c], BN (folded) + ReLU
-  const float lo = relu ? 0.f : -__builtin_inff();
-  for (int e = t; e < Fw * Cout; e += 256) {
-    const int i = e / Cout, co = e - i * Cout;
-    float u = 0.f;
-#pragma unroll
-    for (int d = 0; d < 3; ++d)
-#pragma unroll
-      for (int kx = 0; kx < 3; ++kx) {
-        const f32x4 pv = p3[d][i + kx];
-        const float *wr = w0s + ((d * 3 + kx) * 4) * Cout + co;
-        u += wr[0] * pv.x;
-        u += wr[Cout] * pv.y;
-        u += wr[2 * Cout] * pv.z;
-        u += wr[3 * Cout] * pv.w;
-      }
-    y0[(((size_t)b * Fh + j) * Fw + i) * Cout + co] = fmaxf(u * scale[co] + shift[co], lo);
   }
 }
 
+// Two sigmoids, because they round differently: the exact division for the general paste, the box and the score (the results
+// the parity tests pinned first); the one-instruction reciprocal (1 ulp) for paste_win_kernel, whose pixels are instruction issue.
 __device__ inline float sigmoidf(float z) { return 1.0f / (1.0f + __expf(-z)); }
+__device__ inline float fast_sigmoid(float z) { return __builtin_amdgcn_rcpf(1.0f + __expf(-z)); }
 
 // y[b,l,w] = sigmoid(e^g * sum_j sum_i fy(l,j) P[j,i] fx(w,i) + beta) [* (1 - canvas)];
 // canvas = max(canvas, y).  One workgroup per kPasteRows image rows.  MODE 0: paste, 1: attention box.
@@ -389,6 +261,26 @@ struct ScoreArgs {
   int K0, K1;
   size_t stride;
 };
+// the rider workgroup of image b (grid.x is one larger when a score is requested); scratch: nthr / 64 floats of LDS.
+// nthr = blockDim.x, handed over by the kernel: paste_win_kernel knows it at compile time, and with it read from the dispatch
+// packet here its window path, 45 instructions further down, measured 1 % slower on small windows.
+__device__ __forceinline__ void score_rider(const ScoreArgs &sc, int b, float *scratch, int nthr) {
+  const int t = threadIdx.x;
+  float s = 0.0f;
+  const int K = sc.K0 + sc.K1;
+  for (int k = t; k < K; k += nthr) {
+    const float xv = (k < sc.K0) ? sc.h[(size_t)b * sc.K0 + k] : sc.core[(size_t)b * sc.K1 + (k - sc.K0)];
+    s += xv * sc.w[k];
+  }
+  s = wave_sum(s);
+  if ((t & 63) == 0) scratch[t >> 6] = s;
+  __syncthreads();
+  if (t == 0) {
+    float tot = sc.bias ? sc.bias[0] : 0.0f;
+    for (int wv = 0; wv < (nthr >> 6); ++wv) tot += scratch[wv];
+    sc.s_out[(size_t)b * sc.stride] = sigmoidf(tot);
+  }
+}
 
 template <int MODE>
 __global__ __launch_bounds__(256) void paste_direct_kernel(const float *patch, int Cp, int pc,
@@ -400,24 +292,7 @@ __global__ __launch_bounds__(256) void paste_direct_kernel(const float *patch, i
                                                             ScoreArgs sc) {
   extern __shared__ float V[];  // [kPasteRows][Fw]:  V[r][i] = sum_j fy(l0 + r, j) P[j,i]
   const int l0 = blockIdx.x * kPasteRows, b = blockIdx.y, t = threadIdx.x;
-  if (l0 >= H) {  // the rider workgroup (grid.x is one larger when a score is requested)
-    float s = 0.0f;
-    const int K = sc.K0 + sc.K1;
-    for (int k = t; k < K; k += blockDim.x) {
-      const float xv = (k < sc.K0) ? sc.h[(size_t)b * sc.K0 + k] : sc.core[(size_t)b * sc.K1 + (k - sc.K0)];
-      s += xv * sc.w[k];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if ((t & 63) == 0) V[t >> 6] = s;
-    __syncthreads();
-    if (t == 0) {
-      float tot = sc.bias ? sc.bias[0] : 0.0f;
-      for (int wv = 0; wv < (int)(blockDim.x >> 6); ++wv) tot += V[wv];
-      sc.s_out[(size_t)b * sc.stride] = sigmoidf(tot);
-    }
-    return;
-  }
+  if (l0 >= H) return score_rider(sc, b, V, blockDim.x);
   const float *rec = attn + (size_t)b * RA_ATTN_STRIDE;
   const Axis Ay = make_axis(rec, 0, H, Fh), Ax = make_axis(rec, 1, W, Fw);
   const int nrow = (H - l0) < kPasteRows ? (H - l0) : kPasteRows;
@@ -430,14 +305,7 @@ __global__ __launch_bounds__(256) void paste_direct_kernel(const float *patch, i
   Ay.taps(l0 + nrow - 1, jtmp, jall_hi);  // tap ranges are monotone in l: union over the rows
   if (skip_dead && jall_lo >= jall_hi) return;
   int wbeg = 0, wend = W;
-  if (skip_dead) {
-    int w0, w1, tmp;
-    Ax.band(0, w0, tmp);
-    Ax.band(Fw - 1, tmp, w1);
-    wbeg = w0 & ~3;
-    wend = (w1 + 3) & ~3;
-    wend = wend < W ? wend : W;
-  }
+  if (skip_dead) Ax.span4(wbeg, wend);
   const bool vec = (W % 4 == 0) && ((reinterpret_cast<uintptr_t>(y_out) & 15) == 0) && ((y_stride_b & 3) == 0) &&
                    (!canvas || (reinterpret_cast<uintptr_t>(canvas) & 15) == 0);
   const int ngrp = (wend - wbeg + 3) >> 2;  // float4 column groups of the window
@@ -554,8 +422,6 @@ __global__ __launch_bounds__(256) void paste_direct_kernel(const float *patch, i
 // buffer stores with a scalar row offset (no 64-bit address arithmetic per pixel).
 constexpr int kPsQuads = 3;  // float4 groups of the patch plane a thread stages (3 x 256 x 4 = 3072 >= 48 x 48)
 
-__device__ inline float fast_sigmoid(float z) { return __builtin_amdgcn_rcpf(1.0f + __expf(-z)); }
-
 template <int MODE, int RB>
 __global__ __launch_bounds__(256) void paste_win_kernel(const float *__restrict__ patch,
                                                          const float *__restrict__ attn, int H, int W, int Fh, int Fw,
@@ -571,24 +437,7 @@ __global__ __launch_bounds__(256) void paste_win_kernel(const float *__restrict_
   float *Cs = reinterpret_cast<float *>(smem4);
   float *V = reinterpret_cast<float *>(smem4 + CVQ * nthr);
   float *Ps = V + RB * Fw;
-  if (l0 >= H) {  // the rider workgroup (grid.x is one larger when a score is requested)
-    float s = 0.0f;
-    const int K = sc.K0 + sc.K1;
-    for (int k = t; k < K; k += nthr) {
-      const float xv = (k < sc.K0) ? sc.h[(size_t)b * sc.K0 + k] : sc.core[(size_t)b * sc.K1 + (k - sc.K0)];
-      s += xv * sc.w[k];
-    }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) V[wv] = s;
-    __syncthreads();
-    if (t == 0) {
-      float tot = sc.bias ? sc.bias[0] : 0.0f;
-      for (int k = 0; k < (nthr >> 6); ++k) tot += V[k];
-      sc.s_out[(size_t)b * sc.stride] = sigmoidf(tot);
-    }
-    return;
-  }
+  if (l0 >= H) return score_rider(sc, b, V, nthr);
   RA_PROBE_AT(0);
   const int nrow = (H - l0) < RB ? (H - l0) : RB;
   // (1) the record: which of this workgroup's rows hold window pixels (60 % of the workgroups of a cfg2
@@ -628,17 +477,9 @@ __global__ __launch_bounds__(256) void paste_win_kernel(const float *__restrict_
       cvp[q] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsV, (t + q * nthr) * 16, 0, 0));
   }
   int wbeg, wend;
-  {
-    int w0, w1, tmp;
-    Ax.band(0, w0, tmp);
-    Ax.band(Fw - 1, tmp, w1);
-    wbeg = w0 & ~3;
-    wend = (w1 + 3) & ~3;
-    wend = wend < W ? wend : W;
-    if (wend < wbeg) wend = wbeg;
-    wbeg = __builtin_amdgcn_readfirstlane(wbeg);
-    wend = __builtin_amdgcn_readfirstlane(wend);
-  }
+  Ax.span4(wbeg, wend);
+  wbeg = __builtin_amdgcn_readfirstlane(wbeg);
+  wend = __builtin_amdgcn_readfirstlane(wend);
   const float y_dead = fast_sigmoid(beta);
   if (wend > -1000000) RA_PROBE_AT(1);  // the record has arrived
 
@@ -758,51 +599,42 @@ __global__ __launch_bounds__(256) void paste_win_kernel(const float *__restrict_
 using namespace ra;
 
 namespace {
-// paste_win_kernel where its shape conditions hold (the decode loop's launches), the general kernel otherwise.
-// plan != nullptr (ra_paste_plan): the same chain of choices, ending in a record instead of a launch; no pointer is followed.
+// What a paste launch looks like, chosen from facts alone: paste_win_kernel where its shape conditions hold (the decode
+// loop's launches), the general kernel otherwise.  grid_x counts the workgroups that hold image rows (a score rider adds one).
+struct PastePlan {
+  int kernel, rows, grid_x, threads;
+  size_t lds;
+};
+PastePlan choose_paste(int mode, int H, int W, int Fh, int Fw, int Cp, int pc, bool has_canvas, bool has_img, size_t y_stride_b,
+                       bool aligned16, attnd::PasteGeo pg) {
+  const int rb = pg.rows == 8 ? 8 : 4;
+  const bool win_ok = W % 4 == 0 && Fw <= 64 && rb * W <= 4096 && (y_stride_b & 3) == 0 && aligned16 &&
+                      (size_t)H * W * 4 < 0x7fffffffu && Fh * Fw % 4 == 0 && Fh * Fw <= 4 * attnd::kPsQuads * 256 &&
+                      (mode == 1 || (has_canvas && !has_img && Cp == 1 && pc == 0));
+  if (!win_ok)
+    return {RA_PASTE_KERNEL_GENERAL, pg.rows, ceil_div(H, pg.rows), pg.threads, (size_t)(pg.rows * Fw > 8 ? pg.rows * Fw : 8) * sizeof(float)};
+  return {RA_PASTE_KERNEL_WINDOW, rb, ceil_div(H, rb), 256, (size_t)rb * 256 * 16 + (size_t)(rb * Fw + Fh * Fw + 16) * sizeof(float)};
+}
+
 template <int MODE>
 void launch_paste(int extra_wg, const float *patch, int Cp, int pc, const float *attn_rec, int B, int H, int W, int Fh,
                   int Fw, float beta, int disable_overwrite, float *canvas, float *img, int Ci, int canvas_chan,
-                  float *y_out, size_t y_stride_b, int flags, attnd::ScoreArgs sc, void *stream, int *plan = nullptr) {
-  const attnd::PasteGeo pg = attnd::paste_geo();
-  const int rb = pg.rows == 8 ? 8 : 4;
+                  float *y_out, size_t y_stride_b, int flags, attnd::ScoreArgs sc, void *stream) {
   const bool a16 = ((reinterpret_cast<uintptr_t>(y_out) | reinterpret_cast<uintptr_t>(canvas) |
                      reinterpret_cast<uintptr_t>(patch)) & 15) == 0;
-  const bool win_ok = W % 4 == 0 && Fw <= 64 && rb * W <= 4096 && (y_stride_b & 3) == 0 && a16 &&
-                      (size_t)H * W * 4 < 0x7fffffffu && Fh * Fw % 4 == 0 && Fh * Fw <= 4 * attnd::kPsQuads * 256 &&
-                      (MODE == 1 || (canvas && !img && Cp == 1 && pc == 0));
-  if (!win_ok) {
-    const size_t lds = (size_t)(pg.rows * Fw > 8 ? pg.rows * Fw : 8) * sizeof(float);
-    if (plan) {
-      plan[RA_PASTE_PLAN_KERNEL] = RA_PASTE_KERNEL_GENERAL;
-      plan[RA_PASTE_PLAN_ROWS] = pg.rows;
-      plan[RA_PASTE_PLAN_GRID_X] = ceil_div(H, pg.rows) + extra_wg;
-      plan[RA_PASTE_PLAN_THREADS] = pg.threads;
-      plan[RA_PASTE_PLAN_LDS] = (int)lds;
-      return;
-    }
-    hipLaunchKernelGGL(attnd::paste_direct_kernel<MODE>, dim3(ceil_div(H, pg.rows) + extra_wg, B), dim3(pg.threads), lds,
-                       as_stream(stream), patch, Cp, pc, attn_rec, H, W, Fh, Fw, beta, disable_overwrite, canvas, img, Ci,
-                       canvas_chan, y_out, y_stride_b, flags, pg.rows, sc);
+  const PastePlan p = choose_paste(MODE, H, W, Fh, Fw, Cp, pc, canvas != nullptr, img != nullptr, y_stride_b, a16, attnd::paste_geo());
+  const dim3 grid(p.grid_x + extra_wg, B);
+  if (p.kernel == RA_PASTE_KERNEL_GENERAL) {
+    hipLaunchKernelGGL(attnd::paste_direct_kernel<MODE>, grid, dim3(p.threads), p.lds, as_stream(stream), patch, Cp, pc, attn_rec,
+                       H, W, Fh, Fw, beta, disable_overwrite, canvas, img, Ci, canvas_chan, y_out, y_stride_b, flags, p.rows, sc);
     return;
   }
-  const size_t lds = (size_t)rb * 256 * 16 + (size_t)(rb * Fw + Fh * Fw + 16) * sizeof(float);
-  if (plan) {
-    plan[RA_PASTE_PLAN_KERNEL] = RA_PASTE_KERNEL_WINDOW;
-    plan[RA_PASTE_PLAN_ROWS] = rb;
-    plan[RA_PASTE_PLAN_GRID_X] = ceil_div(H, rb) + extra_wg;
-    plan[RA_PASTE_PLAN_THREADS] = 256;
-    plan[RA_PASTE_PLAN_LDS] = (int)lds;
-    return;
-  }
-  if (rb == 8)
-    hipLaunchKernelGGL((attnd::paste_win_kernel<MODE, 8>), dim3(ceil_div(H, 8) + extra_wg, B), dim3(256), lds,
-                       as_stream(stream), patch, attn_rec, H, W, Fh, Fw, beta, disable_overwrite, canvas, y_out, y_stride_b,
-                       flags, sc, tail_prio());
-  else
-    hipLaunchKernelGGL((attnd::paste_win_kernel<MODE, 4>), dim3(ceil_div(H, 4) + extra_wg, B), dim3(256), lds,
-                       as_stream(stream), patch, attn_rec, H, W, Fh, Fw, beta, disable_overwrite, canvas, y_out, y_stride_b,
-                       flags, sc, tail_prio());
+  const auto window = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, grid, dim3(p.threads), p.lds, as_stream(stream), patch, attn_rec, H, W, Fh, Fw, beta,
+                       disable_overwrite, canvas, y_out, y_stride_b, flags, sc, tail_prio());
+  };
+  if (p.rows == 8) window(attnd::paste_win_kernel<MODE, 8>);
+  else window(attnd::paste_win_kernel<MODE, 4>);
 }
 }  // namespace
 
@@ -815,8 +647,9 @@ extern "C" int ra_extract_direct_f32(const float *img, int Ci, int chan0, const 
     return fail(RA_E_SHAPE, "ra_extract_direct_f32: Ci=%d chan0=%d Cp=%d Fw=%d", Ci, chan0, Cp, Fw);
   if ((size_t)H * W * Ci * 4 >= 0x7fffffffu) return fail(RA_E_SHAPE, "ra_extract_direct_f32: one image exceeds 2 GiB");
   const int n_items = Fh * (Cp / 4) * B, chunk = ceil_div(n_items, 8);
-  hipLaunchKernelGGL((attnd::extract_rows_kernel<4>), dim3(8 * chunk), dim3(256), 0, as_stream(stream), img, Ci, chan0,
-                     canvas, canvas_chan, attn_rec, H, W, Fh, Fw, Cp, use_gamma, patch, n_items, chunk, tail_prio());
+  hipLaunchKernelGGL((attnd::extract_rows_kernel<1, 4>), dim3(8 * chunk), dim3(256), 0, as_stream(stream), img, Ci, chan0,
+                     canvas, canvas_chan, attn_rec, H, W, Fh, Fw, Cp, use_gamma, patch, attnd::Conv0Args{}, n_items, chunk,
+                     tail_prio());
   return launch_status("ra_extract_direct_f32");
 }
 
@@ -835,12 +668,12 @@ extern "C" int ra_extract_conv0_f32(const float *img, int Ci, int chan0, const f
   if ((size_t)H * W * Ci * 4 >= 0x7fffffffu) return fail(RA_E_SHAPE, "ra_extract_conv0_f32: one image exceeds 2 GiB");
   const int n_items = Fh * B, chunk = ceil_div(n_items, 8);
   static const int kr = env_int("RA_EXC0_KR", 5) == 4 ? 4 : 5;  // =4: tuning aid (rows per wave and load round; 5 covers cfg2's 38-row union in two rounds)
-  if (kr == 4)
-    hipLaunchKernelGGL((attnd::extract_conv0_kernel<4>), dim3(8 * chunk), dim3(256), 0, as_stream(stream), img, Ci, chan0, canvas,
-                       canvas_chan, attn_rec, H, W, Fh, Fw, use_gamma, patch, w0, scale, shift, Cout, relu, y0, n_items, chunk);
-  else
-    hipLaunchKernelGGL((attnd::extract_conv0_kernel<5>), dim3(8 * chunk), dim3(256), 0, as_stream(stream), img, Ci, chan0, canvas,
-                       canvas_chan, attn_rec, H, W, Fh, Fw, use_gamma, patch, w0, scale, shift, Cout, relu, y0, n_items, chunk);
+  const auto fused = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(8 * chunk), dim3(256), 0, as_stream(stream), img, Ci, chan0, canvas, canvas_chan, attn_rec, H, W,
+                       Fh, Fw, 4, use_gamma, patch, attnd::Conv0Args{w0, scale, shift, Cout, relu, y0}, n_items, chunk, 0);
+  };
+  if (kr == 4) fused(attnd::extract_rows_kernel<3, 4>);
+  else fused(attnd::extract_rows_kernel<3, 5>);
   return launch_status("ra_extract_conv0_f32");
 }
 
@@ -870,17 +703,13 @@ extern "C" int ra_paste_plan(int mode, int B, int H, int W, int Fh, int Fw, int 
   if (!plan || (mode != 0 && mode != 1) || B <= 0 || H <= 0 || W <= 0 || Fh <= 0 || Fw <= 0 ||
       (mode == 0 && (Cp <= 0 || pc < 0 || pc >= Cp)))
     return fail(RA_E_INVALID, "ra_paste_plan: bad argument");
+  const PastePlan p = choose_paste(mode, H, W, Fh, Fw, Cp, pc, has_canvas != 0, has_img != 0, y_stride_b, aligned16 != 0, attnd::paste_geo());
   for (int i = 0; i < RA_PASTE_PLAN_INTS; ++i) plan[i] = 0;
-  // stand-ins for the pointers, with the alignment and presence asked about: the chain only looks at their low bits and
-  // at whether they are null
-  float *const there = reinterpret_cast<float *>(uintptr_t(64));
-  float *const y_out = reinterpret_cast<float *>(uintptr_t(aligned16 ? 64 : 68));
-  if (mode == 0)
-    launch_paste<0>(0, there, Cp, pc, nullptr, B, H, W, Fh, Fw, 0.0f, 0, has_canvas ? there : nullptr, has_img ? there : nullptr,
-                    0, -1, y_out, y_stride_b, 0, attnd::ScoreArgs{}, nullptr, plan);
-  else
-    launch_paste<1>(0, nullptr, 1, 0, nullptr, B, H, W, Fh, Fw, 0.0f, 0, nullptr, nullptr, 0, -1, y_out, y_stride_b, 0,
-                    attnd::ScoreArgs{}, nullptr, plan);
+  plan[RA_PASTE_PLAN_KERNEL] = p.kernel;
+  plan[RA_PASTE_PLAN_ROWS] = p.rows;
+  plan[RA_PASTE_PLAN_GRID_X] = p.grid_x;
+  plan[RA_PASTE_PLAN_THREADS] = p.threads;
+  plan[RA_PASTE_PLAN_LDS] = (int)p.lds;
   return 0;
 }
 

@@ -14,18 +14,15 @@
 // d fx[w,i] = sum_{l,j,c} fy[l,j] X[l,w,c] Q[j,i,c]  with the filters' derivatives
 //   d w / d mu = w (l - mu) / var,  d mu_j / d ctr = 1,  d mu_j / d size = (j - (F-1)/2) / F,
 //   d w / d lg_var = w (-1/2 + (l - mu)^2 / (2 var)).
-// Workgroup = (tap j, channel group, image), the geometry of extract_rows_kernel: its tap's row band x the
-// window's columns, one pass.  Everything is restricted to the band where the weight exceeds e^-30 of the peak.
-#include "ra_attn_axis.h"
+// Workgroup = (tap j, channel group, image), the band walk of extract_rows_kernel (ra_attn_parts.h): its tap's row band x
+// the window's columns, one pass.  Everything is restricted to the band where the weight exceeds e^-30 of the peak.
+#include "ra_attn_parts.h"
 #include "ra_common.h"
 
 namespace ra {
 namespace attnt {
 
-using attnd::Axis;
-using attnd::f32x4;
-using attnd::make_axis;
-using attnd::readlane_f;
+using namespace attnd;
 
 constexpr int kKR = 4;
 
@@ -46,12 +43,6 @@ struct VT<1> {
   static __device__ inline float splat(float v) { return v; }
 };
 
-__device__ inline float wave_sum(float v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
 struct BwdArgs {
   const float *X;   // NC = 4: [B,H,W,Cx], channels chan0 + 4 cg ..  (PASTE: unused)
   int Cx, chan0;
@@ -70,22 +61,20 @@ template <int NC, bool PASTE>
 __global__ __launch_bounds__(256) void resample_bwd_kernel(const BwdArgs a, int n_items, int chunk) {
   typedef typename VT<NC>::type V;
   constexpr int KR = kKR;
-  __shared__ V red[4][256];
+  __shared__ V red[1][4][256];
   __shared__ V Qs[256];
   __shared__ float sred[4][8];
   const int t = threadIdx.x, lane = t & 63, wv = __builtin_amdgcn_readfirstlane(t >> 6);
-  const int slot = blockIdx.x >> 3;
-  const int item = (blockIdx.x & 7) * chunk + slot;  // XCD-contiguous: the taps of an image share an L2
-  if (slot >= chunk || item >= n_items) return;
+  int item;
+  if (!band_item(n_items, chunk, item)) return;
   const int H = a.H, W = a.W, Fh = a.Fh, Fw = a.Fw, ncg = a.ncg;
   const int b = item / (Fh * ncg), rem = item - b * Fh * ncg;
   const int j = rem / ncg, cg = rem - j * ncg;
   const float *rec = a.rec + (size_t)b * RA_ATTN_STRIDE;
   const Axis Ay = make_axis(rec, 0, H, Fh), Ax = make_axis(rec, 1, W, Fw);
-  int l0, l1, w0, w1, tmp;
+  int l0, l1, w0, w1;
   Ay.band(j, l0, l1);
-  Ax.band(0, w0, tmp);
-  Ax.band(Fw - 1, tmp, w1);
+  Ax.span(w0, w1);
   const float gain = PASTE ? (a.gain_mode ? rec[7] : __expf(rec[8])) : 1.0f;
   const float ivy = 2.0f * Ay.inv2var, ivx = 2.0f * Ax.inv2var;  // 1 / var
   const float muj = Ay.mu(j);
@@ -100,7 +89,6 @@ __global__ __launch_bounds__(256) void resample_bwd_kernel(const BwdArgs a, int 
     Qs[i] = q;
   }
   __syncthreads();
-  constexpr int kOOB = 0x7fffffff;
   const size_t img_px = (size_t)H * W;
   const __amdgpu_buffer_rsrc_t rsX = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float *>(PASTE ? a.dY + (size_t)b * img_px : a.X + (size_t)b * img_px * a.Cx + a.chan0 + 4 * cg), 0,
@@ -108,12 +96,8 @@ __global__ __launch_bounds__(256) void resample_bwd_kernel(const BwdArgs a, int 
   const __amdgpu_buffer_rsrc_t rsY = __builtin_amdgcn_make_buffer_rsrc(
       const_cast<float *>(PASTE ? a.Yv + (size_t)b * img_px : a.rec), 0, PASTE ? (int)(img_px * 4) : 0, 0x00020000);
 
-  // stage-2 role: output column oi of this tap, its band's columns dealt to `parts` neighbouring lanes
-  const int parts = (Fw * 4 <= 256) ? 4 : (Fw * 2 <= 256) ? 2 : 1;
-  const int oi = t / parts, part = t - oi * parts;
-  const bool owner = oi < Fw;
-  int bi_lo = 0, bi_hi = 0;
-  if (owner) Ax.band(oi, bi_lo, bi_hi);
+  const Role ro = stage2_role<0>(Ax, t);
+  const int oi = ro.oi;
   const float mui = Ax.mu(oi);
   V P = VT<NC>::zero();
   float py0 = 0.f, py1 = 0.f, py2 = 0.f, px0 = 0.f, px1 = 0.f, px2 = 0.f;
@@ -133,30 +117,26 @@ __global__ __launch_bounds__(256) void resample_bwd_kernel(const BwdArgs a, int 
       }
       G[p] = g;
     }
-    V acc[4];
+    V acc[1][4];
 #pragma unroll
-    for (int p = 0; p < 4; ++p) acc[p] = VT<NC>::zero();
+    for (int p = 0; p < 4; ++p) acc[0][p] = VT<NC>::zero();
     for (int rb = l0; rb < l1; rb += 4 * KR) {
       V xv[KR][4];
 #pragma unroll
-      for (int k = 0; k < KR; ++k) {
-        const int row = rb + 4 * k + wv;
+      for (int k = 0; k < KR; ++k)
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
-          const int col = cp + 64 * p + lane;
-          const int pix = (row < l1 && col < w1) ? row * W + col : -1;
+          const int pix = round_pix(rb, k, wv, cp, p, lane, l1, w1, W);
           if constexpr (PASTE) {
-            const float dy = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX, pix >= 0 ? pix * 4 : kOOB, 0, 0));
-            const float yv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsY, pix >= 0 ? pix * 4 : kOOB, 0, 0));
+            const float dy = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsX, pix_off(pix, 4), 0, 0));
+            const float yv = __builtin_bit_cast(float, __builtin_amdgcn_raw_buffer_load_b32(rsY, pix_off(pix, 4), 0, 0));
             xv[k][p] = gain * dy * yv * (1.0f - yv);
           } else {
-            xv[k][p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsX, pix >= 0 ? pix * a.Cx * 4 : kOOB, 0, 0));
+            xv[k][p] = __builtin_bit_cast(f32x4, __builtin_amdgcn_raw_buffer_load_b128(rsX, pix_off(pix, a.Cx * 4), 0, 0));
           }
         }
-      }
-      // the row filter of this wave's KR rows: lane k evaluates row rb + 4k + wv
       const int rowl = rb + 4 * lane + wv;
-      const float fyv = (lane < KR && rowl < l1) ? Ay.w((float)rowl, j) : 0.0f;
+      const float fyv = row_weight<KR>(Ay, j, rowl, lane, l1);
       float smine = 0.0f;  // lane k: sum_w X[row_k, w] . G[w]
 #pragma unroll
       for (int k = 0; k < KR; ++k) {
@@ -165,7 +145,7 @@ __global__ __launch_bounds__(256) void resample_bwd_kernel(const BwdArgs a, int 
 #pragma unroll
         for (int p = 0; p < 4; ++p) {
           rd += VT<NC>::dot(xv[k][p], G[p]);
-          acc[p] += wy * xv[k][p];
+          acc[0][p] += wy * xv[k][p];
         }
         rd = wave_sum(rd);
         smine = (lane == k) ? rd : smine;
@@ -175,19 +155,14 @@ __global__ __launch_bounds__(256) void resample_bwd_kernel(const BwdArgs a, int 
       py0 += tt * d * ivy;
       py2 += tt * (-0.5f + 0.5f * d * d * ivy);
     }
-    __syncthreads();  // the previous column group's stage 2 is done with `red`
-#pragma unroll
-    for (int p = 0; p < 4; ++p) red[wv][64 * p + lane] = acc[p];
-    __syncthreads();
-    red[0][t] = (red[0][t] + red[1][t]) + (red[2][t] + red[3][t]);  // T1[w] = sum_l fy[l, j] X[l, w]
-    __syncthreads();
-    if (owner) {
+    reduce_waves(red, acc, t, wv, lane);  // red[0][0][w - cp] = T1[w] = sum_l fy[l, j] X[l, w]
+    if (ro.owner) {
       const int cend = (cp + 256 < w1) ? cp + 256 : w1;
-      const int lo = bi_lo > cp ? bi_lo : cp, hi = bi_hi < cend ? bi_hi : cend;
+      const int lo = ro.bi_lo > cp ? ro.bi_lo : cp, hi = ro.bi_hi < cend ? ro.bi_hi : cend;
       const V q = Qs[oi];
-      for (int ww = lo + part; ww < hi; ww += parts) {
+      for (int ww = lo + ro.part; ww < hi; ww += ro.parts) {
         const float f = Ax.w((float)ww, oi);
-        const V T1 = red[0][ww - cp];
+        const V T1 = red[0][0][ww - cp];
         P += f * T1;
         const float d = (float)ww - mui, tt = VT<NC>::dot(T1, q) * f;  // d fx[w, i] * fx[w, i]
         px0 += tt * d * ivx;
@@ -200,21 +175,8 @@ __global__ __launch_bounds__(256) void resample_bwd_kernel(const BwdArgs a, int 
   // E[j, oi] and sum E . Q
   float eq = 0.0f;
   {
-    V v = P;
-    if constexpr (NC == 4) {
-      if (parts >= 2) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] += __shfl_xor(v[c], 1);
-      }
-      if (parts >= 4) {
-#pragma unroll
-        for (int c = 0; c < 4; ++c) v[c] += __shfl_xor(v[c], 2);
-      }
-    } else {
-      if (parts >= 2) v += __shfl_xor(v, 1);
-      if (parts >= 4) v += __shfl_xor(v, 2);
-    }
-    if (owner && part == 0) {
+    const V v = parts_sum(P, ro.parts);
+    if (ro.owner && ro.part == 0) {
       eq = VT<NC>::dot(v, Qs[oi]);
       if (a.E) {
         float *ep = a.E + (((size_t)b * Fh + j) * Fw + oi) * a.Ce + (NC == 4 ? 4 * cg : 0);

@@ -120,6 +120,31 @@ def test_every_paste_form_is_reached_in_both_modes():
     assert plans[(sid, 'plane')].startswith('general') and plans[(sid, 'box')].startswith('general'), sid
 
 
+# shape -> (grid_x, LDS bytes of the general kernel, LDS bytes of the window kernel or None where the shape never reaches it):
+# the whole record ra_paste_plan returned before the chooser became a function of its own (rows 4, 256 threads throughout)
+PLAN_RECORDS = {'s40x72': (10, 256, 17728), 's37x50': (10, 192, None), 's64x64': (16, 768, 26432), 's6x1028': (2, 256, None),
+                's22x40': (6, 192, 17024), 'f_fw80': (10, 1280, None), 'f_fw130': (10, 2080, None), 'f_64x64': (10, 1024, None),
+                'f_3x3': (10, 48, None)}
+PLAN_FLIPS = {'base': {}, 'no_canvas': dict(has_canvas=False), 'img': dict(has_img=True), 'unaligned': dict(aligned16=False),
+              'odd_stride': None}
+
+
+def test_paste_plan_records_with_each_fact_flipped():
+  """ops.paste_plan from the decode loop's facts with each of has_canvas / has_img / aligned16 / the stride flipped on its own,
+  paste and box: every field of the record.  A canvas or an image does not count for the box."""
+  import ra_ops as ops
+  assert set(PLAN_RECORDS) == set(ag.PASTE_CASES)
+  for sid, (grid_x, lds_general, lds_window) in PLAN_RECORDS.items():
+    H, W, Fh, Fw = ag.all_shapes()[sid]
+    for mode in ('paste', 'box'):
+      for flip, kw in PLAN_FLIPS.items():
+        stride = ag.odd_stride(H, W) if flip == 'odd_stride' else 2 * H * W
+        got = ops.paste_plan(mode, ag.B_LAUNCH, H, W, Fh, Fw, y_stride_b=stride, **(kw or {}))
+        window = lds_window is not None and (flip == 'base' or (mode == 'box' and flip in ('no_canvas', 'img')))
+        want = dict(kernel='window' if window else 'general', rows=4, grid_x=grid_x, threads=256, lds=lds_window if window else lds_general)
+        assert got == want, (sid, mode, flip, got)
+
+
 @pytest.mark.parametrize('sid', tuple(ag.SHAPES))
 def test_float32_bank_is_eight_times_inside_its_bound(sid):
   """The dense bank (ra_gaussian_filter_f32's reference) per record and axis: float32 against float64 at an eighth of the GPU

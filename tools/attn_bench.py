@@ -1,9 +1,12 @@
 #!/usr/bin/env python
 """Graph-replay timing of the attention kernels at cfg2 shapes (the bench's attention records).
-  RA_PASTE_GEO=<rows>,<threads> picks the paste geometry (read once per process)."""
+  RA_PASTE_GEO=<rows>,<threads> picks the paste geometry (read once per process); RA_LIB = another build of the library."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, 'rec-attend-public_amd')); sys.path.insert(0, ROOT)
+import ra_native as rn
+if os.environ.get('RA_LIB'):  # A/B: another build of the library (same ABI)
+  rn.LIB_PATH = os.environ['RA_LIB']
 import torch, bench, full_model, ra_ops as ops
 
 def gtime(fn, reps=50, inner=8):

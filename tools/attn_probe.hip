@@ -97,9 +97,9 @@ int main(int argc, char **argv) {
   using namespace ra::attnd;
   {
     const int n_items = Fh * (Cp / 4) * B, chunk = (n_items + 7) / 8;
-    run("extract_rows<4>", 8 * chunk, 4, [&] {
-      hipLaunchKernelGGL((extract_rows_kernel<4>), dim3(8 * chunk), dim3(256), 0, 0, img, Ci, 0, canvas, 3, attn, H, W, Fh,
-                         Fw, Cp, 1, patch, n_items, chunk, 0);
+    run("extract_rows<1,4>", 8 * chunk, 4, [&] {
+      hipLaunchKernelGGL((extract_rows_kernel<1, 4>), dim3(8 * chunk), dim3(256), 0, 0, img, Ci, 0, canvas, 3, attn, H, W, Fh,
+                         Fw, Cp, 1, patch, Conv0Args{}, n_items, chunk, 0);
     });
   }
   for (int flags : {3, 2, 0}) {
