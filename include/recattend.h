@@ -959,6 +959,41 @@ int ra_labels_assemble_i32(const int *gt_ids, const int *ids, const int *count, 
                            unsigned char *fg_gt_full, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The image stage in front of the label stage (csrc/ra_image.hip): the network's input x from the full-size colour image,
+ * data_api/ins_seg_assembler.py:116 (cv2.resize(img, inp_shape, interpolation=cv2.INTER_CUBIC) on the uint8 BGR array of
+ * cv2.imread) as ins_seg_dataset.py:149 reads it back (x / 255 in float32), and the row filters of the PNG files the images
+ * come in.  cv2 is not part of this stack and was never run: what follows RESTATES the fixed-point recipe its source has for
+ * 8-bit images, and equality is claimed with this statement.
+ *
+ * One axis of source length S and destination length D: scale = (double)S / D; f = (float)((d + 0.5) * scale - 0.5);
+ *   s = floor(f), t = f - s in float32; with A = -0.75 the float32 weights
+ *     c0 = ((A*(t+1) - 5A)*(t+1) + 8A)*(t+1) - 4A      c1 = ((A+2)*t - (A+3))*t*t + 1
+ *     c2 = ((A+2)*(1-t) - (A+3))*(1-t)*(1-t) + 1       c3 = 1 - c0 - c1 - c2
+ *   q[k] = (short)rint(c[k] * 2048), half to even, the sum NOT corrected (2047 and 2049 occur); tap k reads source index
+ *   clamp(s - 1 + k, 0, S - 1).  A pixel: h = sum_k qx[k] * src[..] in int32 along x, v = sum_k qy[k] * h_k along y,
+ *   out = clamp((v + (1 << 21)) >> 22, 0, 255), an arithmetic shift.
+ *
+ * ra_resize_cubic_tables — HOST code, no GPU call: ofs[D] = s and coef[D][4] = q of one axis.  S, D >= 1, else RA_E_SHAPE.
+ * ra_resize_cubic_u8 — src uint8 [N,Hs,Ws,C], C = 1 | 3, and the tables of the y axis (Hs -> H) and of the x axis (Ws -> W)
+ *   in DEVICE memory -> dst_u8 uint8 [N,H,W,C] and / or dst_f32 float [N,H,W,C] = (float)level / 255.0f, a correctly
+ *   rounded float32 division (NumPy's u8.astype(float32) / 255, bit for bit); a NULL output is skipped.  Any Hs, Ws, H, W
+ *   >= 1, enlarging included; Hs * Ws * C < 2^31, the bytes of an output plane (H * W * C, x 4 with dst_f32) < 2^31,
+ *   1 <= N <= 65535; anything else, a NULL src or a NULL table is RA_E_SHAPE before anything is launched.  One launch, no
+ *   allocation, no synchronisation.  Source rows are staged with 16-byte loads when Ws * C % 16 == 0 and src is 16-byte
+ *   aligned, the outputs are stored 4 values at a time when W * C % 4 == 0 and they are aligned (dst_u8 4, dst_f32 16
+ *   bytes); the other forms read and write single bytes / floats.  Tap indices are clamped inside the kernel: tables of
+ *   another shape give wrong pixels, never an access outside src.
+ * ra_png_unfilter_u8 — HOST code, no GPU call: the filters of PNG specification 9.2 undone.  raw: H scanlines of one
+ *   filter-type byte + stride bytes; bpp: bytes per complete pixel (1 .. 8, stride a multiple of it); out: uint8 [H,stride].
+ *   A filter type above 4 or a bad size is RA_E_SHAPE and names the row.
+ * ---------------------------------------------------------------------------------- */
+int ra_resize_cubic_tables(int S, int D, int *ofs, short *coef);
+int ra_resize_cubic_u8(const unsigned char *src, int N, int Hs, int Ws, int C, int H, int W, const int *ofs_y,
+                       const short *coef_y, const int *ofs_x, const short *coef_x, unsigned char *dst_u8, float *dst_f32,
+                       void *stream);
+int ra_png_unfilter_u8(const unsigned char *raw, int H, int stride, int bpp, unsigned char *out);
+
+/* ------------------------------------------------------------------------------------
  * Evaluating the pre-stage fg_model (csrc/ra_fg_eval.hip).
  *
  * ra_fg_stats_f32 — the sums behind the six statistics the reference's Evaluator logs (fg_model_train.py:131-133), replacing

@@ -30,7 +30,7 @@ class CtrlDesc(C.Structure):
 
 
 _SCALARS = {'int': C.c_int, 'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t}
-_POINTEES = ('float', 'int', 'void', 'unsigned short', 'double', 'unsigned char', 'unsigned long long')
+_POINTEES = ('float', 'int', 'void', 'unsigned short', 'double', 'unsigned char', 'unsigned long long', 'short')
 
 
 def _ctype(words, name):

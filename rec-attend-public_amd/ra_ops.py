@@ -1930,3 +1930,62 @@ def assemble_labels(gt_ids, H, W, T, dataset, want=('y_gt', 's_gt'), names=None)
   out = assemble_labels_raw(gt_ids, (ids, pixels, count), H, W, T, dataset, want)
   _raise_gt_status(status, names, 'assemble_labels')
   return out
+
+
+# ---- the image stage (csrc/ra_image.hip): x at network size from the full-size colour image
+RESIZE_OUTPUTS = ('x', 'u8')
+RESIZE_MAX_N = 65535  # images per launch (the grid's y extent)
+_CUBIC_TABLES = {}    # (S, D, device) -> (ofs int32 [D], coef int16 [D,4]) on that device
+
+
+def cubic_tables(S, D):
+  """ra_resize_cubic_tables (host code, no device): one axis of cv2.resize(..., INTER_CUBIC) on 8-bit images, source length
+  S -> destination length D, as include/recattend.h restates it -> (ofs int32 [D], coef int16 [D,4]) NumPy arrays: tap k of
+  destination index d reads source index clamp(ofs[d] - 1 + k, 0, S - 1) with weight coef[d, k] / 2048."""
+  S, D = int(S), int(D)
+  ofs, coef = np.empty((max(D, 0),), np.int32), np.empty((max(D, 0), 4), np.int16)
+  check(rn.lib().ra_resize_cubic_tables(S, D, ptr(ofs), ptr(coef)), 'ra_resize_cubic_tables')
+  return ofs, coef
+
+
+def _cubic_tables_dev(S, D, device):
+  key = (S, D, str(device))
+  if key not in _CUBIC_TABLES:
+    ofs, coef = cubic_tables(S, D)
+    _CUBIC_TABLES[key] = (torch.from_numpy(ofs).to(device), torch.from_numpy(coef).to(device))
+  return _CUBIC_TABLES[key]
+
+
+def resize_cubic(src, H, W, want=('x',)):
+  """ins_seg_assembler.py:116 and ins_seg_dataset.py:149 on the device (ra_resize_cubic_u8): src uint8 [N,Hs,Ws,C], C = 1 | 3
+  — a device tensor or a NumPy array — -> {'x': float32 [N,H,W,C] = level / 255, 'u8': uint8 [N,H,W,C]} over `want`.  The
+  channel order is the caller's (cv2's BGR in the reference).  The tables of an (S, D) pair are made once per device."""
+  want = tuple(want)
+  if not want or any(k not in RESIZE_OUTPUTS for k in want):
+    raise rn.RecAttendError('resize_cubic: want %s (any of %s)' % (list(want), ', '.join(RESIZE_OUTPUTS)))
+  if isinstance(src, np.ndarray):
+    if src.dtype != np.uint8:
+      raise rn.RecAttendError('resize_cubic: src must be uint8, got %s' % src.dtype)
+    if not torch.cuda.is_available():
+      raise rn.RecAttendError('recattend kernels need CUDA (HIP) tensors; no device is available. There is no CPU fallback.')
+    src = torch.from_numpy(np.ascontiguousarray(src)).cuda()
+  _need_dev(src, torch.uint8, 'src')
+  H, W = int(H), int(W)
+  if src.dim() != 4 or min(src.shape) < 1 or src.shape[3] not in (1, 3) or H < 1 or W < 1:
+    raise rn.RecAttendError('resize_cubic: src must be [N,Hs,Ws,C] with C = 1 or 3 and H, W >= 1, got %s -> %d x %d' % (
+        tuple(src.shape), H, W))
+  N, Hs, Ws, Cc = src.shape
+  if N > RESIZE_MAX_N or Hs * Ws * Cc >= 1 << 31 or H * W * Cc * (4 if 'x' in want else 1) >= 1 << 31:
+    raise rn.RecAttendError('resize_cubic: N=%d, %d x %d -> %d x %d, C=%d (N <= %d, every plane below 2^31 bytes)' % (
+        N, Hs, Ws, H, W, Cc, RESIZE_MAX_N))
+  dev = src.device
+  oy, cy = _cubic_tables_dev(Hs, H, dev)
+  ox, cx = _cubic_tables_dev(Ws, W, dev)
+  out = {}
+  if 'x' in want:
+    out['x'] = torch.empty((N, H, W, Cc), dtype=torch.float32, device=dev)
+  if 'u8' in want:
+    out['u8'] = torch.empty((N, H, W, Cc), dtype=torch.uint8, device=dev)
+  check(rn.lib().ra_resize_cubic_u8(ptr(src), N, Hs, Ws, Cc, H, W, ptr(oy), ptr(cy), ptr(ox), ptr(cx), ptr(out.get('u8')),
+                                    ptr(out.get('x')), rn.stream_ptr()), 'ra_resize_cubic_u8')
+  return out

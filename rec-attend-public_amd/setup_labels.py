@@ -5,8 +5,22 @@ to the ground truth the train and eval entry points read, as data_api/ins_seg_da
 them.
 
   --input PATH      an .npz with gt_instance_ids [N,Hf,Wf] (+ names [N], + optionally x [N,H,W,3] at network size, which is
-                    passed through), or a folder searched for *.png: one-channel 8- or 16-bit label images (Cityscapes'
-                    *_instanceIds.png), read with utils/png.py, all of one size;
+                    passed through, or x_full uint8 [N,Hf,Wf,3] and no x, which is resized to x as --images does), or a
+                    folder searched for *.png: one-channel 8- or 16-bit label images (Cityscapes' *_instanceIds.png), read
+                    with utils/png.py, all of one size;
+  --images DIR      (opt-in) the colour image of every label file, read with utils/png.read_colour8 (uint8, cv2's BGR order)
+                    and resized to network size on the device in batches (ra_ops.resize_cubic, the INTER_CUBIC of
+                    ins_seg_assembler.py:116): the archive then holds x float32 [N,H,W,3] (BGR, / 255) and orig_size int32
+                    [N,2].  The label folder is then filtered by the dataset's label pattern, and the image is
+                      cityscapes  <key>_leftImg8bit.png anywhere below DIR for <key>_gtFine_instanceIds.png,
+                      kitti       the label file's basename below DIR,
+                      cvppp       plantNNN_rgb.png for plantNNN_label.png (DIR may be --input itself);
+                    where DIR holds the name more than once, the one in the label's own sub-folder.  A label without an
+                    image, or an image whose size is not its label's, is an error that names the file;
+  --colour_labels   (opt-in) label files may be colour PNG files (CVPPP's and KITTI's, cvppp.py:58, kitti.py:57): per image
+                    code = B << 16 | G << 8 | R (sep_labels.py:15 on cv2's BGR array), the distinct non-zero codes in
+                    ascending order become the ids 1, 2, ... and 0 stays 0, on the host (np.unique).  Grey files pass
+                    through unchanged;
   --dataset         cityscapes (an id is an instance iff id > 1000 and id // 1000 is one of the eight instance labels; nine
                     semantic channels) | kitti | cvppp (every id != 0 is an instance; one semantic channel);
   --height, --width, --timespan   the network size and the number of instance slots (default: the dataset's,
@@ -18,13 +32,16 @@ them.
   --output FILE     the .npz that is written.
 
 The instances of an image are sorted by their area at network size, descending; equal areas put the larger id first
-(DESIGN.md).  Limits, stated: colour label images (the three-channel files of CVPPP and KITTI: pack the colour into an id in
-[1, 65535] yourself), the INTER_CUBIC resize of the colour image to network size (bring x at network size, or none) and HDF5
-output are not built.  An image with more than ra_ops.MAX_GT distinct ids or an id above 65535 is an error that names it.
+(DESIGN.md).  Limits, stated: without the two flags a colour label image is refused (pack the colour into an id in [1, 65535]
+yourself) and x comes at network size or not at all; colour files are 8-bit and not interlaced, x is in BGR order; all
+images and labels of a run have ONE full size (mixed sizes are refused: "one full size per run"); HDF5 output is not built.
+The resize equals the recipe include/recattend.h restates from cv2's source, not a cv2 that was run.  An image with more than
+ra_ops.MAX_GT distinct ids (under --colour_labels: more than MAX_GT - 1 colours) or an id above 65535 is an error that names it.
 There is no CPU path: without a GPU the script raises RecAttendError once the input has been read."""
 import argparse
 import fnmatch
 import os
+import re
 
 import numpy as np
 
@@ -38,6 +55,7 @@ TARGETS = {
     'all': {'y_gt_ins': 'y_gt', 's_gt': 's_gt', 'c_gt': 'c_gt', 'd_gt': 'd_gt', 'd_cls': 'd_cls', 'fg_gt_full': 'fg_gt_full',
             'inst_id': 'inst_id', 'area': 'area', 'sem_cls': 'sem_cls', 'num_obj': 'num_obj'},
 }  # archive key -> ra_ops.assemble_labels output
+LABEL_PATTERNS = {'cityscapes': '*_gtFine_instanceIds.png', 'kitti': '*.png', 'cvppp': 'plant*_label.png'}  # under --images
 
 
 def build_parser():
@@ -50,17 +68,37 @@ def build_parser():
   p.add_argument('--target', default='full_model', choices=sorted(TARGETS))
   p.add_argument('--output', required=True, help='the .npz to write')
   p.add_argument('--batch_size', type=int, default=8)
+  p.add_argument('--images', default=None, help='folder of the colour images: resized to x at network size on the device')
+  p.add_argument('--colour_labels', action='store_true', help='label files may be colour PNG files: colours become ids')
   return p
 
 
-def read_label_png(path):
-  """A one-channel, non-interlaced 8- or 16-bit PNG -> int32 [Hf,Wf]."""
+def colour_ids(bgr, path):
+  """sep_labels.py:12-26 on cv2's BGR array: uint8 [Hf,Wf,3] -> int32 ids, 0 for the code 0 and 1, 2, ... for the other
+  distinct codes B << 16 | G << 8 | R in ascending order."""
+  import ra_ops as ops
+  code = (bgr[:, :, 0].astype(np.int32) << 16) | (bgr[:, :, 1].astype(np.int32) << 8) | bgr[:, :, 2]
+  codes, inverse = np.unique(code, return_inverse=True)
+  n = len(codes) - (1 if codes[0] == 0 else 0)
+  if n > ops.MAX_GT - 1:
+    raise RecAttendError('%s: %d distinct colours, at most %d are instances of one image' % (path, n, ops.MAX_GT - 1))
+  first = 0 if codes[0] == 0 else 1  # the id of the smallest code
+  return (inverse.reshape(code.shape) + first).astype(np.int32)
+
+
+def read_label_png(path, colour_labels=False):
+  """A one-channel, non-interlaced 8- or 16-bit PNG -> int32 [Hf,Wf]; with colour_labels also a colour PNG (colour_ids)."""
   from utils import png
   with open(path, 'rb') as f:
     data = f.read()
   if len(data) < 26 or data[:8] != png.SIGNATURE:
     raise RecAttendError('%s is not a PNG file' % path)
   depth, colour = data[24], data[25]
+  if colour_labels and not (colour == 0 and depth in (8, 16)):
+    try:
+      return colour_ids(png.decode_colour8(data), path)
+    except ValueError as e:
+      raise RecAttendError('%s: %s' % (path, e))
   if colour != 0 or depth not in (8, 16):
     raise RecAttendError('%s: colour type %d, bit depth %d — only one-channel 8- or 16-bit label images are read (pack a colour '
                          'label image into ids in [1, 65535] first)' % (path, colour, depth))
@@ -70,20 +108,53 @@ def read_label_png(path):
     raise RecAttendError('%s: %s' % (path, e))
 
 
-def load_input(path):
-  """-> (gt_instance_ids integer [N,Hf,Wf], names [N], x or None)"""
+def find_files(path, pattern='*.png'):
+  """The files below `path` whose name matches `pattern`, sorted."""
+  found = []
+  for root, _, files in os.walk(path):
+    found += [os.path.join(root, f) for f in fnmatch.filter(files, pattern)]
+  return sorted(found)
+
+
+def image_name(dataset, label_name):
+  """The colour image's file name for a label file's (ins_seg_assembler.py's datasets: cityscapes.py, kitti.py, cvppp.py:41)."""
+  if dataset == 'cityscapes':
+    return label_name[:-len('_gtFine_instanceIds.png')] + '_leftImg8bit.png'
+  if dataset == 'cvppp':
+    return re.sub(r'_label\.png$', '_rgb.png', label_name)
+  return label_name
+
+
+def pair_images(label_paths, label_root, image_root, dataset):
+  """The colour image of every label file below image_root: by name; of several of one name, the one whose sub-folder of
+  image_root is the label's sub-folder of label_root."""
+  by_name = {}
+  for f in find_files(image_root):
+    by_name.setdefault(os.path.basename(f), []).append(f)
+  out = []
+  for lab in label_paths:
+    name = image_name(dataset, os.path.basename(lab))
+    cands = [c for c in by_name.get(name, []) if os.path.abspath(c) != os.path.abspath(lab)]
+    if len(cands) > 1:
+      sub = os.path.relpath(os.path.dirname(lab), label_root)
+      cands = [c for c in cands if os.path.relpath(os.path.dirname(c), image_root) == sub] or cands
+    if len(cands) != 1:
+      raise RecAttendError('%s: %s %s below %s' % (lab, 'more than one image' if cands else 'no image', name, image_root))
+    out.append(cands[0])
+  return out
+
+
+def load_input(path, pattern='*.png', colour_labels=False, want_paths=False):
+  """-> (gt_instance_ids integer [N,Hf,Wf], names [N], x or None); want_paths: the files' paths in place of the names"""
   if os.path.isdir(path):
-    found = []
-    for root, _, files in os.walk(path):
-      found += [os.path.join(root, f) for f in fnmatch.filter(files, '*.png')]
+    found = find_files(path, pattern)
     if not found:
-      raise RecAttendError('no *.png below %s' % path)
-    found.sort()
-    imgs = [read_label_png(f) for f in found]
+      raise RecAttendError('no %s below %s' % (pattern, path))
+    imgs = [read_label_png(f, colour_labels) for f in found]
     if len({im.shape for im in imgs}) != 1:
       raise RecAttendError('%s: the label images have different sizes (%s); one full size per run' % (
           path, ', '.join(sorted({'%dx%d' % im.shape for im in imgs}))))
-    return np.stack(imgs), [os.path.basename(f) for f in found], None
+    return np.stack(imgs), (found if want_paths else [os.path.basename(f) for f in found]), None
   data = np.load(path, allow_pickle=False)
   if 'gt_instance_ids' not in data:
     raise RecAttendError('--input %s lacks gt_instance_ids' % path)
@@ -105,8 +176,8 @@ def assemble_archive(ids, names, x, dataset, H, W, T, target, batch_size=8):
     raise RecAttendError('--height %d --width %d --timespan %d for label images of %d x %d (1 <= timespan <= %d, the network '
                          'size no larger than the labels)' % (H, W, T, Hf, Wf, ops.LABELS_MAX_T))
   if x is not None and tuple(x.shape[:3]) != (N, H, W):
-    raise RecAttendError('--input: x is %s, expected [%d,%d,%d,3] at network size (the resize of the colour image is not '
-                         'built)' % (tuple(x.shape), N, H, W))
+    raise RecAttendError('--input: x is %s, expected [%d,%d,%d,3] at network size (full-size images are resized under '
+                         '--images, or from x_full in place of x)' % (tuple(x.shape), N, H, W))
   if not torch.cuda.is_available():
     raise RecAttendError('setup_labels runs on the GPU; no device is available and there is no CPU fallback')
   keys = TARGETS[target]
@@ -125,12 +196,62 @@ def assemble_archive(ids, names, x, dataset, H, W, T, target, batch_size=8):
   return out
 
 
+def resize_images(read, N, full, H, W, batch_size=8):
+  """x float32 [N,H,W,3] of the N full-size images read(i) -> uint8 [Hf,Wf,3] (every one of size `full`, or read raises):
+  ra_ops.resize_cubic on the device, batch_size images at a time, so that the full-size images never exist together."""
+  import torch
+  import ra_ops as ops
+  if not torch.cuda.is_available():
+    raise RecAttendError('setup_labels runs on the GPU; no device is available and there is no CPU fallback')
+  bs = max(1, min(int(batch_size), MAX_BATCH_ELEMS // max(1, full[0] * full[1] * 3), MAX_BATCH_ELEMS // max(1, H * W * 3)))
+  parts = []
+  for b0 in range(0, N, bs):
+    batch = np.stack([read(i) for i in range(b0, min(N, b0 + bs))])
+    parts.append(ops.resize_cubic(batch, H, W, want=('x',))['x'].cpu().numpy())
+  return np.concatenate(parts)
+
+
+def read_image_of(label_path, image_path, full):
+  """The colour image of a label file, uint8 [Hf,Wf,3] BGR, checked against the labels' size."""
+  from utils import png
+  try:
+    img = png.read_colour8(image_path)
+  except ValueError as e:
+    raise RecAttendError('%s: %s' % (image_path, e))
+  if tuple(img.shape[:2]) != tuple(full):
+    raise RecAttendError('%s is %d x %d, its label image %s %d x %d' % (image_path, img.shape[0], img.shape[1], label_path,
+                                                                       full[0], full[1]))
+  return img
+
+
 def main(argv=None):
   args = build_parser().parse_args(argv)
   h, w, t = cap.INP_DIM[args.dataset]
   H, W, T = args.height or h, args.width or w, args.timespan or t
-  ids, names, x = load_input(args.input)
+  orig_size = None
+  if args.images:
+    if not os.path.isdir(args.input) or not os.path.isdir(args.images):
+      raise RecAttendError('--images %s needs folders for --input and --images' % args.images)
+    ids, paths, _ = load_input(args.input, LABEL_PATTERNS[args.dataset], args.colour_labels, want_paths=True)
+    images = pair_images(paths, args.input, args.images, args.dataset)
+    names, full = [os.path.basename(f) for f in paths], ids.shape[1:]
+    x = resize_images(lambda i: read_image_of(paths[i], images[i], full), len(paths), full, H, W, args.batch_size)
+    orig_size = np.tile(np.asarray(full, np.int32), (len(paths), 1))
+  else:
+    ids, names, x = load_input(args.input, colour_labels=args.colour_labels)
+    x_full = None
+    if x is None and not os.path.isdir(args.input):
+      data = np.load(args.input, allow_pickle=False)
+      x_full = data['x_full'] if 'x_full' in data else None
+    if x_full is not None:
+      if x_full.dtype != np.uint8 or x_full.ndim != 4 or x_full.shape[3] != 3 or tuple(x_full.shape[:3]) != tuple(ids.shape):
+        raise RecAttendError('--input %s: x_full is %s %s, expected uint8 [%d,%d,%d,3] (the labels\' size)' % (
+            args.input, x_full.dtype, tuple(x_full.shape), ids.shape[0], ids.shape[1], ids.shape[2]))
+      x = resize_images(lambda i: x_full[i], ids.shape[0], ids.shape[1:], H, W, args.batch_size)
+      orig_size = np.tile(np.asarray(ids.shape[1:], np.int32), (ids.shape[0], 1))
   out = assemble_archive(ids, names, x, args.dataset, H, W, T, args.target, args.batch_size)
+  if orig_size is not None:
+    out['orig_size'] = orig_size
   folder = os.path.dirname(os.path.abspath(args.output))
   os.makedirs(folder, exist_ok=True)
   np.savez(args.output, **out)

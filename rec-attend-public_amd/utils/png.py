@@ -5,7 +5,12 @@ every row.  `decode_gray8` reads exactly that subset back (tests, tools).
 `decode_gray16` / `read_gray16` read 16-bit greyscale files (*_gtFine_instanceIds.png of the Cityscapes ground truth) as
 other encoders write them: any number of IDAT chunks and all five row filters of the PNG specification (section 9).  A
 file whose rows use None, Sub and Up is undone a row at a time (tens of ms for 1024 x 2048); one that holds Average or Paeth
-rows is undone by anti-diagonals, about a second for that size in NumPy, which a compiled loop would cut further (not built)."""
+rows is undone by the library's compiled loop (ra_png_unfilter_u8, host code), and by anti-diagonals in NumPy, about a
+second for that size, where librecattend.so cannot be loaded: this module imports and works without it.
+
+`decode_colour8` / `read_colour8` read what cv2.imread(path) reads for the datasets' colour files (leftImg8bit, KITTI's and
+CVPPP's images and colour label files): uint8 [H,W,3] in cv2's BGR order from 8-bit RGB, RGBA (alpha dropped), palette
+(depths 1, 2, 4, 8) and grey files.  Interlaced files and 16-bit colour are refused."""
 import struct
 import zlib
 
@@ -123,7 +128,31 @@ def _unfilter(raw, H, stride, bpp):
   if raw[:, 0].max() > 4:
     r = int(np.argmax(raw[:, 0] > 4))
     raise ValueError('PNG row %d has filter type %d' % (r, raw[r, 0]))
-  return (_unfilter_diagonals if (raw[:, 0] >= 3).any() else _unfilter_rows)(raw, H, stride, bpp)
+  if not (raw[:, 0] >= 3).any():
+    return _unfilter_rows(raw, H, stride, bpp)
+  return (_unfilter_native if _native() else _unfilter_diagonals)(raw, H, stride, bpp)
+
+
+_NATIVE = []  # [the loaded library, or None where it cannot be loaded], filled at the first file that needs it
+
+
+def _native():
+  if not _NATIVE:
+    try:
+      import ra_native
+      _NATIVE.append(ra_native.lib())
+    except (ImportError, OSError, RuntimeError):
+      _NATIVE.append(None)
+  return _NATIVE[0]
+
+
+def _unfilter_native(raw, H, stride, bpp):
+  """_unfilter_diagonals' result from ra_png_unfilter_u8: one compiled pass over the scanlines."""
+  raw = np.ascontiguousarray(raw)
+  out = np.empty((H, stride), dtype=np.uint8)
+  if _native().ra_png_unfilter_u8(raw.ctypes.data, H, stride, bpp, out.ctypes.data) != 0:
+    raise ValueError((_native().ra_last_error_string() or b'ra_png_unfilter_u8 failed').decode())
+  return out
 
 
 def decode_gray16(data):
@@ -154,3 +183,61 @@ def decode_gray16(data):
 def read_gray16(path):
   with open(path, 'rb') as f:
     return decode_gray16(f.read())
+
+
+_CHANNELS = {0: 1, 2: 3, 3: 1, 6: 4}  # samples per pixel of the colour types read by decode_colour8
+
+
+def decode_colour8(data):
+  """What cv2.imread(path) (IMREAD_COLOR) gives for an 8-bit PNG: uint8 [H,W,3] in BGR order.  Colour type 2 (RGB) and 6
+  (RGBA: the alpha channel is dropped, not blended) at bit depth 8, 3 (palette) at depths 1, 2, 4, 8 expanded through PLTE
+  (tRNS ignored), 0 (grey) at depth 8 replicated to three channels; any number of IDAT chunks, all five row filters, CRCs
+  checked.  Interlaced files, 16-bit samples and everything else raise ValueError."""
+  head, idat, palette = None, b'', None
+  for tag, payload, crc in iter_chunks(data):
+    if zlib.crc32(tag + payload) & 0xffffffff != crc:
+      raise ValueError('bad CRC in chunk %r' % tag)
+    if tag == b'IHDR':
+      if len(payload) != 13:
+        raise ValueError('IHDR chunk of %d bytes' % len(payload))
+      W, H, depth, colour, comp, flt, lace = struct.unpack('>IIBBBBB', payload)
+      ok = (depth == 8 and colour in (0, 2, 6)) or (colour == 3 and depth in (1, 2, 4, 8))
+      if not ok or (comp, flt, lace) != (0, 0, 0) or W < 1 or H < 1:
+        raise ValueError('only 8-bit RGB, RGBA and grey and 1-, 2-, 4-, 8-bit palette PNG files without interlace are read here '
+                         '(%d x %d, bit depth %d, colour type %d, interlace %d)' % (W, H, depth, colour, lace))
+      head = (H, W, depth, colour)
+    elif tag == b'PLTE':
+      if len(payload) % 3 or not payload:
+        raise ValueError('PLTE chunk of %d bytes' % len(payload))
+      palette = np.frombuffer(payload, dtype=np.uint8).reshape(-1, 3)
+    elif tag == b'IDAT':
+      idat += payload
+  if head is None:
+    raise ValueError('no IHDR chunk')
+  H, W, depth, colour = head
+  try:
+    raw = zlib.decompress(idat)
+  except zlib.error as e:
+    raise ValueError('PNG image data does not inflate: %s' % e)
+  ch = _CHANNELS[colour]
+  stride = (W * ch * depth + 7) // 8
+  rows = _unfilter(raw, H, stride, max(1, ch * depth // 8))
+  if colour == 3:
+    if palette is None:
+      raise ValueError('a palette PNG file without a PLTE chunk')
+    if depth < 8:  # the leftmost sample in the high bits; the padding bits of a row are dropped
+      bits = np.unpackbits(rows, axis=1).reshape(H, -1, depth)[:, :W]
+      rows = (bits << np.arange(depth - 1, -1, -1, dtype=np.uint8)).sum(axis=2).astype(np.uint8)
+    if int(rows.max()) >= len(palette):
+      raise ValueError('palette index %d, the palette has %d entries' % (int(rows.max()), len(palette)))
+    rgb = palette[rows]
+  elif colour == 0:
+    rgb = np.repeat(rows[:, :, None], 3, axis=2)
+  else:
+    rgb = rows.reshape(H, W, ch)[:, :, :3]
+  return np.ascontiguousarray(rgb[:, :, ::-1])
+
+
+def read_colour8(path):
+  with open(path, 'rb') as f:
+    return decode_colour8(f.read())
