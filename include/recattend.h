@@ -1316,7 +1316,9 @@ int ra_gauss_filter_strided_bwd_f32(const float *ctr, const float *size, const f
  *   ra_loss_head_bwd_f32  g (device scalar, NULL = 1): d loss upstream.  Writes the coefficients of the two pairwise-IoU
  *                         adjoints, c1 [B,T,T] / c0 [B,T] for ra_weighted_sum_multi_f32 (from inter / sum_a / sum_b of
  *                         ra_pair_stats_f32, HW = pixels per plane), and d s_out [B,T] (the cumulative extrema route their
- *                         gradient to the positions torch.cummin / cummax report). */
+ *                         gradient to the positions torch.cummin / cummax report on the CPU: among equal scores the LAST
+ *                         position of the running minimum, and the smallest index >= t holding the maximum of s[t..T)).
+ *   B <= 256, T <= 64, else RA_E_SHAPE and nothing is launched. */
 int ra_loss_head_f32(const float *iou_s, const float *iou_b, const float *m_s, const float *m_b, const float *s_out, int B, int T,
                      float mix, float *pieces, void *stream);
 int ra_loss_head_bwd_f32(const float *g, const float *m_s, const float *m_b, const float *s_out, const float *inter_s,

@@ -183,6 +183,22 @@ __device__ inline float block_sum256(float v, float *red) {
   return r;
 }
 
+// A float32 product / sum / difference rounded on its own.  HIP's __fmul_rn / __fadd_rn / __fsub_rn are the plain operators (clang's
+// __clang_hip_math.h without OCML_BASIC_ROUNDED_OPERATIONS), which the default -ffp-contract=fast-honor-pragmas fuses into an FMA once
+// they are inlined next to each other; an operator compiled under contract(off) carries no such licence and is never fused.
+__device__ __forceinline__ float mul_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a * b;
+}
+__device__ __forceinline__ float add_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a + b;
+}
+__device__ __forceinline__ float sub_rn(float a, float b) {
+#pragma clang fp contract(off)
+  return a - b;
+}
+
 __host__ __device__ inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 __host__ __device__ inline int round_up(int a, int b) { return ceil_div(a, b) * b; }
 

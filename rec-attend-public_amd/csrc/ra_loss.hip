@@ -271,19 +271,19 @@ __global__ void knob_setup_kernel(const float *partial, int ninst, int T, const 
     sum += q[s * 5 + 4];
   }
   const float nz = sum > 0.f ? 1.f : 0.f;
-  const float far = __fmul_rn(1.f - nz, 2.f * min_pad);
+  const float far = mul_rn(1.f - nz, 2.f * min_pad);
   for (int k = 0; k < 2; ++k) {
     const float sz = br[k] - tl[k];
-    const float padv = fmaxf(__fmul_rn(pad[inst], sz), min_pad);
-    const float sh = __fmul_rn(shift[inst * 2 + k], sz);
-    const float tln = __fmul_rn(__fsub_rn(__fadd_rn(tl[k], sh), padv), nz);
-    const float brn = __fadd_rn(__fmul_rn(nz, __fadd_rn(__fadd_rn(br[k], sh), padv)), far);
-    ctr[inst * 2 + k] = __fadd_rn(tln, brn) / 2.f;
-    size[inst * 2 + k] = __fsub_rn(brn, tln);
+    const float padv = fmaxf(mul_rn(pad[inst], sz), min_pad);
+    const float sh = mul_rn(shift[inst * 2 + k], sz);
+    const float tln = mul_rn(sub_rn(add_rn(tl[k], sh), padv), nz);
+    const float brn = add_rn(mul_rn(nz, add_rn(add_rn(br[k], sh), padv)), far);
+    ctr[inst * 2 + k] = add_rn(tln, brn) / 2.f;
+    size[inst * 2 + k] = sub_rn(brn, tln);
   }
   const float scale = timescale ? 1.f + logf(1.f + (float)(inst % T) * 3.f) : 1.f;
-  kbox[inst] = u_box[inst] <= fminf(__fmul_rn(sched[0], scale), 1.f) ? 1.f : 0.f;
-  ksegm[inst] = u_segm[inst] <= fminf(__fmul_rn(sched[1], scale), 1.f) ? 1.f : 0.f;
+  kbox[inst] = u_box[inst] <= fminf(mul_rn(sched[0], scale), 1.f) ? 1.f : 0.f;
+  ksegm[inst] = u_segm[inst] <= fminf(mul_rn(sched[1], scale), 1.f) ? 1.f : 0.f;
 }
 
 __global__ __launch_bounds__(256) void gt_box_fill_kernel(const float *params, int H, int W, float *box) {
@@ -533,7 +533,7 @@ struct LossHeadArgs {
   const float *g;                                              // backward: upstream gradient of `loss` (device scalar) or null = 1
   int B, T, HW;
   float mix;
-  float *pieces;    // forward: [6 + 3 B]: loss, box_loss, segm_loss, conf, iou_soft, iou_box, then per image (iou_s, iou_b, conf)
+  float *pieces;    // forward: [6]: loss, box_loss, segm_loss, conf, iou_soft, iou_box (the per-image terms stay in LDS, per[][])
   float *c1_s, *c0_s, *c1_b, *c0_b, *ds;  // backward
 };
 __device__ inline float wave_sum(float v) {

@@ -147,11 +147,11 @@ __global__ __launch_bounds__(256) void canvas_step_kernel(const f32x4 *prev, int
     const float *yb = y_gt + (size_t)b * T * HW + p;
     for (int t = 0; t < T; ++t) {
       const float wt = match[(size_t)b * T + t];
-      if (wt != 0.f) g = __fadd_rn(g, __fmul_rn(wt, yb[(size_t)t * HW]));  // uniform per image
+      if (wt != 0.f) g = add_rn(g, mul_rn(wt, yb[(size_t)t * HW]));  // uniform per image
     }
-    if (noise) g = __fsub_rn(g, __fmul_rn(g, noise[px]));
+    if (noise) g = sub_rn(g, mul_rn(g, noise[px]));
     const float k = knob[(size_t)b * knob_stride];
-    yc = __fadd_rn(__fmul_rn(k, g), __fmul_rn(__fsub_rn(1.0f, k), yc));
+    yc = add_rn(mul_rn(k, g), mul_rn(sub_rn(1.0f, k), yc));
   }
   const int cg = cc >> 2, cl = cc & 3;
   for (int q = 0; q < C4; ++q) {

@@ -264,7 +264,7 @@ class LossHead(torch.autograd.Function):
   def forward(ctx, y_out, attn_box, s_out, y_gt, box_gt, st_s, st_b, m_s, m_b, tmajor, mix):
     B, T = s_out.shape
     s_out = s_out.contiguous()
-    buf = torch.empty(8, dtype=torch.float32, device=s_out.device)
+    buf = torch.empty(6, dtype=torch.float32, device=s_out.device)  # pieces[0..5]: all ra_loss_head_f32 writes
     check(rn.lib().ra_loss_head_f32(ptr(st_s['iou_soft']), ptr(st_b['iou_soft']), ptr(m_s), ptr(m_b), ptr(s_out), B, T, float(mix), ptr(buf),
                                     rn.stream_ptr()), 'ra_loss_head_f32')
     ctx.save_for_backward(y_gt, box_gt, s_out, m_s, m_b, st_s['inter'], st_s['sum_a'], st_s['sum_b'], st_b['inter'], st_b['sum_a'],
