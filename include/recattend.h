@@ -994,6 +994,40 @@ int ra_resize_cubic_u8(const unsigned char *src, int N, int Hs, int Ws, int C, i
 int ra_png_unfilter_u8(const unsigned char *raw, int H, int stride, int bpp, unsigned char *out);
 
 /* ------------------------------------------------------------------------------------
+ * The render stage behind the evaluators (csrc/ra_render.hip): the colour images the reference's analyzers write, composed
+ * while the masks are on the device.  img is uint8 [B,H,W,3] in the memory order cv2.imwrite takes (B, G, R), the
+ * convention of utils/png.read_colour8; colour tables are in that same order.  One launch each, no atomics, no workspace.
+ *
+ * ra_render_instances_u8 — y float32 [B,T,H,W], colour uint8 [B,T,3] (a table per image).  With u(v) = the float
+ *   truncated to an integer, taken mod 256 (NumPy's .astype('uint8')), per pixel and channel k:
+ *     RA_RENDER_ADD    analysis.py:137-147 (RenderInstanceAnalyzer): img_k = (sum_t u(y_t) * colour[b,t,k]) mod 256 — the
+ *                      reference's uint8 product and its uint8 += both wrap; its `size > 0` gate changes nothing, an empty
+ *                      plane adds zero.
+ *     RA_RENDER_FIRST  analysis.py:166-187 (RenderGroundtruthInstanceAnalyzer): in the order t = 0 .. T - 1,
+ *                      if img_k == 0: img_k = (u(y_t) * colour[b,t,k]) mod 256.  Decided PER CHANNEL, not per pixel
+ *                      ((total_img == 0) is an [H,W,3] array there): a later overlapping plane fills exactly the channels the
+ *                      earlier colour left at 0.
+ *   The domain is finite 0 <= y <= 255 (binary masks in practice; a soft 0.7 gives 0); outside it the reference's cast is
+ *   undefined and the bytes written here are unspecified.  y is read once: a lane takes four consecutive pixels with one
+ *   16-byte load per plane and writes its 12 bytes as three dwords when H * W % 4 == 0, y is 16-byte and img 4-byte aligned;
+ *   element loads and byte stores otherwise.  1 <= T <= RA_RENDER_MAX_T, planes up to 2^30 pixels, B <= 65535, else
+ *   RA_E_SHAPE; another mode is RA_E_INVALID; nothing is launched then.
+ * ra_render_orientation_u8 — fg_model_eval.py:128-132,154-164 with data_api/orientation.py:13-28: d float32 [B,Hs,Ws,C] at
+ *   network size, mask float32 [B,H,W], wheel uint8 [C,3].  Every channel of d is resized to H x W with the linear
+ *   resample of ra_sem_labels_u8 (cv2.resize INTER_LINEAR, float32, the source coordinate in double: the same device
+ *   function), the FIRST maximum over the channels is the class, img = (uint8)(wheel[class] * mask).  No full-size plane of
+ *   d is written.  The domain is mask = 0 or 1: beyond it the reference's float-to-uint8 cast of colour * mask is undefined.
+ *   2 <= C <= 16, planes up to 2^30 pixels, B <= 65535, else RA_E_SHAPE and nothing is launched.
+ * ---------------------------------------------------------------------------------- */
+#define RA_RENDER_ADD 0
+#define RA_RENDER_FIRST 1
+#define RA_RENDER_MAX_T 1024
+int ra_render_instances_u8(const float *y, int B, int T, int H, int W, const unsigned char *colour, int mode,
+                           unsigned char *img, void *stream);
+int ra_render_orientation_u8(const float *d, int B, int Hs, int Ws, int C, const float *mask, int H, int W,
+                             const unsigned char *wheel, unsigned char *img, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Evaluating the pre-stage fg_model (csrc/ra_fg_eval.hip).
  *
  * ra_fg_stats_f32 — the sums behind the six statistics the reference's Evaluator logs (fg_model_train.py:131-133), replacing

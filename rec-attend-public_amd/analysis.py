@@ -3,9 +3,13 @@
 `results` is the dict full_model_eval.py:128-135 builds — 'y_out' (thresholded, [B,T,H,W]),
 'y_gt', 's_out', 's_gt' — with float32 CUDA tensors.  All functions share one device pass
 (ops.eval_metrics: pairwise intersections on the MFMA streaming kernel + one small metrics
-kernel), cached on the dict.  Of the analyzers that render images or write CSV files (:52-311,
-:790-900) only RenderCityScapesOutputAnalyzer (:196-267, the Cityscapes instance-level output) is built; the others are
-out of scope.  ForegroundIOUAnalyzer / BackgroundIOUAnalyzer (:834-906) accumulate over a whole dataset, in
+kernel), cached on the dict.  Of the analyzers that render images or write CSV files (:52-311, :790-900) these are built:
+CountAnalyzer (:67-92), RenderInstanceAnalyzer (:95-153), RenderGroundtruthInstanceAnalyzer (:156-193) and
+RenderOrientationAnalyzer (:270-283) — the colour images are composed on the device (ops.render_instances /
+ops.render_orientation) and written by utils/png.py — and RenderCityScapesOutputAnalyzer (:196-267, the Cityscapes
+instance-level output).  StatsAnalyzer's per-metric CSV files (:790-831), RenderForegroundAnalyzer (fg_model_eval.py writes
+those planes itself) and the plots stay out of scope.  ForegroundIOUAnalyzer / BackgroundIOUAnalyzer
+(:834-906) accumulate over a whole dataset, in
 exact integers, from the counters of ops.fg_sweep_counts; fg_model_eval.py drives them and they are not per-image functions,
 so ANALYZERS does not list them."""
 import os
@@ -220,7 +224,133 @@ class RenderCityScapesOutputAnalyzer(object):
     pass
 
 
-# ---- Cityscapes instance-level AP (data_api/cityscapes_scripts/evaluation/evalInstanceLevelSemanticLabeling.py) ----
+# ---- the colour images and the count file (:67-193, :270-283) ----
+# :103-124, one row per instance slot (row t % 22).  The reference's last row reads [319, 29, 82] in a uint8 array, which
+# old NumPy stores as 319 mod 256 = 63 (NumPy 2 raises on it): 63 is what it draws with.
+# Channel convention: the instance analyzers swap [2, 1, 0] before cv2.imwrite (:147, :187), so a row is the R, G, B of the FILE.
+INSTANCE_CMAP = ((192, 57, 43), (243, 156, 18), (26, 188, 156), (41, 128, 185), (142, 68, 173), (44, 62, 80), (127, 140, 141),
+                 (17, 75, 95), (2, 128, 144), (228, 253, 225), (69, 105, 144), (244, 91, 105), (91, 192, 235), (253, 231, 76),
+                 (155, 197, 61), (229, 89, 52), (250, 121, 33), (124, 82, 47), (86, 15, 94), (38, 63, 77), (1, 52, 55),
+                 (63, 29, 82))
+# data_api/orientation.py:3-11, one row per orientation class.  Channel convention: build_orientation_img's array goes to
+# cv2.imwrite UNSWAPPED (:278-282), so a row is the B, G, R of the file — the file's R, G, B is the row REVERSED.
+ORIENTATION_WHEEL = ((255, 17, 0), (255, 137, 0), (230, 255, 0), (34, 255, 0), (0, 255, 213), (0, 154, 255), (9, 0, 255),
+                     (255, 0, 255))
+
+
+def groundtruth_colours(iou_pairwise):
+  """:168-182 on the host: the colour of every ground-truth plane from iou_pairwise [B,T_out,T_gt] (what _m caches) -> uint8
+  [B,T_gt,3], rows of INSTANCE_CMAP (the file's R, G, B).  Per image, in the order of the planes: the output with the largest
+  IoU (first maximum; an empty plane's column is all zero, so 0) names the colour; if that colour is taken, the first free
+  one counted from the END of the palette; with all 22 taken the previous plane's colour stays.  Every plane consumes a colour,
+  empty ones too.  A winning index >= 22 raises IndexError, as the reference's flag[max_idx] does."""
+  import numpy as np
+  iou = iou_pairwise.detach().cpu().numpy() if isinstance(iou_pairwise, torch.Tensor) else np.asarray(iou_pairwise)
+  if iou.ndim != 3 or iou.shape[1] < 1:
+    raise ValueError('groundtruth_colours: iou_pairwise must be [B,T_out,T_gt] with T_out >= 1, got %s' % (iou.shape,))
+  cmap = np.array(INSTANCE_CMAP, dtype=np.uint8)
+  n = cmap.shape[0]
+  out = np.zeros((iou.shape[0], iou.shape[2], 3), dtype=np.uint8)
+  for ii in range(iou.shape[0]):
+    used = [False] * n
+    colour = None
+    for jj in range(iou.shape[2]):
+      best = int(np.argmax(iou[ii, :, jj]))
+      if best >= n:
+        raise IndexError('index %d is out of bounds for the %d colours of the palette' % (best, n))
+      if not used[best]:
+        colour, used[best] = cmap[best], True
+      else:
+        for idx in range(n - 1, -1, -1):
+          if not used[idx]:
+            colour, used[idx] = cmap[idx], True
+            break
+      out[ii, jj] = colour
+  return out
+
+
+class CountAnalyzer(object):
+  """:67-92.  The file starts with the header line; stage() appends '<index>,<count out>,<count gt>' per image, from
+  f_count_out(y_out).sum(1) (the output planes that have a pixel) and s_gt.sum(1)."""
+
+  def __init__(self, fname):
+    self.fname = fname
+    with open(fname, 'w') as f:
+      f.write('Image ID,Count Out,Count GT\n')  # :72
+
+  def stage(self, results):
+    count_out = f_count_out(results['y_out']).sum(dim=1).cpu().numpy()
+    count_gt = results['s_gt'].sum(dim=1).cpu().numpy()
+    with open(self.fname, 'a') as f:
+      for ii, idx in enumerate(results['indices']):
+        f.write('{},{:d},{:d}\n'.format(idx, int(count_out[ii]), int(count_gt[ii])))  # :85-86
+
+  def finalize(self):
+    pass
+
+
+class _RenderBase(object):
+  """names: the file name of every image, indexed by results['indices']; an image goes to <folder>/<name without .png>.png."""
+
+  def __init__(self, folder, names):
+    if folder is None:
+      raise Exception('No output folder')
+    self.folder = folder
+    self.names = list(names)
+    self.written = []
+    os.makedirs(folder, exist_ok=True)
+
+  def _write(self, img, indices):
+    from utils import png
+    host = img.cpu().numpy()
+    for ii in range(host.shape[0]):
+      path = os.path.join(self.folder, _stem(str(self.names[int(indices[ii])])) + '.png')
+      png.write_colour8(path, host[ii])
+      self.written.append(path)
+
+  def finalize(self):
+    pass
+
+
+class RenderInstanceAnalyzer(_RenderBase):
+  """:95-153: one colour image per input, every plane of results['y_out'] [B,T,H,W] in its own colour (INSTANCE_CMAP[t % 22]),
+  summed in uint8 as the reference sums them (overlaps wrap).  One launch of ops.render_instances; the file's R, G, B is
+  the cmap row (the reference swaps before cv2.imwrite)."""
+
+  def stage(self, results):
+    self._write(ops.render_instances(results['y_out']), results['indices'])
+
+
+class RenderGroundtruthInstanceAnalyzer(_RenderBase):
+  """:156-193: the ground truth results['y_gt'] [B,T_gt,H,W], every plane in the colour of its best-matching prediction
+  (groundtruth_colours on results['iou_pairwise'], chosen on the host), an earlier plane on top — per channel, as there.  One
+  RA_RENDER_FIRST launch.  'iou_pairwise' is what the metrics pass (_m) caches on the dict; where no metric has run it is
+  f_iou_pairwise(y_out, y_gt), which takes any pair of plane counts, and is cached likewise."""
+
+  def stage(self, results):
+    import numpy as np
+    if 'iou_pairwise' not in results:
+      results['iou_pairwise'] = f_iou_pairwise(results['y_out'], results['y_gt'])
+    y_gt = results['y_gt']
+    rgb = groundtruth_colours(results['iou_pairwise'])
+    if rgb.shape[:2] != tuple(y_gt.shape[:2]):
+      raise ops.rn.RecAttendError('RenderGroundtruthInstanceAnalyzer: iou_pairwise gives colours for %s planes, y_gt is %s' % (
+          rgb.shape[:2], tuple(y_gt.shape)))
+    bgr = torch.as_tensor(np.ascontiguousarray(rgb[:, :, ::-1])).to(y_gt.device)  # the image's memory order
+    self._write(ops.render_instances(y_gt, colours=bgr, first=True), results['indices'])
+
+
+class RenderOrientationAnalyzer(_RenderBase):
+  """:270-283 with fg_model_eval.py:128-132,154-164: results['d_out'] [B,Hs,Ws,C] at NETWORK size (the reference hands over
+  the resized planes; here the resize is evaluated inside the kernel) and results['mask'] [B,H,W] of 0 / 1 at full size ->
+  the wheel colour of the arg-max class times the mask.  The array goes to the file unswapped there, so the file's R, G, B
+  is the ORIENTATION_WHEEL row reversed."""
+
+  def stage(self, results):
+    self._write(ops.render_orientation(results['d_out'], results['mask']), results['indices'])
+
+
+# ---- Cityscapes instance-level AP(data_api/cityscapes_scripts/evaluation/evalInstanceLevelSemanticLabeling.py) ----
 # Line numbers below are that script's.  The pixel work (assignGt2Preds' count_nonzero per prediction and ground-truth
 # instance, :306-333) runs on the device (ops.gt_instance_catalog, ops.instance_overlap); what is left is a few hundred
 # integers per image, the MATCH RECORD, and float64 NumPy on those.

@@ -34,7 +34,12 @@ and are not built HERE: the default lists run without them and say so on standar
 
 --lrr_seg, --foreground_folder and --render_gt are accepted and refused: they read files of the authors' machines (LRR .mat
 files, a foreground folder, the HDF5 dataset); --lrr_filename is accepted and unused (its default there is a path of that
-cluster).  --split_id / --num_split select images [split_id * num_split, (split_id + 1) * num_split) (:41-46).  There is no
+cluster).  --render_instances (not a reference flag: the reference's runner always renders, cityscapes_eval.py:67-75) writes per
+threshold <output>/output_<split>/<NN>/<name>.png, NN = int(threshold * 100) — every instance of that threshold's y_out in its own
+colour, composed on the device (analysis.RenderInstanceAnalyzer) — with s_gt in --input also <NN>/count.csv
+(analysis.CountAnalyzer needs the ground-truth count), and with y_gt_full also <output>/output_<split>/gt/<name>.png, the ground
+truth coloured by its best-matching prediction of the last threshold (analysis.RenderGroundtruthInstanceAnalyzer; unlike
+--render_gt it reads the labels from --input).  --split_id / --num_split select images [split_id * num_split, (split_id + 1) * num_split) (:41-46).  There is no
 CPU path: without a GPU the stage raises RecAttendError."""
 import argparse
 import os
@@ -58,7 +63,8 @@ REFUSED = {
                'semantic map as y_out in --input instead',
     'foreground_folder': '--foreground_folder reads a folder of foreground images of the authors\' cluster; give the semantic '
                          'map as y_out in --input instead',
-    'render_gt': '--render_gt renders the ground truth from the HDF5 dataset, which is out of scope here',
+    'render_gt': '--render_gt renders the ground truth from the HDF5 dataset, which is out of scope here; --render_instances '
+                 'renders it from y_gt_full of --input',
 }
 
 
@@ -68,6 +74,10 @@ def build_parser():
     cap.add_flags(p, table)
   p.add_argument('--input', default=None, help='.npz with y_out_ins [N,T,h,w], s_out [N,T], y_out [N,h,w,C] '
                                                '(+ y_gt_full, s_gt, names, full_size)')
+  p.add_argument('--render_instances', action='store_true',
+                 help='not a reference flag (the reference always renders): write every threshold\'s instances as a colour image into '
+                      '<output>/output_<split>/<NN>/, count.csv beside them when --input has s_gt, and the ground truth coloured by '
+                      'its best match into gt/ when it has y_gt_full')
   return p
 
 
@@ -176,13 +186,23 @@ def main(argv=None):
     raise RecAttendError('--input: gt_instance_ids is %s, expected %s (N images at full_size)' % (tuple(all_ids.shape), (N, H, W)))
   scorers = [analysis.CityscapesAPAnalyzer(names) for _ in thresholds] if have_ids else []
   acc = [{n: [] for n in an_names} for _ in thresholds]
+  img_render, counters, gt_render, have_y_gt = [], [], None, 'y_gt_full' in data
+  if args.render_instances:
+    folders = [os.path.join(out_dir, '{:02d}'.format(int(th * 100))) for th in thresholds]  # cityscapes_eval.py:65
+    img_render = [analysis.RenderInstanceAnalyzer(f, names) for f in folders]
+    if 's_gt' in data:
+      counters = [analysis.CountAnalyzer(os.path.join(f, 'count.csv')) for f in folders]
+    else:
+      print('--render_instances: no count.csv, --input has no s_gt to count against')
+    if have_y_gt:
+      gt_render = analysis.RenderGroundtruthInstanceAnalyzer(os.path.join(out_dir, 'gt'), names)
   bs = max(1, min(opt['batch_size'], MAX_BATCH_ELEMS // max(1, T * H * W)))
   dev = torch.device('cuda', torch.cuda.current_device())
   up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
   for b0 in range(lo, hi, bs):
     b1 = min(hi, b0 + bs)
-    gt = up(data['y_gt_full'][b0:b1]) if have_gt else None
-    sg = up(data['s_gt'][b0:b1]) if have_gt else None
+    gt = up(data['y_gt_full'][b0:b1]) if have_gt or gt_render is not None else None
+    sg = up(data['s_gt'][b0:b1]) if have_gt or counters else None
     ids = torch.as_tensor(np.ascontiguousarray(all_ids[b0:b1], dtype=np.int32)).to(dev) if have_ids else None
     chain = iter_label_instances(up(data['y_out_ins'][b0:b1]), up(data['s_out'][b0:b1]), up(data['y_out'][b0:b1]), (H, W),
                                  thresholds, opt['remove_tiny'])
@@ -195,6 +215,13 @@ def main(argv=None):
         for n in an_names:
           acc[tt][n].append(analysis.create_analyzer(n)(res).cpu().numpy())
       renders[tt].stage(res)
+      if img_render:
+        img_render[tt].stage(res)
+        if counters:
+          counters[tt].stage(dict(res, s_gt=sg))
+        if gt_render is not None and tt == len(thresholds) - 1:  # after the last threshold, as full_model_eval.py:139-140
+          iou = res['iou_pairwise'] if 'iou_pairwise' in res else analysis.f_iou_pairwise(res['y_out'], gt)
+          gt_render.stage({'y_gt': gt, 'iou_pairwise': iou, 'indices': res['indices']})
       if have_ids:
         res['gt_ids'] = ids
         scorers[tt].stage(res)

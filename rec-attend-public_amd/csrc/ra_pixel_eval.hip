@@ -57,21 +57,7 @@ struct SemSrc {
 
 // The label of pixel (r, c) of the H x W image behind the semantic map semb [Hs,Ws,C] of one image.
 __device__ __forceinline__ int label_at(const float *semb, int Hs, int Ws, int C, double sy, double sx, int r, int c) {
-  int y0, y1, x0, x1;
-  float fy, fx;
-  resample::tap(r, Hs, sy, y0, y1, fy);
-  resample::tap(c, Ws, sx, x0, x1, fx);
-  const float *p00 = semb + ((size_t)y0 * Ws + x0) * C, *p01 = semb + ((size_t)y0 * Ws + x1) * C;
-  const float *p10 = semb + ((size_t)y1 * Ws + x0) * C, *p11 = semb + ((size_t)y1 * Ws + x1) * C;
-  const float gx = 1.f - fx, gy = 1.f - fy;
-  float best = 0.f;
-  int arg = 0;
-  for (int ch = 0; ch < C; ++ch) {
-    const float top = p00[ch] * gx + p01[ch] * fx;
-    const float bot = p10[ch] * gx + p11[ch] * fx;
-    const float v = top * gy + bot * fy;
-    if (ch == 0 || v > best) best = v, arg = ch;  // strict: the first maximum, like numpy.argmax
-  }
+  const int arg = resample::argmax_channel_at(semb, Hs, Ws, C, sy, sx, r, c);
   return arg == 0 ? 0 : gtid::cs_label_id(arg - 1);  // arg - 1 < kMaxC - 1 = kCsClasses
 }
 

@@ -37,6 +37,31 @@ __device__ __forceinline__ void tap(int d, int n_src, double scale, int &i0, int
   w = fr;
 }
 
+// The channel holding the FIRST maximum (numpy.argmax) at pixel (r, c) of the H x W resize of the channel-last map semb
+// [Hs,Ws,C] of one image; sy = Hs / H and sx = Ws / W in double.  All channels go through one loop body with the pixel's taps
+// and weights, every product and sum rounded on its own, so channels that are equal at the four taps give exactly equal values
+// and the lower index wins.  The label image of the semantic map (ra_pixel_eval.hip) and the orientation image
+// (ra_render.hip) both call this one.
+__device__ __forceinline__ int argmax_channel_at(const float *semb, int Hs, int Ws, int C, double sy, double sx, int r, int c) {
+#pragma clang fp contract(off)
+  int y0, y1, x0, x1;
+  float fy, fx;
+  tap(r, Hs, sy, y0, y1, fy);
+  tap(c, Ws, sx, x0, x1, fx);
+  const float *p00 = semb + ((size_t)y0 * Ws + x0) * C, *p01 = semb + ((size_t)y0 * Ws + x1) * C;
+  const float *p10 = semb + ((size_t)y1 * Ws + x0) * C, *p11 = semb + ((size_t)y1 * Ws + x1) * C;
+  const float gx = 1.f - fx, gy = 1.f - fy;
+  float best = 0.f;
+  int arg = 0;
+  for (int ch = 0; ch < C; ++ch) {
+    const float top = p00[ch] * gx + p01[ch] * fx;
+    const float bot = p10[ch] * gx + p11[ch] * fx;
+    const float v = top * gy + bot * fy;
+    if (ch == 0 || v > best) best = v, arg = ch;  // strict: the first maximum, like numpy.argmax
+  }
+  return arg;
+}
+
 // pixel (r, c) of the H x W resize of the plane p [Hs, Ws]
 __device__ inline float resize_linear_at(const float *p, int Hs, int Ws, int H, int W, int r, int c) {
   const float sy = (float)Hs / (float)H, sx = (float)Ws / (float)W;

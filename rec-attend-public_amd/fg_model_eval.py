@@ -23,8 +23,10 @@ Outputs: <output>/metrics.yaml — per threshold fg_iou_all, bg_iou_all and the 
 pixels), plus 'statistics' when ground truth at network size was given; <output>/<NN>/<name>.png, NN = int(threshold * 100)
 (:66) — the thresholded full-size map times 255 (RenderForegroundAnalyzer); <output>/soft/ and <output>/gt/ under
 --render_soft / --render_gt (the soft map and the labels, times 255 and clipped to 8 bits).  --output defaults to
-<results>/<model_id>/output (:184-186).  --render_ori is accepted and refused: it needs the colour orientation image of
-data_api/orientation.py, and utils/png.py writes 8-bit grey only.
+<results>/<model_id>/output (:184-186).  --render_ori is accepted and refused: the reference's flag renders from its HDF5
+dataset's labels; the orientation image itself is built behind --render_orientation (not a reference flag): <output>/ori/<name>.png,
+the colour-wheel image of data_api/orientation.py:13-28 from the model's d_out — resized to the labels' size and arg-maxed inside
+one kernel (analysis.RenderOrientationAnalyzer) — with fg_gt_full > 0 as the mask; a model without add_orientation is refused.
 
 Pixel-level class scores: when --input also holds gt_instance_ids [N,H,W] (the *_gtFine_instanceIds.png values; optionally
 gt_label_ids uint8 [N,H,W], the *_gtFine_labelIds.png values, else a pixel's label is derived from its id) and the model has
@@ -48,8 +50,8 @@ from ra_native import RecAttendError
 
 MAX_BATCH_ELEMS = 1 << 29  # floats of one [B,H,W] plane at full size (2 GiB)
 REFUSED = {
-    'render_ori': '--render_ori renders the orientation classes as a colour image (data_api/orientation.py); utils/png.py writes '
-                  '8-bit grey only, so it is not built',
+    'render_ori': '--render_ori renders the orientation classes as a colour image (data_api/orientation.py) from the labels of the '
+                  'HDF5 dataset, which is out of scope here; --render_orientation writes that image from --input',
 }
 STAT_NAMES = ('iou_soft', 'iou_hard', 'foreground_loss', 'loss', 'orientation_ce', 'orientation_acc')
 
@@ -59,6 +61,9 @@ def build_parser():
   cap.add_flags(p, cap.FG_EVAL_FLAGS)
   cap.add_flags(p, cap.DATA_FLAGS)
   p.add_argument('--input', default=None, help='.npz with x [N,h,w,3], fg_gt_full [N,H,W] uint8 (+ names, y_gt, d_gt)')
+  p.add_argument('--render_orientation', action='store_true',
+                 help='not a reference flag: write the orientation classes of the model\'s d_out as a colour-wheel image, masked '
+                      'by fg_gt_full, into <output>/ori/; needs a model with add_orientation')
   return p
 
 
@@ -105,6 +110,9 @@ def main(argv=None):
     raise RecAttendError('--threshold_list: %d thresholds (1 .. %d)' % (len(thresholds), ops.FG_SWEEP_MAX_K))
   out_dir = opt['output'] if opt['output'] is not None else os.path.join(args.results, args.model_id, 'output')
   model = fg_model_pack.restore_model(args.results, args.model_id)
+  if args.render_orientation and not model.dims['no']:
+    raise RecAttendError('--render_orientation: fg_model %s was built without add_orientation and has no d_out to render' % args.model_id)
+  ori_render = None
   data = np.load(args.input, allow_pickle=False)
   for k in ('x', 'fg_gt_full'):
     if k not in data:
@@ -134,6 +142,8 @@ def main(argv=None):
       print('pixel-level class scores are left out: the model has %d semantic classes, and only %d (the background and the '
             'labels %s) map to Cityscapes label ids' % (nsc, 1 + len(analysis.CITYSCAPES_LABELS),
                                                         ', '.join(n for n, _ in analysis.CITYSCAPES_LABELS)))
+  if args.render_orientation:
+    ori_render = analysis.RenderOrientationAnalyzer(os.path.join(out_dir, 'ori'), [os.path.basename(n) for n in names])
   fg_an = [analysis.ForegroundIOUAnalyzer('fg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]  # :62-69
   bg_an = [analysis.BackgroundIOUAnalyzer('bg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]
   totals = [{'count_a': 0, 'sum_ab': 0, 'sum_b': 0, 'pixels': 0} for _ in thresholds]
@@ -147,7 +157,10 @@ def main(argv=None):
     b1 = min(N, b0 + bs)
     x = up(x_all[b0:b1])
     gt = torch.as_tensor(np.ascontiguousarray(gt_all[b0:b1])).to(dev)
-    y_out = model.run('y_out', {'x': x, 'phase_train': False})
+    if ori_render is not None:
+      y_out, d_out = model.run(['y_out', 'd_out'], {'x': x, 'phase_train': False})
+    else:
+      y_out = model.run('y_out', {'x': x, 'phase_train': False})
     soft = foreground_plane(y_out)
     if pixel_an is not None:
       res_px = {'sem': y_out.contiguous(), 'size': (H, W), 'indices': list(range(b0, b1)),
@@ -171,6 +184,8 @@ def main(argv=None):
       _write_planes(os.path.join(out_dir, 'soft'), names[b0:b1], to8(full))
     if opt['render_gt']:
       _write_planes(os.path.join(out_dir, 'gt'), names[b0:b1], to8(gt.to(torch.float32)))
+    if ori_render is not None:  # :154-164: d_out at network size, the labels as the mask
+      ori_render.stage({'d_out': d_out.contiguous(), 'mask': (gt > 0).to(torch.float32), 'indices': list(range(b0, b1))})
     if have_stats:
       stats.append(model.statistics(x, up(y_gt_all[b0:b1]), None if d_gt_all is None else up(d_gt_all[b0:b1])))
   summary = {}

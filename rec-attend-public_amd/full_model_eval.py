@@ -23,7 +23,14 @@ behind the loop: every decoded batch and the pre-stage's y_in go through citysca
 chain, not the one above: upsample before apply_confidence, the semantic map's own foreground mask, conf carried across the
 thresholds — at --threshold_list / --remove_tiny, and DIR/<run>/<name>.txt + one PNG per written instance come out
 (analysis.RenderCityScapesOutputAnalyzer; the labels' size is y_gt's or full_size's of --input, else the network's; file
-names from `names` of --input, else image_<index>).  pred_rank<r>.npz is the same with and without the flag."""
+names from `names` of --input, else image_<index>).  pred_rank<r>.npz is the same with and without the flag.
+--render (not a reference flag; the reference's runner always renders, full_model_eval.py:170) writes what the write_log chain
+ends in there: per threshold <output>/output_<split>/<NN>/<name>.png, NN = int(threshold * 100) (:65) — every instance of the
+chain's thresholded masks in its own colour, composed on the device (analysis.RenderInstanceAnalyzer) — and <NN>/count.csv
+(analysis.CountAnalyzer); --render_gt_instances adds <output>/output_<split>/gt/<name>.png, the ground truth coloured by its
+best-matching prediction of the LAST threshold (:139-140, analysis.RenderGroundtruthInstanceAnalyzer).  Both need y_gt and s_gt in
+--input, where the chain runs.  With several ranks each rank writes the images of its shard and its counts go to
+<NN>/count_rank<r>.csv."""
 import argparse
 import os
 import time
@@ -51,6 +58,12 @@ def build_parser():
   p.add_argument('--cityscapes_output', default=None,
                  help='not a reference flag: write the Cityscapes instance-level output (a mask, a class id and a score per instance) '
                       'of every decoded image into this folder; needs --fg_model_id with 9 semantic classes')
+  p.add_argument('--render', action='store_true',
+                 help='not a reference flag (the reference always renders): write every thresholded output as a colour image, one '
+                      'colour per instance, and count.csv into <output>/output_<split>/<NN>/; needs y_gt and s_gt in --input')
+  p.add_argument('--render_gt_instances', action='store_true',
+                 help='not a reference flag: write the ground truth, coloured by its best-matching prediction, into '
+                      '<output>/output_<split>/gt/; needs y_gt and s_gt in --input')
   p.add_argument('--in_flight', type=int, default=8, help='batches submitted to one GPU at a time (four decode concurrently, the rest queue behind them)')
   return p
 
@@ -63,6 +76,17 @@ def main(argv=None):
   if args.cityscapes_output and not args.fg_model_id:
     from ra_native import RecAttendError
     raise RecAttendError('--cityscapes_output needs --fg_model_id: the instance classes are voted on the pre-stage\'s semantic map')
+  if args.render or args.render_gt_instances:  # before anything is restored: the flags render the write_log chain's masks
+    from ra_native import RecAttendError
+    flags = ' / '.join(f for f, on in (('--render', args.render), ('--render_gt_instances', args.render_gt_instances)) if on)
+    if not args.input:
+      raise RecAttendError('%s needs --input with y_gt and s_gt: the write_log chain, whose masks it renders, runs on labelled '
+                           'input only, and synthetic input has no labels' % flags)
+    with np.load(args.input) as peek:
+      missing = [k for k in ('y_gt', 's_gt') if k not in peek.files]
+    if missing:
+      raise RecAttendError('%s needs y_gt and s_gt in --input (the write_log chain, whose masks it renders, runs on labelled '
+                           'input only): %s lacks %s' % (flags, args.input, ' and '.join(missing)))
   restore = os.path.join(args.results, args.model_id)
   with open(os.path.join(restore, 'model_opt.yaml')) as f:
     model_opt = yaml.safe_load(f)
@@ -101,17 +125,30 @@ def main(argv=None):
                                   'obj_pr', 'obj_re', 'count_acc', 'count_mse', 'dic', 'dic_abs']
   else:
     names = [n for n in args.analyzers.split(',') if n]
-  analyze = bool(names) and 'y_gt' in data and 's_gt' in data
+  want_render = args.render or args.render_gt_instances
+  analyze = (bool(names) or want_render) and 'y_gt' in data and 's_gt' in data
   acc = {th: {n: [] for n in names} for th in thresholds}
   ys, ss, t0 = [], [], time.time()
   try:
-    _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0, fg=fg)
+    _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0, fg=fg, world=world)
   finally:
     ra_dist.barrier()  # always reached: a rank that fails must not leave the others hanging
 
 
-def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0, fg=None):
+def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0, fg=None, world=1):
   import torch
+  out_dir = os.path.join(args.output or restore, 'output_' + args.split.split(',')[0])
+  img_render, counters, gt_render = {}, {}, None
+  if getattr(args, 'render', False) or getattr(args, 'render_gt_instances', False):
+    import analysis
+    img_names = [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(data['x'].shape[0])]
+    if args.render:
+      for th in thresholds:
+        folder = os.path.join(out_dir, '{:02d}'.format(int(th * 100)))  # full_model_eval.py:65
+        img_render[th] = analysis.RenderInstanceAnalyzer(folder, img_names)
+        counters[th] = analysis.CountAnalyzer(os.path.join(folder, 'count.csv' if world == 1 else 'count_rank%d.csv' % rank))
+    if args.render_gt_instances:
+      gt_render = analysis.RenderGroundtruthInstanceAnalyzer(os.path.join(out_dir, 'gt'), img_names)
   cs_dir, sems, render = getattr(args, 'cityscapes_output', None), {}, None
   if cs_dir:
     import analysis
@@ -160,6 +197,13 @@ def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, anal
         results = {'y_out': y_bin, 'y_gt': gt, 's_out': s_hard, 's_gt': sg}
         for n in names:
           acc[th][n].append(analysis.create_analyzer(n)(results).cpu().numpy())
+        if th in img_render:  # :71-79: the instance image and the count file of this threshold
+          results['indices'] = list(range(b0, b1))
+          img_render[th].stage(results)
+          counters[th].stage(results)
+      if gt_render is not None:  # :139-140: after the last threshold, with its iou_pairwise
+        results['indices'] = list(range(b0, b1))
+        gt_render.stage(results)
     ys.append(y_dev if isinstance(y_dev, np.ndarray) else y_dev.cpu().numpy())  # to_host: already host arrays
     ss.append(s_dev if isinstance(s_dev, np.ndarray) else s_dev.cpu().numpy())
 
@@ -189,7 +233,6 @@ def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, anal
     spans.append((b0, b1))
   while len(pipe):
     consume(*(spans.pop(0) + tuple(pipe.collect())))
-  out_dir = os.path.join(args.output or restore, 'output_' + args.split.split(',')[0])
   os.makedirs(out_dir, exist_ok=True)
   path = os.path.join(out_dir, 'pred_rank%d.npz' % rank)
   T, H, W = model.dims['T'], model.dims['H'], model.dims['W']

@@ -1989,3 +1989,79 @@ def resize_cubic(src, H, W, want=('x',)):
   check(rn.lib().ra_resize_cubic_u8(ptr(src), N, Hs, Ws, Cc, H, W, ptr(oy), ptr(cy), ptr(ox), ptr(cx), ptr(out.get('u8')),
                                     ptr(out.get('x')), rn.stream_ptr()), 'ra_resize_cubic_u8')
   return out
+
+
+# ---- the render stage (csrc/ra_render.hip): the colour images of analysis.py's render analyzers
+RENDER_MAX_T = rn.RA_RENDER_MAX_T
+RENDER_MIN_C, RENDER_MAX_C = 2, 16  # channels of d the orientation image takes
+_RENDER_TABLES = {}                 # (what, T, device) -> uint8 table on that device
+
+
+def _render_table(what, T, device):
+  """The default colour tables, in the image's memory order (B, G, R): 'instances' — analysis.INSTANCE_CMAP[t % 22] reversed
+  (the reference swaps its R, G, B image before cv2.imwrite) for t < T; 'wheel' — the first T rows of
+  analysis.ORIENTATION_WHEEL as they stand (that array goes to cv2.imwrite unswapped)."""
+  key = (what, T, str(device))
+  if key not in _RENDER_TABLES:
+    import analysis
+    if what == 'instances':
+      cmap = np.array(analysis.INSTANCE_CMAP, dtype=np.uint8)
+      tab = cmap[np.arange(T) % cmap.shape[0]][:, ::-1]
+    else:
+      tab = np.array(analysis.ORIENTATION_WHEEL, dtype=np.uint8)[:T]
+    _RENDER_TABLES[key] = torch.from_numpy(np.ascontiguousarray(tab)).to(device)
+  return _RENDER_TABLES[key]
+
+
+def render_instances(y, colours=None, first=False):
+  """analysis.py:137-147 (first=False, RA_RENDER_ADD) / :166-187 (first=True, RA_RENDER_FIRST) on the device
+  (ra_render_instances_u8): y float32 [B,T,H,W] with finite 0 <= y <= 255 -> uint8 [B,H,W,3] in the memory order cv2.imwrite
+  takes (B, G, R; what utils/png.write_colour8 writes and read_colour8 reads).  Every plane is cast to uint8 and multiplied
+  with its colour; the planes are summed in uint8 (both wrap), or with first=True laid UNDER what is there, decided per
+  channel.  colours: uint8 [T,3] or [B,T,3] in the image's channel order (B, G, R); None = analysis.INSTANCE_CMAP[t % 22]
+  as the file's R, G, B.  y is read once and not copied: a contiguous view at any offset is taken as it is."""
+  _need_dev(y, torch.float32, 'y')
+  if y.dim() != 4 or min(y.shape) < 1:
+    raise rn.RecAttendError('render_instances: y must be [B,T,H,W], got %s' % (tuple(y.shape),))
+  B, T, H, W = y.shape
+  if T > RENDER_MAX_T or H * W > 1 << 30 or B > OVERLAP_MAX_B:
+    raise rn.RecAttendError('render_instances: B=%d, T=%d, H * W = %d (B <= %d, T <= %d, H * W <= 2^30)' % (
+        B, T, H * W, OVERLAP_MAX_B, RENDER_MAX_T))
+  if colours is None:
+    colours = _render_table('instances', T, y.device)
+  _need_dev(colours, torch.uint8, 'colours')
+  if tuple(colours.shape) == (T, 3):
+    colours = colours.unsqueeze(0).expand(B, T, 3).contiguous()
+  if tuple(colours.shape) != (B, T, 3):
+    raise rn.RecAttendError('render_instances: colours must be [T,3] or [B,T,3] = [%d,%d,3], got %s' % (B, T, tuple(colours.shape)))
+  img = torch.empty((B, H, W, 3), dtype=torch.uint8, device=y.device)
+  check(rn.lib().ra_render_instances_u8(ptr(y), B, T, H, W, ptr(colours), rn.RA_RENDER_FIRST if first else rn.RA_RENDER_ADD,
+                                        ptr(img), rn.stream_ptr()), 'ra_render_instances_u8')
+  return img
+
+
+def render_orientation(d, mask, size=None):
+  """fg_model_eval.py:128-132,154-164 with data_api/orientation.py:13-28 on the device (ra_render_orientation_u8): d float32
+  [B,Hs,Ws,C] at network size (2 <= C <= 8, the rows of analysis.ORIENTATION_WHEEL), mask float32 [B,H,W] of 0 / 1 at the
+  labels' size (size, when given, must be its (H, W)) -> uint8 [B,H,W,3] in the memory order cv2.imwrite takes.  Every
+  channel of d is resized with the linear resample of sem_labels inside the kernel, the first maximum is the class, the pixel
+  its wheel row times the mask — written to a file as it stands, so the file's R, G, B is the wheel row reversed."""
+  _need_dev(d, torch.float32, 'd')
+  _need_dev(mask, torch.float32, 'mask')
+  if d.dim() != 4 or mask.dim() != 3 or min(d.shape) < 1 or min(mask.shape) < 1 or mask.shape[0] != d.shape[0]:
+    raise rn.RecAttendError('render_orientation: d must be [B,Hs,Ws,C] and mask [B,H,W], got %s and %s' % (
+        tuple(d.shape), tuple(mask.shape)))
+  B, Hs, Ws, Cc = d.shape
+  H, W = int(mask.shape[1]), int(mask.shape[2])
+  if size is not None and (int(size[0]), int(size[1])) != (H, W):
+    raise rn.RecAttendError('render_orientation: size %s, but mask is %d x %d' % (tuple(size), H, W))
+  wheel = _render_table('wheel', Cc, d.device)
+  if not RENDER_MIN_C <= Cc <= min(RENDER_MAX_C, wheel.shape[0]) or wheel.shape[0] != Cc:
+    raise rn.RecAttendError('render_orientation: d has %d channels (%d .. 8, the classes of the colour wheel)' % (Cc, RENDER_MIN_C))
+  if H * W > 1 << 30 or Hs * Ws * Cc >= 1 << 31 or B > OVERLAP_MAX_B:
+    raise rn.RecAttendError('render_orientation: B=%d, %d x %d x %d -> %d x %d (B <= %d, planes up to 2^30 pixels)' % (
+        B, Hs, Ws, Cc, H, W, OVERLAP_MAX_B))
+  img = torch.empty((B, H, W, 3), dtype=torch.uint8, device=d.device)
+  check(rn.lib().ra_render_orientation_u8(ptr(d), B, Hs, Ws, Cc, ptr(mask), H, W, ptr(wheel), ptr(img), rn.stream_ptr()),
+        'ra_render_orientation_u8')
+  return img

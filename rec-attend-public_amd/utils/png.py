@@ -10,7 +10,10 @@ second for that size, where librecattend.so cannot be loaded: this module import
 
 `decode_colour8` / `read_colour8` read what cv2.imread(path) reads for the datasets' colour files (leftImg8bit, KITTI's and
 CVPPP's images and colour label files): uint8 [H,W,3] in cv2's BGR order from 8-bit RGB, RGBA (alpha dropped), palette
-(depths 1, 2, 4, 8) and grey files.  Interlaced files and 16-bit colour are refused."""
+(depths 1, 2, 4, 8) and grey files.  Interlaced files and 16-bit colour are refused.
+
+`encode_colour8` / `write_colour8` write such a BGR array as an 8-bit RGB file (what cv2.imwrite stores for the colour images
+of analysis.py's render analyzers), with the same one-IDAT, filter-0 layout as `encode_gray8`."""
 import struct
 import zlib
 
@@ -241,3 +244,23 @@ def decode_colour8(data):
 def read_colour8(path):
   with open(path, 'rb') as f:
     return decode_colour8(f.read())
+
+
+def encode_colour8(img, level=6):
+  """What cv2.imwrite(name, img) stores for a uint8 [H,W,3] array in cv2's BGR order: the bytes of an 8-bit RGB PNG file
+  (colour type 2, bit depth 8, no interlace; one IHDR, one IDAT, one IEND chunk, filter type 0 on every row).
+  decode_colour8(encode_colour8(img)) is img."""
+  img = np.asarray(img)
+  if img.dtype != np.uint8 or img.ndim != 3 or img.shape[2] != 3 or img.shape[0] < 1 or img.shape[1] < 1:
+    raise ValueError('encode_colour8 needs a uint8 [H,W,3] array, got %s %s' % (img.dtype, img.shape))
+  H, W, _ = img.shape
+  rows = np.zeros((H, 3 * W + 1), dtype=np.uint8)  # a filter-type byte (0 = None) in front of every row
+  rows[:, 1:] = img[:, :, ::-1].reshape(H, 3 * W)  # B, G, R in memory -> R, G, B in the file
+  ihdr = struct.pack('>IIBBBBB', W, H, 8, 2, 0, 0, 0)
+  return SIGNATURE + _chunk(b'IHDR', ihdr) + _chunk(b'IDAT', zlib.compress(rows.tobytes(), level)) + _chunk(b'IEND', b'')
+
+
+def write_colour8(path, img, level=6):
+  with open(path, 'wb') as f:
+    f.write(encode_colour8(img, level))
+  return path
