@@ -831,6 +831,47 @@ int ra_instance_class_pick_f32(const float *vote, const float *conf, int B, int 
                                void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The same stage behind an EXTERNAL semantic segmentation given as a label image (csrc/ra_label_vote.hip): the
+ * reference's --lrr_seg path, cityscapes_eval.py:162-164 and 212-232, where the label image becomes a one-hot [H,W,9] map,
+ * the foreground mask is "one of the eight thing classes" and the vote of analysis.py:235-237 counts pixels per class.
+ * y float32 [B,T,H,W] are the masks after upsample and apply_confidence (cityscapes_eval.py:179-180), labels uint8 [B,H,W]
+ * the label image at the same size, lut 256 bytes ON THE HOST (copied into the launch): label value -> 0 (background or
+ * ignored) or 1 .. 8 = person .. bicycle in the order of analysis.py:203-210.  Per pixel p: t* = the first maximum of
+ * y[b,:,p] (postprocess.py:45), v = y[b,t*,p], c = lut[labels[b,p]].  y is read with 16-byte loads when H * W % 4 == 0 and
+ * it is 16-byte aligned, labels with 4-byte loads when H * W % 4 == 0 and they are 4-byte aligned, element loads otherwise.
+ * 1 <= T <= 32, B <= 65535, H * W <= 2^30, every lut entry <= 8 — and 1 <= K <= 16 for the sweep — else RA_E_SHAPE and
+ * nothing is launched.
+ *
+ * ra_label_vote_sweep_f32 — the threshold loop of cityscapes_eval.py:183-189 with the vote and the pick of
+ *   analysis.py:232-261, for all K thresholds (a HOST array) from ONE read of y.  counts int32 [K,B,T,8], zeroed by the call:
+ *   counts[k,b,t*,c-1] = the pixels with c > 0 and v > (float)thresholds[k] — strict and in float32, postprocess.py:12 on a
+ *   float32 array.  The thresholds may be unsorted and repeat.  Integer counters (LDS, then global atomics): exact at any
+ *   size, the same bits on every run.  Then, walking the thresholds in list order (all outputs with a leading K axis):
+ *     sizes int32 [K,B,T]     the sum of counts over the classes: the plane's pixels after mask_foreground
+ *     keep uint8 [K,B,T]      remove_tiny == 0 (postprocess.py:115) or sizes > remove_tiny (:131)
+ *     conf float [K,B,T]      conf[k] = keep[k] ? conf[k-1] : 0, conf[-1] = conf_in [B,T]: carried from threshold to
+ *                             threshold as cityscapes_eval.py:188-189 re-assigns it
+ *     vote float [K,B,T,9]    vote[..., 0] = 0 (no background pixel is left under a mask), vote[..., 1+c] = counts /
+ *                             (H * W) rounded once; all zero for a plane that is not kept
+ *     class_idx, label_id int32 [K,B,T]   conf[k] > 0.5: the first maximum of the counts and its label of
+ *                             (24, 25, 26, 27, 28, 31, 32, 33); otherwise -1.  The gate vote[0] <= 0.7 of analysis.py:252 is
+ *                             always open here.
+ *   The integer counts define the class; the reference's float32 means of means equal counts / (H * W) exactly when H and
+ *   W are powers of two and can otherwise differ in near-ties of two classes.
+ * ra_label_planes_f32 — one threshold's planes, one read and one write: y_bin[b,t,p] = (t == t*) && v > (float)thresh &&
+ *   c > 0 && keep[b,t] as 0 / 1 floats; keep uint8 [B,T], NULL = keep all.  For thresh >= 0 this is apply_one_label ->
+ *   apply_threshold -> mask_foreground -> remove_tiny (postprocess.py:5-52, 109-145) to the bit.  (Below zero the
+ *   reference's chain also marks every plane that lost the arg-max, whose one-label value 0 exceeds the threshold; here
+ *   only the arg-max plane is ever marked, in the planes and in the counts.)
+ * ---------------------------------------------------------------------------------- */
+int ra_label_vote_sweep_f32(const float *y, const unsigned char *labels, const unsigned char *lut, int B, int T, int H,
+                            int W, const double *thresholds, int K, const float *conf_in, int remove_tiny, int *counts,
+                            int *sizes, unsigned char *keep, float *conf, float *vote, int *class_idx, int *label_id,
+                            void *stream);
+int ra_label_planes_f32(const float *y, const unsigned char *labels, const unsigned char *lut, int B, int T, int H, int W,
+                        double thresh, const unsigned char *keep, float *y_bin, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * The matching step of the Cityscapes instance-level evaluation (csrc/ra_instance_overlap.hip), cited as lines of
  * data_api/cityscapes_scripts/evaluation/evalInstanceLevelSemanticLabeling.py unless a file is named.  gt_ids is int32
  * [B,H,W]: the values of *_gtFine_instanceIds.png, a label id below 1000 or labelId * 1000 + k.  H * W < 2^31.

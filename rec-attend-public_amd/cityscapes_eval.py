@@ -32,6 +32,15 @@ The per-threshold means of the analyzers go to <output>/output_<split>/metrics.y
 and are not built HERE: the default lists run without them and say so on standard output; naming one explicitly is an error
 (the two accumulators themselves are analysis.ForegroundIOUAnalyzer / BackgroundIOUAnalyzer, driven by fg_model_eval.py).
 
+--semantic_labels PATH (not a reference flag) names the instances from an EXTERNAL semantic segmentation given as label images,
+the reference's --lrr_seg path (:162-164, :212-232) behind any segmenter: PATH is a folder holding one
+<city>_<seq>_<frame>*.png of label values per image name (8-bit grey, at full_size), or an .npz with labels uint8 [N,H,W] and
+names; --semantic_label_ids labelIds|trainIds|lrr says which values are the eight thing classes (default labelIds).  --input
+then need not hold y_out: the one-hot map, its foreground mask ("a thing class") and the vote are integer counting, done for
+every threshold from one read of the masks (iter_label_instances_from_labels, csrc/ra_label_vote.hip).  The integer counts
+define the class; the reference's float32 means of means equal counts / (H * W) exactly when H and W are powers of two
+(1024 x 2048 is) and can otherwise differ only in near-ties of two classes.
+
 --lrr_seg, --foreground_folder and --render_gt are accepted and refused: they read files of the authors' machines (LRR .mat
 files, a foreground folder, the HDF5 dataset); --lrr_filename is accepted and unused (its default there is a path of that
 cluster).  --render_instances (not a reference flag: the reference's runner always renders, cityscapes_eval.py:67-75) writes per
@@ -56,13 +65,14 @@ DEFAULT_ANALYZERS = ['sbd', 'wt_cov', 'unwt_cov', 'fg_dice', 'fg_iou', 'fg_iou_a
 TEST_ANALYZERS = ['fg_iou', 'fg_iou_all', 'bg_iou_all']  # :292
 # whole-dataset foreground / background IoU (analysis.py:834-900): accumulating analyzers, not per-image functions; not built
 NOT_BUILT = ('fg_iou_all', 'bg_iou_all')
+SEMANTIC_LABEL_IDS = ('labelIds', 'trainIds', 'lrr')  # the keys of ra_ops.LABEL_CLASS_IDS (not imported here: no torch yet)
 MAX_BATCH_ELEMS = 1 << 29  # floats of one [B,T,H,W] tensor of the chain (2 GiB); several are alive at a time
 
 REFUSED = {
     'lrr_seg': '--lrr_seg reads the LRR segmentation .mat files of the authors\' cluster (cityscapes_eval.py:207-230); give the '
-               'semantic map as y_out in --input instead',
+               'semantic map as y_out in --input instead, or the segmentation as label images with --semantic_labels',
     'foreground_folder': '--foreground_folder reads a folder of foreground images of the authors\' cluster; give the semantic '
-                         'map as y_out in --input instead',
+                         'map as y_out in --input instead, or a segmentation as label images with --semantic_labels',
     'render_gt': '--render_gt renders the ground truth from the HDF5 dataset, which is out of scope here; --render_instances '
                  'renders it from y_gt_full of --input',
 }
@@ -78,6 +88,13 @@ def build_parser():
                  help='not a reference flag (the reference always renders): write every threshold\'s instances as a colour image into '
                       '<output>/output_<split>/<NN>/, count.csv beside them when --input has s_gt, and the ground truth coloured by '
                       'its best match into gt/ when it has y_gt_full')
+  p.add_argument('--semantic_labels', default=None,
+                 help='not a reference flag: name the instances from an external semantic segmentation given as label images (the '
+                      '--lrr_seg path behind any segmenter): a folder with one <city>_<seq>_<frame>*.png per image name, or an '
+                      '.npz with labels uint8 [N,H,W] and names; --input then need not hold y_out')
+  p.add_argument('--semantic_label_ids', default='labelIds', choices=SEMANTIC_LABEL_IDS,
+                 help='which values of --semantic_labels are the eight thing classes: labelIds 24..28,31..33, trainIds 11..18, '
+                      'lrr 12..19 (cityscapes_eval.py:213-216)')
   return p
 
 
@@ -144,6 +161,95 @@ def label_instances(y_ins, s_out, sem, size, thresholds, remove_tiny=400):
   return list(iter_label_instances(y_ins, s_out, sem, size, thresholds, remove_tiny))
 
 
+def iter_label_instances_from_labels(y_ins, s_out, labels, size, thresholds, remove_tiny=400, ids='labelIds', planes=True):
+  """iter_label_instances behind an external semantic segmentation given as a label image (the reference's --lrr_seg path,
+  :162-164, :212-232): labels uint8 [B,H,W] at size = (H, W), ids the convention of its values (ra_ops.label_class_lut).
+  Yields the same keys per threshold, so the analyzers and renderers take it unchanged: 'y_in' is None, 'labels' the label
+  image, 'fg' [B,H,W] = "a thing class", 'vote' [B,T,9] = counts / (H * W) with channel 0 zero, and '_instance_class' is
+  supplied, so analysis.f_instance_class never calls the resampling vote; also 'sizes' [B,T] and 'counts' [B,T,8] (int32).
+  One read of the masks serves every threshold (ops.label_vote_sweep), one read and one write makes a threshold's planes
+  (ops.label_planes).  planes=False: 'y_out' is None and only the sweep runs — class, score and size of every instance at
+  every threshold, without the masks (the analyzers and renderers need the masks)."""
+  torch = _need_device()
+  import ra_ops as ops
+  from utils import postprocess as pp
+  for t in (y_ins, s_out, labels):
+    if not t.is_cuda:
+      raise RecAttendError('the Cityscapes output stage needs device tensors; there is no CPU fallback')
+  H, W = int(size[0]), int(size[1])
+  if labels.dtype != torch.uint8 or tuple(labels.shape) != (y_ins.shape[0], H, W):
+    raise RecAttendError('labels must be uint8 %s (one label image per example at size), got %s %s'
+                         % ((y_ins.shape[0], H, W), labels.dtype, tuple(labels.shape)))
+  if s_out.dim() == 3:
+    s_out = s_out[:, :, 0]
+  s_out = s_out.contiguous().to(torch.float32)
+  labels = labels.contiguous()
+  lut = ops.label_class_lut(ids)
+  fg = (torch.from_numpy(lut).to(labels.device)[labels.long()] > 0).to(torch.float32)  # :164: 1 - onehot[..., 0]
+  y = pp.upsample(y_ins.contiguous(), (H, W))                 # :179
+  y, conf_hard = pp.apply_confidence(y, s_out)                # :180
+  thresholds = [float(th) for th in thresholds]
+  conf = s_out
+  for k0 in range(0, len(thresholds), ops.LABEL_VOTE_MAX_K):   # conf carries over from one sweep to the next
+    part = thresholds[k0:k0 + ops.LABEL_VOTE_MAX_K]
+    sw = ops.label_vote_sweep(y, labels, lut, part, conf, remove_tiny)
+    conf = sw['conf'][-1]
+    for k, th in enumerate(part):
+      y_bin = ops.label_planes(y, labels, lut, th, keep=sw['keep'][k]) if planes else None
+      idx, lab, vote = sw['class_idx'][k], sw['label_id'][k], sw['vote'][k]
+      yield {'threshold': th, 'y_out': y_bin, 's_out': conf_hard, 'conf': sw['conf'][k], 'y_in': None, 'labels': labels, 'fg': fg,
+             'class_idx': idx, 'label_id': lab, 'vote': vote, 'sizes': sw['sizes'][k], 'counts': sw['counts'][k],
+             '_instance_class': (idx, lab, vote)}
+
+
+def semantic_label_reader(path, names, size):
+  """--semantic_labels: a function i -> the label image uint8 [H,W] of image names[i].  path is a folder searched as
+  cityscapes_pixel.find_prediction searches --pred (the one <city>_<seq>_<frame>*.png below it), or an .npz with labels uint8
+  [N,H,W] and names.  No match, several matches and a size other than size = (H, W) are errors, raised when the image is
+  asked for."""
+  H, W = int(size[0]), int(size[1])
+  if os.path.isdir(path):
+    import fnmatch
+    from cityscapes_ap import image_stem
+    from utils import png
+    walk = [(root, files) for root, _, files in os.walk(path)]
+
+    def read(i):
+      name = str(names[i])
+      hits = [os.path.join(root, f) for root, files in walk for f in fnmatch.filter(files, image_stem(name) + '*.png')]
+      if not hits:
+        raise RecAttendError('--semantic_labels: found no label image for %s below %s' % (name, path))
+      if len(hits) > 1:
+        raise RecAttendError('--semantic_labels: found several label images for %s: %s' % (name, ', '.join(sorted(hits))))
+      img = png.read_gray8(hits[0])
+      if img.shape != (H, W):
+        raise RecAttendError('--semantic_labels: %s is %d x %d, expected full_size %d x %d' % ((hits[0],) + img.shape + (H, W)))
+      return img
+    return read
+  if not os.path.isfile(path):
+    raise RecAttendError('--semantic_labels: %s is neither a folder nor an .npz file' % path)
+  data = np.load(path, allow_pickle=False)
+  for k in ('labels', 'names'):
+    if k not in data:
+      raise RecAttendError('--semantic_labels %s lacks %s' % (path, k))
+  labels, have = data['labels'], [str(n) for n in data['names']]
+  if labels.dtype != np.uint8 or labels.ndim != 3 or labels.shape[0] != len(have):
+    raise RecAttendError('--semantic_labels %s: labels is %s %s, expected uint8 [N,H,W] for its %d names'
+                         % (path, labels.dtype, labels.shape, len(have)))
+
+  def pick(i):
+    name = str(names[i])
+    hits = [j for j, n in enumerate(have) if n == name]
+    if not hits:
+      raise RecAttendError('--semantic_labels: %s has no label image for %s' % (path, name))
+    if len(hits) > 1:
+      raise RecAttendError('--semantic_labels: %s names %s %d times' % (path, name, len(hits)))
+    if labels.shape[1:] != (H, W):
+      raise RecAttendError('--semantic_labels: %s is %d x %d, expected full_size %d x %d' % ((path,) + labels.shape[1:] + (H, W)))
+    return labels[hits[0]]
+  return pick
+
+
 def _full_size(data, dataset):
   if 'full_size' in data:
     return int(data['full_size'][0]), int(data['full_size'][1])
@@ -166,7 +272,7 @@ def main(argv=None):
   torch = _need_device()
   import analysis
   data = dict(np.load(args.input, allow_pickle=False))
-  for k in ('y_out_ins', 's_out', 'y_out'):
+  for k in ('y_out_ins', 's_out') + (() if args.semantic_labels else ('y_out',)):
     if k not in data:
       raise RecAttendError('--input lacks %s' % k)
   N, T = data['y_out_ins'].shape[:2]
@@ -174,6 +280,7 @@ def main(argv=None):
   names = [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(N)]
   lo, hi = (0, N) if opt['split_id'] == -1 else (min(N, opt['split_id'] * opt['num_split']),
                                                 min(N, (opt['split_id'] + 1) * opt['num_split']))  # :41-46
+  read_labels = semantic_label_reader(args.semantic_labels, names, (H, W)) if args.semantic_labels else None
   have_gt = 'y_gt_full' in data and 's_gt' in data
   an_names = opt['analyzers'] if have_gt else []
   out_dir = os.path.join(opt['output'], 'output_' + opt['split'][0])
@@ -204,8 +311,13 @@ def main(argv=None):
     gt = up(data['y_gt_full'][b0:b1]) if have_gt or gt_render is not None else None
     sg = up(data['s_gt'][b0:b1]) if have_gt or counters else None
     ids = torch.as_tensor(np.ascontiguousarray(all_ids[b0:b1], dtype=np.int32)).to(dev) if have_ids else None
-    chain = iter_label_instances(up(data['y_out_ins'][b0:b1]), up(data['s_out'][b0:b1]), up(data['y_out'][b0:b1]), (H, W),
-                                 thresholds, opt['remove_tiny'])
+    if read_labels is not None:
+      seg = torch.from_numpy(np.stack([read_labels(i) for i in range(b0, b1)])).to(dev)
+      chain = iter_label_instances_from_labels(up(data['y_out_ins'][b0:b1]), up(data['s_out'][b0:b1]), seg, (H, W), thresholds,
+                                               opt['remove_tiny'], ids=args.semantic_label_ids)
+    else:
+      chain = iter_label_instances(up(data['y_out_ins'][b0:b1]), up(data['s_out'][b0:b1]), up(data['y_out'][b0:b1]), (H, W),
+                                   thresholds, opt['remove_tiny'])
     for tt, res in enumerate(chain):
       res['indices'] = list(range(b0, b1))
       if have_gt:

@@ -1532,6 +1532,102 @@ def instance_class_pick(vote, conf):
   return idx, lab
 
 
+# ---------------------------------------------------------------------------- ... behind a label-image segmentation
+LABEL_VOTE_MAX_T = 32   # instances per launch of ra_label_vote_sweep_f32 / ra_label_planes_f32
+LABEL_VOTE_MAX_K = 16   # thresholds per sweep
+# label value of class 1 .. 8 (person .. bicycle, analysis.py:203-210) under each convention of a label image
+LABEL_CLASS_IDS = {
+    'labelIds': (24, 25, 26, 27, 28, 31, 32, 33),  # *_labelIds.png (helpers/labels.py: id)
+    'trainIds': (11, 12, 13, 14, 15, 16, 17, 18),  # *_labelTrainIds.png (helpers/labels.py: trainId)
+    'lrr': (12, 13, 14, 15, 16, 17, 18, 19),       # cityscapes_eval.py:213-216
+}
+
+
+def label_class_lut(ids='labelIds'):
+  """np.uint8[256]: label value -> 0 (background or ignored) or 1 .. 8 = person .. bicycle, for ids in LABEL_CLASS_IDS."""
+  if ids not in LABEL_CLASS_IDS:
+    raise rn.RecAttendError('label_class_lut: ids must be one of %s, got %r' % (', '.join(sorted(LABEL_CLASS_IDS)), ids))
+  lut = np.zeros(256, np.uint8)
+  for c, v in enumerate(LABEL_CLASS_IDS[ids]):
+    lut[v] = c + 1
+  return lut
+
+
+def _label_vote_args(who, y, labels, lut):
+  """The checks ra_label_vote_sweep_f32 and ra_label_planes_f32 share; -> (B, T, H, W, lut as contiguous uint8[256])."""
+  for name, t, dt, nd in (('y', y, torch.float32, 4), ('labels', labels, torch.uint8, 3)):
+    if not isinstance(t, torch.Tensor) or not t.is_cuda:
+      raise rn.RecAttendError('%s: %s must be a CUDA (HIP) tensor; there is no CPU fallback' % (who, name))
+    if t.dtype != dt or t.dim() != nd:
+      raise rn.RecAttendError('%s: %s must be a %s tensor of %d dimensions, got %s %s' % (who, name, dt, nd, t.dtype, tuple(t.shape)))
+    if not t.is_contiguous():
+      raise rn.RecAttendError('%s: %s must be contiguous, got strides %s for shape %s' % (who, name, tuple(t.stride()), tuple(t.shape)))
+  B, T, H, W = y.shape
+  if tuple(labels.shape) != (B, H, W):
+    raise rn.RecAttendError('%s: labels %s do not belong to y %s (expected %s)' % (who, tuple(labels.shape), tuple(y.shape), (B, H, W)))
+  if T < 1 or T > LABEL_VOTE_MAX_T:
+    raise rn.RecAttendError('%s: y has T = %d instances (1 <= T <= %d)' % (who, T, LABEL_VOTE_MAX_T))
+  lut = np.ascontiguousarray(lut.detach().cpu().numpy() if isinstance(lut, torch.Tensor) else lut)
+  if lut.dtype != np.uint8 or lut.shape != (256,):
+    raise rn.RecAttendError('%s: lut must be uint8[256], got %s %s' % (who, lut.dtype, lut.shape))
+  if lut.max() > 8:
+    raise rn.RecAttendError('%s: lut[%d] = %d: a lut entry is 0 or a class 1 .. 8' % (who, int(lut.argmax()), int(lut.max())))
+  return B, T, H, W, lut
+
+
+def label_vote_sweep(y, labels, lut, thresholds, conf, remove_tiny=400):
+  """cityscapes_eval.py:183-189 + analysis.py:232-261 behind a label-image segmentation, every threshold from one read of y
+  (ra_label_vote_sweep_f32): y float32 [B,T,H,W] (after upsample and apply_confidence), labels uint8 [B,H,W], lut uint8[256]
+  on the host (label_class_lut), thresholds a sequence of K <= 16 floats in any order, conf float32 [B,T], remove_tiny a
+  non-negative integer.  Returns a dict of device tensors with a leading K axis: counts int32 [K,B,T,8], sizes int32 [K,B,T],
+  conf float32, keep uint8, vote float32 [K,B,T,9], class_idx, label_id int32 (-1 = not written)."""
+  who = 'label_vote_sweep'
+  B, T, H, W, lut = _label_vote_args(who, y, labels, lut)
+  th = np.ascontiguousarray(np.asarray(thresholds, np.float64).reshape(-1))
+  K = int(th.size)
+  if K < 1 or K > LABEL_VOTE_MAX_K:
+    raise rn.RecAttendError('%s: thresholds has K = %d entries (1 <= K <= %d)' % (who, K, LABEL_VOTE_MAX_K))
+  if np.isnan(th).any():
+    raise rn.RecAttendError('%s: thresholds holds a NaN' % who)
+  if not isinstance(conf, torch.Tensor) or not conf.is_cuda:
+    raise rn.RecAttendError('%s: conf must be a CUDA (HIP) tensor; there is no CPU fallback' % who)
+  if conf.dtype != torch.float32 or tuple(conf.shape) != (B, T):
+    raise rn.RecAttendError('%s: conf must be float32 %s, got %s %s' % (who, (B, T), conf.dtype, tuple(conf.shape)))
+  if int(remove_tiny) != remove_tiny or remove_tiny < 0:
+    raise rn.RecAttendError('%s: remove_tiny must be a non-negative integer (a pixel count), got %r' % (who, remove_tiny))
+  conf = conf.contiguous()
+  dev = y.device
+  new = lambda shape, dt: torch.empty(shape, dtype=dt, device=dev)
+  out = {'counts': new((K, B, T, 8), torch.int32), 'sizes': new((K, B, T), torch.int32), 'keep': new((K, B, T), torch.uint8),
+         'conf': new((K, B, T), torch.float32), 'vote': new((K, B, T, 9), torch.float32),
+         'class_idx': new((K, B, T), torch.int32), 'label_id': new((K, B, T), torch.int32)}
+  check(rn.lib().ra_label_vote_sweep_f32(ptr(y), ptr(labels), ptr(lut), B, T, H, W, ptr(th), K, ptr(conf), int(remove_tiny),
+                                         ptr(out['counts']), ptr(out['sizes']), ptr(out['keep']), ptr(out['conf']),
+                                         ptr(out['vote']), ptr(out['class_idx']), ptr(out['label_id']), rn.stream_ptr()),
+        'ra_label_vote_sweep_f32')
+  return out
+
+
+def label_planes(y, labels, lut, thresh, keep=None):
+  """One threshold's binary planes [B,T,H,W] from y and a label image in one read and one write (ra_label_planes_f32):
+  apply_one_label -> apply_threshold(thresh) -> mask_foreground(lut[labels] > 0) -> remove_tiny as keep uint8 [B,T] (None:
+  keep all), bit-equal to those ops for thresh >= 0."""
+  who = 'label_planes'
+  B, T, H, W, lut = _label_vote_args(who, y, labels, lut)
+  if keep is not None:
+    if not isinstance(keep, torch.Tensor) or not keep.is_cuda:
+      raise rn.RecAttendError('%s: keep must be a CUDA (HIP) tensor; there is no CPU fallback' % who)
+    if keep.dtype != torch.uint8 or tuple(keep.shape) != (B, T):
+      raise rn.RecAttendError('%s: keep must be uint8 %s, got %s %s' % (who, (B, T), keep.dtype, tuple(keep.shape)))
+    keep = keep.contiguous()
+  if np.isnan(float(thresh)):
+    raise rn.RecAttendError('%s: thresh is a NaN' % who)
+  y_bin = torch.empty_like(y)
+  check(rn.lib().ra_label_planes_f32(ptr(y), ptr(labels), ptr(lut), B, T, H, W, C.c_double(float(thresh)), ptr(keep), ptr(y_bin),
+                                     rn.stream_ptr()), 'ra_label_planes_f32')
+  return y_bin
+
+
 # ---------------------------------------------------------------------------- Cityscapes instance-level AP: the matching step
 MAX_GT = rn.RA_OVERLAP_MAX_GT  # distinct ids per image: a constant of the kernels, resting on no measurement of the dataset
 OVERLAP_MAX_T = 32   # predictions per launch of ra_instance_overlap_f32
