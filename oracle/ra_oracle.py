@@ -495,7 +495,8 @@ def pp_upsample(y_out, H, W, sigma_color=10.0, sigma_space=10.0):
   top = a[..., y0, :][..., :, x0] * (1 - wx) + a[..., y0, :][..., :, x1] * wx
   bot = a[..., y1, :][..., :, x0] * (1 - wx) + a[..., y1, :][..., :, x1] * wx
   b = top * (1 - wy)[:, None] + bot * wy[:, None]
-  ref = lambda i, n: np.abs(i) if n == 1 else (lambda j: np.where(j >= n, 2 * (n - 1) - j, j))(np.abs(i))
+  once = lambda i, n: (lambda j: np.where(j >= n, 2 * (n - 1) - j, j))(np.abs(i))
+  ref = lambda i, n: np.zeros_like(i) if n == 1 else once(once(i, n), n)  # an offset of 2 reflects twice through n = 2
   num, den = np.zeros_like(b), np.zeros_like(b)
   rr, cc = np.arange(H), np.arange(W)
   for dy in range(-2, 3):

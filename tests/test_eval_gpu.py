@@ -1,7 +1,11 @@
 """Parity of the evaluation post-processing and metrics (csrc/ra_eval.hip through the C ABI;
 host modules utils/postprocess.py and analysis.py with the reference's names) against the
 NumPy oracle restating utils/postprocess.py:5-147 and analysis.py:314-787.
-Binary masks and counts are exact (integers below 2^24 in float32); ratios within 1e-6."""
+Binary masks and counts are exact (integers below 2^24 in float32); ratios within 1e-6.
+
+These are example-shaped cases through the host modules.  The kernels' dimension space — odd sizes, tails, thresholds hit
+exactly, null pointers, refusals — is the table tests/eval_cases.py, run by tests/test_eval_cases_gpu.py (and held to its own
+conditions on the host by tests/test_eval_cases.py)."""
 import numpy as np
 import pytest
 import torch
