@@ -1115,6 +1115,33 @@ int ra_fg_sweep_counts_f32(const float *src, const unsigned char *gt, int N, int
                            const float *thresholds, int K, unsigned long long *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The decode loop's evaluator at the labels' size, from instance-id images (csrc/ra_instance_eval.hip).
+ *
+ * ra_instance_eval_counts_f32 — the reference's write_log chain behind apply_confidence (full_model_eval.py:112-124: upsample,
+ *   postprocess.py:75-106; morph, :55-72; apply_one_label, :32-52; per threshold apply_threshold, :5-12, and mask_foreground,
+ *   :139-147) reduced to the integers its analyzers read (analysis.py:314-787), for every threshold at once, in one pass that
+ *   writes no [., Hf, Wf] plane.  yc [B,T,Hs,Ws]: y_out * s_out at network size (apply_confidence, :15-29, stays with the
+ *   caller); gt_ids int32 [B,Hf,Wf] the instance-id image; inst_id int32 [B,T]: the id of ground-truth slot j, negative for
+ *   an empty slot (what ra_labels_assemble_i32 at NETWORK size returns, so the slots keep the reference's order); fg uint8
+ *   [B,Hf,Wf] or NULL, non-zero = foreground; morph: 0 | 1; thresholds: K floats in HOST memory, in any order.
+ *   Per full-size pixel and t, v_t = bilateralFilter(resize(yc_t, (Wf, Hf)), 5, 10, 10) with the arithmetic of
+ *   ra_resize_linear_f32 + ra_bilateral5_f32, with morph the maximum of that over the 5 x 5 window, pixels outside the image
+ *   ignored (ra_dilate_f32).  The pixel goes to t* = the FIRST maximum over t, of value m; at threshold k it belongs to
+ *   prediction t* iff m > thresholds[k] (and fg != 0 when fg is given); its ground-truth slot j is the first one with
+ *   inst_id[b,j] equal to its id, T when there is none.  Outputs, exact integers: inter [B,K,T,T + 1] = the pixels of
+ *   (prediction t*, slot j) at threshold k — column T holds the prediction's pixels on no listed instance, so a prediction's
+ *   area is its row sum — and area_b [B,T] = the pixels of slot j.  Both are cleared on the stream first; integer atomics
+ *   only, so two runs give the same bits.
+ *   1 <= K <= RA_INS_EVAL_MAX_K, every threshold >= 0 (below zero the zeros of the planes that lost the arg-max would pass
+ *   apply_threshold: another computation), 1 <= T <= RA_LABELS_MAX_T, Hf * Wf <= 2^24 (every count is then exact in the float32
+ *   ra_eval_metrics_f32 takes), Hs * Ws < 2^31, B <= 65535: else RA_E_SHAPE before anything is launched.
+ * ---------------------------------------------------------------------------------- */
+#define RA_INS_EVAL_MAX_K 16
+int ra_instance_eval_counts_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg, int B, int T,
+                                int Hs, int Ws, int Hf, int Wf, int morph, const float *thresholds, int K, int *inter,
+                                int *area_b, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Training the pre-stage fg_model (csrc/ra_fg_loss.hip).
  *
  * ra_fg_loss_bwd_f32 — the gradient of the loss head of fg_model.py:196-248 with respect to the logits [npix, nsc + no]; the

@@ -3,7 +3,9 @@
 `results` is the dict full_model_eval.py:128-135 builds — 'y_out' (thresholded, [B,T,H,W]),
 'y_gt', 's_out', 's_gt' — with float32 CUDA tensors.  All functions share one device pass
 (ops.eval_metrics: pairwise intersections on the MFMA streaming kernel + one small metrics
-kernel), cached on the dict.  Of the analyzers that render images or write CSV files (:52-311, :790-900) these are built:
+kernel), cached on the dict as results['_metrics'].  A caller that has the numbers already puts them there itself and needs
+no masks at all: full_model_eval.py's id-image path hands over ops.eval_metrics_from_counts' dict (the same metrics kernel, fed
+the integers of ops.instance_eval_counts), with 's_out' and 's_gt' beside it.  Of the analyzers that render images or write CSV files (:52-311, :790-900) these are built:
 CountAnalyzer (:67-92), RenderInstanceAnalyzer (:95-153), RenderGroundtruthInstanceAnalyzer (:156-193) and
 RenderOrientationAnalyzer (:270-283) — the colour images are composed on the device (ops.render_instances /
 ops.render_orientation) and written by utils/png.py — and RenderCityScapesOutputAnalyzer (:196-267, the Cityscapes

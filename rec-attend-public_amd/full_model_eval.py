@@ -5,7 +5,7 @@ Restores results/<model_id>/{model_opt.yaml, weights.npz}, forces `use_knob=Fals
 (full_model_eval.py:172-174), feeds {x, phase_train=False[, d_in, y_in]} and fetches
 ['y_out', 's_out'] (full_model_eval.py:35; runner.py:91-105) batch by batch on the MI355X
 kernels, sharding the images over the ranks when launched with torch.distributed.run.  Inputs
-come from --input (an .npz with x [N,H,W,3] and optionally d_in / y_in / y_gt / s_gt / fg) or are
+come from --input (an .npz with x [N,H,W,3] and optionally d_in / y_in / y_gt / s_gt / fg / gt_instance_ids / names) or are
 synthetic; with --fg_model_id (not a reference flag) d_in / y_in come from that fg_model's prestage() on the device, batch by
 batch, as the 8-bit values fg_model_pack.py would store; the reference's HDF5 datasets are out of scope.  The raw outputs are
 written to <output>/output_<split>/pred_rank<r>.npz.  With y_gt and s_gt in the input the
@@ -18,6 +18,17 @@ to the labels' size, then bilateralFilter(5, 10, 10), which on [0, 1] maps is cl
 the labels already have the network's size (full_model_eval.py:114), and the dilation runs when a foreground mask is given and
 --no_morph is not.  --fused_postprocess (not a reference flag) skips the bilateral step when no resize is needed: the chain
 then collapses into one fused device pass; masks and metrics near the threshold differ from the reference's in that mode.
+The labels may instead be instance-id images: an --input with gt_instance_ids [N,Hf,Wf] (integers, what setup_labels.py reads)
+and NO y_gt evaluates at the labels' own size without ever holding a [T,Hf,Wf] float plane.  Per batch ops.assemble_labels at
+network size, under the --dataset rule, gives the slots' ids (the reference's order, by area at network size) and s_gt — an
+image it cannot take is reported by its name of `names` — and behind apply_confidence the whole chain is ONE counting pass for
+all thresholds (ops.instance_eval_counts: resize + bilateral filter, the dilation when a foreground is given and --no_morph is
+not, first maximum, threshold, foreground mask) whose integers ops.eval_metrics_from_counts turns into what every analyzer
+reads; --remove_tiny acts on the counted areas where a foreground is given, as in the chain.  fg, optional, is then a 0 / 1
+mask [N,Hf,Wf]; another value is an error naming the image.  metrics_rank<r>.yaml has the same format on both paths.  The
+thresholds must be >= 0 there.  --render and --render_gt_instances draw the thresholded masks, which this path never writes,
+and --fused_postprocess has nothing to skip on it: all three are refused by name.  An archive that holds y_gt takes the plane
+path, whatever else it holds.  Limit: one full size per archive (KITTI's mixed sizes stay out of scope).
 --cityscapes_output DIR (not a reference flag; needs --fg_model_id with a 9-class pre-stage) puts the reference's THIRD stage
 behind the loop: every decoded batch and the pre-stage's y_in go through cityscapes_eval.label_instances on the device — its
 chain, not the one above: upsample before apply_confidence, the semantic map's own foreground mask, conf carried across the
@@ -68,6 +79,12 @@ def build_parser():
   return p
 
 
+def _id_path(keys):
+  """The labels of --input are instance-id images: gt_instance_ids [N,Hf,Wf] and no y_gt (an archive with y_gt keeps the
+  plane path it always took)."""
+  return 'gt_instance_ids' in keys and 'y_gt' not in keys
+
+
 def main(argv=None):
   import torch
   args = build_parser().parse_args(argv)
@@ -76,7 +93,19 @@ def main(argv=None):
   if args.cityscapes_output and not args.fg_model_id:
     from ra_native import RecAttendError
     raise RecAttendError('--cityscapes_output needs --fg_model_id: the instance classes are voted on the pre-stage\'s semantic map')
-  if args.render or args.render_gt_instances:  # before anything is restored: the flags render the write_log chain's masks
+  if args.input:  # before anything is restored: what the id path cannot do is refused by name
+    with np.load(args.input) as peek:
+      id_path = _id_path(peek.files)
+    refused = [f for f, on in (('--render', args.render), ('--render_gt_instances', args.render_gt_instances),
+                               ('--fused_postprocess', args.fused_postprocess)) if on]
+    if id_path and refused:
+      from ra_native import RecAttendError
+      raise RecAttendError(
+          '%s cannot be used with an --input that holds gt_instance_ids and no y_gt (%s): from id images the write_log chain runs '
+          'as one counting pass that never writes the thresholded masks --render / --render_gt_instances draw, and that always '
+          'upsamples, so --fused_postprocess has nothing to skip; put y_gt and s_gt into --input for these flags' % (
+              ' / '.join(refused), args.input))
+  if args.render or args.render_gt_instances:  # the flags render the write_log chain's masks
     from ra_native import RecAttendError
     flags = ' / '.join(f for f, on in (('--render', args.render), ('--render_gt_instances', args.render_gt_instances)) if on)
     if not args.input:
@@ -127,12 +156,65 @@ def main(argv=None):
     names = [n for n in args.analyzers.split(',') if n]
   want_render = args.render or args.render_gt_instances
   analyze = (bool(names) or want_render) and 'y_gt' in data and 's_gt' in data
+  if bool(names) and _id_path(data):
+    analyze = True
+    _check_id_labels(args, data, model)
   acc = {th: {n: [] for n in names} for th in thresholds}
   ys, ss, t0 = [], [], time.time()
   try:
     _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0, fg=fg, world=world)
   finally:
     ra_dist.barrier()  # always reached: a rank that fails must not leave the others hanging
+
+
+def _image_names(data):
+  return [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(data['x'].shape[0])]
+
+
+def _check_id_labels(args, data, model):
+  """The id path's input, checked on the host before the first batch is decoded."""
+  from ra_native import RecAttendError
+  import ra_ops as ops
+  ids, n = data['gt_instance_ids'], data['x'].shape[0]
+  if ids.ndim != 3 or ids.shape[0] != n or not np.issubdtype(ids.dtype, np.integer):
+    raise RecAttendError('--input %s: gt_instance_ids must be integers [N,Hf,Wf] with N = %d images (one full size per archive), '
+                         'got %s %s' % (args.input, n, ids.dtype, ids.shape))
+  ops.label_dataset_rule(args.dataset)
+  if 'fg' in data:
+    fg, names = data['fg'], _image_names(data)
+    if fg.shape != ids.shape:
+      raise RecAttendError('--input %s: fg must be a 0 / 1 mask %s at the labels\' size, got %s' % (args.input, ids.shape, fg.shape))
+    for i in range(n):
+      if not np.isin(fg[i], (0, 1)).all():
+        raise RecAttendError('--input %s: fg of image %s holds values other than 0 and 1' % (args.input, names[i]))
+
+
+def _analyze_ids(args, model, data, b0, b1, y_dev, s_dev, thresholds, names, acc):
+  """The write_log chain (full_model_eval.py:97-139) of one batch from instance-id images: apply_confidence at network size,
+  then ONE counting pass at the labels' size for all thresholds (ops.instance_eval_counts) and the analyzers' numbers from
+  the counts (ops.eval_metrics_from_counts), handed to analysis through the cache analysis._m honours."""
+  import torch
+  import analysis
+  import ra_ops as ops
+  from utils import postprocess as pp
+  dev = y_dev.device
+  ids = torch.as_tensor(np.ascontiguousarray(np.asarray(data['gt_instance_ids'][b0:b1]).astype(np.int32))).to(dev)
+  # the slots in the reference's order — by area at NETWORK size — under the --dataset rule, as setup_labels.py assembles them
+  lab = ops.assemble_labels(ids, model.dims['H'], model.dims['W'], model.dims['T'], args.dataset, want=('inst_id', 's_gt'),
+                            names=_image_names(data)[b0:b1])
+  fg = torch.as_tensor(np.ascontiguousarray(np.asarray(data['fg'][b0:b1]).astype(np.uint8))).to(dev) if 'fg' in data else None
+  s2 = s_dev[:, :, 0].contiguous() if s_dev.dim() == 3 else s_dev   # multi-class: :108-110
+  yc, s_conf = pp.apply_confidence(y_dev, s2)
+  for k0 in range(0, len(thresholds), ops.INS_EVAL_MAX_K):
+    ths = thresholds[k0:k0 + ops.INS_EVAL_MAX_K]
+    inter, area_b = ops.instance_eval_counts(yc.contiguous(), ids, lab['inst_id'], ths, fg=fg,
+                                             morph=fg is not None and not args.no_morph, check_fg=False)
+    # remove_tiny only where a foreground is given, as in the chain (:121-124)
+    per = ops.eval_metrics_from_counts(inter, area_b, lab['s_gt'], remove_tiny=args.remove_tiny if fg is not None else 0, conf=s_conf)
+    for th, met in zip(ths, per):
+      results = {'_metrics': met, 'iou_pairwise': met['iou_pairwise'], 's_out': met['conf'], 's_gt': lab['s_gt']}
+      for n in names:
+        acc[th][n].append(analysis.create_analyzer(n)(results).cpu().numpy())
 
 
 def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0, fg=None, world=1):
@@ -166,7 +248,9 @@ def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, anal
       for res in cityscapes_eval.iter_label_instances(y_dev, s_dev, sems.pop(b0), cs_size, thresholds, args.remove_tiny):
         res['indices'] = list(range(b0, b1))
         render.stage(res)
-    if analyze:
+    if analyze and _id_path(data):
+      _analyze_ids(args, model, data, b0, b1, y_dev, s_dev, thresholds, names, acc)
+    elif analyze:
       import analysis
       from utils import postprocess as pp
       dev = y_dev.device

@@ -1950,6 +1950,104 @@ def fg_sweep_counts(src, gt, thresholds):
           'pixels': int(gt.shape[1] * gt.shape[2]), 'thresholds': [float(t) for t in _sweep_thresholds(thresholds)]}
 
 
+# ---------------------------------------------------- the decode loop's evaluator from instance-id images (csrc/ra_instance_eval.hip)
+INS_EVAL_MAX_K = rn.RA_INS_EVAL_MAX_K
+INS_EVAL_MAX_PIXELS = 1 << 24  # every count stays exact in the float32 ra_eval_metrics_f32 takes
+
+
+def _ins_eval_thresholds(thresholds):
+  thr = np.ascontiguousarray(np.asarray(thresholds, dtype=np.float32).reshape(-1))
+  if not 1 <= thr.size <= INS_EVAL_MAX_K:
+    raise rn.RecAttendError('instance_eval_counts: %d thresholds (1 .. %d)' % (thr.size, INS_EVAL_MAX_K))
+  if not (thr >= 0).all():
+    raise rn.RecAttendError('instance_eval_counts: thresholds %s; every one must be >= 0 (below zero the zeros of the planes that '
+                            'lost the arg-max pass apply_threshold, which this pass does not count)' % thr.tolist())
+  return thr
+
+
+def instance_eval_counts(yc, gt_ids, inst_id, thresholds, fg=None, morph=False, check_fg=True):
+  """ra_instance_eval_counts_f32: the chain of full_model_eval.py:112-124 behind apply_confidence — upsample [-> morph] ->
+  apply_one_label -> per threshold apply_threshold [-> mask_foreground] — as exact counts, for all thresholds in one pass.
+  yc float32 [B,T,Hs,Ws] (y_out * s_out at network size), gt_ids int32 [B,Hf,Wf], inst_id int32 [B,T] (the id of ground-truth
+  slot j, -1 = empty: assemble_labels(..., want=('inst_id',)) at NETWORK size), thresholds: 1 .. 16 host values >= 0 in any
+  order, fg uint8 [B,Hf,Wf] 0 / 1 or None, morph: dilate 5 x 5 behind the filter -> (inter int32 [B,K,T,T + 1], area_b int32
+  [B,T]) on the device: inter[b,k,t,j] = the pixels of prediction t on ground-truth slot j at threshold k (column T: on no
+  listed instance; a prediction's area is its row sum), area_b[b,j] = the pixels of slot j.  check_fg: look at fg's largest
+  value (one device-to-host copy) and refuse anything but 0 / 1, which is where the chain's mask_foreground is a mask."""
+  thr = _ins_eval_thresholds(thresholds)
+  ts = (yc, gt_ids, inst_id) + (() if fg is None else (fg,))
+  if not all(isinstance(t, torch.Tensor) for t in ts) or not all(t.is_cuda for t in ts):
+    raise rn.RecAttendError('instance_eval_counts needs CUDA (HIP) tensors; got a CPU tensor. There is no CPU fallback.')
+  if yc.dtype != torch.float32 or gt_ids.dtype != torch.int32 or inst_id.dtype != torch.int32 or not all(t.is_contiguous() for t in ts):
+    raise rn.RecAttendError('instance_eval_counts: yc must be contiguous float32, gt_ids and inst_id contiguous int32, got %s, %s, %s' % (
+        yc.dtype, gt_ids.dtype, inst_id.dtype))
+  if yc.dim() != 4 or gt_ids.dim() != 3 or min(yc.shape) < 1 or min(gt_ids.shape) < 1 or gt_ids.shape[0] != yc.shape[0] or \
+      tuple(inst_id.shape) != tuple(yc.shape[:2]):
+    raise rn.RecAttendError('instance_eval_counts: yc must be [B,T,Hs,Ws], gt_ids [B,Hf,Wf] and inst_id [B,T], got %s, %s, %s' % (
+        tuple(yc.shape), tuple(gt_ids.shape), tuple(inst_id.shape)))
+  B, T, Hs, Ws = yc.shape
+  Hf, Wf = gt_ids.shape[1:]
+  if not (T <= LABELS_MAX_T and Hf * Wf <= INS_EVAL_MAX_PIXELS and Hs * Ws < 1 << 31 and B <= 65535):
+    raise rn.RecAttendError('instance_eval_counts: T=%d, B=%d, %d x %d -> %d x %d (T <= %d, B <= 65535, Hf * Wf <= 2^24 so that '
+                            'every count is exact in float32, Hs * Ws < 2^31)' % (T, B, Hs, Ws, Hf, Wf, LABELS_MAX_T))
+  if fg is not None:
+    if fg.dtype != torch.uint8 or tuple(fg.shape) != tuple(gt_ids.shape):
+      raise rn.RecAttendError('instance_eval_counts: fg must be uint8 %s, got %s %s' % (tuple(gt_ids.shape), fg.dtype, tuple(fg.shape)))
+    if check_fg and int(fg.max()) > 1:
+      raise rn.RecAttendError('instance_eval_counts: fg holds %d; a foreground mask is 0 / 1' % int(fg.max()))
+  K = int(thr.size)
+  inter = torch.empty((B, K, T, T + 1), dtype=torch.int32, device=yc.device)
+  area_b = torch.empty((B, T), dtype=torch.int32, device=yc.device)
+  check(rn.lib().ra_instance_eval_counts_f32(ptr(yc), ptr(gt_ids), ptr(inst_id), ptr(fg), B, T, Hs, Ws, Hf, Wf, int(bool(morph)),
+                                             ptr(thr), K, ptr(inter), ptr(area_b), rn.stream_ptr()), 'ra_instance_eval_counts_f32')
+  return inter, area_b
+
+
+def eval_metrics_from_counts(inter, area_b, s_gt, remove_tiny=0, conf=None):
+  """What eval_metrics returns — dict(iou_pairwise [B,T,T], stats [B,len(EVAL_NAMES)], inst [B,len(EVALI_NAMES),T], sizes
+  [B,T]) — for every threshold of instance_eval_counts' (inter [B,K,T,T + 1], area_b [B,T]): a list of K dicts, from ONE
+  ra_eval_metrics_f32 launch over the B * K problems.  remove_tiny (postprocess.py:109-136) acts on the counts: a prediction
+  whose area is <= remove_tiny loses its row, and its entry of conf [B,T] (apply_confidence's s_out > 0.5) becomes 0; every
+  dict then carries 'conf' [B,T].  The chain applies it only where a foreground was given (full_model_eval.py:121-124): pass 0
+  otherwise.  The kernel's foreground terms are sums of the counts: the predictions are disjoint after apply_one_label and
+  the instances of an id image are disjoint by construction, so the area of a union is the sum of the areas.  Every number
+  is an integer below 2^24, exact in float32 in any order of summation."""
+  if not all(isinstance(t, torch.Tensor) and t.is_cuda for t in (inter, area_b, s_gt)):
+    raise rn.RecAttendError('eval_metrics_from_counts needs CUDA (HIP) tensors; got a CPU tensor. There is no CPU fallback.')
+  if inter.dim() != 4 or inter.shape[3] != inter.shape[2] + 1 or tuple(area_b.shape) != (inter.shape[0], inter.shape[2]) or \
+      tuple(s_gt.shape) != tuple(area_b.shape):
+    raise rn.RecAttendError('eval_metrics_from_counts: inter must be [B,K,T,T + 1], area_b and s_gt [B,T], got %s, %s, %s' % (
+        tuple(inter.shape), tuple(area_b.shape), tuple(s_gt.shape)))
+  B, K, T, _ = inter.shape
+  dev = inter.device
+  cnt = inter.to(torch.float32)
+  sum_a = cnt.sum(dim=3)  # [B,K,T]: the predictions' areas
+  conf_k = None if conf is None else conf.to(torch.float32)[:, None, :].expand(B, K, T)
+  if remove_tiny:
+    keep = (sum_a > float(remove_tiny)).to(torch.float32)
+    cnt, sum_a = cnt * keep[..., None], sum_a * keep
+    conf_k = None if conf_k is None else conf_k * keep
+  main = cnt[..., :T].reshape(B * K, T, T).contiguous()
+  sum_a = sum_a.reshape(B * K, T).contiguous()
+  sum_b = area_b.to(torch.float32)[:, None, :].expand(B, K, T).reshape(B * K, T).contiguous()
+  sg = s_gt.to(torch.float32)[:, None, :].expand(B, K, T).reshape(B * K, T).contiguous()
+  fg_inter, fg_a, fg_b = main.sum(dim=(1, 2)).contiguous(), sum_a.sum(dim=1).contiguous(), sum_b.sum(dim=1).contiguous()
+  a_fgb, b_fga = main.sum(dim=2).contiguous(), main.sum(dim=1).contiguous()
+  iou = torch.empty((B * K, T, T), dtype=torch.float32, device=dev)
+  stats = torch.empty((B * K, len(EVAL_NAMES)), dtype=torch.float32, device=dev)
+  inst = torch.empty((B * K, len(EVALI_NAMES), T), dtype=torch.float32, device=dev)
+  check(rn.lib().ra_eval_metrics_f32(ptr(main), ptr(sum_a), ptr(sum_b), ptr(sg), ptr(fg_inter), ptr(fg_a), ptr(fg_b), ptr(a_fgb),
+                                     ptr(b_fga), B * K, T, ptr(iou), ptr(stats), ptr(inst), rn.stream_ptr()), 'ra_eval_metrics_f32')
+  iou, stats, inst, sum_a = (iou.view(B, K, T, T), stats.view(B, K, -1), inst.view(B, K, len(EVALI_NAMES), T), sum_a.view(B, K, T))
+  out = []
+  for k in range(K):
+    d = {'iou_pairwise': iou[:, k], 'stats': stats[:, k], 'inst': inst[:, k], 'sizes': sum_a[:, k]}
+    if conf_k is not None:
+      d['conf'] = conf_k[:, k]
+    out.append(d)
+  return out
+
+
 # ---------------------------------------------------------------------------- the label stage: ground truth from instance ids
 LABELS_MAX_T = rn.RA_LABELS_MAX_T
 LABEL_DATASETS = {'cvppp': rn.RA_LABELS_PLAIN, 'kitti': rn.RA_LABELS_PLAIN, 'plain': rn.RA_LABELS_PLAIN,
