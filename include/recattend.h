@@ -38,8 +38,10 @@ extern "C" {
 /* ABI version: bumped whenever an entry point of this header is removed or changes its signature (additions do not
  * bump it).  101 = round 3's removal of the table-form attention entry points and the phase-fused patch net; 102-113 =
  * rounds 3-5 (signature changes of the controller / conv entry points as the kernels were rebuilt; `git log -p
- * include/recattend.h` has each).  ra_native.py refuses a library whose version differs from the header it was written against. */
-#define RA_ABI_VERSION 114
+ * include/recattend.h` has each); 115 = the ragged entry points and struct ra_image_geo, an addition that was given a
+ * number of its own so that a binding built for them meets a library that has them.  ra_native.py refuses a library whose
+ * version differs from the header it was written against. */
+#define RA_ABI_VERSION 115
 int ra_version(void);
 /* Human-readable description of the last non-zero return on this thread. */
 const char *ra_last_error_string(void);
@@ -1140,6 +1142,55 @@ int ra_fg_sweep_counts_f32(const float *src, const unsigned char *gt, int N, int
 int ra_instance_eval_counts_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg, int B, int T,
                                 int Hs, int Ws, int Hf, int Wf, int morph, const float *thresholds, int K, int *inter,
                                 int *area_b, void *stream);
+
+/* ------------------------------------------------------------------------------------
+ * Mixed full sizes in one batch (KITTI): the ragged forms of the four entry points that work at the labels' own size.
+ *
+ * A batch of B full-size images of different sizes is ONE flat buffer per per-pixel tensor (gt_ids int32, fg uint8,
+ * fg_gt_full uint8, the sweep's gt uint8), all with the same geometry: image b is the h x w rows, packed with pitch w, that
+ * start at element `offset` of the buffer (counted in elements, not bytes).  `total` is the buffer's element count.
+ * Every entry takes the table twice: geo, B entries in HOST memory, checked before anything is launched or cleared, and
+ * geo_dev, a caller-provided DEVICE buffer of B entries which the entry fills on the stream ahead of its kernels.  RA_E_SHAPE,
+ * with a message that names the image, for: h < 1 or w < 1; an image that starts before the end of the one before it (the
+ * table is in ascending order of offset; gaps are fine); an image that ends beyond `total`; an image that breaks a per-image
+ * bound of the uniform entry point (h * w < 2^31; h * w <= 2^24 for ra_instance_eval_counts_ragged_f32; 1 <= H <= h and
+ * 1 <= W <= w for ra_labels_assemble_ragged_i32).
+ * Offsets need not be aligned.  The wide loads (16 bytes of ids, 4 bytes of uint8 labels per lane) are a PER-IMAGE decision,
+ * made once per workgroup: they need w % 4 == 0, offset % 4 == 0 and base pointers aligned as the uniform forms want them; an
+ * image that misses any of these takes element loads and its neighbours are unaffected.  The load width touches no arithmetic.
+ * The kernels are the uniform forms' own, instantiated over the geometry source (csrc/ra_ragged.h): one table entry read per
+ * workgroup into scalar registers; the grid's x extent follows the LARGEST image's tile count and a workgroup's loop bound is
+ * its own image's, so one launch chain serves the batch.  Everything that is uniform in the batch stays a dense tensor: yc
+ * [B,T,Hs,Ws], inst_id [B,T], src [N,Hs,Ws], the catalogue, the counts, the network-size labels [B,T,H,W] etc.
+ *
+ * ra_gt_instance_catalog_ragged_i32 — ra_gt_instance_catalog_i32 per image.  ws: ra_gt_instance_catalog_ragged_workspace_ints
+ *   (geo, B) ints, sized from the largest image; the record of a workgroup whose image has fewer tiles than the grid is
+ *   written empty, never left as it was.
+ * ra_labels_assemble_ragged_i32 — ra_labels_assemble_i32 with the sampling scales sy, sx per image (the same double
+ *   expressions, evaluated on the device once per workgroup); fg_gt_full is written flat at gt_ids' offsets (elements between
+ *   images are not touched).  ws: ra_labels_workspace_bytes(B, H, W).
+ * ra_instance_eval_counts_ragged_f32 — ra_instance_eval_counts_f32; gt_ids and fg (nullable) are flat, and the resize
+ *   coordinates, reflect101, the in-image test of the dilation and the tile walk use the image's own h, w.
+ * ra_fg_sweep_counts_ragged_f32 — ra_fg_sweep_counts_f32 with gt flat; counts [N, RA_FG_SWEEP_SLOTS] as there.
+ * ---------------------------------------------------------------------------------- */
+typedef struct ra_image_geo {
+  long long offset;
+  int h;
+  int w;
+} ra_image_geo;
+size_t ra_gt_instance_catalog_ragged_workspace_ints(const ra_image_geo *geo, int B);
+int ra_gt_instance_catalog_ragged_i32(const int *gt_ids, size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev, int B,
+                                      int *ws, size_t ws_ints, int *ids, int *pixels, int *count, int *status, void *stream);
+int ra_labels_assemble_ragged_i32(const int *gt_ids, size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev,
+                                  const int *ids, const int *count, int B, int H, int W, int T, int dataset, void *ws,
+                                  size_t ws_bytes, int *num_obj, float *s_gt, int *inst_id, int *area, int *sem_cls, float *y_gt,
+                                  unsigned char *d_cls, float *d_gt, float *c_gt, unsigned char *fg_gt_full, void *stream);
+int ra_instance_eval_counts_ragged_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg,
+                                       size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev, int B, int T, int Hs, int Ws,
+                                       int morph, const float *thresholds, int K, int *inter, int *area_b, void *stream);
+int ra_fg_sweep_counts_ragged_f32(const float *src, const unsigned char *gt, size_t total, const ra_image_geo *geo,
+                                  ra_image_geo *geo_dev, int N, int Hs, int Ws, const float *thresholds, int K,
+                                  unsigned long long *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------
  * Training the pre-stage fg_model (csrc/ra_fg_loss.hip).

@@ -749,7 +749,8 @@ def _fg_counts_of(results, index):
     ca, sab = c['count_a'], c['sum_ab']
     n = len(c['sum_b'])
     pick = (lambda a: [int(v[index]) for v in a]) if getattr(ca, 'ndim', 2) == 2 else (lambda a: [int(v) for v in a])
-    return sum(pick(ca)), sum(pick(sab)), sum(int(v) for v in c['sum_b']), int(c['pixels']) * n
+    pix = c['pixels']  # one number for images of one size, or one per image (ops.fg_sweep_counts_ragged)
+    return sum(pick(ca)), sum(pick(sab)), sum(int(v) for v in c['sum_b']), sum(int(v) for v in pix) if hasattr(pix, '__len__') else int(pix) * n
   a, b = results['y_out'], results['y_gt']
   if not (isinstance(a, torch.Tensor) and isinstance(b, torch.Tensor) and a.is_cuda and b.is_cuda):
     raise ops.rn.RecAttendError('the whole-dataset IoU analyzers take results[\'fg_counts\'] or device tensors y_out / y_gt; '

@@ -37,7 +37,8 @@ def build_parser():
   for table in (cap.TRAIN_FLAGS, cap.DATA_FLAGS, cap.MODEL_FLAGS):
     cap.add_flags(p, table)
   cap.add_size_overrides(p)
-  p.add_argument('--input', default=None, help='.npz with x and y_gt, s_gt or gt_instance_ids (default: synthetic batches)')
+  p.add_argument('--input', default=None, help='.npz with x and y_gt, s_gt or gt_instance_ids, or the ids of mixed full sizes as gt_instance_ids_flat + pixel_offset + '
+                 'orig_size (default: synthetic batches)')
   p.add_argument('--seed', type=int, default=1234)
   p.add_argument('--sync_bn', action='store_true', help='BatchNorm batch moments over the whole data-parallel batch')
   p.add_argument('--train_any_filter', action='store_true',

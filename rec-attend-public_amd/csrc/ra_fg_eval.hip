@@ -29,10 +29,12 @@
 //           constant; counting count_a by wave masks in scalar registers instead spilled 294 of them at K = 16), reduced
 //           across the wave by shuffles, across the four waves in LDS, and leave the workgroup as ONE 64-bit integer atomic
 //           add per counter: integer sums do not depend on the order.  The grid is capped (kSweepWgs workgroups in all) and a workgroup walks several tiles, so the
-//           number of atomics does not grow with the image.
+//           number of atomics does not grow with the image.  ra_fg_sweep_counts_ragged_f32 runs the same kernel over a batch of
+//           mixed full sizes: gt flat, image n at its entry of the geometry table (ra_ragged.h), read once per workgroup.
 #include <cstdint>
 
 #include "ra_common.h"
+#include "ra_ragged.h"
 #include "ra_resample.h"
 
 namespace ra {
@@ -200,15 +202,20 @@ inline int sweep_wgs(int N, int H, int W) {
 }
 
 // KP: thresholds compared per pixel (K padded with +inf, which no value exceeds).  VEC: 4 bytes of gt as one 32-bit load.
-template <int KP, bool VEC>
-__global__ __launch_bounds__(256) void sweep_kernel(const float *src, const unsigned char *gt, int Hs, int Ws, int H, int W,
+// GEO: geo::Uniform (gt is [N,H,W]; VEC is the launch's decision) or geo::Ragged (gt flat, image n at its table entry with its
+// own H, W; VEC says the base pointer allows it and the image's own vec decides, once per workgroup).
+template <int KP, bool VEC, class GEO>
+__global__ __launch_bounds__(256) void sweep_kernel(const float *src, const unsigned char *gt, int Hs, int Ws, const GEO geom,
                                                      const Thresholds thr, unsigned long long *counts) {
   __shared__ __attribute__((aligned(16))) float tile[kLH * kLW];
   __shared__ unsigned red[4][2 * KP + 1];
   const int n = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
   const int tx = tid & 31, ty = tid >> 5;  // 4 pixels at column 4 tx of the rows ty and ty + 8
   const float *sp = src + (size_t)n * Hs * Ws;
-  const unsigned char *gp = gt + (size_t)n * H * W;
+  const geo::Image im = geom.at(n);
+  const int H = im.h, W = im.w;
+  const bool vec = VEC && (!GEO::kRagged || im.vec);
+  const unsigned char *gp = gt + im.off;
   const float gs = resample::bilateral_gain(10.f), gc = resample::bilateral_gain(10.f);  // fg_model_eval.py:116
   const int ntx = sweep_tiles_x(W), ntiles = sweep_tiles(H, W);
   unsigned cnt_a[KP], sum_ab[KP], sum_b = 0;  // per lane
@@ -229,7 +236,7 @@ __global__ __launch_bounds__(256) void sweep_kernel(const float *src, const unsi
       const int row = ty + 8 * half, r = r0 + row, c = c0 + 4 * tx;
       unsigned g[4] = {0, 0, 0, 0};
       const bool row_in = r < H;
-      if (VEC) {
+      if (vec) {
         if (row_in && c < W) {  // W % 4 == 0: c + 3 < W
           const unsigned w = *reinterpret_cast<const unsigned *>(gp + (size_t)r * W + c);
 #pragma unroll
@@ -291,13 +298,32 @@ __global__ __launch_bounds__(256) void sweep_kernel(const float *src, const unsi
   }
 }
 
-template <int KP>
-void launch_sweep(bool vec, dim3 grid, hipStream_t st, const float *src, const unsigned char *gt, int Hs, int Ws, int H, int W,
+template <int KP, class GEO>
+void launch_sweep(bool vec, dim3 grid, hipStream_t st, const float *src, const unsigned char *gt, int Hs, int Ws, const GEO &geom,
                   const Thresholds &thr, unsigned long long *counts) {
   if (vec)
-    hipLaunchKernelGGL((sweep_kernel<KP, true>), grid, dim3(256), 0, st, src, gt, Hs, Ws, H, W, thr, counts);
+    hipLaunchKernelGGL((sweep_kernel<KP, true, GEO>), grid, dim3(256), 0, st, src, gt, Hs, Ws, geom, thr, counts);
   else
-    hipLaunchKernelGGL((sweep_kernel<KP, false>), grid, dim3(256), 0, st, src, gt, Hs, Ws, H, W, thr, counts);
+    hipLaunchKernelGGL((sweep_kernel<KP, false, GEO>), grid, dim3(256), 0, st, src, gt, Hs, Ws, geom, thr, counts);
+}
+
+// clear -> sweep on one stream, gx workgroups per image; vec: whether the launch may load 4 bytes of gt at once
+template <class GEO>
+int sweep_all(const char *who, const float *src, const unsigned char *gt, int N, int Hs, int Ws, const GEO &geom, int gx, bool vec,
+              const float *thresholds, int K, unsigned long long *counts, hipStream_t st) {
+  Thresholds thr;
+  for (int k = 0; k < kMaxK; ++k) thr.t[k] = k < K ? thresholds[k] : __builtin_inff();
+  char what[96];
+  if (hipMemsetAsync(counts, 0, (size_t)N * kSlots * sizeof(unsigned long long), st) != hipSuccess) {
+    snprintf(what, sizeof(what), "%s (clear)", who);
+    return launch_status(what);
+  }
+  const dim3 grid(gx, N);
+  if (K <= 4)
+    launch_sweep<4>(vec, grid, st, src, gt, Hs, Ws, geom, thr, counts);
+  else
+    launch_sweep<16>(vec, grid, st, src, gt, Hs, Ws, geom, thr, counts);
+  return launch_status(who);
 }
 
 }  // namespace fge
@@ -334,16 +360,28 @@ extern "C" int ra_fg_sweep_counts_f32(const float *src, const unsigned char *gt,
   if (K < 1 || K > fge::kMaxK) return fail(RA_E_SHAPE, "ra_fg_sweep_counts_f32: K=%d thresholds (1 .. %d)", K, fge::kMaxK);
   if ((long long)H * W >= (1ll << 31) || (long long)Hs * Ws >= (1ll << 31) || N > 65535)
     return fail(RA_E_SHAPE, "ra_fg_sweep_counts_f32: %dx%d -> %dx%d, N=%d (planes below 2^31 pixels, N <= 65535)", Hs, Ws, H, W, N);
-  fge::Thresholds thr;
-  for (int k = 0; k < fge::kMaxK; ++k) thr.t[k] = k < K ? thresholds[k] : __builtin_inff();
-  hipStream_t st = as_stream(stream);
-  if (hipMemsetAsync(counts, 0, (size_t)N * fge::kSlots * sizeof(unsigned long long), st) != hipSuccess)
-    return launch_status("ra_fg_sweep_counts_f32 (clear)");
   const bool vec = W % 4 == 0 && (reinterpret_cast<uintptr_t>(gt) & 3) == 0;
-  const dim3 grid(fge::sweep_wgs(N, H, W), N);
-  if (K <= 4)
-    fge::launch_sweep<4>(vec, grid, st, src, gt, Hs, Ws, H, W, thr, counts);
-  else
-    fge::launch_sweep<16>(vec, grid, st, src, gt, Hs, Ws, H, W, thr, counts);
-  return launch_status("ra_fg_sweep_counts_f32");
+  return fge::sweep_all("ra_fg_sweep_counts_f32", src, gt, N, Hs, Ws, geo::Uniform{H, W, vec ? 1 : 0}, fge::sweep_wgs(N, H, W), vec,
+                        thresholds, K, counts, as_stream(stream));
+}
+
+extern "C" int ra_fg_sweep_counts_ragged_f32(const float *src, const unsigned char *gt, size_t total, const ra_image_geo *geo,
+                                             ra_image_geo *geo_dev, int N, int Hs, int Ws, const float *thresholds, int K,
+                                             unsigned long long *counts, void *stream) {
+  const char *who = "ra_fg_sweep_counts_ragged_f32";
+  if (!src || !gt || !geo || !geo_dev || !thresholds || !counts || N <= 0 || Hs <= 0 || Ws <= 0)
+    return fail(RA_E_INVALID, "%s: bad argument", who);
+  if (K < 1 || K > fge::kMaxK) return fail(RA_E_SHAPE, "%s: K=%d thresholds (1 .. %d)", who, K, fge::kMaxK);
+  if ((long long)Hs * Ws >= (1ll << 31) || N > 65535)
+    return fail(RA_E_SHAPE, "%s: %dx%d, N=%d (planes below 2^31 pixels, N <= 65535)", who, Hs, Ws, N);
+  if (int rc = geo::check(who, geo, N, total, (1ll << 31) - 1, "h * w < 2^31")) return rc;
+  int ntiles = 0;  // of the largest image: the grid; a workgroup's loop bound is its own image's count
+  for (int n = 0; n < N; ++n)
+    ntiles = fge::sweep_tiles(geo[n].h, geo[n].w) > ntiles ? fge::sweep_tiles(geo[n].h, geo[n].w) : ntiles;
+  const int want = fge::kSweepWgs / N > 0 ? fge::kSweepWgs / N : 1;
+  hipStream_t st = as_stream(stream);
+  if (int rc = geo::upload(who, geo, geo_dev, N, st)) return rc;
+  const bool vec = (reinterpret_cast<uintptr_t>(gt) & 3) == 0;
+  return fge::sweep_all(who, src, gt, N, Hs, Ws, geo::Ragged{geo_dev, vec ? 1 : 0}, ntiles < want ? ntiles : want, vec, thresholds, K,
+                        counts, st);
 }

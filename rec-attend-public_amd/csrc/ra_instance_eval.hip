@@ -33,9 +33,12 @@
 //           its K numbers before it writes any, and no other thread touches them).
 // Integer atomics only: the counts are the same bits on every run.  Hf * Wf <= 2^24 keeps every count exact in the float32
 // that ra_eval_metrics_f32 takes.
+// Mixed full sizes in one batch (ra_instance_eval_counts_ragged_f32): count_kernel is a template over the geometry source of
+// ra_ragged.h — gt_ids and fg flat, image b at its table entry, read once per workgroup — and the same body runs either form.
 #include <cstdint>
 
 #include "ra_common.h"
+#include "ra_ragged.h"
 #include "ra_resample.h"
 
 namespace ra {
@@ -130,10 +133,12 @@ __device__ __forceinline__ void add4(int *base, int (&key)[4]) {
 }
 
 // vec: W % 4 == 0 and gt_ids 16-byte, fg 4-byte aligned — a lane's 4 ids are one 16-byte load, its 4 fg bytes one 32-bit load
-template <bool MORPH>
+// GEO: geo::Uniform (gt_ids and fg are [B,H,W]) or geo::Ragged (both flat, image b at its table entry: its own H, W in the
+// resize, in reflect101, in the in-image test and in the tile walk; a workgroup beyond its image's tiles adds nothing).
+template <bool MORPH, class GEO>
 __global__ __launch_bounds__(256) void count_kernel(const float *yc, const int *gt_ids, const int *inst_id,
-                                                     const unsigned char *fg, int T, int Hs, int Ws, int H, int W,
-                                                     const Thresholds thr, int K, int vec, int *inter, int *area_b) {
+                                                     const unsigned char *fg, int T, int Hs, int Ws, const GEO src,
+                                                     const Thresholds thr, int K, int *inter, int *area_b) {
   using G = Geo<MORPH>;
   __shared__ __attribute__((aligned(16))) float rs[G::kRH * G::kRW];
   __shared__ __attribute__((aligned(16))) float fl[MORPH ? G::kFH * G::kFW : 4];
@@ -147,8 +152,10 @@ __global__ __launch_bounds__(256) void count_kernel(const float *yc, const int *
   if (tid < kMaxT) sid[tid] = tid < T ? inst_id[(size_t)b * T + tid] : -1;
   if (tid < kMaxK) sthr[tid] = thr.t[tid];
   const float gs = resample::bilateral_gain(10.f), gc = resample::bilateral_gain(10.f);  // postprocess.py:105
-  const int *gp = gt_ids + (size_t)b * H * W;
-  const unsigned char *fp = fg ? fg + (size_t)b * H * W : nullptr;
+  const geo::Image im = src.at(b);
+  const int H = im.h, W = im.w, vec = im.vec;
+  const int *gp = gt_ids + im.off;
+  const unsigned char *fp = fg ? fg + im.off : nullptr;
   const int ntx = tiles_x(W), ntiles = tiles(H, W);
 
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -272,13 +279,61 @@ __global__ __launch_bounds__(256) void finish_kernel(int *inter, const Order ord
     }
 }
 
-template <bool MORPH>
+
+template <bool MORPH, class GEO>
 void launch_count(dim3 grid, size_t lds, hipStream_t st, const float *yc, const int *gt_ids, const int *inst_id,
-                  const unsigned char *fg, int T, int Hs, int Ws, int H, int W, const Thresholds &thr, int K, int vec, int *inter,
+                  const unsigned char *fg, int T, int Hs, int Ws, const GEO &src, const Thresholds &thr, int K, int *inter,
                   int *area_b) {
-  static const MaxDynamicLds raise{count_kernel<MORPH>, hist_ints(kMaxK, kMaxT) * sizeof(int)};
-  hipLaunchKernelGGL((count_kernel<MORPH>), grid, dim3(256), lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, H, W, thr, K, vec,
-                     inter, area_b);
+  static const MaxDynamicLds raise{count_kernel<MORPH, GEO>, hist_ints(kMaxK, kMaxT) * sizeof(int)};
+  hipLaunchKernelGGL((count_kernel<MORPH, GEO>), grid, dim3(256), lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K, inter,
+                     area_b);
+}
+
+// The checks both entry points share, and the thresholds sorted for the kernel.
+inline int prepare(const char *who, int B, int T, int Hs, int Ws, const float *thresholds, int K, Thresholds &thr, Order &order) {
+  if (K < 1 || K > kMaxK) return fail(RA_E_SHAPE, "%s: K=%d thresholds (1 .. %d)", who, K, kMaxK);
+  if (T < 1 || T > kMaxT) return fail(RA_E_SHAPE, "%s: T=%d (1 .. %d)", who, T, kMaxT);
+  float sorted[kMaxK];
+  for (int k = 0; k < K; ++k) {
+    if (!(thresholds[k] >= 0.f))
+      return fail(RA_E_SHAPE, "%s: threshold %d is %g (>= 0: below zero the planes that lost the arg-max pass apply_threshold)",
+                  who, k, (double)thresholds[k]);
+    int i = k;  // insertion sort, ascending
+    for (; i > 0 && sorted[i - 1] > thresholds[k]; --i) sorted[i] = sorted[i - 1];
+    sorted[i] = thresholds[k];
+  }
+  for (int k = 0; k < kMaxK; ++k) {
+    thr.t[k] = k < K ? sorted[k] : __builtin_inff();
+    order.pos[k] = 0;
+    if (k < K)
+      for (int i = 0; i < K; ++i) order.pos[k] += thresholds[i] < thresholds[k] ? 1 : 0;
+  }
+  return 0;
+}
+
+// clear -> count -> finish on one stream; grid_x workgroups per image.
+template <class GEO>
+int launch_all(const char *who, const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg, int B, int T,
+               int Hs, int Ws, const GEO &src, int gx, int morph, const Thresholds &thr, const Order &order, int K, int *inter,
+               int *area_b, hipStream_t st) {
+  char what[96];
+  const auto status = [&](const char *stage) {
+    snprintf(what, sizeof(what), "%s%s", who, stage);
+    return launch_status(what);
+  };
+  const int TT1 = T * (T + 1);
+  if (hipMemsetAsync(inter, 0, (size_t)B * K * TT1 * sizeof(int), st) != hipSuccess ||
+      hipMemsetAsync(area_b, 0, (size_t)B * T * sizeof(int), st) != hipSuccess)
+    return status(" (clear)");
+  const dim3 grid(gx, B);
+  const size_t lds = hist_ints(K, T) * sizeof(int);
+  if (morph)
+    launch_count<true>(grid, lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K, inter, area_b);
+  else
+    launch_count<false>(grid, lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K, inter, area_b);
+  if (int rc = status("")) return rc;
+  hipLaunchKernelGGL(finish_kernel, dim3(ceil_div(B * TT1, 256)), dim3(256), 0, st, inter, order, K, TT1, B * TT1);
+  return status(" (finish)");
 }
 
 }  // namespace inse
@@ -297,36 +352,33 @@ extern "C" int ra_instance_eval_counts_f32(const float *yc, const int *gt_ids, c
   if ((long long)Hf * Wf > inse::kMaxPixels || (long long)Hs * Ws >= (1ll << 31) || B > 65535)
     return fail(RA_E_SHAPE, "%s: %dx%d -> %dx%d, B=%d (Hf * Wf <= 2^24, so that every count is exact in float32; Hs * Ws < 2^31; "
                 "B <= 65535)", who, Hs, Ws, Hf, Wf, B);
-  float sorted[inse::kMaxK];
-  for (int k = 0; k < K; ++k) {
-    if (!(thresholds[k] >= 0.f))
-      return fail(RA_E_SHAPE, "%s: threshold %d is %g (>= 0: below zero the planes that lost the arg-max pass apply_threshold)",
-                  who, k, (double)thresholds[k]);
-    int i = k;  // insertion sort, ascending
-    for (; i > 0 && sorted[i - 1] > thresholds[k]; --i) sorted[i] = sorted[i - 1];
-    sorted[i] = thresholds[k];
-  }
   inse::Thresholds thr;
   inse::Order order;
-  for (int k = 0; k < inse::kMaxK; ++k) {
-    thr.t[k] = k < K ? sorted[k] : __builtin_inff();
-    order.pos[k] = 0;
-    if (k < K)
-      for (int i = 0; i < K; ++i) order.pos[k] += thresholds[i] < thresholds[k] ? 1 : 0;
-  }
-  hipStream_t st = as_stream(stream);
-  const int TT1 = T * (T + 1);
-  if (hipMemsetAsync(inter, 0, (size_t)B * K * TT1 * sizeof(int), st) != hipSuccess ||
-      hipMemsetAsync(area_b, 0, (size_t)B * T * sizeof(int), st) != hipSuccess)
-    return launch_status("ra_instance_eval_counts_f32 (clear)");
+  if (int rc = inse::prepare(who, B, T, Hs, Ws, thresholds, K, thr, order)) return rc;
   const int vec = Wf % 4 == 0 && (reinterpret_cast<uintptr_t>(gt_ids) & 15) == 0 && (!fg || (reinterpret_cast<uintptr_t>(fg) & 3) == 0);
-  const dim3 grid(inse::grid_x(B, Hf, Wf), B);
-  const size_t lds = inse::hist_ints(K, T) * sizeof(int);
-  if (morph)
-    inse::launch_count<true>(grid, lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, Hf, Wf, thr, K, vec, inter, area_b);
-  else
-    inse::launch_count<false>(grid, lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, Hf, Wf, thr, K, vec, inter, area_b);
-  if (int rc = launch_status("ra_instance_eval_counts_f32")) return rc;
-  hipLaunchKernelGGL(inse::finish_kernel, dim3(ceil_div(B * TT1, 256)), dim3(256), 0, st, inter, order, K, TT1, B * TT1);
-  return launch_status("ra_instance_eval_counts_f32 (finish)");
+  return inse::launch_all(who, yc, gt_ids, inst_id, fg, B, T, Hs, Ws, geo::Uniform{Hf, Wf, vec}, inse::grid_x(B, Hf, Wf), morph, thr,
+                          order, K, inter, area_b, as_stream(stream));
+}
+
+extern "C" int ra_instance_eval_counts_ragged_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg,
+                                                  size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev, int B, int T,
+                                                  int Hs, int Ws, int morph, const float *thresholds, int K, int *inter,
+                                                  int *area_b, void *stream) {
+  const char *who = "ra_instance_eval_counts_ragged_f32";
+  if (!yc || !gt_ids || !inst_id || !geo || !geo_dev || !thresholds || !inter || !area_b || B <= 0 || Hs <= 0 || Ws <= 0)
+    return fail(RA_E_INVALID, "%s: bad argument", who);
+  if ((long long)Hs * Ws >= (1ll << 31) || B > 65535)
+    return fail(RA_E_SHAPE, "%s: %dx%d, B=%d (Hs * Ws < 2^31; B <= 65535)", who, Hs, Ws, B);
+  inse::Thresholds thr;
+  inse::Order order;
+  if (int rc = inse::prepare(who, B, T, Hs, Ws, thresholds, K, thr, order)) return rc;
+  if (int rc = geo::check(who, geo, B, total, inse::kMaxPixels, "h * w <= 2^24, so that every count is exact in float32")) return rc;
+  int ntiles = 0;  // of the largest image: the grid; a workgroup's loop bound is its own image's count
+  for (int b = 0; b < B; ++b) ntiles = inse::tiles(geo[b].h, geo[b].w) > ntiles ? inse::tiles(geo[b].h, geo[b].w) : ntiles;
+  const int want = inse::kWgs / B > 0 ? inse::kWgs / B : 1;
+  hipStream_t st = as_stream(stream);
+  if (int rc = geo::upload(who, geo, geo_dev, B, st)) return rc;
+  const int vec = (reinterpret_cast<uintptr_t>(gt_ids) & 15) == 0 && (!fg || (reinterpret_cast<uintptr_t>(fg) & 3) == 0);
+  return inse::launch_all(who, yc, gt_ids, inst_id, fg, B, T, Hs, Ws, geo::Ragged{geo_dev, vec}, ntiles < want ? ntiles : want, morph,
+                          thr, order, K, inter, area_b, st);
 }

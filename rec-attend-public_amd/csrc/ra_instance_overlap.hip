@@ -7,6 +7,8 @@
 //               workgroups' tables in a table of its own, ranks the keys and writes the sorted catalogue.  No global
 //               atomics and no table indexed by an id: an id outside [0, 65535] or beyond the cap goes to a reject counter
 //               and raises the image's status word.
+//               cat_partial is a template over the geometry source of ra_ragged.h: a batch of mixed full sizes in one flat
+//               buffer takes the same two launches (ra_gt_instance_catalog_ragged_i32).
 //   overlap     inter[b,t,g] = count_nonzero(gt == id_g & y[b,t] != 0) (:333) and pred_pixels[b,t] = count_nonzero(y[b,t]
 //               != 0) (:306-307) — a joint histogram.  A workgroup walks tiles of 1024 pixels of one image: 16 bytes of
 //               gt_ids per lane, the slot of each id by a binary search in the catalogue (LDS), then y plane by plane, 16
@@ -24,6 +26,7 @@
 
 #include "ra_common.h"
 #include "ra_gt_ids.h"
+#include "ra_ragged.h"
 
 namespace ra {
 namespace iov {
@@ -78,13 +81,19 @@ __device__ __forceinline__ void hash_add(int *keys, int *cnts, int *rej, int *fl
 // Workgroup (x, b) walks the tiles x, x + gridDim.x, ... of image b.  Per tile a wave peels the distinct ids of its 256 pixels
 // (one iteration each: the id of the first lane that still has one, four ballots, four population counts) and carries the
 // last id and its count in scalar registers from tile to tile, so a run of equal ids costs one table update when it ends.
-__global__ __launch_bounds__(256) void cat_partial_kernel(const int *gt, unsigned HW, int ntiles, int vec_ok, int *part) {
+// GEO: geo::Uniform (gt [B,h,w]) or geo::Ragged (gt flat, image b at its table entry).  A workgroup whose image has fewer tiles
+// than the grid is wide walks none and leaves an empty record.
+template <class GEO>
+__global__ __launch_bounds__(256) void cat_partial_kernel(const int *gt, const GEO src, int *part) {
   __shared__ int keys[kHash], cnts[kHash], misc[4];  // misc: n, flags, reject
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
   for (int i = tid; i < kHash; i += 256) keys[i] = -1, cnts[i] = 0;
   if (tid < 4) misc[tid] = 0;
   __syncthreads();
-  const int *g = gt + (size_t)b * HW;
+  const geo::Image im = src.at(b);
+  const unsigned HW = (unsigned)im.h * (unsigned)im.w;  // < 2^31
+  const int ntiles = (int)((HW + kTile - 1) / kTile), vec_ok = im.vec;
+  const int *g = gt + im.off;
   int run_key = -1, run_cnt = 0;  // wave-uniform
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const unsigned base = (unsigned)tile * kTile + 4 * tid;  // < 2^31 + kTile
@@ -317,10 +326,35 @@ extern "C" int ra_gt_instance_catalog_i32(const int *gt_ids, int B, int H, int W
   const int nwg = iov::cat_wgs(B, HW);
   const int vec_ok = HW % 4 == 0 && (reinterpret_cast<uintptr_t>(gt_ids) & 15) == 0;
   hipStream_t st = as_stream(stream);
-  hipLaunchKernelGGL(iov::cat_partial_kernel, dim3(nwg, B), dim3(256), 0, st, gt_ids, (unsigned)HW, iov::ntiles_of(HW), vec_ok, ws);
+  hipLaunchKernelGGL(iov::cat_partial_kernel<geo::Uniform>, dim3(nwg, B), dim3(256), 0, st, gt_ids, geo::Uniform{H, W, vec_ok}, ws);
   if (int rc = launch_status("ra_gt_instance_catalog_i32")) return rc;
   hipLaunchKernelGGL(iov::cat_merge_kernel, dim3(B), dim3(256), 0, st, ws, nwg, ids, pixels, count, status);
   return launch_status("ra_gt_instance_catalog_i32 (merge)");
+}
+
+extern "C" size_t ra_gt_instance_catalog_ragged_workspace_ints(const ra_image_geo *geo, int B) {
+  const long long px = geo::max_pixels(geo, B);
+  if (B <= 0 || px <= 0 || px >= (1ll << 31)) return 0;
+  return (size_t)B * iov::cat_wgs(B, px) * iov::kPartStride;
+}
+
+extern "C" int ra_gt_instance_catalog_ragged_i32(const int *gt_ids, size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev,
+                                                 int B, int *ws, size_t ws_ints, int *ids, int *pixels, int *count, int *status,
+                                                 void *stream) {
+  const char *who = "ra_gt_instance_catalog_ragged_i32";
+  if (!gt_ids || !geo || !geo_dev || !ws || !ids || !pixels || !count || !status || B <= 0)
+    return fail(RA_E_INVALID, "%s: bad argument", who);
+  if (B > 65535) return fail(RA_E_SHAPE, "%s: B=%d (B <= 65535)", who, B);
+  if (int rc = geo::check(who, geo, B, total, (1ll << 31) - 1, "h * w < 2^31")) return rc;
+  if (ws_ints < ra_gt_instance_catalog_ragged_workspace_ints(geo, B)) return fail(RA_E_WORKSPACE, "%s: workspace", who);
+  const int nwg = iov::cat_wgs(B, geo::max_pixels(geo, B));  // the largest image's tiles; an image's own count bounds its walk
+  const int vec = (reinterpret_cast<uintptr_t>(gt_ids) & 15) == 0;
+  hipStream_t st = as_stream(stream);
+  if (int rc = geo::upload(who, geo, geo_dev, B, st)) return rc;
+  hipLaunchKernelGGL(iov::cat_partial_kernel<geo::Ragged>, dim3(nwg, B), dim3(256), 0, st, gt_ids, geo::Ragged{geo_dev, vec}, ws);
+  if (int rc = launch_status(who)) return rc;
+  hipLaunchKernelGGL(iov::cat_merge_kernel, dim3(B), dim3(256), 0, st, ws, nwg, ids, pixels, count, status);
+  return launch_status("ra_gt_instance_catalog_ragged_i32 (merge)");
 }
 
 extern "C" size_t ra_instance_overlap_workspace_ints(int B, int T, int H, int W) {

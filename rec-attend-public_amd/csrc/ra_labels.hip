@@ -23,11 +23,14 @@
 //             the set of accepted catalogue entries.
 //
 // Integer counters and a fixed order of addition: exact, and the same bits on every run.  Nothing is indexed by an id.
+// Mixed full sizes in one batch (ra_labels_assemble_ragged_i32): moments, fill and fg_full are templates over the geometry source of
+// ra_ragged.h; the network-size outputs stay dense, the sampling scales become each image's own, fg_full is written flat.
 #include <cmath>
 #include <cstdint>
 
 #include "ra_common.h"
 #include "ra_gt_ids.h"
+#include "ra_ragged.h"
 
 namespace ra {
 namespace lab {
@@ -64,10 +67,29 @@ __device__ __forceinline__ int nn_src(int d, double scale, int n_src) {
 
 __device__ __forceinline__ int clamp_count(int n) { return n < 0 ? 0 : (n > kMaxGt ? kMaxGt : n); }
 
+// The sampling of image b: where its ids start, its full size and the scales of nn_src.  GEO = geo::Uniform: gt is [B,Hf,Wf] and
+// the scales are the launch's (formed on the host); geo::Ragged: gt is flat, the image's table entry gives offset and size, and
+// the scales are the same double expressions 1.0 / ((double)H / Hf), evaluated once per workgroup (IEEE division: the same bits).
+struct Sampling {
+  const int *g;
+  int Hf, Wf;
+  double sy, sx;
+};
+template <class GEO>
+__device__ __forceinline__ Sampling sampling_of(const int *gt, const GEO &src, int b, int H, int W, double sy, double sx) {
+  const geo::Image im = src.at(b);
+  if (GEO::kRagged) {
+    sy = 1.0 / ((double)H / (double)im.h);
+    sx = 1.0 / ((double)W / (double)im.w);
+  }
+  return Sampling{gt + im.off, im.h, im.w, sy, sx};
+}
+
 // Workgroup (x, b) walks the tiles (256 network pixels) x, x + gridDim.x, ... of image b.
 // part[b][x][q][g < n], q = area, sum of rows, sum of columns.
-__global__ __launch_bounds__(256) void moments_kernel(const int *gt, const int *ids, const int *count, int Hf, int Wf, int HW,
-                                                       int W, double sy, double sx, int ntiles, u64 *part) {
+template <class GEO>
+__global__ __launch_bounds__(256) void moments_kernel(const int *gt, const int *ids, const int *count, const GEO src, int H, int HW,
+                                                       int W, double sy_, double sx_, int ntiles, u64 *part) {
   __shared__ int cat[kMaxGt];
   __shared__ u64 m[3][kMaxGt];
   const int b = blockIdx.y, tid = threadIdx.x, lane = tid & 63;
@@ -75,7 +97,10 @@ __global__ __launch_bounds__(256) void moments_kernel(const int *gt, const int *
   cat[tid] = tid < n ? ids[(size_t)b * kMaxGt + tid] : 0x7fffffff;
   m[0][tid] = m[1][tid] = m[2][tid] = 0;
   __syncthreads();
-  const int *g = gt + (size_t)b * Hf * Wf;
+  const Sampling sm = sampling_of(gt, src, b, H, W, sy_, sx_);
+  const int *g = sm.g;
+  const int Hf = sm.Hf, Wf = sm.Wf;
+  const double sy = sm.sy, sx = sm.sx;
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
     const unsigned p = (unsigned)tile * 256 + tid;  // < 2^31 + 256
     int s = -1, r = 0, c = 0;
@@ -174,10 +199,10 @@ __device__ __forceinline__ int orientation_class(int r, int c, double cy, double
 
 // Thread i of workgroup (x, b) owns the network pixels 4 i .. 4 i + 3 of the workgroup's kFillPix.  VEC: H * W % 4 == 0 and
 // every output 16-byte aligned (d_cls: 4-byte), so the 4 pixels exist together and every store below is one aligned vector.
-template <bool VEC>
+template <bool VEC, class GEO>
 __global__ __launch_bounds__(256) void fill_kernel(const int *gt, const int *ids, const int *count, const int *tab,
-                                                    const double *cen, int Hf, int Wf, int HW, int W, int T, int nc,
-                                                    double sy, double sx, float *y_gt, unsigned char *d_cls, float *d_gt,
+                                                    const double *cen, const GEO src, int H, int HW, int W, int T, int nc,
+                                                    double sy_, double sx_, float *y_gt, unsigned char *d_cls, float *d_gt,
                                                     float *c_gt) {
   __shared__ int cat[kMaxGt], info[kMaxGt];
   __shared__ double ceny[kMaxGt], cenx[kMaxGt];
@@ -190,7 +215,10 @@ __global__ __launch_bounds__(256) void fill_kernel(const int *gt, const int *ids
   __syncthreads();
   const long long base = (long long)blockIdx.x * kFillPix + 4 * tid;  // <= HW + kFillPix
   if (base >= HW) return;
-  const int *g = gt + (size_t)b * Hf * Wf;
+  const Sampling sm = sampling_of(gt, src, b, H, W, sy_, sx_);
+  const int *g = sm.g;
+  const int Hf = sm.Hf, Wf = sm.Wf;
+  const double sy = sm.sy, sx = sm.sx;
   int rank[4], cls[4], dc[4];
   bool ok[4];
   int prev_id = 0, prev_s = -1;
@@ -285,14 +313,19 @@ __global__ __launch_bounds__(256) void fill_kernel(const int *gt, const int *ids
 }
 
 // Thread i of workgroup (x, b) owns the full-size pixels 4 i .. 4 i + 3 of the workgroup's kFillPix.
-__global__ __launch_bounds__(256) void fg_full_kernel(const int *gt, unsigned HWf, int dataset, int vec_ok, unsigned char *fg) {
-  const int b = blockIdx.y;
+// fg has the layout of gt: [B,Hf,Wf], or flat at the same offsets.  The grid covers the largest image; a workgroup beyond
+// its own image's pixels leaves.
+template <class GEO>
+__global__ __launch_bounds__(256) void fg_full_kernel(const int *gt, const GEO src, int dataset, unsigned char *fg) {
+  const geo::Image im = src.at(blockIdx.y);
+  const unsigned HWf = (unsigned)im.h * (unsigned)im.w;  // < 2^31
+  const int vec_ok = im.vec;
   const unsigned long long base = (unsigned long long)blockIdx.x * kFillPix + 4 * threadIdx.x;
   if (base >= HWf) return;
-  const int *g = gt + (size_t)b * HWf + base;
-  unsigned char *o = fg + (size_t)b * HWf + base;
+  const int *g = gt + im.off + base;
+  unsigned char *o = fg + im.off + base;
   int cls;
-  if (vec_ok) {  // HWf % 4 == 0, gt 16-byte and fg 4-byte aligned
+  if (vec_ok) {  // the 4 pixels exist together (uniform: HWf % 4 == 0; ragged: w % 4 == 0), gt 16-byte and fg 4-byte aligned
     const i32x4 v = __builtin_nontemporal_load(reinterpret_cast<const i32x4 *>(g));
     unsigned w = 0;
 #pragma unroll
@@ -315,6 +348,53 @@ inline size_t part_bytes(int B, int H, int W) { return (size_t)B * mom_wgs(B, (l
 inline size_t cen_bytes(int B) { return (size_t)B * 2 * kMaxGt * sizeof(double); }
 inline size_t tab_bytes(int B) { return (size_t)B * kMaxGt * sizeof(int); }
 
+// The stage's launches behind the argument checks, for either geometry source.  src_fg: the source with fg_full's vector
+// rule (its own alignment needs); max_HWf: the largest image's pixels (fg_full's grid); sy, sx: the uniform form's scales.
+template <class GEO>
+int launch_stage(const char *who, const int *gt_ids, const GEO &src, const GEO &src_fg, long long max_HWf, const int *ids,
+                 const int *count, int B, int H, int W, int T, int dataset, double sy, double sx, void *ws, int *num_obj,
+                 float *s_gt, int *inst_id, int *area, int *sem_cls, float *y_gt, unsigned char *d_cls, float *d_gt, float *c_gt,
+                 unsigned char *fg_gt_full, hipStream_t st) {
+  char what[96];
+  const auto status = [&](const char *stage) {
+    snprintf(what, sizeof(what), "%s (%s)", who, stage);
+    return launch_status(what);
+  };
+  const int HW = H * W;
+  const bool want_fill = y_gt || d_cls || d_gt || c_gt;
+  if (want_fill || num_obj || s_gt || inst_id || area || sem_cls) {
+    u64 *part = static_cast<u64 *>(ws);
+    double *cen = reinterpret_cast<double *>(static_cast<char *>(ws) + part_bytes(B, H, W));
+    int *tab = reinterpret_cast<int *>(reinterpret_cast<char *>(cen) + cen_bytes(B));
+    const int nwg = mom_wgs(B, HW);
+    hipLaunchKernelGGL(moments_kernel<GEO>, dim3(nwg, B), dim3(256), 0, st, gt_ids, ids, count, src, H, HW, W, sy, sx,
+                       (int)(((long long)HW + 255) / 256), part);
+    if (int rc = status("moments")) return rc;
+    hipLaunchKernelGGL(rank_kernel, dim3(B), dim3(256), 0, st, part, nwg, ids, count, T, dataset, num_obj, s_gt, inst_id, area,
+                       sem_cls, tab, cen);
+    if (int rc = status("rank")) return rc;
+    if (want_fill) {
+      const int nc = dataset == RA_LABELS_CITYSCAPES ? 1 + gtid::kCsClasses : 1;
+      const uintptr_t al = reinterpret_cast<uintptr_t>(y_gt) | reinterpret_cast<uintptr_t>(d_gt) | reinterpret_cast<uintptr_t>(c_gt);
+      const bool vec = HW % 4 == 0 && (al & 15) == 0 && (reinterpret_cast<uintptr_t>(d_cls) & 3) == 0;
+      const dim3 grid((unsigned)(((long long)HW + kFillPix - 1) / kFillPix), B);
+      if (vec)
+        hipLaunchKernelGGL((fill_kernel<true, GEO>), grid, dim3(256), 0, st, gt_ids, ids, count, tab, cen, src, H, HW, W, T, nc, sy,
+                           sx, y_gt, d_cls, d_gt, c_gt);
+      else
+        hipLaunchKernelGGL((fill_kernel<false, GEO>), grid, dim3(256), 0, st, gt_ids, ids, count, tab, cen, src, H, HW, W, T, nc,
+                           sy, sx, y_gt, d_cls, d_gt, c_gt);
+      if (int rc = status("fill")) return rc;
+    }
+  }
+  if (fg_gt_full) {
+    hipLaunchKernelGGL(fg_full_kernel<GEO>, dim3((unsigned)((max_HWf + kFillPix - 1) / kFillPix), B), dim3(256), 0, st, gt_ids,
+                       src_fg, dataset, fg_gt_full);
+    if (int rc = status("fg_full")) return rc;
+  }
+  return 0;
+}
+
 }  // namespace lab
 }  // namespace ra
 
@@ -336,41 +416,35 @@ extern "C" int ra_labels_assemble_i32(const int *gt_ids, const int *ids, const i
     return fail(RA_E_SHAPE, "ra_labels_assemble_i32: T=%d ids %dx%d -> %dx%d B=%d dataset=%d (1 <= T <= %d, 1 <= H <= Hf, 1 <= W <= Wf, "
                 "Hf * Wf < 2^31, B <= 65535)", T, Hf, Wf, H, W, B, dataset, lab::kMaxT);
   if (ws_bytes < ra_labels_workspace_bytes(B, H, W)) return fail(RA_E_WORKSPACE, "ra_labels_assemble_i32: workspace");
-  const int HW = H * W;
   const long long HWf = (long long)Hf * Wf;
   const double sy = 1.0 / ((double)H / (double)Hf), sx = 1.0 / ((double)W / (double)Wf);
+  const int vec_fg = HWf % 4 == 0 && (reinterpret_cast<uintptr_t>(gt_ids) & 15) == 0 && (reinterpret_cast<uintptr_t>(fg_gt_full) & 3) == 0;
+  return lab::launch_stage("ra_labels_assemble_i32", gt_ids, geo::Uniform{Hf, Wf, 0}, geo::Uniform{Hf, Wf, vec_fg}, HWf, ids, count, B,
+                           H, W, T, dataset, sy, sx, ws, num_obj, s_gt, inst_id, area, sem_cls, y_gt, d_cls, d_gt, c_gt, fg_gt_full,
+                           as_stream(stream));
+}
+
+extern "C" int ra_labels_assemble_ragged_i32(const int *gt_ids, size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev,
+                                             const int *ids, const int *count, int B, int H, int W, int T, int dataset, void *ws,
+                                             size_t ws_bytes, int *num_obj, float *s_gt, int *inst_id, int *area, int *sem_cls,
+                                             float *y_gt, unsigned char *d_cls, float *d_gt, float *c_gt,
+                                             unsigned char *fg_gt_full, void *stream) {
+  const char *who = "ra_labels_assemble_ragged_i32";
+  if (!gt_ids || !geo || !geo_dev || !ids || !count || !ws || B <= 0 || (reinterpret_cast<uintptr_t>(ws) & 7))
+    return fail(RA_E_INVALID, "%s: bad argument", who);
+  if (T < 1 || T > lab::kMaxT || !lab::plane_ok(H, W) || B > 65535 || (dataset != RA_LABELS_PLAIN && dataset != RA_LABELS_CITYSCAPES))
+    return fail(RA_E_SHAPE, "%s: T=%d -> %dx%d B=%d dataset=%d (1 <= T <= %d, H, W >= 1, H * W < 2^31, B <= 65535)", who, T, H, W, B,
+                dataset, lab::kMaxT);
+  if (int rc = geo::check(who, geo, B, total, (1ll << 31) - 1, "h * w < 2^31")) return rc;
+  for (int b = 0; b < B; ++b)
+    if (H > geo[b].h || W > geo[b].w)
+      return fail(RA_E_SHAPE, "%s: image %d is %d x %d, below the network size %d x %d (1 <= H <= h, 1 <= W <= w for every image)",
+                  who, b, geo[b].h, geo[b].w, H, W);
+  if (ws_bytes < ra_labels_workspace_bytes(B, H, W)) return fail(RA_E_WORKSPACE, "%s: workspace", who);
   hipStream_t st = as_stream(stream);
-  const bool want_fill = y_gt || d_cls || d_gt || c_gt;
-  if (want_fill || num_obj || s_gt || inst_id || area || sem_cls) {
-    lab::u64 *part = static_cast<lab::u64 *>(ws);
-    double *cen = reinterpret_cast<double *>(static_cast<char *>(ws) + lab::part_bytes(B, H, W));
-    int *tab = reinterpret_cast<int *>(reinterpret_cast<char *>(cen) + lab::cen_bytes(B));
-    const int nwg = lab::mom_wgs(B, HW);
-    hipLaunchKernelGGL(lab::moments_kernel, dim3(nwg, B), dim3(256), 0, st, gt_ids, ids, count, Hf, Wf, HW, W, sy, sx,
-                       (int)(((long long)HW + 255) / 256), part);
-    if (int rc = launch_status("ra_labels_assemble_i32 (moments)")) return rc;
-    hipLaunchKernelGGL(lab::rank_kernel, dim3(B), dim3(256), 0, st, part, nwg, ids, count, T, dataset, num_obj, s_gt, inst_id,
-                       area, sem_cls, tab, cen);
-    if (int rc = launch_status("ra_labels_assemble_i32 (rank)")) return rc;
-    if (want_fill) {
-      const int nc = dataset == RA_LABELS_CITYSCAPES ? 1 + gtid::kCsClasses : 1;
-      const uintptr_t al = reinterpret_cast<uintptr_t>(y_gt) | reinterpret_cast<uintptr_t>(d_gt) | reinterpret_cast<uintptr_t>(c_gt);
-      const bool vec = HW % 4 == 0 && (al & 15) == 0 && (reinterpret_cast<uintptr_t>(d_cls) & 3) == 0;
-      const dim3 grid((unsigned)(((long long)HW + lab::kFillPix - 1) / lab::kFillPix), B);
-      if (vec)
-        hipLaunchKernelGGL(lab::fill_kernel<true>, grid, dim3(256), 0, st, gt_ids, ids, count, tab, cen, Hf, Wf, HW, W, T, nc, sy,
-                           sx, y_gt, d_cls, d_gt, c_gt);
-      else
-        hipLaunchKernelGGL(lab::fill_kernel<false>, grid, dim3(256), 0, st, gt_ids, ids, count, tab, cen, Hf, Wf, HW, W, T, nc,
-                           sy, sx, y_gt, d_cls, d_gt, c_gt);
-      if (int rc = launch_status("ra_labels_assemble_i32 (fill)")) return rc;
-    }
-  }
-  if (fg_gt_full) {
-    const int vec_ok = HWf % 4 == 0 && (reinterpret_cast<uintptr_t>(gt_ids) & 15) == 0 && (reinterpret_cast<uintptr_t>(fg_gt_full) & 3) == 0;
-    hipLaunchKernelGGL(lab::fg_full_kernel, dim3((unsigned)((HWf + lab::kFillPix - 1) / lab::kFillPix), B), dim3(256), 0, st, gt_ids,
-                       (unsigned)HWf, dataset, vec_ok, fg_gt_full);
-    if (int rc = launch_status("ra_labels_assemble_i32 (fg_full)")) return rc;
-  }
-  return 0;
+  if (int rc = geo::upload(who, geo, geo_dev, B, st)) return rc;
+  const int vec_fg = (reinterpret_cast<uintptr_t>(gt_ids) & 15) == 0 && (reinterpret_cast<uintptr_t>(fg_gt_full) & 3) == 0;
+  return lab::launch_stage(who, gt_ids, geo::Ragged{geo_dev, 0}, geo::Ragged{geo_dev, vec_fg}, geo::max_pixels(geo, B), ids, count,
+                           B, H, W, T, dataset, 0.0, 0.0, ws, num_obj, s_gt, inst_id, area, sem_cls, y_gt, d_cls, d_gt, c_gt,
+                           fg_gt_full, st);
 }

@@ -11,7 +11,13 @@ The model is restored from <results>/<model_id>/{model_opt.yaml, weights.npz} ex
                           instances overlap, counted as the reference's a * b and b.sum() count them),
 and optionally names (N file names, default 'image_<i>') and y_gt [N,h,w] or [N,h,w,nsc] (+ d_gt [N,h,w,8] for a net with
 orientation): then fg_model.Model.statistics runs on every batch and the means over the batches are reported, as the
-Evaluator averages them.  All images of one archive share one full size: a stated limit, as in cityscapes_eval.py.
+Evaluator averages them.  The images of such an archive share one full size.  Mixed full sizes (KITTI): in place of fg_gt_full
+the archive holds fg_gt_full_flat uint8 [P], pixel_offset int64 [N + 1] and orig_size int32 [N,2] (what setup_labels.py
+--mixed_sizes --target fg_model writes: image i is the orig_size[i] rows from element pixel_offset[i] on).  The sweep of a batch
+is then ONE ops.fg_sweep_counts_ragged call, `pixels` is summed per image, and the thresholded, soft and ground-truth PNG files
+are written image by image at each image's own size through the same pp.upsample — that path writes files and is bound by the
+host; run_kitti.sh feeds these PNG files to the next stage as the foreground.  --render_orientation and the pixel-level scores
+(gt_instance_ids / gt_label_ids in --input) are refused by name on a mixed archive: their kernels take one size per call.
 
 Per batch, on the device (write_log, :134-173): y_out of the net; the foreground plane is y_out[..., 0] for one semantic class
 and 1 - y_out[..., 0] for several (channel 0 is the background: the convention of ops.sem_foreground — the reference's runner
@@ -114,9 +120,12 @@ def main(argv=None):
     raise RecAttendError('--render_orientation: fg_model %s was built without add_orientation and has no d_out to render' % args.model_id)
   ori_render = None
   data = np.load(args.input, allow_pickle=False)
-  for k in ('x', 'fg_gt_full'):
+  mixed = 'fg_gt_full_flat' in data and 'fg_gt_full' not in data
+  for k in ('x',) + (('fg_gt_full_flat', 'pixel_offset', 'orig_size') if mixed else ('fg_gt_full',)):
     if k not in data:
       raise RecAttendError('--input lacks %s' % k)
+  if mixed:
+    return _main_mixed(args, opt, data, model, out_dir, thresholds)
   x_all, gt_all = data['x'], data['fg_gt_full']
   N = x_all.shape[0]
   if gt_all.ndim != 3 or gt_all.shape[0] != N or gt_all.dtype != np.uint8:
@@ -201,6 +210,79 @@ def main(argv=None):
   with open(os.path.join(out_dir, 'metrics.yaml'), 'w') as f:
     yaml.safe_dump(summary, f)
   print('%d images -> %s' % (N, out_dir))
+  return summary
+
+
+def _main_mixed(args, opt, data, model, out_dir, thresholds):
+  """main() on an archive of mixed full sizes: fg_gt_full_flat, pixel_offset, orig_size (the module's docstring)."""
+  import torch
+  import analysis
+  import ra_ops as ops
+  import setup_labels
+  from utils import postprocess as pp
+  if args.render_orientation:
+    raise RecAttendError('--render_orientation cannot be used with an --input of mixed full sizes (%s holds fg_gt_full_flat): the '
+                         'orientation image is rendered for one full size per call' % args.input)
+  for k in ('gt_instance_ids', 'gt_label_ids'):
+    if k in data:
+      raise RecAttendError('the pixel-level class scores (%s in --input) cannot be computed on an --input of mixed full sizes (%s '
+                           'holds fg_gt_full_flat): the confusion kernels take one full size per call' % (k, args.input))
+  x_all, gt_all, off, size = data['x'], data['fg_gt_full_flat'], data['pixel_offset'], data['orig_size']
+  N = x_all.shape[0]
+  if gt_all.dtype != np.uint8:
+    raise RecAttendError('--input: fg_gt_full_flat is %s, expected uint8 [P]' % gt_all.dtype)
+  setup_labels.check_flat('--input %s' % args.input, gt_all, off, size, N)
+  names = [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(N)]
+  if len(names) != N:
+    raise RecAttendError('--input: %d names for %d images' % (len(names), N))
+  have_stats = 'y_gt' in data
+  y_gt_all = data['y_gt'] if have_stats else None
+  d_gt_all = data['d_gt'] if have_stats and 'd_gt' in data else None
+  fg_an = [analysis.ForegroundIOUAnalyzer('fg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]  # :62-69
+  bg_an = [analysis.BackgroundIOUAnalyzer('bg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]
+  totals = [{'count_a': 0, 'sum_ab': 0, 'sum_b': 0, 'pixels': 0} for _ in thresholds]
+  stats = []
+  os.makedirs(out_dir, exist_ok=True)
+  dev = torch.device('cuda', torch.cuda.current_device())
+  up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
+  to8 = lambda t: (t * 255.0).clamp(0, 255).to(torch.uint8).cpu().numpy()
+  bs = max(1, opt['batch_size'])
+  for b0 in range(0, N, bs):
+    b1 = min(N, b0 + bs)
+    p0, p1 = int(off[b0]), int(off[b1])
+    geo = setup_labels.flat_geometry(off, size, b0, b1)
+    x = up(x_all[b0:b1])
+    gt = torch.as_tensor(np.ascontiguousarray(gt_all[p0:p1])).to(dev)
+    soft = foreground_plane(model.run('y_out', {'x': x, 'phase_train': False}))
+    counts = ops.fg_sweep_counts_ragged(soft, gt, geo, thresholds)  # one launch chain for the batch, whatever its sizes
+    res = {'fg_counts': counts, 'indices': list(range(b0, b1))}
+    for k in range(len(thresholds)):
+      fg_an[k].stage(res)
+      bg_an[k].stage(res)
+      totals[k]['count_a'] += int(counts['count_a'][:, k].sum())
+      totals[k]['sum_ab'] += int(counts['sum_ab'][:, k].sum())
+      totals[k]['sum_b'] += int(counts['sum_b'].sum())
+      totals[k]['pixels'] += int(counts['pixels'].sum())
+    for i, (o, h, w) in enumerate(geo.tolist()):  # the rendering path only (:146, :166-173), image by image at its own size
+      full = pp.upsample(soft[i:i + 1].contiguous(), (h, w))
+      for t in thresholds:
+        _write_planes(os.path.join(out_dir, '{:02d}'.format(int(t * 100))), names[b0 + i:b0 + i + 1], to8((full > float(t)).to(torch.float32)))
+      if opt['render_soft']:
+        _write_planes(os.path.join(out_dir, 'soft'), names[b0 + i:b0 + i + 1], to8(full))
+      if opt['render_gt']:
+        _write_planes(os.path.join(out_dir, 'gt'), names[b0 + i:b0 + i + 1], to8(gt[o:o + h * w].view(1, h, w).to(torch.float32)))
+    if have_stats:
+      stats.append(model.statistics(x, up(y_gt_all[b0:b1]), None if d_gt_all is None else up(d_gt_all[b0:b1])))
+  summary = {}
+  for k, t in enumerate(thresholds):
+    summary['%.2f' % t] = dict(totals[k], fg_iou_all=float(fg_an[k].finalize()), bg_iou_all=float(bg_an[k].finalize()))
+  if have_stats:
+    summary['statistics'] = {n: float(np.mean([s[n] for s in stats])) for n in STAT_NAMES if n in stats[0]}
+    for n, v in summary['statistics'].items():
+      print('{:17s}{:7.4f}'.format(n, v))
+  with open(os.path.join(out_dir, 'metrics.yaml'), 'w') as f:
+    yaml.safe_dump(summary, f)
+  print('%d images of mixed sizes -> %s' % (N, out_dir))
   return summary
 
 

@@ -28,7 +28,11 @@ reads; --remove_tiny acts on the counted areas where a foreground is given, as i
 mask [N,Hf,Wf]; another value is an error naming the image.  metrics_rank<r>.yaml has the same format on both paths.  The
 thresholds must be >= 0 there.  --render and --render_gt_instances draw the thresholded masks, which this path never writes,
 and --fused_postprocess has nothing to skip on it: all three are refused by name.  An archive that holds y_gt takes the plane
-path, whatever else it holds.  Limit: one full size per archive (KITTI's mixed sizes stay out of scope).
+path, whatever else it holds.  Mixed full sizes (KITTI): an --input with gt_instance_ids_flat [P], pixel_offset [N + 1] and
+orig_size [N,2] (what setup_labels.py --mixed_sizes writes) and no y_gt takes the same id path through the ragged entry points
+(ops.assemble_labels_ragged, ops.instance_eval_counts_ragged): every batch is still ONE launch chain, each image resized,
+filtered and counted at its own size; an optional fg_flat uint8 [P] is the 0 / 1 foreground at the same offsets.  On such an
+archive --render, --render_gt_instances, --fused_postprocess and --cityscapes_output are refused by name.
 --cityscapes_output DIR (not a reference flag; needs --fg_model_id with a 9-class pre-stage) puts the reference's THIRD stage
 behind the loop: every decoded batch and the pre-stage's y_in go through cityscapes_eval.label_instances on the device — its
 chain, not the one above: upsample before apply_confidence, the semantic map's own foreground mask, conf carried across the
@@ -79,10 +83,18 @@ def build_parser():
   return p
 
 
+FLAT_KEYS = ('gt_instance_ids_flat', 'pixel_offset', 'orig_size')
+
+
+def _flat_path(keys):
+  """The labels of --input are instance-id images of mixed full sizes in the flat layout, and no y_gt."""
+  return all(k in keys for k in FLAT_KEYS) and 'y_gt' not in keys
+
+
 def _id_path(keys):
-  """The labels of --input are instance-id images: gt_instance_ids [N,Hf,Wf] and no y_gt (an archive with y_gt keeps the
-  plane path it always took)."""
-  return 'gt_instance_ids' in keys and 'y_gt' not in keys
+  """The labels of --input are instance-id images: gt_instance_ids [N,Hf,Wf], or the flat layout of mixed sizes, and no y_gt
+  (an archive with y_gt keeps the plane path it always took)."""
+  return ('gt_instance_ids' in keys or _flat_path(keys)) and 'y_gt' not in keys
 
 
 def main(argv=None):
@@ -95,7 +107,16 @@ def main(argv=None):
     raise RecAttendError('--cityscapes_output needs --fg_model_id: the instance classes are voted on the pre-stage\'s semantic map')
   if args.input:  # before anything is restored: what the id path cannot do is refused by name
     with np.load(args.input) as peek:
-      id_path = _id_path(peek.files)
+      id_path, flat_path = _id_path(peek.files), _flat_path(peek.files)
+    if flat_path:
+      for f, on in (('--render', args.render), ('--render_gt_instances', args.render_gt_instances),
+                    ('--fused_postprocess', args.fused_postprocess), ('--cityscapes_output', args.cityscapes_output)):
+        if on:
+          from ra_native import RecAttendError
+          raise RecAttendError(
+              '%s cannot be used with an --input of mixed full sizes (%s holds gt_instance_ids_flat): the images are counted at '
+              'their own sizes in one pass that writes no mask, and the render and Cityscapes stages take one size per call' % (
+                  f, args.input))
     refused = [f for f, on in (('--render', args.render), ('--render_gt_instances', args.render_gt_instances),
                                ('--fused_postprocess', args.fused_postprocess)) if on]
     if id_path and refused:
@@ -175,7 +196,23 @@ def _check_id_labels(args, data, model):
   """The id path's input, checked on the host before the first batch is decoded."""
   from ra_native import RecAttendError
   import ra_ops as ops
-  ids, n = data['gt_instance_ids'], data['x'].shape[0]
+  n = data['x'].shape[0]
+  if _flat_path(data):
+    import setup_labels
+    ids = data['gt_instance_ids_flat']
+    if not np.issubdtype(ids.dtype, np.integer):
+      raise RecAttendError('--input %s: gt_instance_ids_flat must hold integers, got %s' % (args.input, ids.dtype))
+    setup_labels.check_flat('--input %s' % args.input, ids, data['pixel_offset'], data['orig_size'], n)
+    ops.label_dataset_rule(args.dataset)
+    if 'fg_flat' in data:
+      fg, off, size, names = data['fg_flat'], data['pixel_offset'], data['orig_size'], _image_names(data)
+      if fg.shape != ids.shape:
+        raise RecAttendError('--input %s: fg_flat must be a 0 / 1 mask %s at the ids\' offsets, got %s' % (args.input, ids.shape, fg.shape))
+      for i in range(n):
+        if not np.isin(fg[off[i]:off[i] + int(size[i, 0]) * int(size[i, 1])], (0, 1)).all():
+          raise RecAttendError('--input %s: fg_flat of image %s holds values other than 0 and 1' % (args.input, names[i]))
+    return
+  ids = data['gt_instance_ids']
   if ids.ndim != 3 or ids.shape[0] != n or not np.issubdtype(ids.dtype, np.integer):
     raise RecAttendError('--input %s: gt_instance_ids must be integers [N,Hf,Wf] with N = %d images (one full size per archive), '
                          'got %s %s' % (args.input, n, ids.dtype, ids.shape))
@@ -194,21 +231,40 @@ def _analyze_ids(args, model, data, b0, b1, y_dev, s_dev, thresholds, names, acc
   then ONE counting pass at the labels' size for all thresholds (ops.instance_eval_counts) and the analyzers' numbers from
   the counts (ops.eval_metrics_from_counts), handed to analysis through the cache analysis._m honours."""
   import torch
-  import analysis
   import ra_ops as ops
-  from utils import postprocess as pp
   dev = y_dev.device
+  if _flat_path(data):  # mixed full sizes: the same chain through the ragged entry points, one launch chain per batch
+    import setup_labels
+    off, size = data['pixel_offset'], data['orig_size']
+    p0, p1 = int(off[b0]), int(off[b1])
+    geo = setup_labels.flat_geometry(off, size, b0, b1)
+    ids = torch.as_tensor(np.ascontiguousarray(np.asarray(data['gt_instance_ids_flat'][p0:p1]).astype(np.int32))).to(dev)
+    lab = ops.assemble_labels_ragged(ids, geo, model.dims['H'], model.dims['W'], model.dims['T'], args.dataset,
+                                     want=('inst_id', 's_gt'), names=_image_names(data)[b0:b1])
+    fg = torch.as_tensor(np.ascontiguousarray(np.asarray(data['fg_flat'][p0:p1]).astype(np.uint8))).to(dev) if 'fg_flat' in data else None
+    count = lambda yc, ths: ops.instance_eval_counts_ragged(yc, ids, geo, lab['inst_id'], ths, fg_flat=fg,
+                                                            morph=fg is not None and not args.no_morph, check_fg=False)
+    return _analyze_counts(args, count, lab, fg, y_dev, s_dev, thresholds, names, acc)
   ids = torch.as_tensor(np.ascontiguousarray(np.asarray(data['gt_instance_ids'][b0:b1]).astype(np.int32))).to(dev)
   # the slots in the reference's order — by area at NETWORK size — under the --dataset rule, as setup_labels.py assembles them
   lab = ops.assemble_labels(ids, model.dims['H'], model.dims['W'], model.dims['T'], args.dataset, want=('inst_id', 's_gt'),
                             names=_image_names(data)[b0:b1])
   fg = torch.as_tensor(np.ascontiguousarray(np.asarray(data['fg'][b0:b1]).astype(np.uint8))).to(dev) if 'fg' in data else None
+  count = lambda yc, ths: ops.instance_eval_counts(yc, ids, lab['inst_id'], ths, fg=fg, morph=fg is not None and not args.no_morph,
+                                                   check_fg=False)
+  _analyze_counts(args, count, lab, fg, y_dev, s_dev, thresholds, names, acc)
+
+
+def _analyze_counts(args, count, lab, fg, y_dev, s_dev, thresholds, names, acc):
+  """apply_confidence, count(yc, thresholds) -> (inter, area_b) in groups of INS_EVAL_MAX_K thresholds, and the analyzers."""
+  import analysis
+  import ra_ops as ops
+  from utils import postprocess as pp
   s2 = s_dev[:, :, 0].contiguous() if s_dev.dim() == 3 else s_dev   # multi-class: :108-110
   yc, s_conf = pp.apply_confidence(y_dev, s2)
   for k0 in range(0, len(thresholds), ops.INS_EVAL_MAX_K):
     ths = thresholds[k0:k0 + ops.INS_EVAL_MAX_K]
-    inter, area_b = ops.instance_eval_counts(yc.contiguous(), ids, lab['inst_id'], ths, fg=fg,
-                                             morph=fg is not None and not args.no_morph, check_fg=False)
+    inter, area_b = count(yc.contiguous(), ths)
     # remove_tiny only where a foreground is given, as in the chain (:121-124)
     per = ops.eval_metrics_from_counts(inter, area_b, lab['s_gt'], remove_tiny=args.remove_tiny if fg is not None else 0, conf=s_conf)
     for th, met in zip(ths, per):

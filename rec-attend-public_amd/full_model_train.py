@@ -12,7 +12,9 @@ its own shard of the global --batch_size), clip + Adam, BN EMA (ra_train.TrainSt
 
 Data: --input (an .npz with x [N,H,W,3] and either y_gt [N,T,H,W], s_gt [N,T] or gt_instance_ids
 [N,Hf,Wf]: then y_gt / s_gt of every batch are assembled on the device from the ids by the --dataset's
-rule, ra_ops.assemble_labels, eagerly in front of the captured step) or synthetic CVPPP-shaped
+rule, ra_ops.assemble_labels, eagerly in front of the captured step; ids of mixed full sizes come as
+gt_instance_ids_flat, pixel_offset and orig_size, what setup_labels.py --mixed_sizes writes, and go
+through ra_ops.assemble_labels_ragged in the same place) or synthetic CVPPP-shaped
 batches (8..T-1 ellipses per image, sorted by area); the reference's HDF5 datasets,
 plots and CSV loggers are out of scope.  BatchNorm moments are taken over the
 rank's shard, or over the whole batch with --sync_bn.  Checkpoints (weights.npz +
@@ -38,7 +40,8 @@ def build_parser():
   cap.add_size_overrides(p)
   p.add_argument('--init_only', action='store_true',
                  help='write model_opt.yaml + initial weights and stop')
-  p.add_argument('--input', default=None, help='.npz with x and y_gt, s_gt or gt_instance_ids (default: synthetic batches)')
+  p.add_argument('--input', default=None, help='.npz with x and y_gt, s_gt or gt_instance_ids, or the ids of mixed full sizes as gt_instance_ids_flat + pixel_offset + '
+                 'orig_size (default: synthetic batches)')
   p.add_argument('--seed', type=int, default=1234)
   p.add_argument('--save_rank_weights', action='store_true',
                  help='every rank also writes weights_rank<r>.npz (its own weights, EMA shadows and per-step losses) at the end: '
@@ -98,10 +101,18 @@ def batch_labels(data, idx, H, W, T, dataset):
   y_gt — assembled on the device from the ids (ins_seg_dataset.py:158-172,267-271 on setup_*.py's output), device tensors."""
   if 'y_gt' in data:
     return data['y_gt'][idx], data['s_gt'][idx]
-  if 'gt_instance_ids' not in data:
-    raise KeyError('--input holds neither y_gt nor gt_instance_ids')
   import ra_ops
   names = [str(n) for n in data['names'][idx]] if 'names' in data else ['image %d' % i for i in idx]
+  if 'gt_instance_ids' not in data and all(k in data for k in ('gt_instance_ids_flat', 'pixel_offset', 'orig_size')):
+    # mixed full sizes (setup_labels.py --mixed_sizes): the batch's images gathered into one flat buffer, one launch chain
+    import torch
+    off, size = data['pixel_offset'], data['orig_size']
+    imgs = [data['gt_instance_ids_flat'][int(off[i]):int(off[i]) + int(size[i, 0]) * int(size[i, 1])].reshape(tuple(size[i])) for i in idx]
+    flat, geo = ra_ops.pack_ragged(imgs, torch.int32)
+    got = ra_ops.assemble_labels_ragged(flat, geo, H, W, T, dataset, want=('y_gt', 's_gt'), names=names)
+    return got['y_gt'], got['s_gt']
+  if 'gt_instance_ids' not in data:
+    raise KeyError('--input holds neither y_gt nor gt_instance_ids')
   got = ra_ops.assemble_labels(data['gt_instance_ids'][idx], H, W, T, dataset, want=('y_gt', 's_gt'), names=names)
   return got['y_gt'], got['s_gt']
 

@@ -29,8 +29,13 @@ class CtrlDesc(C.Structure):
   """struct ra_ctrl_desc; its _fields_ are read from the header below."""
 
 
+class ImageGeo(C.Structure):
+  """struct ra_image_geo, one image of a ragged batch; its _fields_ are read from the header below."""
+
+
 _SCALARS = {'int': C.c_int, 'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t}
-_POINTEES = ('float', 'int', 'void', 'unsigned short', 'double', 'unsigned char', 'unsigned long long', 'short')
+_POINTEES = ('float', 'int', 'void', 'unsigned short', 'double', 'unsigned char', 'unsigned long long', 'short', 'ra_image_geo')
+_MEMBERS = {'int': C.c_int, 'long long': C.c_longlong}
 
 
 def _ctype(words, name):
@@ -45,10 +50,24 @@ def _ctype(words, name):
   raise RecAttendError('include/recattend.h: %s: no ctypes mapping for the type "%s"' % (name, ' '.join(words)))
 
 
-def read_header(text):
+def _struct_members(text, name):
+  """[(member, ctypes type)] of `typedef struct name { ... } name;` whose members are ints and long longs; [] when the text
+  has no such struct."""
+  struct = re.search(r'typedef\s+struct\s+%s\s*\{([^{}]*)\}\s*%s\s*;' % (name, name), text)
+  out = []
+  for decl in filter(None, (d.strip() for d in struct.group(1).split(';'))) if struct else ():
+    m = re.match(r'(long\s+long|int)\s+(\w+(?:\s*,\s*\w+)*)$', decl)
+    if m is None:
+      raise RecAttendError('include/recattend.h: %s: member "%s" is neither an int nor a long long' % (name, decl))
+    out += [(n, _MEMBERS[' '.join(m.group(1).split())]) for n in re.findall(r'\w+', m.group(2))]
+  return out
+
+
+def read_header(text, geo_fields=None):
   """(signatures, constants, ra_ctrl_desc field names) of the text of recattend.h.  signatures: {name: (restype,
   [argtypes])} of every `ret ra_name(args);`, constants: {name: int} of every `#define RA_NAME integer`.  The header is
   the only statement of the ABI, so a prototype this cannot split or a type it has no mapping for is an error, never a guess."""
+  geo_fields = [] if geo_fields is None else geo_fields  # receives struct ra_image_geo's members, where the text has it
   text = re.sub(r'/\*.*?\*/', ' ', text, flags=re.S)
   constants = {m.group(1): int(m.group(2))
                for m in re.finditer(r'^#define[ \t]+(RA_\w+)[ \t]+\(?(-?\d+)\)?[ \t]*$', text, re.M)}
@@ -61,6 +80,7 @@ def read_header(text):
     if not re.match(r'int\s+\w+(\s*,\s*\w+)*$', decl):
       raise RecAttendError('include/recattend.h: ra_ctrl_desc: member "%s" is not an int' % decl)
     fields += re.findall(r'\w+', decl)[1:]
+  geo_fields.extend(_struct_members(text, 'ra_image_geo'))
   text = re.sub(r'(typedef\s+struct\s+\w+|enum)\s*\{[^{}]*\}\s*\w*\s*;', '', text)
   text = re.sub(r'extern\s+"C"\s*\{(.*)\}', r'\1', text, flags=re.S)
   signatures = {}
@@ -84,9 +104,11 @@ def read_header(text):
 
 # name -> (restype, argtypes) of every symbol, the RA_* integer constants and the controller descriptor, all as
 # include/recattend.h states them
+_geo_fields = []
 with open(HEADER_PATH) as _f:
-  SIGNATURES, CONSTANTS, _fields = read_header(_f.read())
+  SIGNATURES, CONSTANTS, _fields = read_header(_f.read(), _geo_fields)
 CtrlDesc._fields_ = [(n, C.c_int) for n in _fields]
+ImageGeo._fields_ = _geo_fields
 globals().update(CONSTANTS)  # RA_ABI_VERSION, RA_E_*, RA_CONV_TRANSPOSED, RA_ATTN_STRIDE, RA_PASTE_*, RA_RESAMPLE_*
 
 _lib = None

@@ -2259,3 +2259,198 @@ def render_orientation(d, mask, size=None):
   check(rn.lib().ra_render_orientation_u8(ptr(d), B, Hs, Ws, Cc, ptr(mask), H, W, ptr(wheel), ptr(img), rn.stream_ptr()),
         'ra_render_orientation_u8')
   return img
+
+
+# ------------------------------------------------------------- mixed full sizes in one batch (KITTI): the ragged entry points
+# A batch of full-size images of different sizes is ONE flat tensor per per-pixel quantity plus its geometry: an int64 NumPy
+# array [B,3] of (offset, h, w) rows on the host — image b is the h x w rows, packed with pitch w, from element `offset` on
+# (include/recattend.h, ra_image_geo).
+RAGGED_ALIGN = 4  # elements: pack_ragged starts every image at a multiple, so that real data takes the kernels' wide loads
+
+
+def ragged_geometry(sizes, align=RAGGED_ALIGN):
+  """The geometry [B,3] int64 of images of the given (h, w) sizes laid out in that order, each at the next multiple of
+  `align` elements (align=1: no padding), and the flat buffer's element count."""
+  geo = np.zeros((len(sizes), 3), dtype=np.int64)
+  end = 0
+  for b, (h, w) in enumerate(sizes):
+    if int(h) < 1 or int(w) < 1:
+      raise rn.RecAttendError('ragged_geometry: image %d is %d x %d (h, w >= 1)' % (b, h, w))
+    start = -(-end // int(align)) * int(align)
+    geo[b] = (start, int(h), int(w))
+    end = start + int(h) * int(w)
+  return geo, int(end)
+
+
+def pack_ragged(arrays, dtype, device='cuda', align=RAGGED_ALIGN):
+  """A list of [h,w] arrays (NumPy or torch) -> (flat tensor of `dtype` on `device`, geometry [B,3]): every image starts at a
+  multiple of `align` elements, rows packed with pitch w, the gaps zero."""
+  if not len(arrays) or any(getattr(a, 'ndim', 0) != 2 for a in arrays):
+    raise rn.RecAttendError('pack_ragged: a non-empty list of [h,w] arrays')
+  geo, total = ragged_geometry([tuple(a.shape) for a in arrays], align)
+  flat = torch.zeros((total,), dtype=dtype)
+  for (off, h, w), a in zip(geo.tolist(), arrays):
+    a = a.detach().cpu() if isinstance(a, torch.Tensor) else torch.as_tensor(np.ascontiguousarray(a))
+    flat[off:off + h * w] = a.reshape(-1).to(dtype)
+  return flat.to(device), geo
+
+
+def unpack_ragged(flat, geo):
+  """The images of a flat tensor as a list of [h,w] views."""
+  return [flat[off:off + h * w].view(h, w) for off, h, w in np.asarray(geo).tolist()]
+
+
+def _geo_table(who, geo, flat_tensors, device):
+  """(ctypes table, device buffer, B, total) of a geometry [B,3] for flat tensors of one element count."""
+  g = np.asarray(geo)
+  if g.ndim != 2 or g.shape[1] != 3 or g.shape[0] < 1 or not np.issubdtype(g.dtype, np.integer):
+    raise rn.RecAttendError('%s: geometry must be an integer array [B,3] of (offset, h, w), got %s %s' % (who, g.dtype, g.shape))
+  B = int(g.shape[0])
+  if B > OVERLAP_MAX_B:
+    raise rn.RecAttendError('%s: B=%d (B <= %d)' % (who, B, OVERLAP_MAX_B))
+  if np.abs(g[:, 1:]).max() >= 1 << 31:
+    raise rn.RecAttendError('%s: geometry holds a size beyond 2^31' % who)
+  total = int(flat_tensors[0].numel())
+  for t in flat_tensors:
+    if t.dim() != 1 or int(t.numel()) != total:
+      raise rn.RecAttendError('%s: the flat tensors must be one-dimensional and of one length, got %s' % (
+          who, [tuple(t.shape) for t in flat_tensors]))
+  tab = (rn.ImageGeo * B)(*[rn.ImageGeo(int(o), int(h), int(w)) for o, h, w in g.tolist()])
+  dev = torch.empty((B * C.sizeof(rn.ImageGeo) // 8,), dtype=torch.int64, device=device)
+  return tab, dev, B, total
+
+
+def gt_instance_catalog_ragged(gt_flat, geo, check_status=True, names=None):
+  """gt_instance_catalog for a ragged batch: gt_flat int32 [P] and its geometry [B,3] -> (ids, pixels, count) as there, one
+  catalogue per image (ra_gt_instance_catalog_ragged_i32).  check_status=False returns the status words as a fourth tensor."""
+  _need_cuda_i32(gt_flat, 'gt_flat')
+  tab, gdev, B, total = _geo_table('gt_instance_catalog_ragged', geo, (gt_flat,), gt_flat.device)
+  dev = gt_flat.device
+  n = rn.lib().ra_gt_instance_catalog_ragged_workspace_ints(tab, B)
+  ws = torch.empty((max(n, 1),), dtype=torch.int32, device=dev)
+  ids = torch.empty((B, MAX_GT), dtype=torch.int32, device=dev)
+  pixels = torch.empty((B, MAX_GT), dtype=torch.int32, device=dev)
+  count = torch.empty((B,), dtype=torch.int32, device=dev)
+  status = torch.empty((B,), dtype=torch.int32, device=dev)
+  check(rn.lib().ra_gt_instance_catalog_ragged_i32(ptr(gt_flat), total, tab, ptr(gdev), B, ptr(ws), n, ptr(ids), ptr(pixels),
+                                                   ptr(count), ptr(status), rn.stream_ptr()), 'ra_gt_instance_catalog_ragged_i32')
+  if not check_status:
+    return ids, pixels, count, status
+  _raise_gt_status(status, names, 'gt_instance_catalog_ragged')
+  return ids, pixels, count
+
+
+def assemble_labels_ragged_raw(gt_flat, geo, catalog, H, W, T, dataset, want=LABEL_OUTPUTS):
+  """ra_labels_assemble_ragged_i32 on gt_flat int32 [P], its geometry and catalog = gt_instance_catalog_ragged(gt_flat, geo,
+  ...): {name: device tensor} over `want` — the network-size outputs dense as assemble_labels_raw has them, 'fg_gt_full' uint8
+  [P] flat at gt_flat's offsets (the gaps between images zero); no status is looked at."""
+  who = 'assemble_labels_ragged'
+  _need_cuda_i32(gt_flat, 'gt_flat')
+  ids, count = catalog[0], catalog[2]
+  _need_cuda_i32(ids, 'catalog ids')
+  _need_cuda_i32(count, 'catalog count')
+  rule = label_dataset_rule(dataset)
+  unknown = [k for k in want if k not in LABEL_OUTPUTS]
+  if unknown or not want:
+    raise rn.RecAttendError('%s: want %s (any of %s)' % (who, list(want), ', '.join(LABEL_OUTPUTS)))
+  tab, gdev, B, total = _geo_table(who, geo, (gt_flat,), gt_flat.device)
+  H, W, T = int(H), int(W), int(T)
+  if tuple(ids.shape) != (B, MAX_GT) or tuple(count.shape) != (B,):
+    raise rn.RecAttendError('%s: %d images, catalog ids %s, count %s do not belong together' % (
+        who, B, tuple(ids.shape), tuple(count.shape)))
+  if not (1 <= T <= LABELS_MAX_T and H >= 1 and W >= 1 and H * W < 1 << 31):
+    raise rn.RecAttendError('%s: T=%d -> %d x %d (1 <= T <= %d, H, W >= 1, H * W < 2^31)' % (who, T, H, W, LABELS_MAX_T))
+  dev = gt_flat.device
+  nc = 1 + len(_cityscapes_labels()) if rule == rn.RA_LABELS_CITYSCAPES else 1
+  spec = {'num_obj': ((B,), torch.int32), 's_gt': ((B, T), torch.float32), 'inst_id': ((B, T), torch.int32),
+          'area': ((B, T), torch.int32), 'sem_cls': ((B, T), torch.int32), 'y_gt': ((B, T, H, W), torch.float32),
+          'd_cls': ((B, H, W), torch.uint8), 'd_gt': ((B, H, W, 8), torch.float32), 'c_gt': ((B, H, W, nc), torch.float32)}
+  out = {k: torch.empty(spec[k][0], dtype=spec[k][1], device=dev) for k in LABEL_OUTPUTS if k in want and k in spec}
+  if 'fg_gt_full' in want:
+    out['fg_gt_full'] = torch.zeros((total,), dtype=torch.uint8, device=dev)
+  n = rn.lib().ra_labels_workspace_bytes(B, H, W)
+  ws = torch.empty((max(n // 8, 1),), dtype=torch.int64, device=dev)
+  check(rn.lib().ra_labels_assemble_ragged_i32(ptr(gt_flat), total, tab, ptr(gdev), ptr(ids), ptr(count), B, H, W, T, rule, ptr(ws),
+                                               n, *[ptr(out.get(k)) for k in LABEL_OUTPUTS], rn.stream_ptr()),
+        'ra_labels_assemble_ragged_i32')
+  return out
+
+
+def assemble_labels_ragged(gt_flat, geo, H, W, T, dataset, want=('y_gt', 's_gt'), names=None):
+  """assemble_labels for a ragged batch (KITTI's mixed full sizes): gt_flat int32 [P] on the device with its geometry [B,3] (what
+  pack_ragged returns) -> {name: device tensor} over `want`.  The network-size outputs are dense ([B,T,H,W] and the like), the
+  nearest-neighbour sampling scale is each image's own, and 'fg_gt_full' is flat at gt_flat's offsets.  1 <= H <= h and 1 <= W <=
+  w must hold for every image.  Status words as in assemble_labels."""
+  label_dataset_rule(dataset)
+  _need_cuda_i32(gt_flat, 'gt_flat')
+  ids, pixels, count, status = gt_instance_catalog_ragged(gt_flat, geo, check_status=False)
+  out = assemble_labels_ragged_raw(gt_flat, geo, (ids, pixels, count), H, W, T, dataset, want)
+  _raise_gt_status(status, names, 'assemble_labels_ragged')
+  return out
+
+
+def instance_eval_counts_ragged(yc, gt_flat, geo, inst_id, thresholds, fg_flat=None, morph=False, check_fg=True):
+  """instance_eval_counts for a ragged batch: yc float32 [B,T,Hs,Ws] and inst_id int32 [B,T] dense, gt_flat int32 [P] and
+  fg_flat uint8 [P] (or None) flat with one geometry [B,3] -> (inter int32 [B,K,T,T + 1], area_b int32 [B,T]) as there; every
+  image is resized, filtered and walked at its own h x w, h * w <= 2^24 (ra_instance_eval_counts_ragged_f32)."""
+  who = 'instance_eval_counts_ragged'
+  thr = _ins_eval_thresholds(thresholds)
+  ts = (yc, gt_flat, inst_id) + (() if fg_flat is None else (fg_flat,))
+  if not all(isinstance(t, torch.Tensor) for t in ts) or not all(t.is_cuda for t in ts):
+    raise rn.RecAttendError('%s needs CUDA (HIP) tensors; got a CPU tensor. There is no CPU fallback.' % who)
+  if yc.dtype != torch.float32 or gt_flat.dtype != torch.int32 or inst_id.dtype != torch.int32 or not all(t.is_contiguous() for t in ts):
+    raise rn.RecAttendError('%s: yc must be contiguous float32, gt_flat and inst_id contiguous int32, got %s, %s, %s' % (
+        who, yc.dtype, gt_flat.dtype, inst_id.dtype))
+  if fg_flat is not None and fg_flat.dtype != torch.uint8:
+    raise rn.RecAttendError('%s: fg_flat must be uint8, got %s' % (who, fg_flat.dtype))
+  tab, gdev, B, total = _geo_table(who, geo, (gt_flat,) + (() if fg_flat is None else (fg_flat,)), yc.device)
+  if yc.dim() != 4 or min(yc.shape) < 1 or yc.shape[0] != B or tuple(inst_id.shape) != tuple(yc.shape[:2]):
+    raise rn.RecAttendError('%s: yc must be [B,T,Hs,Ws] and inst_id [B,T] for the geometry\'s %d images, got %s, %s' % (
+        who, B, tuple(yc.shape), tuple(inst_id.shape)))
+  _, T, Hs, Ws = yc.shape
+  if not (T <= LABELS_MAX_T and Hs * Ws < 1 << 31):
+    raise rn.RecAttendError('%s: T=%d, %d x %d (T <= %d, Hs * Ws < 2^31)' % (who, T, Hs, Ws, LABELS_MAX_T))
+  if fg_flat is not None and check_fg and int(fg_flat.max()) > 1:
+    raise rn.RecAttendError('%s: fg_flat holds %d; a foreground mask is 0 / 1' % (who, int(fg_flat.max())))
+  K = int(thr.size)
+  inter = torch.empty((B, K, T, T + 1), dtype=torch.int32, device=yc.device)
+  area_b = torch.empty((B, T), dtype=torch.int32, device=yc.device)
+  check(rn.lib().ra_instance_eval_counts_ragged_f32(ptr(yc), ptr(gt_flat), ptr(inst_id), ptr(fg_flat), total, tab, ptr(gdev), B, T,
+                                                    Hs, Ws, int(bool(morph)), ptr(thr), K, ptr(inter), ptr(area_b),
+                                                    rn.stream_ptr()), 'ra_instance_eval_counts_ragged_f32')
+  return inter, area_b
+
+
+def fg_sweep_counts_ragged_device(src, gt_flat, geo, thresholds, out=None):
+  """ra_fg_sweep_counts_ragged_f32 without the copy to the host: src float32 [N,Hs,Ws], gt_flat uint8 [P] with its geometry
+  [N,3] -> int64 device tensor [N, RA_FG_SWEEP_SLOTS] as fg_sweep_counts_device returns it."""
+  who = 'fg_sweep_counts_ragged'
+  thr = _sweep_thresholds(thresholds)
+  if not (isinstance(src, torch.Tensor) and isinstance(gt_flat, torch.Tensor)) or not src.is_cuda or not gt_flat.is_cuda:
+    raise rn.RecAttendError('%s needs CUDA (HIP) tensors; got a CPU tensor. There is no CPU fallback.' % who)
+  if src.dtype != torch.float32 or gt_flat.dtype != torch.uint8 or not src.is_contiguous() or not gt_flat.is_contiguous():
+    raise rn.RecAttendError('%s: src must be contiguous float32 and gt_flat contiguous uint8, got %s and %s' % (
+        who, src.dtype, gt_flat.dtype))
+  tab, gdev, N, total = _geo_table(who, geo, (gt_flat,), src.device)
+  if src.dim() != 3 or min(src.shape) < 1 or src.shape[0] != N:
+    raise rn.RecAttendError('%s: src must be [N,Hs,Ws] for the geometry\'s %d images, got %s' % (who, N, tuple(src.shape)))
+  _, Hs, Ws = src.shape
+  if Hs * Ws >= 1 << 31:
+    raise rn.RecAttendError('%s: %d x %d (planes below 2^31 pixels)' % (who, Hs, Ws))
+  if out is None:
+    out = torch.empty((N, rn.RA_FG_SWEEP_SLOTS), dtype=torch.int64, device=src.device)
+  elif tuple(out.shape) != (N, rn.RA_FG_SWEEP_SLOTS) or out.dtype != torch.int64 or not out.is_cuda or not out.is_contiguous():
+    raise rn.RecAttendError('%s: out must be a contiguous int64 device tensor [%d, %d]' % (who, N, rn.RA_FG_SWEEP_SLOTS))
+  check(rn.lib().ra_fg_sweep_counts_ragged_f32(ptr(src), ptr(gt_flat), total, tab, ptr(gdev), N, Hs, Ws, ptr(thr), int(thr.size),
+                                               ptr(out), rn.stream_ptr()), 'ra_fg_sweep_counts_ragged_f32')
+  return out
+
+
+def fg_sweep_counts_ragged(src, gt_flat, geo, thresholds):
+  """fg_sweep_counts for a ragged batch -> {'count_a' [N,K], 'sum_ab' [N,K], 'sum_b' [N], 'pixels' [N] (h * w PER IMAGE),
+  'thresholds'}: NumPy int64 on the host."""
+  c = fg_sweep_counts_ragged_device(src, gt_flat, geo, thresholds).cpu().numpy()
+  K = len(_sweep_thresholds(thresholds))
+  g = np.asarray(geo, dtype=np.int64)
+  return {'count_a': c[:, :K].copy(), 'sum_ab': c[:, FG_SWEEP_MAX_K:FG_SWEEP_MAX_K + K].copy(), 'sum_b': c[:, 2 * FG_SWEEP_MAX_K].copy(),
+          'pixels': (g[:, 1] * g[:, 2]).copy(), 'thresholds': [float(t) for t in _sweep_thresholds(thresholds)]}
