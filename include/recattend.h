@@ -1071,6 +1071,68 @@ int ra_render_orientation_u8(const float *d, int B, int Hs, int Ws, int C, const
                              const unsigned char *wheel, unsigned char *img, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * PNG output on the device (csrc/ra_png.hip): the deflate stage of utils/png.encode_gray8 / encode_colour8 for a batch of
+ * images in device memory.  Per image a finished zlib stream leaves; the host wraps it (signature, IHDR, IDAT with
+ * zlib.crc32 over the stream, IEND: utils/png.wrap).  The files decode to the pixels of the host writers' files; their
+ * bytes differ, so the output stages use this only when asked (device_png).
+ *
+ * THE STREAM (three implementations agree on it byte for byte: the kernels, ra_png_deflate_host, tests/png_deflate_oracle.py)
+ *   scanline  one filter-type byte 0, then the row: W bytes (grey, d = 1) or 3 W bytes in the FILE's order R, G, B (d = 3;
+ *             the source is in cv2's memory order B, G, R and is swapped in the load).  Filter 0 on every row.
+ *   segment   one scanline, n = 1 + W * bpp bytes, encoded on its own and ending on a byte boundary:
+ *               a block with BFINAL = 0, BTYPE = 01 (the fixed Huffman code of RFC 1951 3.2.6), its tokens, end-of-block,
+ *               then an empty stored block as a sync flush: bits 0, 00, zero bits up to the byte boundary, 00 00 FF FF.
+ *   tokens    the greedy left-to-right run code at distance d: at byte i >= d of the segment, L = the number of following
+ *             bytes, at most 258, that each equal the byte d before it; L >= 3: one match (length L, distance d), else the
+ *             literal b[i].  The first d bytes are literals; no match reaches outside its segment.  Closed form, per maximal
+ *             stretch of R positions with b[i] == b[i-d]: R / 258 matches of 258, then one match of R % 258 if that is >= 3,
+ *             else R % 258 literals.
+ *   stream    78 01, the segments of rows 0 .. H - 1, the final empty fixed block 03 00, the big-endian Adler-32 of all
+ *             scanline bytes.
+ *   bound     a literal takes at most 9 bits, a match of L >= 3 bytes at most 8 + 5 + 5 = 18 <= 9 L, so a segment takes at
+ *             most 3 + 9n + 7 + 3 bits before padding: at most ceil(9n / 8) + 7 bytes with the pad and LEN/NLEN; a stream at
+ *             most 8 + H * (ceil(9n / 8) + 7) bytes.
+ *   Adler-32  per segment (A, B) from (1, 0), reduced per thread chunk (a colour row of 6145 bytes of 255 overflows 32-bit
+ *             sums reduced only at the end); segments combine exactly: A = A1 + A2 - 1, B = B1 + B2 + n2 (A1 - 1) mod 65521.
+ *   A run code within a row: masks and flat-colour images shrink to a few tens of KB (2.5 x what zlib level 6 makes of a
+ *   flat-colour image, 6 - 7 x for a binary mask: profiles/png_device.txt), continuous-valued planes GROW; those stay with the host's zlib.
+ *
+ * Sources (kind): RA_PNG_GRAY8 uint8 [M,H,W]; RA_PNG_BGR8 uint8 [M,H,W,3] in B, G, R order; RA_PNG_F32 float [M,H,W],
+ *   quantised in the load as (uint8)(v * 255.0f), what (y * 255).to(torch.uint8) gives for 0 <= v <= 1 (outside it the cast
+ *   is undefined there and the bytes here unspecified).  plane (nullable): int32 [N], image i of the call is source image
+ *   plane[i], indices may skip, repeat and reorder; NULL: image i is source image i and N <= M.  The host entry refuses an
+ *   index outside [0, M) with RA_E_SHAPE; the device entry cannot read the list and clamps it in the kernel: wrong pixels,
+ *   never an access outside src.
+ *
+ * ra_png_deflate_bound — bpp: 1 (grey and float sources) or 3.  *stream_bytes: the bound of one stream; *workspace_bytes: what
+ *   ra_png_deflate_u8 needs for N such images (a 16-byte record and a worst-case slot per segment).
+ * ra_png_deflate_u8 — every pointer, the plane list included, in DEVICE memory.  out: N streams back to back, stream i at
+ *   out + offsets[i] with sizes[i] bytes (offsets[0] = 0, offsets[i + 1] = offsets[i] + sizes[i]); adler[i]: its Adler-32.
+ *   Three plain launches on the stream (encode: a workgroup per scanline; scan: a workgroup per image; compact: a wave per
+ *   segment), no allocation, no synchronisation, no workgroup waits for another.  Rows are staged with 16-byte loads when src
+ *   is 16-byte aligned and W % 16 == 0 (float: W % 4 == 0), with element loads otherwise.
+ * ra_png_deflate_host — HOST code, no GPU call: the same arguments in host memory (ws may be NULL), the rule above in plain
+ *   sequential C++.  The same bytes as the device entry.
+ * Refusals, all before anything is read, written or launched: a NULL src, out, sizes, offsets or adler, or another kind:
+ *   RA_E_INVALID.  N < 1 or N > RA_PNG_MAX_IMAGES, M < 1, H < 1, W < 1, N > M without a plane list, scanlines above
+ *   RA_PNG_MAX_ROW_BYTES (the segment and its bits wait in LDS), an image of 2^31 source bytes or a stream bound of 2^31, bpp
+ *   other than 1 or 3 (bound query): RA_E_SHAPE.  out_bytes < N * stream bound, a NULL, short or not 16-byte aligned ws
+ *   (device entry): RA_E_WORKSPACE.  The message names the argument.
+ * ---------------------------------------------------------------------------------- */
+#define RA_PNG_GRAY8 0
+#define RA_PNG_BGR8 1
+#define RA_PNG_F32 2
+#define RA_PNG_MAX_ROW_BYTES 24576
+#define RA_PNG_MAX_IMAGES 65535
+int ra_png_deflate_bound(int N, int H, int W, int bpp, unsigned long long *stream_bytes, unsigned long long *workspace_bytes);
+int ra_png_deflate_u8(const void *src, int kind, int M, int N, int H, int W, const int *plane, unsigned char *out,
+                      size_t out_bytes, int *sizes, unsigned long long *offsets, unsigned int *adler, void *ws, size_t ws_bytes,
+                      void *stream);
+int ra_png_deflate_host(const void *src, int kind, int M, int N, int H, int W, const int *plane, unsigned char *out,
+                        size_t out_bytes, int *sizes, unsigned long long *offsets, unsigned int *adler, void *ws,
+                        size_t ws_bytes);
+
+/* ------------------------------------------------------------------------------------
  * Evaluating the pre-stage fg_model (csrc/ra_fg_eval.hip).
  *
  * ra_fg_stats_f32 — the sums behind the six statistics the reference's Evaluator logs (fg_model_train.py:131-133), replacing

@@ -186,13 +186,16 @@ class RenderCityScapesOutputAnalyzer(object):
   indexed by results['indices'].  stage() writes <folder>/<run>/<name>.txt — one line '<name>_<t:03d>.png <label_id> <score>'
   per written instance — and every written mask as an 8-bit PNG, (seg * 255).astype('uint8'); <run> is the name up to its
   first '_'.  As in the reference the text file is opened anew by every stage() call: with several thresholds sharing one
-  folder the last one staged is what remains."""
+  folder the last one staged is what remains.  device_png: the masks are compressed on the device (utils/png.write_gray8_dev:
+  ONE ops.png_deflate call per stage() over the kept (ii, jj) planes of y_out, read as floats and never materialised as uint8)
+  instead of copied to the host plane by plane; the files decode to the same pixels, their bytes differ."""
 
-  def __init__(self, folder, names):
+  def __init__(self, folder, names, device_png=False):
     if folder is None:
       raise Exception('No output folder')
     self.folder = folder
     self.names = list(names)
+    self.device_png = bool(device_png)
     self.labels = CITYSCAPES_LABELS
     self.written = []  # (text file, [(png file, label_id, score), ...]) per staged image
     os.makedirs(folder, exist_ok=True)
@@ -205,6 +208,7 @@ class RenderCityScapesOutputAnalyzer(object):
     if ((idx_h >= 0) & (lab_h < 0)).any():  # the reference's self.labels[sem_idx] raises there too
       raise IndexError('a class index beyond the %d Cityscapes instance classes' % len(self.labels))
     score = results['conf'].cpu().numpy()
+    kept = []  # device_png: (plane of y_out as [B * T, H, W], path) of every mask to write
     for ii in range(y_out.shape[0]):
       fn1 = _stem(str(self.names[int(indices[ii])]))
       runfolder = os.path.join(self.folder, fn1.split('_')[0])
@@ -216,11 +220,17 @@ class RenderCityScapesOutputAnalyzer(object):
           if idx_h[ii, jj] < 0:
             continue
           img_file = fn1 + '_{:03d}.png'.format(jj)
-          seg = (y_out[ii, jj] * 255).to(torch.uint8).cpu().numpy()
-          png.write_gray8(os.path.join(runfolder, img_file), seg)
+          if self.device_png:
+            kept.append((ii * y_out.shape[1] + jj, os.path.join(runfolder, img_file)))
+          else:
+            seg = (y_out[ii, jj] * 255).to(torch.uint8).cpu().numpy()
+            png.write_gray8(os.path.join(runfolder, img_file), seg)
           text_file.write(cityscapes_line(img_file, lab_h[ii, jj], score[ii, jj]))
           lines.append((img_file, int(lab_h[ii, jj]), float(score[ii, jj])))
       self.written.append((text_fn, lines))
+    if kept:
+      planes = y_out.contiguous().to(torch.float32).view(-1, y_out.shape[2], y_out.shape[3])
+      png.write_gray8_dev([path for _, path in kept], planes, [k for k, _ in kept])
 
   def finalize(self):
     pass
@@ -292,18 +302,25 @@ class CountAnalyzer(object):
 
 
 class _RenderBase(object):
-  """names: the file name of every image, indexed by results['indices']; an image goes to <folder>/<name without .png>.png."""
+  """names: the file name of every image, indexed by results['indices']; an image goes to <folder>/<name without .png>.png.
+  device_png: the batch is compressed on the device (utils/png.write_colour8_dev, one ops.png_deflate call) and only the
+  streams are copied; the files decode to the same pixels, their bytes differ."""
 
-  def __init__(self, folder, names):
+  def __init__(self, folder, names, device_png=False):
     if folder is None:
       raise Exception('No output folder')
     self.folder = folder
     self.names = list(names)
+    self.device_png = bool(device_png)
     self.written = []
     os.makedirs(folder, exist_ok=True)
 
   def _write(self, img, indices):
     from utils import png
+    if self.device_png:
+      paths = [os.path.join(self.folder, _stem(str(self.names[int(indices[ii])])) + '.png') for ii in range(img.shape[0])]
+      self.written += png.write_colour8_dev(paths, img)
+      return
     host = img.cpu().numpy()
     for ii in range(host.shape[0]):
       path = os.path.join(self.folder, _stem(str(self.names[int(indices[ii])])) + '.png')

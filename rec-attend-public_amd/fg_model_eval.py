@@ -33,6 +33,8 @@ pixels), plus 'statistics' when ground truth at network size was given; <output>
 dataset's labels; the orientation image itself is built behind --render_orientation (not a reference flag): <output>/ori/<name>.png,
 the colour-wheel image of data_api/orientation.py:13-28 from the model's d_out — resized to the labels' size and arg-maxed inside
 one kernel (analysis.RenderOrientationAnalyzer) — with fg_gt_full > 0 as the mask; a model without add_orientation is refused.
+--device_png (not a reference flag) compresses the thresholded planes, gt/ and ori/ on the device (utils/png.write_*_dev): the same
+pixels in files of other bytes.  soft/ is continuous-valued, a run code would enlarge it: it stays with the host's zlib, unchanged.
 
 Pixel-level class scores: when --input also holds gt_instance_ids [N,H,W] (the *_gtFine_instanceIds.png values; optionally
 gt_label_ids uint8 [N,H,W], the *_gtFine_labelIds.png values, else a pixel's label is derived from its id) and the model has
@@ -70,6 +72,11 @@ def build_parser():
   p.add_argument('--render_orientation', action='store_true',
                  help='not a reference flag: write the orientation classes of the model\'s d_out as a colour-wheel image, masked '
                       'by fg_gt_full, into <output>/ori/; needs a model with add_orientation')
+  p.add_argument('--device_png', action='store_true',
+                 help='not a reference flag: compress the thresholded planes, the --render_gt planes and the --render_orientation '
+                      'images on the device (a run code within each row, utils/png.write_*_dev); the files decode to the same '
+                      'pixels, their bytes differ and they are larger.  The --render_soft planes are continuous-valued, a run '
+                      'code would enlarge them: they stay with the host\'s zlib and do not change')
   return p
 
 
@@ -90,6 +97,13 @@ def _write_planes(folder, names, planes):
   os.makedirs(folder, exist_ok=True)
   for name, img in zip(names, planes):
     png.write_gray8(os.path.join(folder, os.path.splitext(os.path.basename(name))[0] + '.png'), img)
+
+
+def _write_planes_dev(folder, names, planes):
+  """_write_planes for uint8 [B,H,W] planes still on the DEVICE (--device_png): one png_deflate call for the batch."""
+  from utils import png
+  os.makedirs(folder, exist_ok=True)
+  png.write_gray8_dev([os.path.join(folder, os.path.splitext(os.path.basename(name))[0] + '.png') for name in names], planes)
 
 
 def foreground_plane(y_out):
@@ -152,7 +166,8 @@ def main(argv=None):
             'labels %s) map to Cityscapes label ids' % (nsc, 1 + len(analysis.CITYSCAPES_LABELS),
                                                         ', '.join(n for n, _ in analysis.CITYSCAPES_LABELS)))
   if args.render_orientation:
-    ori_render = analysis.RenderOrientationAnalyzer(os.path.join(out_dir, 'ori'), [os.path.basename(n) for n in names])
+    ori_render = analysis.RenderOrientationAnalyzer(os.path.join(out_dir, 'ori'), [os.path.basename(n) for n in names],
+                                                    device_png=args.device_png)
   fg_an = [analysis.ForegroundIOUAnalyzer('fg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]  # :62-69
   bg_an = [analysis.BackgroundIOUAnalyzer('bg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]
   totals = [{'count_a': 0, 'sum_ab': 0, 'sum_b': 0, 'pixels': 0} for _ in thresholds]
@@ -162,6 +177,9 @@ def main(argv=None):
   dev = torch.device('cuda', torch.cuda.current_device())
   up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
   to8 = lambda t: (t * 255.0).clamp(0, 255).to(torch.uint8).cpu().numpy()
+  # --device_png: the same quantisation, the plane left on the device and compressed there
+  write_hard = (lambda f, n, t: _write_planes_dev(f, n, (t * 255.0).clamp(0, 255).to(torch.uint8))) if args.device_png else (
+      lambda f, n, t: _write_planes(f, n, to8(t)))
   for b0 in range(0, N, bs):
     b1 = min(N, b0 + bs)
     x = up(x_all[b0:b1])
@@ -188,11 +206,11 @@ def main(argv=None):
       totals[k]['pixels'] += counts['pixels'] * (b1 - b0)
     full = pp.upsample(soft, (H, W))  # the rendering path only: :146, :166-173
     for t in thresholds:
-      _write_planes(os.path.join(out_dir, '{:02d}'.format(int(t * 100))), names[b0:b1], to8((full > float(t)).to(torch.float32)))
+      write_hard(os.path.join(out_dir, '{:02d}'.format(int(t * 100))), names[b0:b1], (full > float(t)).to(torch.float32))
     if opt['render_soft']:
       _write_planes(os.path.join(out_dir, 'soft'), names[b0:b1], to8(full))
     if opt['render_gt']:
-      _write_planes(os.path.join(out_dir, 'gt'), names[b0:b1], to8(gt.to(torch.float32)))
+      write_hard(os.path.join(out_dir, 'gt'), names[b0:b1], gt.to(torch.float32))
     if ori_render is not None:  # :154-164: d_out at network size, the labels as the mask
       ori_render.stage({'d_out': d_out.contiguous(), 'mask': (gt > 0).to(torch.float32), 'indices': list(range(b0, b1))})
     if have_stats:
@@ -246,6 +264,9 @@ def _main_mixed(args, opt, data, model, out_dir, thresholds):
   dev = torch.device('cuda', torch.cuda.current_device())
   up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
   to8 = lambda t: (t * 255.0).clamp(0, 255).to(torch.uint8).cpu().numpy()
+  # --device_png: the same quantisation, the plane left on the device and compressed there
+  write_hard = (lambda f, n, t: _write_planes_dev(f, n, (t * 255.0).clamp(0, 255).to(torch.uint8))) if args.device_png else (
+      lambda f, n, t: _write_planes(f, n, to8(t)))
   bs = max(1, opt['batch_size'])
   for b0 in range(0, N, bs):
     b1 = min(N, b0 + bs)
@@ -266,11 +287,11 @@ def _main_mixed(args, opt, data, model, out_dir, thresholds):
     for i, (o, h, w) in enumerate(geo.tolist()):  # the rendering path only (:146, :166-173), image by image at its own size
       full = pp.upsample(soft[i:i + 1].contiguous(), (h, w))
       for t in thresholds:
-        _write_planes(os.path.join(out_dir, '{:02d}'.format(int(t * 100))), names[b0 + i:b0 + i + 1], to8((full > float(t)).to(torch.float32)))
+        write_hard(os.path.join(out_dir, '{:02d}'.format(int(t * 100))), names[b0 + i:b0 + i + 1], (full > float(t)).to(torch.float32))
       if opt['render_soft']:
         _write_planes(os.path.join(out_dir, 'soft'), names[b0 + i:b0 + i + 1], to8(full))
       if opt['render_gt']:
-        _write_planes(os.path.join(out_dir, 'gt'), names[b0 + i:b0 + i + 1], to8(gt[o:o + h * w].view(1, h, w).to(torch.float32)))
+        write_hard(os.path.join(out_dir, 'gt'), names[b0 + i:b0 + i + 1], gt[o:o + h * w].view(1, h, w).to(torch.float32))
     if have_stats:
       stats.append(model.statistics(x, up(y_gt_all[b0:b1]), None if d_gt_all is None else up(d_gt_all[b0:b1])))
   summary = {}

@@ -79,6 +79,10 @@ def build_parser():
   p.add_argument('--render_gt_instances', action='store_true',
                  help='not a reference flag: write the ground truth, coloured by its best-matching prediction, into '
                       '<output>/output_<split>/gt/; needs y_gt and s_gt in --input')
+  p.add_argument('--device_png', action='store_true',
+                 help='not a reference flag: compress the files of --render, --render_gt_instances and --cityscapes_output on the '
+                      'device (a run code within each row, utils/png.write_*_dev) instead of copying every plane to the host for '
+                      'zlib; the files decode to the same pixels, their bytes differ and they are larger')
   p.add_argument('--in_flight', type=int, default=8, help='batches submitted to one GPU at a time (four decode concurrently, the rest queue behind them)')
   return p
 
@@ -277,23 +281,24 @@ def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, anal
   import torch
   out_dir = os.path.join(args.output or restore, 'output_' + args.split.split(',')[0])
   img_render, counters, gt_render = {}, {}, None
+  dpng = bool(getattr(args, 'device_png', False))
   if getattr(args, 'render', False) or getattr(args, 'render_gt_instances', False):
     import analysis
     img_names = [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(data['x'].shape[0])]
     if args.render:
       for th in thresholds:
         folder = os.path.join(out_dir, '{:02d}'.format(int(th * 100)))  # full_model_eval.py:65
-        img_render[th] = analysis.RenderInstanceAnalyzer(folder, img_names)
+        img_render[th] = analysis.RenderInstanceAnalyzer(folder, img_names, device_png=dpng)
         counters[th] = analysis.CountAnalyzer(os.path.join(folder, 'count.csv' if world == 1 else 'count_rank%d.csv' % rank))
     if args.render_gt_instances:
-      gt_render = analysis.RenderGroundtruthInstanceAnalyzer(os.path.join(out_dir, 'gt'), img_names)
+      gt_render = analysis.RenderGroundtruthInstanceAnalyzer(os.path.join(out_dir, 'gt'), img_names, device_png=dpng)
   cs_dir, sems, render = getattr(args, 'cityscapes_output', None), {}, None
   if cs_dir:
     import analysis
     import cityscapes_eval
     n_all = data['x'].shape[0]
     render = analysis.RenderCityScapesOutputAnalyzer(
-        cs_dir, [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(n_all)])
+        cs_dir, [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(n_all)], device_png=dpng)
     if 'full_size' in data:
       cs_size = (int(data['full_size'][0]), int(data['full_size'][1]))
     else:

@@ -34,7 +34,8 @@ class ImageGeo(C.Structure):
 
 
 _SCALARS = {'int': C.c_int, 'float': C.c_float, 'double': C.c_double, 'size_t': C.c_size_t}
-_POINTEES = ('float', 'int', 'void', 'unsigned short', 'double', 'unsigned char', 'unsigned long long', 'short', 'ra_image_geo')
+_POINTEES = ('float', 'int', 'void', 'unsigned short', 'double', 'unsigned char', 'unsigned long long', 'short', 'ra_image_geo',
+             'unsigned int')
 _MEMBERS = {'int': C.c_int, 'long long': C.c_longlong}
 
 

@@ -2261,6 +2261,93 @@ def render_orientation(d, mask, size=None):
   return img
 
 
+# ------------------------------------------------------------- PNG output on the device (csrc/ra_png.hip)
+_PNG_BUFFERS = {}  # device -> [workspace, out]: uint8 tensors that only grow, reused by every call on that device
+
+
+def png_deflate_bound(N, H, W, bpp):
+  """(bytes of one stream at most, bytes of workspace for N images) of ra_png_deflate_bound; bpp 1 (grey, float) or 3."""
+  stream, ws = C.c_ulonglong(0), C.c_ulonglong(0)
+  check(rn.lib().ra_png_deflate_bound(int(N), int(H), int(W), int(bpp), C.addressof(stream), C.addressof(ws)), 'ra_png_deflate_bound')
+  return int(stream.value), int(ws.value)
+
+
+def _png_source(who, src):
+  """(kind, M, H, W, bpp) of a source tensor of png_deflate."""
+  if not isinstance(src, torch.Tensor) or not src.is_contiguous():
+    raise rn.RecAttendError('%s: src must be a contiguous tensor' % who)
+  if src.dtype == torch.uint8 and src.dim() == 3:
+    kind, bpp = rn.RA_PNG_GRAY8, 1
+  elif src.dtype == torch.uint8 and src.dim() == 4 and src.shape[3] == 3:
+    kind, bpp = rn.RA_PNG_BGR8, 3
+  elif src.dtype == torch.float32 and src.dim() == 3:
+    kind, bpp = rn.RA_PNG_F32, 1
+  else:
+    raise rn.RecAttendError('%s: src must be uint8 [N,H,W], uint8 [N,H,W,3] (B, G, R) or float32 [M,H,W], got %s %s' % (
+        who, src.dtype, tuple(src.shape)))
+  if min(src.shape) < 1:
+    raise rn.RecAttendError('%s: src has an empty dimension: %s' % (who, tuple(src.shape)))
+  return kind, int(src.shape[0]), int(src.shape[1]), int(src.shape[2]), bpp
+
+
+def _png_planes(who, plane_index, M):
+  """plane_index (a sequence or tensor of indices into the M source images) -> int32 NumPy array, checked on the host."""
+  idx = plane_index.detach().cpu().numpy() if isinstance(plane_index, torch.Tensor) else np.asarray(plane_index)
+  idx = idx.astype(np.int64).reshape(-1)
+  if idx.size < 1 or idx.min() < 0 or idx.max() >= M:
+    raise rn.RecAttendError('%s: plane_index must hold at least one index in [0, %d)' % (who, M))
+  return np.ascontiguousarray(idx.astype(np.int32))
+
+
+def png_deflate(src, plane_index=None, with_meta=False):
+  """The zlib streams of PNG image data (include/recattend.h, ra_png_deflate_u8: filter 0, one fixed-Huffman run-coded
+  segment per scanline) for a batch of images on the device -> a list of bytes, one stream per image.  src: uint8 [N,H,W]
+  (grey), uint8 [N,H,W,3] in B, G, R order (written as R, G, B) or float32 [M,H,W] quantised as (v * 255).to(uint8) for
+  0 <= v <= 1.  plane_index: which source images to encode, in the order given (skipping, repeating and reordering are
+  fine); None = all of them.  One launch chain, one small copy of the sizes and offsets, one copy of exactly the bytes used.
+  with_meta: also return (sizes, offsets, adler) as the kernels wrote them, int64 / int64 / uint32 NumPy arrays [N]."""
+  kind, M, H, W, bpp = _png_source('png_deflate', src)
+  if not src.is_cuda:
+    raise rn.RecAttendError('png_deflate: src must be on the device (png_deflate_host takes host arrays)')
+  idx = None if plane_index is None else _png_planes('png_deflate', plane_index, M)
+  N = M if idx is None else int(idx.size)
+  stream, ws_bytes = png_deflate_bound(N, H, W, bpp)
+  key = str(src.device)
+  bufs = _PNG_BUFFERS.setdefault(key, [None, None])
+  for k, need in enumerate((ws_bytes, N * stream)):
+    if bufs[k] is None or bufs[k].numel() < need:
+      bufs[k] = None
+      bufs[k] = torch.empty((need,), dtype=torch.uint8, device=src.device)
+  ws, out = bufs
+  planes = None if idx is None else torch.from_numpy(idx).to(src.device)
+  # sizes int32 [N], adler uint32 [N], offsets uint64 [N] in ONE tensor of 4 N words, so that one copy brings them back
+  meta = torch.empty((4 * N,), dtype=torch.int32, device=src.device)
+  check(rn.lib().ra_png_deflate_u8(ptr(src), kind, M, N, H, W, ptr(planes), ptr(out), out.numel(), ptr(meta[:N]),
+                                   ptr(meta[2 * N:]), ptr(meta[N:2 * N]), ptr(ws), ws.numel(), rn.stream_ptr()),
+        'ra_png_deflate_u8')
+  host = meta.cpu().numpy()
+  sizes, offsets = host[:N].astype(np.int64), host[2 * N:].view(np.int64)
+  used = int(offsets[-1] + sizes[-1])
+  data = out[:used].cpu().numpy().tobytes()
+  streams = [data[int(o):int(o) + int(n)] for n, o in zip(sizes, offsets)]
+  return (streams, sizes, offsets.copy(), host[N:2 * N].view(np.uint32).copy()) if with_meta else streams
+
+
+def png_deflate_host(src, plane_index=None):
+  """png_deflate on host arrays through ra_png_deflate_host (plain sequential C++, no GPU call): src a NumPy array of one of
+  png_deflate's three kinds -> (list of streams, adler uint32 [N]).  What the device is compared with byte for byte."""
+  src = np.ascontiguousarray(src)
+  kind, M, H, W, bpp = _png_source('png_deflate_host', torch.from_numpy(src))
+  idx = None if plane_index is None else _png_planes('png_deflate_host', plane_index, M)
+  N = M if idx is None else int(idx.size)
+  stream, _ = png_deflate_bound(N, H, W, bpp)
+  out = np.zeros((N * stream,), dtype=np.uint8)
+  sizes, offsets, adler = np.zeros((N,), np.int32), np.zeros((N,), np.uint64), np.zeros((N,), np.uint32)
+  check(rn.lib().ra_png_deflate_host(ptr(src), kind, M, N, H, W, ptr(idx), ptr(out), out.size, ptr(sizes), ptr(offsets),
+                                     ptr(adler), None, 0), 'ra_png_deflate_host')
+  return [out[int(o):int(o) + int(n)].tobytes() for n, o in zip(sizes, offsets)], adler
+
+
 # ------------------------------------------------------------- mixed full sizes in one batch (KITTI): the ragged entry points
 # A batch of full-size images of different sizes is ONE flat tensor per per-pixel quantity plus its geometry: an int64 NumPy
 # array [B,3] of (offset, h, w) rows on the host — image b is the h x w rows, packed with pitch w, from element `offset` on

@@ -13,7 +13,13 @@ CVPPP's images and colour label files): uint8 [H,W,3] in cv2's BGR order from 8-
 (depths 1, 2, 4, 8) and grey files.  Interlaced files and 16-bit colour are refused.
 
 `encode_colour8` / `write_colour8` write such a BGR array as an 8-bit RGB file (what cv2.imwrite stores for the colour images
-of analysis.py's render analyzers), with the same one-IDAT, filter-0 layout as `encode_gray8`."""
+of analysis.py's render analyzers), with the same one-IDAT, filter-0 layout as `encode_gray8`.
+
+`encode_gray8_dev` / `encode_colour8_dev` / `write_gray8_dev` / `write_colour8_dev` take a BATCH of images in device memory
+and return / write one file per image: the deflate stage runs on the device (ra_ops.png_deflate, csrc/ra_png.hip — filter 0, a
+fixed-Huffman run code within each row), only the finished streams leave it, and `wrap` puts the container around a stream.
+The files decode to the same pixels as the host writers' files; their bytes differ and they are 2.5 x (flat colour) to 7 x (binary masks) as large as zlib
+level 6 makes them, so the output stages use them only when asked (device_png).  Only these four need the library and a GPU."""
 import struct
 import zlib
 
@@ -264,3 +270,54 @@ def write_colour8(path, img, level=6):
   with open(path, 'wb') as f:
     f.write(encode_colour8(img, level))
   return path
+
+
+def wrap(H, W, colour_type, zstream):
+  """The bytes of a PNG file around a finished zlib stream of its scanlines: signature, IHDR (bit depth 8, no interlace;
+  colour_type 0 = grey, 2 = RGB), one IDAT whose CRC-32 is taken here over the compressed bytes, IEND."""
+  if colour_type not in (0, 2) or H < 1 or W < 1:
+    raise ValueError('wrap: %d x %d, colour type %d (0 = grey or 2 = RGB, at least one pixel)' % (H, W, colour_type))
+  ihdr = struct.pack('>IIBBBBB', W, H, 8, colour_type, 0, 0, 0)
+  return SIGNATURE + _chunk(b'IHDR', ihdr) + _chunk(b'IDAT', bytes(zstream)) + _chunk(b'IEND', b'')
+
+
+def encode_gray8_dev(t, plane_index=None):
+  """t: a DEVICE tensor, uint8 [N,H,W] or float32 [M,H,W] (written as (t * 255).to(uint8), 0 <= t <= 1; plane_index then picks
+  the planes to write, in its order) -> the bytes of one PNG file per image, a list.  The deflate stage runs on the device
+  (ra_ops.png_deflate: filter 0, a run code within each row); the files decode to the pixels encode_gray8 stores, their
+  bytes differ.  Needs librecattend.so and a GPU."""
+  import ra_ops
+  if t.dim() != 3:
+    raise ValueError('encode_gray8_dev needs a uint8 or float32 [N,H,W] tensor, got %s' % (tuple(t.shape),))
+  H, W = int(t.shape[1]), int(t.shape[2])
+  return [wrap(H, W, 0, z) for z in ra_ops.png_deflate(t.contiguous(), plane_index)]
+
+
+def encode_colour8_dev(t):
+  """t: a DEVICE tensor uint8 [N,H,W,3] in cv2's B, G, R order -> the bytes of one 8-bit RGB PNG file per image, a list; the
+  device twin of encode_colour8 (see encode_gray8_dev)."""
+  import ra_ops
+  if t.dim() != 4 or t.shape[3] != 3:
+    raise ValueError('encode_colour8_dev needs a uint8 [N,H,W,3] tensor, got %s' % (tuple(t.shape),))
+  H, W = int(t.shape[1]), int(t.shape[2])
+  return [wrap(H, W, 2, z) for z in ra_ops.png_deflate(t.contiguous())]
+
+
+def _write_files(paths, files):
+  paths = list(paths)
+  if len(paths) != len(files):
+    raise ValueError('%d paths for %d images' % (len(paths), len(files)))
+  for path, data in zip(paths, files):
+    with open(path, 'wb') as f:
+      f.write(data)
+  return paths
+
+
+def write_gray8_dev(paths, t, plane_index=None):
+  """One file per image of encode_gray8_dev(t, plane_index), in the order of paths."""
+  return _write_files(paths, encode_gray8_dev(t, plane_index))
+
+
+def write_colour8_dev(paths, t):
+  """One file per image of encode_colour8_dev(t), in the order of paths."""
+  return _write_files(paths, encode_colour8_dev(t))
