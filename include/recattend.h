@@ -1133,6 +1133,62 @@ int ra_png_deflate_host(const void *src, int kind, int M, int N, int H, int W, c
                         size_t ws_bytes);
 
 /* ------------------------------------------------------------------------------------
+ * The second stream format of the device PNG encoder, "dynamic" (csrc/ra_png_dyn.hip): ONE dynamic-Huffman block per image with
+ * the rows bit-contiguous, the literal / length code built on the device from the image's own histogram.  A 1024 x 2048 binary
+ * mask takes about a fifth of the fixed format's bytes and 1.15 - 1.25 x what zlib level 6 makes of it (profiles/png_dynamic.txt).
+ * The fixed format above keeps its bytes and stays the default.
+ *
+ * THE STREAM (three implementations agree on it byte for byte: the kernels, ra_png_deflate_dyn_host, tests/png_dynamic_oracle.py)
+ *   scanline  as above: a filter-type byte 0, then W bytes (grey and float sources, d = 1) or 3 W bytes R, G, B (d = 3).
+ *   tokens    as above: the greedy run code at distance d within a scanline; no match leaves its row.
+ *   framing   78 01, then one block: BFINAL = 1, BTYPE = 10, the code header, the tokens of rows 0 .. H - 1 back to back at bit
+ *             granularity (no per-row padding, no per-row block), one end-of-block symbol, zero bits up to the byte boundary,
+ *             the big-endian Adler-32 of all scanline bytes.  No trailing empty block.
+ *   lengths   THE RULE, a function of a histogram alone (ra_png_huffman_lengths): the used symbols (count > 0) sorted by
+ *             (count, symbol index) are the leaves of a Huffman tree built with two queues — the sorted leaves and the internal
+ *             nodes in the order they are made; each step takes the two smallest heads, a leaf before an internal node on a
+ *             tie, and makes their sum a new internal node.  A symbol's length is its leaf's depth.  While the deepest leaf is
+ *             deeper than the limit, every count c > 0 is replaced by (c + 1) >> 1 and the tree is built again (this ends: once
+ *             every count is 1 the tree of at most 286 leaves is balanced at depth <= 9, of 19 leaves at depth <= 5).  Unused
+ *             symbols get length 0; a histogram with one used symbol gives it length 1.  Codes are canonical (RFC 1951 3.2.2).
+ *   literal / length code   over the 286 symbols from the image's histogram of its tokens, end-of-block counted once, limit 15.
+ *             The filter byte and end-of-block are always in use, so the code is complete.  HLIT = (the last used symbol + 1) - 257.
+ *   distance code   exactly one symbol in use, 0 for d = 1 and 2 for d = 3, always of length 1 (also in an image without a match):
+ *             HDIST + 1 = 1 resp. 3 lengths, {1} resp. {0, 0, 1}; a match's distance is the single bit 0.  zlib accepts this
+ *             incomplete one-code set.
+ *   code-length code   the HLIT + 257 literal / length lengths and the HDIST + 1 distance lengths form one sequence.  A run of
+ *             zeros is cut greedily: symbol 18 (11 .. 138 zeros) while at least 11 remain, then one symbol 17 (3 .. 10) if at
+ *             least 3 remain, then single zeros; a run may cross from the literal / length into the distance lengths.  Every
+ *             non-zero length is sent on its own; symbol 16 is not used.  The 19 code-length symbols are coded by THE RULE with
+ *             limit 7 over the histogram of that symbol sequence; HCLEN + 4 = the last used position in the RFC's order (16, 17,
+ *             18, 0, 8, 7, 9, 6, 10, 5, 11, 4, 12, 3, 13, 2, 14, 1, 15), at least 4.
+ *   bound     the header: 16 (78 01) + 3 + 14 + 19 * 3 + at most 7 bits per entry of the sequence of at most 289 = 2113 bits.  A
+ *             literal takes at most 15 bits, a match of L >= 3 bytes at most 15 + 5 + 1 = 21 <= 15 L, end-of-block at most 15:
+ *             a stream of H scanlines of n bytes takes at most ceil((2113 + 15 n H + 15) / 8) + 4 <= 270 + ceil(15 n H / 8)
+ *             bytes, and that is the bound everything sizes buffers with.
+ *
+ * ra_png_deflate_dyn_bound / ra_png_deflate_dyn_u8 / ra_png_deflate_dyn_host — the argument lists, kinds, plane list semantics,
+ *   refusals and RA_E_* codes of their fixed counterparts above, with this format's bound.  On success the bytes of `out` outside
+ *   the N streams are unspecified.  The workspace: per image a histogram (288 words) and a code table (1456 bytes), per row a
+ *   16-byte record, an 8-byte place and a worst-case slot of ceil(15 n / 8) + 4 bytes rounded up to 16.
+ *   The device entry: a stream-ordered clear of the histograms and five plain launches (histogram: a workgroup per scanline,
+ *   32-bit integer atomic adds; code: one workgroup per image builds the lengths, the codes and the header bits; encode: a
+ *   workgroup per scanline, token bits from the image's table in LDS — up to 70.2 KiB of LDS for the longest scanline; scan: a
+ *   workgroup per image, 64-bit bit places; place: owner-computes per destination dword with a funnel shift, no atomics, nothing
+ *   cleared), no allocation, no synchronisation, no workgroup waits for another.  The source is read twice.
+ * ra_png_huffman_lengths — HOST code, no GPU call: THE RULE on counts[0 .. n), the function the code kernel runs.  limit 7 or 15
+ *   (else RA_E_INVALID, as a NULL pointer), 1 <= n <= 286 and n <= 2^limit (else RA_E_SHAPE); lengths: n bytes.
+ * ---------------------------------------------------------------------------------- */
+int ra_png_deflate_dyn_bound(int N, int H, int W, int bpp, unsigned long long *stream_bytes, unsigned long long *workspace_bytes);
+int ra_png_deflate_dyn_u8(const void *src, int kind, int M, int N, int H, int W, const int *plane, unsigned char *out,
+                          size_t out_bytes, int *sizes, unsigned long long *offsets, unsigned int *adler, void *ws, size_t ws_bytes,
+                          void *stream);
+int ra_png_deflate_dyn_host(const void *src, int kind, int M, int N, int H, int W, const int *plane, unsigned char *out,
+                            size_t out_bytes, int *sizes, unsigned long long *offsets, unsigned int *adler, void *ws,
+                            size_t ws_bytes);
+int ra_png_huffman_lengths(const unsigned int *counts, int n, int limit, unsigned char *lengths);
+
+/* ------------------------------------------------------------------------------------
  * Evaluating the pre-stage fg_model (csrc/ra_fg_eval.hip).
  *
  * ra_fg_stats_f32 — the sums behind the six statistics the reference's Evaluator logs (fg_model_train.py:131-133), replacing

@@ -181,6 +181,13 @@ def cityscapes_line(img_file, label_id, score):
   return '{} {:d} {:f}\n'.format(img_file, int(label_id), float(score))
 
 
+def _png_code(code):
+  """device_png_code of the analyzers that write PNG files: the device encoder's stream format."""
+  if code not in ('fixed', 'dynamic'):
+    raise ValueError("device_png_code=%r (one of 'fixed', 'dynamic')" % (code,))
+  return code
+
+
 class RenderCityScapesOutputAnalyzer(object):
   """:196-267.  names: the file name of every image ('<run>_<seq>_<frame>...[.png]', what dataset.get_fname returns there),
   indexed by results['indices'].  stage() writes <folder>/<run>/<name>.txt — one line '<name>_<t:03d>.png <label_id> <score>'
@@ -188,14 +195,16 @@ class RenderCityScapesOutputAnalyzer(object):
   first '_'.  As in the reference the text file is opened anew by every stage() call: with several thresholds sharing one
   folder the last one staged is what remains.  device_png: the masks are compressed on the device (utils/png.write_gray8_dev:
   ONE ops.png_deflate call per stage() over the kept (ii, jj) planes of y_out, read as floats and never materialised as uint8)
-  instead of copied to the host plane by plane; the files decode to the same pixels, their bytes differ."""
+  instead of copied to the host plane by plane; the files decode to the same pixels, their bytes differ.  device_png_code:
+  the device encoder's stream format, 'fixed' or 'dynamic' (one dynamic-Huffman block per image: about a fifth of the bytes)."""
 
-  def __init__(self, folder, names, device_png=False):
+  def __init__(self, folder, names, device_png=False, device_png_code='fixed'):
     if folder is None:
       raise Exception('No output folder')
     self.folder = folder
     self.names = list(names)
     self.device_png = bool(device_png)
+    self.device_png_code = _png_code(device_png_code)
     self.labels = CITYSCAPES_LABELS
     self.written = []  # (text file, [(png file, label_id, score), ...]) per staged image
     os.makedirs(folder, exist_ok=True)
@@ -230,7 +239,7 @@ class RenderCityScapesOutputAnalyzer(object):
       self.written.append((text_fn, lines))
     if kept:
       planes = y_out.contiguous().to(torch.float32).view(-1, y_out.shape[2], y_out.shape[3])
-      png.write_gray8_dev([path for _, path in kept], planes, [k for k, _ in kept])
+      png.write_gray8_dev([path for _, path in kept], planes, [k for k, _ in kept], code=self.device_png_code)
 
   def finalize(self):
     pass
@@ -304,14 +313,16 @@ class CountAnalyzer(object):
 class _RenderBase(object):
   """names: the file name of every image, indexed by results['indices']; an image goes to <folder>/<name without .png>.png.
   device_png: the batch is compressed on the device (utils/png.write_colour8_dev, one ops.png_deflate call) and only the
-  streams are copied; the files decode to the same pixels, their bytes differ."""
+  streams are copied; the files decode to the same pixels, their bytes differ.  device_png_code: the device encoder's stream
+  format, 'fixed' or 'dynamic'."""
 
-  def __init__(self, folder, names, device_png=False):
+  def __init__(self, folder, names, device_png=False, device_png_code='fixed'):
     if folder is None:
       raise Exception('No output folder')
     self.folder = folder
     self.names = list(names)
     self.device_png = bool(device_png)
+    self.device_png_code = _png_code(device_png_code)
     self.written = []
     os.makedirs(folder, exist_ok=True)
 
@@ -319,7 +330,7 @@ class _RenderBase(object):
     from utils import png
     if self.device_png:
       paths = [os.path.join(self.folder, _stem(str(self.names[int(indices[ii])])) + '.png') for ii in range(img.shape[0])]
-      self.written += png.write_colour8_dev(paths, img)
+      self.written += png.write_colour8_dev(paths, img, code=self.device_png_code)
       return
     host = img.cpu().numpy()
     for ii in range(host.shape[0]):

@@ -92,6 +92,7 @@ def build_parser():
                  help='not a reference flag: compress the instance masks and the --render_instances images on the device (a run '
                       'code within each row, utils/png.write_*_dev) instead of copying every plane to the host for zlib; the '
                       'files decode to the same pixels, their bytes differ and they are larger')
+  cap.add_device_png_code(p)
   p.add_argument('--semantic_labels', default=None,
                  help='not a reference flag: name the instances from an external semantic segmentation given as label images (the '
                       '--lrr_seg path behind any segmenter): a folder with one <city>_<seq>_<frame>*.png per image name, or an '
@@ -266,6 +267,7 @@ def _full_size(data, dataset):
 
 def main(argv=None):
   args = build_parser().parse_args(argv)
+  png_code = cap.device_png_code(args)
   opt = make_opt(args)
   if args.input is None:
     raise RecAttendError('--input is required: an .npz with y_out_ins, s_out and y_out (the stage does not run the model)')
@@ -291,7 +293,8 @@ def main(argv=None):
   os.makedirs(out_dir, exist_ok=True)
   thresholds = opt['threshold_list']
   dpng = bool(getattr(args, 'device_png', False))
-  renders = [analysis.RenderCityScapesOutputAnalyzer(os.path.join(out_dir, 'cityscapes'), names, device_png=dpng) for _ in thresholds]
+  renders = [analysis.RenderCityScapesOutputAnalyzer(os.path.join(out_dir, 'cityscapes'), names, device_png=dpng, device_png_code=png_code)
+             for _ in thresholds]
   have_ids = 'gt_instance_ids' in data
   all_ids = data['gt_instance_ids'] if have_ids else None  # the largest array of the file: inflated once, not once per batch
   if have_ids and tuple(all_ids.shape) != (N, H, W):
@@ -301,13 +304,14 @@ def main(argv=None):
   img_render, counters, gt_render, have_y_gt = [], [], None, 'y_gt_full' in data
   if args.render_instances:
     folders = [os.path.join(out_dir, '{:02d}'.format(int(th * 100))) for th in thresholds]  # cityscapes_eval.py:65
-    img_render = [analysis.RenderInstanceAnalyzer(f, names, device_png=dpng) for f in folders]
+    img_render = [analysis.RenderInstanceAnalyzer(f, names, device_png=dpng, device_png_code=png_code) for f in folders]
     if 's_gt' in data:
       counters = [analysis.CountAnalyzer(os.path.join(f, 'count.csv')) for f in folders]
     else:
       print('--render_instances: no count.csv, --input has no s_gt to count against')
     if have_y_gt:
-      gt_render = analysis.RenderGroundtruthInstanceAnalyzer(os.path.join(out_dir, 'gt'), names, device_png=dpng)
+      gt_render = analysis.RenderGroundtruthInstanceAnalyzer(os.path.join(out_dir, 'gt'), names, device_png=dpng,
+                                                                   device_png_code=png_code)
   bs = max(1, min(opt['batch_size'], MAX_BATCH_ELEMS // max(1, T * H * W)))
   dev = torch.device('cuda', torch.cuda.current_device())
   up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)

@@ -142,3 +142,23 @@ def add_size_overrides(parser):
   parser.add_argument('--inp_height', type=int, default=None)
   parser.add_argument('--inp_width', type=int, default=None)
   parser.add_argument('--timespan', type=int, default=None)
+
+
+PNG_CODES = ('fixed', 'dynamic')
+
+
+def add_device_png_code(parser):
+  """--device_png_code (not a reference flag), for the command lines that have --device_png."""
+  parser.add_argument('--device_png_code', default=None, choices=PNG_CODES,
+                      help='not a reference flag: the stream format of --device_png.  fixed (the default): a fixed-Huffman block '
+                           'per row; dynamic: one dynamic-Huffman block per image with a code built on the device, about a fifth '
+                           'of the bytes for a mask (include/recattend.h, ra_png_deflate_dyn_*).  Needs --device_png')
+
+
+def device_png_code(args):
+  """The format --device_png_code names, 'fixed' when it is not given; given without --device_png it is an error."""
+  code = getattr(args, 'device_png_code', None)
+  if code is not None and not getattr(args, 'device_png', False):
+    raise ValueError('--device_png_code %s was given without --device_png: it selects the stream format of the device PNG '
+                     'encoder, which only --device_png turns on' % code)
+  return code or PNG_CODES[0]

@@ -72,6 +72,7 @@ def build_parser():
   p.add_argument('--render_orientation', action='store_true',
                  help='not a reference flag: write the orientation classes of the model\'s d_out as a colour-wheel image, masked '
                       'by fg_gt_full, into <output>/ori/; needs a model with add_orientation')
+  cap.add_device_png_code(p)
   p.add_argument('--device_png', action='store_true',
                  help='not a reference flag: compress the thresholded planes, the --render_gt planes and the --render_orientation '
                       'images on the device (a run code within each row, utils/png.write_*_dev); the files decode to the same '
@@ -99,11 +100,13 @@ def _write_planes(folder, names, planes):
     png.write_gray8(os.path.join(folder, os.path.splitext(os.path.basename(name))[0] + '.png'), img)
 
 
-def _write_planes_dev(folder, names, planes):
-  """_write_planes for uint8 [B,H,W] planes still on the DEVICE (--device_png): one png_deflate call for the batch."""
+def _write_planes_dev(folder, names, planes, code='fixed'):
+  """_write_planes for uint8 [B,H,W] planes still on the DEVICE (--device_png): one png_deflate call for the batch, in the
+  stream format `code` (--device_png_code)."""
   from utils import png
   os.makedirs(folder, exist_ok=True)
-  png.write_gray8_dev([os.path.join(folder, os.path.splitext(os.path.basename(name))[0] + '.png') for name in names], planes)
+  png.write_gray8_dev([os.path.join(folder, os.path.splitext(os.path.basename(name))[0] + '.png') for name in names], planes,
+                      code=code)
 
 
 def foreground_plane(y_out):
@@ -114,6 +117,7 @@ def foreground_plane(y_out):
 def main(argv=None):
   import torch
   args = build_parser().parse_args(argv)
+  args.device_png_code = cap.device_png_code(args)
   opt = make_opt(args)
   if args.model_id is None:
     raise Exception('You must provide model ID')  # cmd_args_parser.py:154-155
@@ -167,7 +171,7 @@ def main(argv=None):
                                                         ', '.join(n for n, _ in analysis.CITYSCAPES_LABELS)))
   if args.render_orientation:
     ori_render = analysis.RenderOrientationAnalyzer(os.path.join(out_dir, 'ori'), [os.path.basename(n) for n in names],
-                                                    device_png=args.device_png)
+                                                    device_png=args.device_png, device_png_code=args.device_png_code)
   fg_an = [analysis.ForegroundIOUAnalyzer('fg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]  # :62-69
   bg_an = [analysis.BackgroundIOUAnalyzer('bg_iou_all {:.2f}'.format(t), index=k) for k, t in enumerate(thresholds)]
   totals = [{'count_a': 0, 'sum_ab': 0, 'sum_b': 0, 'pixels': 0} for _ in thresholds]
@@ -178,7 +182,7 @@ def main(argv=None):
   up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
   to8 = lambda t: (t * 255.0).clamp(0, 255).to(torch.uint8).cpu().numpy()
   # --device_png: the same quantisation, the plane left on the device and compressed there
-  write_hard = (lambda f, n, t: _write_planes_dev(f, n, (t * 255.0).clamp(0, 255).to(torch.uint8))) if args.device_png else (
+  write_hard = (lambda f, n, t: _write_planes_dev(f, n, (t * 255.0).clamp(0, 255).to(torch.uint8), args.device_png_code)) if args.device_png else (
       lambda f, n, t: _write_planes(f, n, to8(t)))
   for b0 in range(0, N, bs):
     b1 = min(N, b0 + bs)
@@ -265,7 +269,7 @@ def _main_mixed(args, opt, data, model, out_dir, thresholds):
   up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
   to8 = lambda t: (t * 255.0).clamp(0, 255).to(torch.uint8).cpu().numpy()
   # --device_png: the same quantisation, the plane left on the device and compressed there
-  write_hard = (lambda f, n, t: _write_planes_dev(f, n, (t * 255.0).clamp(0, 255).to(torch.uint8))) if args.device_png else (
+  write_hard = (lambda f, n, t: _write_planes_dev(f, n, (t * 255.0).clamp(0, 255).to(torch.uint8), args.device_png_code)) if args.device_png else (
       lambda f, n, t: _write_planes(f, n, to8(t)))
   bs = max(1, opt['batch_size'])
   for b0 in range(0, N, bs):

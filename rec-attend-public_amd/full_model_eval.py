@@ -83,6 +83,7 @@ def build_parser():
                  help='not a reference flag: compress the files of --render, --render_gt_instances and --cityscapes_output on the '
                       'device (a run code within each row, utils/png.write_*_dev) instead of copying every plane to the host for '
                       'zlib; the files decode to the same pixels, their bytes differ and they are larger')
+  cap.add_device_png_code(p)
   p.add_argument('--in_flight', type=int, default=8, help='batches submitted to one GPU at a time (four decode concurrently, the rest queue behind them)')
   return p
 
@@ -104,6 +105,7 @@ def _id_path(keys):
 def main(argv=None):
   import torch
   args = build_parser().parse_args(argv)
+  cap.device_png_code(args)  # refused here, before any work, when it comes without --device_png
   if args.model_id is None:
     raise Exception('You must provide model ID')  # cmd_args_parser.py:154-155
   if args.cityscapes_output and not args.fg_model_id:
@@ -281,24 +283,26 @@ def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, anal
   import torch
   out_dir = os.path.join(args.output or restore, 'output_' + args.split.split(',')[0])
   img_render, counters, gt_render = {}, {}, None
-  dpng = bool(getattr(args, 'device_png', False))
+  dpng, png_code = bool(getattr(args, 'device_png', False)), cap.device_png_code(args)
   if getattr(args, 'render', False) or getattr(args, 'render_gt_instances', False):
     import analysis
     img_names = [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(data['x'].shape[0])]
     if args.render:
       for th in thresholds:
         folder = os.path.join(out_dir, '{:02d}'.format(int(th * 100)))  # full_model_eval.py:65
-        img_render[th] = analysis.RenderInstanceAnalyzer(folder, img_names, device_png=dpng)
+        img_render[th] = analysis.RenderInstanceAnalyzer(folder, img_names, device_png=dpng, device_png_code=png_code)
         counters[th] = analysis.CountAnalyzer(os.path.join(folder, 'count.csv' if world == 1 else 'count_rank%d.csv' % rank))
     if args.render_gt_instances:
-      gt_render = analysis.RenderGroundtruthInstanceAnalyzer(os.path.join(out_dir, 'gt'), img_names, device_png=dpng)
+      gt_render = analysis.RenderGroundtruthInstanceAnalyzer(os.path.join(out_dir, 'gt'), img_names, device_png=dpng,
+                                                                   device_png_code=png_code)
   cs_dir, sems, render = getattr(args, 'cityscapes_output', None), {}, None
   if cs_dir:
     import analysis
     import cityscapes_eval
     n_all = data['x'].shape[0]
     render = analysis.RenderCityScapesOutputAnalyzer(
-        cs_dir, [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(n_all)], device_png=dpng)
+        cs_dir, [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(n_all)], device_png=dpng,
+        device_png_code=png_code)
     if 'full_size' in data:
       cs_size = (int(data['full_size'][0]), int(data['full_size'][1]))
     else:

@@ -2265,10 +2265,23 @@ def render_orientation(d, mask, size=None):
 _PNG_BUFFERS = {}  # device -> [workspace, out]: uint8 tensors that only grow, reused by every call on that device
 
 
-def png_deflate_bound(N, H, W, bpp):
-  """(bytes of one stream at most, bytes of workspace for N images) of ra_png_deflate_bound; bpp 1 (grey, float) or 3."""
+PNG_CODES = {'fixed': 'ra_png_deflate', 'dynamic': 'ra_png_deflate_dyn'}  # the stream format -> its entry points' prefix
+
+
+def _png_entry(who, code, suffix):
+  """(the C entry point of the stream format `code`, its name)."""
+  if code not in PNG_CODES:
+    raise rn.RecAttendError("%s: code=%r (one of 'fixed', 'dynamic')" % (who, code))
+  name = PNG_CODES[code] + suffix
+  return getattr(rn.lib(), name), name
+
+
+def png_deflate_bound(N, H, W, bpp, code='fixed'):
+  """(bytes of one stream at most, bytes of workspace for N images) of ra_png_deflate_bound, or of ra_png_deflate_dyn_bound
+  with code='dynamic'; bpp 1 (grey, float) or 3."""
+  fn, name = _png_entry('png_deflate_bound', code, '_bound')
   stream, ws = C.c_ulonglong(0), C.c_ulonglong(0)
-  check(rn.lib().ra_png_deflate_bound(int(N), int(H), int(W), int(bpp), C.addressof(stream), C.addressof(ws)), 'ra_png_deflate_bound')
+  check(fn(int(N), int(H), int(W), int(bpp), C.addressof(stream), C.addressof(ws)), name)
   return int(stream.value), int(ws.value)
 
 
@@ -2299,19 +2312,21 @@ def _png_planes(who, plane_index, M):
   return np.ascontiguousarray(idx.astype(np.int32))
 
 
-def png_deflate(src, plane_index=None, with_meta=False):
+def png_deflate(src, plane_index=None, with_meta=False, code='fixed'):
   """The zlib streams of PNG image data (include/recattend.h, ra_png_deflate_u8: filter 0, one fixed-Huffman run-coded
-  segment per scanline) for a batch of images on the device -> a list of bytes, one stream per image.  src: uint8 [N,H,W]
+  segment per scanline; code='dynamic': ra_png_deflate_dyn_u8, one dynamic-Huffman block per image, about a fifth of the bytes
+  for a mask) for a batch of images on the device -> a list of bytes, one stream per image.  src: uint8 [N,H,W]
   (grey), uint8 [N,H,W,3] in B, G, R order (written as R, G, B) or float32 [M,H,W] quantised as (v * 255).to(uint8) for
   0 <= v <= 1.  plane_index: which source images to encode, in the order given (skipping, repeating and reordering are
   fine); None = all of them.  One launch chain, one small copy of the sizes and offsets, one copy of exactly the bytes used.
   with_meta: also return (sizes, offsets, adler) as the kernels wrote them, int64 / int64 / uint32 NumPy arrays [N]."""
+  fn, name = _png_entry('png_deflate', code, '_u8')
   kind, M, H, W, bpp = _png_source('png_deflate', src)
   if not src.is_cuda:
     raise rn.RecAttendError('png_deflate: src must be on the device (png_deflate_host takes host arrays)')
   idx = None if plane_index is None else _png_planes('png_deflate', plane_index, M)
   N = M if idx is None else int(idx.size)
-  stream, ws_bytes = png_deflate_bound(N, H, W, bpp)
+  stream, ws_bytes = png_deflate_bound(N, H, W, bpp, code)
   key = str(src.device)
   bufs = _PNG_BUFFERS.setdefault(key, [None, None])
   for k, need in enumerate((ws_bytes, N * stream)):
@@ -2322,9 +2337,8 @@ def png_deflate(src, plane_index=None, with_meta=False):
   planes = None if idx is None else torch.from_numpy(idx).to(src.device)
   # sizes int32 [N], adler uint32 [N], offsets uint64 [N] in ONE tensor of 4 N words, so that one copy brings them back
   meta = torch.empty((4 * N,), dtype=torch.int32, device=src.device)
-  check(rn.lib().ra_png_deflate_u8(ptr(src), kind, M, N, H, W, ptr(planes), ptr(out), out.numel(), ptr(meta[:N]),
-                                   ptr(meta[2 * N:]), ptr(meta[N:2 * N]), ptr(ws), ws.numel(), rn.stream_ptr()),
-        'ra_png_deflate_u8')
+  check(fn(ptr(src), kind, M, N, H, W, ptr(planes), ptr(out), out.numel(), ptr(meta[:N]), ptr(meta[2 * N:]), ptr(meta[N:2 * N]),
+           ptr(ws), ws.numel(), rn.stream_ptr()), name)
   host = meta.cpu().numpy()
   sizes, offsets = host[:N].astype(np.int64), host[2 * N:].view(np.int64)
   used = int(offsets[-1] + sizes[-1])
@@ -2333,19 +2347,29 @@ def png_deflate(src, plane_index=None, with_meta=False):
   return (streams, sizes, offsets.copy(), host[N:2 * N].view(np.uint32).copy()) if with_meta else streams
 
 
-def png_deflate_host(src, plane_index=None):
-  """png_deflate on host arrays through ra_png_deflate_host (plain sequential C++, no GPU call): src a NumPy array of one of
-  png_deflate's three kinds -> (list of streams, adler uint32 [N]).  What the device is compared with byte for byte."""
+def png_deflate_host(src, plane_index=None, code='fixed'):
+  """png_deflate on host arrays through ra_png_deflate_host / ra_png_deflate_dyn_host (plain sequential C++, no GPU call): src a
+  NumPy array of one of png_deflate's three kinds -> (list of streams, adler uint32 [N]).  What the device is compared with byte
+  for byte."""
+  fn, name = _png_entry('png_deflate_host', code, '_host')
   src = np.ascontiguousarray(src)
   kind, M, H, W, bpp = _png_source('png_deflate_host', torch.from_numpy(src))
   idx = None if plane_index is None else _png_planes('png_deflate_host', plane_index, M)
   N = M if idx is None else int(idx.size)
-  stream, _ = png_deflate_bound(N, H, W, bpp)
+  stream, _ = png_deflate_bound(N, H, W, bpp, code)
   out = np.zeros((N * stream,), dtype=np.uint8)
   sizes, offsets, adler = np.zeros((N,), np.int32), np.zeros((N,), np.uint64), np.zeros((N,), np.uint32)
-  check(rn.lib().ra_png_deflate_host(ptr(src), kind, M, N, H, W, ptr(idx), ptr(out), out.size, ptr(sizes), ptr(offsets),
-                                     ptr(adler), None, 0), 'ra_png_deflate_host')
+  check(fn(ptr(src), kind, M, N, H, W, ptr(idx), ptr(out), out.size, ptr(sizes), ptr(offsets), ptr(adler), None, 0), name)
   return [out[int(o):int(o) + int(n)].tobytes() for n, o in zip(sizes, offsets)], adler
+
+
+def png_huffman_lengths(counts, limit=15):
+  """ra_png_huffman_lengths (host code): the length-limited Huffman code lengths of the dynamic format's rule for a histogram
+  of up to 286 counts, limit 7 or 15 -> uint8 [n]."""
+  counts = np.ascontiguousarray(counts, dtype=np.uint32).reshape(-1)
+  lengths = np.zeros((counts.size,), np.uint8)
+  check(rn.lib().ra_png_huffman_lengths(ptr(counts), int(counts.size), int(limit), ptr(lengths)), 'ra_png_huffman_lengths')
+  return lengths
 
 
 # ------------------------------------------------------------- mixed full sizes in one batch (KITTI): the ragged entry points

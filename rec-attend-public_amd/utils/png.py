@@ -19,7 +19,9 @@ of analysis.py's render analyzers), with the same one-IDAT, filter-0 layout as `
 and return / write one file per image: the deflate stage runs on the device (ra_ops.png_deflate, csrc/ra_png.hip — filter 0, a
 fixed-Huffman run code within each row), only the finished streams leave it, and `wrap` puts the container around a stream.
 The files decode to the same pixels as the host writers' files; their bytes differ and they are 2.5 x (flat colour) to 7 x (binary masks) as large as zlib
-level 6 makes them, so the output stages use them only when asked (device_png).  Only these four need the library and a GPU."""
+level 6 makes them, so the output stages use them only when asked (device_png).  code='dynamic' selects the encoder's second
+stream format, one dynamic-Huffman block per image with a code built on the device: a mask then takes about a fifth of the fixed
+format's bytes, 1.15 - 1.25 x zlib level 6 (profiles/png_dynamic.txt).  Only these four need the library and a GPU."""
 import struct
 import zlib
 
@@ -281,26 +283,26 @@ def wrap(H, W, colour_type, zstream):
   return SIGNATURE + _chunk(b'IHDR', ihdr) + _chunk(b'IDAT', bytes(zstream)) + _chunk(b'IEND', b'')
 
 
-def encode_gray8_dev(t, plane_index=None):
+def encode_gray8_dev(t, plane_index=None, code='fixed'):
   """t: a DEVICE tensor, uint8 [N,H,W] or float32 [M,H,W] (written as (t * 255).to(uint8), 0 <= t <= 1; plane_index then picks
   the planes to write, in its order) -> the bytes of one PNG file per image, a list.  The deflate stage runs on the device
   (ra_ops.png_deflate: filter 0, a run code within each row); the files decode to the pixels encode_gray8 stores, their
-  bytes differ.  Needs librecattend.so and a GPU."""
+  bytes differ.  code: the stream format, 'fixed' or 'dynamic' (ra_ops.png_deflate).  Needs librecattend.so and a GPU."""
   import ra_ops
   if t.dim() != 3:
     raise ValueError('encode_gray8_dev needs a uint8 or float32 [N,H,W] tensor, got %s' % (tuple(t.shape),))
   H, W = int(t.shape[1]), int(t.shape[2])
-  return [wrap(H, W, 0, z) for z in ra_ops.png_deflate(t.contiguous(), plane_index)]
+  return [wrap(H, W, 0, z) for z in ra_ops.png_deflate(t.contiguous(), plane_index, code=code)]
 
 
-def encode_colour8_dev(t):
+def encode_colour8_dev(t, code='fixed'):
   """t: a DEVICE tensor uint8 [N,H,W,3] in cv2's B, G, R order -> the bytes of one 8-bit RGB PNG file per image, a list; the
   device twin of encode_colour8 (see encode_gray8_dev)."""
   import ra_ops
   if t.dim() != 4 or t.shape[3] != 3:
     raise ValueError('encode_colour8_dev needs a uint8 [N,H,W,3] tensor, got %s' % (tuple(t.shape),))
   H, W = int(t.shape[1]), int(t.shape[2])
-  return [wrap(H, W, 2, z) for z in ra_ops.png_deflate(t.contiguous())]
+  return [wrap(H, W, 2, z) for z in ra_ops.png_deflate(t.contiguous(), code=code)]
 
 
 def _write_files(paths, files):
@@ -313,11 +315,11 @@ def _write_files(paths, files):
   return paths
 
 
-def write_gray8_dev(paths, t, plane_index=None):
-  """One file per image of encode_gray8_dev(t, plane_index), in the order of paths."""
-  return _write_files(paths, encode_gray8_dev(t, plane_index))
+def write_gray8_dev(paths, t, plane_index=None, code='fixed'):
+  """One file per image of encode_gray8_dev(t, plane_index, code), in the order of paths."""
+  return _write_files(paths, encode_gray8_dev(t, plane_index, code))
 
 
-def write_colour8_dev(paths, t):
-  """One file per image of encode_colour8_dev(t), in the order of paths."""
-  return _write_files(paths, encode_colour8_dev(t))
+def write_colour8_dev(paths, t, code='fixed'):
+  """One file per image of encode_colour8_dev(t, code), in the order of paths."""
+  return _write_files(paths, encode_colour8_dev(t, code))
