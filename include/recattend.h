@@ -1311,6 +1311,50 @@ int ra_fg_sweep_counts_ragged_f32(const float *src, const unsigned char *gt, siz
                                   unsigned long long *counts, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * Pictures on the id path: the winner map out of the counting pass (csrc/ra_instance_eval.hip) and the kernels that paint from
+ * it (csrc/ra_instance_paint.hip).  They replace, where the evaluator runs from instance-id images and no [B,T,Hf,Wf] mask
+ * exists, analysis.py:137-147 (RenderInstanceAnalyzer), analysis.py:166-187 (RenderGroundtruthInstanceAnalyzer) and the masks
+ * full_model_eval.py:65-79,139-140 hands them.
+ *
+ * ra_instance_eval_counts_map_f32 / ra_instance_eval_counts_map_ragged_f32 — ra_instance_eval_counts_f32 /
+ *   ra_instance_eval_counts_ragged_f32, the same arguments and the same inter / area_b bit for bit, plus map: uint16 [B,Hf,Wf],
+ *   or uint16 [total] flat at gt_ids' offsets (elements between the images are not written).  One word per pixel: n << 8 | t*,
+ *   t* = the instance that holds the pixel's FIRST maximum m, n = how many of the call's thresholds, in ascending order, m
+ *   exceeds with strict > (0 where fg masks the pixel); the whole word is 0 where n == 0, so the arg-max over values nobody
+ *   reads is no part of the contract.  Threshold k AS GIVEN is passed iff n > pos[k].
+ * ra_instance_eval_threshold_pos — pos[k] = how many of the K thresholds lie strictly below thresholds[k]: host arithmetic,
+ *   the order the counting pass itself uses.  The checks on K and the thresholds are the counting pass's.
+ * ra_instance_paint_u8 / ra_instance_paint_ragged_u8 — map as above; pos: Kp host ints, 1 <= Kp <= RA_INS_EVAL_MAX_K, each
+ *   0 .. RA_INS_EVAL_MAX_K - 1; colour uint8 [B,Kp,T,3] in the memory order of the picture (B, G, R).  out: uint8
+ *   [Kp,B,Hf,Wf,3], or [Kp,total,3] with image b of picture k from byte 3 * (k * total + offset_b) on.  A pixel of picture k
+ *   is colour[b,k,t*] where n > pos[k], else 0 (also where t* >= T, which the counting pass never writes): the reference's
+ *   sum over t of uint8(mask_t) * colour_t on disjoint masks.  remove_tiny is the caller's: a zeroed colour row.
+ * ra_gt_paint_u8 / ra_gt_paint_ragged_u8 — gt_ids int32 [B,Hf,Wf] or [total]; inst_id int32 [B,T]; colour uint8 [B,T,3];
+ *   out uint8 [B,Hf,Wf,3] or [total,3]: the colour of the first slot whose inst_id equals the pixel's id, 0 where no slot
+ *   lists it or the id is negative — RA_RENDER_FIRST on the disjoint planes the id image defines, without the planes.
+ * 1 <= T <= RA_LABELS_MAX_T, Hf * Wf (h * w) <= 2^24, B <= 65535, else RA_E_SHAPE; the ragged forms check the table as
+ * every ragged entry does and name the image.  A lane's 4 pixels move as 8 (map) or 16 (ids) bytes in and 12 bytes out where
+ * the image's first element and its pixel count are multiples of 4 (ragged: w % 4 == 0 and offset % 4 == 0) and the pointers
+ * are aligned for it (picture k of a ragged batch also needs k * total % 4 == 0), per image; as elements and bytes otherwise.
+ * ---------------------------------------------------------------------------------- */
+int ra_instance_eval_counts_map_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg, int B, int T,
+                                    int Hs, int Ws, int Hf, int Wf, int morph, const float *thresholds, int K, int *inter,
+                                    int *area_b, unsigned short *map, void *stream);
+int ra_instance_eval_counts_map_ragged_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg,
+                                           size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev, int B, int T, int Hs,
+                                           int Ws, int morph, const float *thresholds, int K, int *inter, int *area_b,
+                                           unsigned short *map, void *stream);
+int ra_instance_eval_threshold_pos(const float *thresholds, int K, int *pos);
+int ra_instance_paint_u8(const unsigned short *map, int B, int Hf, int Wf, const int *pos, int Kp, int T,
+                         const unsigned char *colour, unsigned char *out, void *stream);
+int ra_instance_paint_ragged_u8(const unsigned short *map, size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev, int B,
+                                const int *pos, int Kp, int T, const unsigned char *colour, unsigned char *out, void *stream);
+int ra_gt_paint_u8(const int *gt_ids, const int *inst_id, int B, int T, int Hf, int Wf, const unsigned char *colour,
+                   unsigned char *out, void *stream);
+int ra_gt_paint_ragged_u8(const int *gt_ids, size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev, const int *inst_id,
+                          int B, int T, const unsigned char *colour, unsigned char *out, void *stream);
+
+/* ------------------------------------------------------------------------------------
  * Training the pre-stage fg_model (csrc/ra_fg_loss.hip).
  *
  * ra_fg_loss_bwd_f32 — the gradient of the loss head of fg_model.py:196-248 with respect to the logits [npix, nsc + no]; the

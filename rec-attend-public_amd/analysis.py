@@ -292,7 +292,8 @@ def groundtruth_colours(iou_pairwise):
 
 class CountAnalyzer(object):
   """:67-92.  The file starts with the header line; stage() appends '<index>,<count out>,<count gt>' per image, from
-  f_count_out(y_out).sum(1) (the output planes that have a pixel) and s_gt.sum(1)."""
+  f_count_out(y_out).sum(1) (the output planes that have a pixel) and s_gt.sum(1).  Results of the id path hold no y_out: there
+  the planes that have a pixel are the non-zero entries of results['_metrics']['sizes'] [B,T], the counted areas."""
 
   def __init__(self, fname):
     self.fname = fname
@@ -300,7 +301,10 @@ class CountAnalyzer(object):
       f.write('Image ID,Count Out,Count GT\n')  # :72
 
   def stage(self, results):
-    count_out = f_count_out(results['y_out']).sum(dim=1).cpu().numpy()
+    if 'y_out' not in results and 'sizes' in results.get('_metrics', {}):
+      count_out = (results['_metrics']['sizes'] > 0).sum(dim=1).cpu().numpy()
+    else:
+      count_out = f_count_out(results['y_out']).sum(dim=1).cpu().numpy()
     count_gt = results['s_gt'].sum(dim=1).cpu().numpy()
     with open(self.fname, 'a') as f:
       for ii, idx in enumerate(results['indices']):
@@ -338,6 +342,20 @@ class _RenderBase(object):
       png.write_colour8(path, host[ii])
       self.written.append(path)
 
+  def _write_pictures(self, picture, indices):
+    """results['picture'] of the id path, painted already (ops.paint_instances / ops.paint_groundtruth): a uint8 [B,H,W,3]
+    batch, or — a batch of mixed sizes — a list of [h,w,3] views.  With device_png the images of a list are encoded one
+    write_colour8_dev call per group of equal size."""
+    if not isinstance(picture, (list, tuple)):
+      return self._write(picture, indices)
+    if len(picture) != len(indices):
+      raise ops.rn.RecAttendError('%s: %d pictures for %d indices' % (type(self).__name__, len(picture), len(indices)))
+    groups = {}
+    for ii, p in enumerate(picture):
+      groups.setdefault(tuple(p.shape) if self.device_png else ii, []).append(ii)
+    for members in groups.values():
+      self._write(torch.stack([picture[ii] for ii in members]), [indices[ii] for ii in members])
+
   def finalize(self):
     pass
 
@@ -345,9 +363,12 @@ class _RenderBase(object):
 class RenderInstanceAnalyzer(_RenderBase):
   """:95-153: one colour image per input, every plane of results['y_out'] [B,T,H,W] in its own colour (INSTANCE_CMAP[t % 22]),
   summed in uint8 as the reference sums them (overlaps wrap).  One launch of ops.render_instances; the file's R, G, B is
-  the cmap row (the reference swaps before cv2.imwrite)."""
+  the cmap row (the reference swaps before cv2.imwrite).  Results that carry 'picture' in place of 'y_out' (the id path) are
+  written as they are."""
 
   def stage(self, results):
+    if 'picture' in results:
+      return self._write_pictures(results['picture'], results['indices'])
     self._write(ops.render_instances(results['y_out']), results['indices'])
 
 
@@ -359,6 +380,8 @@ class RenderGroundtruthInstanceAnalyzer(_RenderBase):
 
   def stage(self, results):
     import numpy as np
+    if 'picture' in results:  # the id path: painted from the id image with groundtruth_colours of the same iou_pairwise
+      return self._write_pictures(results['picture'], results['indices'])
     if 'iou_pairwise' not in results:
       results['iou_pairwise'] = f_iou_pairwise(results['y_out'], results['y_gt'])
     y_gt = results['y_gt']

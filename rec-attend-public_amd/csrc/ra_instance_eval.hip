@@ -35,6 +35,12 @@
 // that ra_eval_metrics_f32 takes.
 // Mixed full sizes in one batch (ra_instance_eval_counts_ragged_f32): count_kernel is a template over the geometry source of
 // ra_ragged.h — gt_ids and fg flat, image b at its table entry, read once per workgroup — and the same body runs either form.
+// The winner map (ra_instance_eval_counts_map_f32 / _ragged_f32): count_kernel<.., MAP = true> also writes what it holds in
+// registers when it increments — (t*, n) per pixel, as ONE uint16 word n << 8 | t* (0 where n == 0) at the pixel's element of
+// gt_ids.  Every thresholded mask of every threshold is in it: threshold k as given is passed iff n > Order::pos[k].  A lane's 4
+// pixels of a row leave as one 8-byte store where W % 4 == 0, the image starts at a multiple of 4 elements and map is 8-byte
+// aligned (decided per image, as the loads are), as element stores otherwise.  No atomics, no LDS; the instantiations without
+// the map are the ones the file had before.
 #include <cstdint>
 
 #include "ra_common.h"
@@ -46,6 +52,7 @@ namespace inse {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));
+typedef unsigned u32x2 __attribute__((ext_vector_type(2)));
 
 constexpr int kMaxK = RA_INS_EVAL_MAX_K;  // 16
 constexpr int kMaxT = RA_LABELS_MAX_T;    // 32
@@ -135,10 +142,11 @@ __device__ __forceinline__ void add4(int *base, int (&key)[4]) {
 // vec: W % 4 == 0 and gt_ids 16-byte, fg 4-byte aligned — a lane's 4 ids are one 16-byte load, its 4 fg bytes one 32-bit load
 // GEO: geo::Uniform (gt_ids and fg are [B,H,W]) or geo::Ragged (both flat, image b at its table entry: its own H, W in the
 // resize, in reflect101, in the in-image test and in the tile walk; a workgroup beyond its image's tiles adds nothing).
-template <bool MORPH, class GEO>
+// MAP: map [as gt_ids] takes n << 8 | t* of every pixel of the image (0 where n == 0); mvec: its 4 words per lane are one store.
+template <bool MORPH, class GEO, bool MAP>
 __global__ __launch_bounds__(256) void count_kernel(const float *yc, const int *gt_ids, const int *inst_id,
                                                      const unsigned char *fg, int T, int Hs, int Ws, const GEO src,
-                                                     const Thresholds thr, int K, int *inter, int *area_b) {
+                                                     const Thresholds thr, int K, int *inter, int *area_b, unsigned short *map) {
   using G = Geo<MORPH>;
   __shared__ __attribute__((aligned(16))) float rs[G::kRH * G::kRW];
   __shared__ __attribute__((aligned(16))) float fl[MORPH ? G::kFH * G::kFW : 4];
@@ -156,6 +164,8 @@ __global__ __launch_bounds__(256) void count_kernel(const float *yc, const int *
   const int H = im.h, W = im.w, vec = im.vec;
   const int *gp = gt_ids + im.off;
   const unsigned char *fp = fg ? fg + im.off : nullptr;
+  unsigned short *mp = MAP ? map + im.off : nullptr;
+  const bool mvec = MAP && W % 4 == 0 && im.off % 4 == 0 && (reinterpret_cast<uintptr_t>(map) & 7) == 0;
   const int ntx = tiles_x(W), ntiles = tiles(H, W);
 
   for (int tile = blockIdx.x; tile < ntiles; tile += gridDim.x) {
@@ -237,6 +247,7 @@ __global__ __launch_bounds__(256) void count_kernel(const float *yc, const int *
           if (want == id[j] && want >= 0) slot[j] = s;
       }
       int key_h[4], key_a[4];
+      unsigned word[4];
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
         const bool in = row_in && c + j < W;
@@ -244,11 +255,22 @@ __global__ __launch_bounds__(256) void count_kernel(const float *yc, const int *
 #pragma unroll
         for (int k = 0; k < kMaxK; ++k) n += best[half][j] > sthr[k] ? 1 : 0;
         if (f[j] == 0u) n = 0;
+        word[j] = n > 0 ? (unsigned)(n << 8 | arg[half][j]) : 0u;
         key_h[j] = in && n > 0 ? ((n - 1) * T + arg[half][j]) * T1 + slot[j] : -1;
         key_a[j] = in && slot[j] < T ? slot[j] : -1;
       }
       add4(hist, key_h);
       add4(hist + nbins, key_a);
+      if (MAP) {
+        if (mvec) {
+          if (row_in && c < W)  // W % 4 == 0: c + 3 < W, and (off + r W + c) * 2 bytes is a multiple of 8
+            *reinterpret_cast<u32x2 *>(mp + (size_t)r * W + c) = u32x2{word[0] | word[1] << 16, word[2] | word[3] << 16};
+        } else {
+#pragma unroll
+          for (int j = 0; j < 4; ++j)
+            if (row_in && c + j < W) mp[(size_t)r * W + c + j] = (unsigned short)word[j];
+        }
+      }
     }
   }
   __syncthreads();
@@ -280,13 +302,13 @@ __global__ __launch_bounds__(256) void finish_kernel(int *inter, const Order ord
 }
 
 
-template <bool MORPH, class GEO>
+template <bool MORPH, class GEO, bool MAP>
 void launch_count(dim3 grid, size_t lds, hipStream_t st, const float *yc, const int *gt_ids, const int *inst_id,
                   const unsigned char *fg, int T, int Hs, int Ws, const GEO &src, const Thresholds &thr, int K, int *inter,
-                  int *area_b) {
-  static const MaxDynamicLds raise{count_kernel<MORPH, GEO>, hist_ints(kMaxK, kMaxT) * sizeof(int)};
-  hipLaunchKernelGGL((count_kernel<MORPH, GEO>), grid, dim3(256), lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K, inter,
-                     area_b);
+                  int *area_b, unsigned short *map) {
+  static const MaxDynamicLds raise{count_kernel<MORPH, GEO, MAP>, hist_ints(kMaxK, kMaxT) * sizeof(int)};
+  hipLaunchKernelGGL((count_kernel<MORPH, GEO, MAP>), grid, dim3(256), lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K,
+                     inter, area_b, map);
 }
 
 // The checks both entry points share, and the thresholds sorted for the kernel.
@@ -311,11 +333,11 @@ inline int prepare(const char *who, int B, int T, int Hs, int Ws, const float *t
   return 0;
 }
 
-// clear -> count -> finish on one stream; grid_x workgroups per image.
+// clear -> count -> finish on one stream; grid_x workgroups per image.  map: NULL, or the winner map the count pass also writes.
 template <class GEO>
 int launch_all(const char *who, const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg, int B, int T,
                int Hs, int Ws, const GEO &src, int gx, int morph, const Thresholds &thr, const Order &order, int K, int *inter,
-               int *area_b, hipStream_t st) {
+               int *area_b, unsigned short *map, hipStream_t st) {
   char what[96];
   const auto status = [&](const char *stage) {
     snprintf(what, sizeof(what), "%s%s", who, stage);
@@ -327,10 +349,14 @@ int launch_all(const char *who, const float *yc, const int *gt_ids, const int *i
     return status(" (clear)");
   const dim3 grid(gx, B);
   const size_t lds = hist_ints(K, T) * sizeof(int);
-  if (morph)
-    launch_count<true>(grid, lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K, inter, area_b);
+  if (morph && map)
+    launch_count<true, GEO, true>(grid, lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K, inter, area_b, map);
+  else if (morph)
+    launch_count<true, GEO, false>(grid, lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K, inter, area_b, nullptr);
+  else if (map)
+    launch_count<false, GEO, true>(grid, lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K, inter, area_b, map);
   else
-    launch_count<false>(grid, lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K, inter, area_b);
+    launch_count<false, GEO, false>(grid, lds, st, yc, gt_ids, inst_id, fg, T, Hs, Ws, src, thr, K, inter, area_b, nullptr);
   if (int rc = status("")) return rc;
   hipLaunchKernelGGL(finish_kernel, dim3(ceil_div(B * TT1, 256)), dim3(256), 0, st, inter, order, K, TT1, B * TT1);
   return status(" (finish)");
@@ -341,10 +367,11 @@ int launch_all(const char *who, const float *yc, const int *gt_ids, const int *i
 
 using namespace ra;
 
-extern "C" int ra_instance_eval_counts_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg,
-                                           int B, int T, int Hs, int Ws, int Hf, int Wf, int morph, const float *thresholds,
-                                           int K, int *inter, int *area_b, void *stream) {
-  const char *who = "ra_instance_eval_counts_f32";
+namespace {
+
+int counts_uniform(const char *who, const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg, int B, int T,
+                   int Hs, int Ws, int Hf, int Wf, int morph, const float *thresholds, int K, int *inter, int *area_b,
+                   unsigned short *map, void *stream) {
   if (!yc || !gt_ids || !inst_id || !thresholds || !inter || !area_b || B <= 0 || Hs <= 0 || Ws <= 0 || Hf <= 0 || Wf <= 0)
     return fail(RA_E_INVALID, "%s: bad argument", who);
   if (K < 1 || K > inse::kMaxK) return fail(RA_E_SHAPE, "%s: K=%d thresholds (1 .. %d)", who, K, inse::kMaxK);
@@ -357,14 +384,12 @@ extern "C" int ra_instance_eval_counts_f32(const float *yc, const int *gt_ids, c
   if (int rc = inse::prepare(who, B, T, Hs, Ws, thresholds, K, thr, order)) return rc;
   const int vec = Wf % 4 == 0 && (reinterpret_cast<uintptr_t>(gt_ids) & 15) == 0 && (!fg || (reinterpret_cast<uintptr_t>(fg) & 3) == 0);
   return inse::launch_all(who, yc, gt_ids, inst_id, fg, B, T, Hs, Ws, geo::Uniform{Hf, Wf, vec}, inse::grid_x(B, Hf, Wf), morph, thr,
-                          order, K, inter, area_b, as_stream(stream));
+                          order, K, inter, area_b, map, as_stream(stream));
 }
 
-extern "C" int ra_instance_eval_counts_ragged_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg,
-                                                  size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev, int B, int T,
-                                                  int Hs, int Ws, int morph, const float *thresholds, int K, int *inter,
-                                                  int *area_b, void *stream) {
-  const char *who = "ra_instance_eval_counts_ragged_f32";
+int counts_ragged(const char *who, const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg, size_t total,
+                  const ra_image_geo *geo, ra_image_geo *geo_dev, int B, int T, int Hs, int Ws, int morph, const float *thresholds,
+                  int K, int *inter, int *area_b, unsigned short *map, void *stream) {
   if (!yc || !gt_ids || !inst_id || !geo || !geo_dev || !thresholds || !inter || !area_b || B <= 0 || Hs <= 0 || Ws <= 0)
     return fail(RA_E_INVALID, "%s: bad argument", who);
   if ((long long)Hs * Ws >= (1ll << 31) || B > 65535)
@@ -380,5 +405,51 @@ extern "C" int ra_instance_eval_counts_ragged_f32(const float *yc, const int *gt
   if (int rc = geo::upload(who, geo, geo_dev, B, st)) return rc;
   const int vec = (reinterpret_cast<uintptr_t>(gt_ids) & 15) == 0 && (!fg || (reinterpret_cast<uintptr_t>(fg) & 3) == 0);
   return inse::launch_all(who, yc, gt_ids, inst_id, fg, B, T, Hs, Ws, geo::Ragged{geo_dev, vec}, ntiles < want ? ntiles : want, morph,
-                          thr, order, K, inter, area_b, st);
+                          thr, order, K, inter, area_b, map, st);
+}
+
+}  // namespace
+
+extern "C" int ra_instance_eval_counts_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg,
+                                           int B, int T, int Hs, int Ws, int Hf, int Wf, int morph, const float *thresholds,
+                                           int K, int *inter, int *area_b, void *stream) {
+  return counts_uniform("ra_instance_eval_counts_f32", yc, gt_ids, inst_id, fg, B, T, Hs, Ws, Hf, Wf, morph, thresholds, K, inter,
+                        area_b, nullptr, stream);
+}
+
+extern "C" int ra_instance_eval_counts_map_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg,
+                                               int B, int T, int Hs, int Ws, int Hf, int Wf, int morph, const float *thresholds,
+                                               int K, int *inter, int *area_b, unsigned short *map, void *stream) {
+  const char *who = "ra_instance_eval_counts_map_f32";
+  if (!map) return fail(RA_E_INVALID, "%s: bad argument", who);
+  return counts_uniform(who, yc, gt_ids, inst_id, fg, B, T, Hs, Ws, Hf, Wf, morph, thresholds, K, inter, area_b, map, stream);
+}
+
+extern "C" int ra_instance_eval_counts_ragged_f32(const float *yc, const int *gt_ids, const int *inst_id, const unsigned char *fg,
+                                                  size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev, int B, int T,
+                                                  int Hs, int Ws, int morph, const float *thresholds, int K, int *inter,
+                                                  int *area_b, void *stream) {
+  return counts_ragged("ra_instance_eval_counts_ragged_f32", yc, gt_ids, inst_id, fg, total, geo, geo_dev, B, T, Hs, Ws, morph,
+                       thresholds, K, inter, area_b, nullptr, stream);
+}
+
+extern "C" int ra_instance_eval_counts_map_ragged_f32(const float *yc, const int *gt_ids, const int *inst_id,
+                                                      const unsigned char *fg, size_t total, const ra_image_geo *geo,
+                                                      ra_image_geo *geo_dev, int B, int T, int Hs, int Ws, int morph,
+                                                      const float *thresholds, int K, int *inter, int *area_b,
+                                                      unsigned short *map, void *stream) {
+  const char *who = "ra_instance_eval_counts_map_ragged_f32";
+  if (!map) return fail(RA_E_INVALID, "%s: bad argument", who);
+  return counts_ragged(who, yc, gt_ids, inst_id, fg, total, geo, geo_dev, B, T, Hs, Ws, morph, thresholds, K, inter, area_b, map,
+                       stream);
+}
+
+extern "C" int ra_instance_eval_threshold_pos(const float *thresholds, int K, int *pos) {
+  const char *who = "ra_instance_eval_threshold_pos";
+  if (!thresholds || !pos) return fail(RA_E_INVALID, "%s: bad argument", who);
+  inse::Thresholds thr;
+  inse::Order order;
+  if (int rc = inse::prepare(who, 1, 1, 1, 1, thresholds, K, thr, order)) return rc;
+  for (int k = 0; k < K; ++k) pos[k] = order.pos[k];
+  return 0;
 }

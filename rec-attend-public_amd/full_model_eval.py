@@ -45,7 +45,15 @@ chain's thresholded masks in its own colour, composed on the device (analysis.Re
 (analysis.CountAnalyzer); --render_gt_instances adds <output>/output_<split>/gt/<name>.png, the ground truth coloured by its
 best-matching prediction of the LAST threshold (:139-140, analysis.RenderGroundtruthInstanceAnalyzer).  Both need y_gt and s_gt in
 --input, where the chain runs.  With several ranks each rank writes the images of its shard and its counts go to
-<NN>/count_rank<r>.csv."""
+<NN>/count_rank<r>.csv.
+--render_from_ids / --render_gt_from_ids (not reference flags) write the same files on the id path, uniform and mixed sizes,
+where no mask exists: the counting pass also returns its winner map — uint16 per full-size pixel, the prediction that holds
+it and how many of the thresholds it passes: every thresholded mask of every threshold at once — requested once per group of
+up to 16 thresholds, and ops.paint_instances looks the pictures up from it behind ops.eval_metrics_from_counts, whose areas
+say which predictions --remove_tiny took; the ground truth is painted from the id image (ops.paint_groundtruth) in
+analysis.groundtruth_colours of the last threshold's iou_pairwise.  Both honour --device_png / --device_png_code (a batch of
+mixed sizes is encoded one call per group of equal size).  Off the id path each is refused by name and points to --render /
+--render_gt_instances, whose refusals on id and mixed-size archives stay as they are."""
 import argparse
 import os
 import time
@@ -79,6 +87,14 @@ def build_parser():
   p.add_argument('--render_gt_instances', action='store_true',
                  help='not a reference flag: write the ground truth, coloured by its best-matching prediction, into '
                       '<output>/output_<split>/gt/; needs y_gt and s_gt in --input')
+  p.add_argument('--render_from_ids', action='store_true',
+                 help='not a reference flag: what --render writes (<NN>/<name>.png per threshold and <NN>/count.csv), on an --input '
+                      'that holds gt_instance_ids (or the flat layout of mixed sizes) and no y_gt: painted from the counting pass\'s '
+                      'winner map, 2 bytes per pixel, so no [T,Hf,Wf] plane is held; the pictures themselves are 3 bytes per pixel and '
+                      'threshold on the device at a time (503 MB at --batch_size 8, 1024 x 2048 and ten thresholds)')
+  p.add_argument('--render_gt_from_ids', action='store_true',
+                 help='not a reference flag: what --render_gt_instances writes (gt/<name>.png), on the same kind of --input: painted '
+                      'from the id images')
   p.add_argument('--device_png', action='store_true',
                  help='not a reference flag: compress the files of --render, --render_gt_instances and --cityscapes_output on the '
                       'device (a run code within each row, utils/png.write_*_dev) instead of copying every plane to the host for '
@@ -111,6 +127,19 @@ def main(argv=None):
   if args.cityscapes_output and not args.fg_model_id:
     from ra_native import RecAttendError
     raise RecAttendError('--cityscapes_output needs --fg_model_id: the instance classes are voted on the pre-stage\'s semantic map')
+  from_ids = [f for f, on in (('--render_from_ids', args.render_from_ids), ('--render_gt_from_ids', args.render_gt_from_ids)) if on]
+  if from_ids:  # the id path's own render flags: refused by name wherever that path does not run
+    from ra_native import RecAttendError
+    if not args.input:
+      raise RecAttendError('%s needs --input with gt_instance_ids (or the flat layout of mixed sizes) and no y_gt: it paints from '
+                           'the id path\'s counting pass, and synthetic input has no labels; with y_gt and s_gt in --input use '
+                           '--render / --render_gt_instances' % ' / '.join(from_ids))
+    with np.load(args.input) as peek:
+      on_id_path = _id_path(peek.files)
+    if not on_id_path:
+      raise RecAttendError('%s cannot be used with an --input that takes the plane path (%s holds y_gt, or no gt_instance_ids): '
+                           'it paints from the id path\'s counting pass; use --render / --render_gt_instances there' % (
+                               ' / '.join(from_ids), args.input))
   if args.input:  # before anything is restored: what the id path cannot do is refused by name
     with np.load(args.input) as peek:
       id_path, flat_path = _id_path(peek.files), _flat_path(peek.files)
@@ -183,7 +212,7 @@ def main(argv=None):
     names = [n for n in args.analyzers.split(',') if n]
   want_render = args.render or args.render_gt_instances
   analyze = (bool(names) or want_render) and 'y_gt' in data and 's_gt' in data
-  if bool(names) and _id_path(data):
+  if (bool(names) or bool(from_ids)) and _id_path(data):
     analyze = True
     _check_id_labels(args, data, model)
   acc = {th: {n: [] for n in names} for th in thresholds}
@@ -232,13 +261,16 @@ def _check_id_labels(args, data, model):
         raise RecAttendError('--input %s: fg of image %s holds values other than 0 and 1' % (args.input, names[i]))
 
 
-def _analyze_ids(args, model, data, b0, b1, y_dev, s_dev, thresholds, names, acc):
+def _analyze_ids(args, model, data, b0, b1, y_dev, s_dev, thresholds, names, acc, render=None):
   """The write_log chain (full_model_eval.py:97-139) of one batch from instance-id images: apply_confidence at network size,
   then ONE counting pass at the labels' size for all thresholds (ops.instance_eval_counts) and the analyzers' numbers from
-  the counts (ops.eval_metrics_from_counts), handed to analysis through the cache analysis._m honours."""
+  the counts (ops.eval_metrics_from_counts), handed to analysis through the cache analysis._m honours.  render: the analyzers
+  of --render_from_ids / --render_gt_from_ids, {'img': {th: analyzer}, 'count': {th: analyzer}, 'gt': analyzer or None}."""
   import torch
   import ra_ops as ops
   dev = y_dev.device
+  if render is not None:
+    render = dict(render, indices=list(range(b0, b1)))
   if _flat_path(data):  # mixed full sizes: the same chain through the ragged entry points, one launch chain per batch
     import setup_labels
     off, size = data['pixel_offset'], data['orig_size']
@@ -248,35 +280,60 @@ def _analyze_ids(args, model, data, b0, b1, y_dev, s_dev, thresholds, names, acc
     lab = ops.assemble_labels_ragged(ids, geo, model.dims['H'], model.dims['W'], model.dims['T'], args.dataset,
                                      want=('inst_id', 's_gt'), names=_image_names(data)[b0:b1])
     fg = torch.as_tensor(np.ascontiguousarray(np.asarray(data['fg_flat'][p0:p1]).astype(np.uint8))).to(dev) if 'fg_flat' in data else None
-    count = lambda yc, ths: ops.instance_eval_counts_ragged(yc, ids, geo, lab['inst_id'], ths, fg_flat=fg,
-                                                            morph=fg is not None and not args.no_morph, check_fg=False)
-    return _analyze_counts(args, count, lab, fg, y_dev, s_dev, thresholds, names, acc)
+    count = lambda yc, ths, want_map=False: ops.instance_eval_counts_ragged(
+        yc, ids, geo, lab['inst_id'], ths, fg_flat=fg, morph=fg is not None and not args.no_morph, check_fg=False, want_map=want_map)
+    paint = {'instances': lambda wmap, ths, keep: ops.paint_instances(wmap, ths, keep=keep, geo=geo),
+             'gt': lambda colours: ops.paint_groundtruth(ids, lab['inst_id'], colours, geo=geo),
+             'views': lambda pic: [pic[o:o + h * w].view(h, w, 3) for o, h, w in geo.tolist()]}
+    return _analyze_counts(args, count, lab, fg, y_dev, s_dev, thresholds, names, acc, paint, render)
   ids = torch.as_tensor(np.ascontiguousarray(np.asarray(data['gt_instance_ids'][b0:b1]).astype(np.int32))).to(dev)
   # the slots in the reference's order — by area at NETWORK size — under the --dataset rule, as setup_labels.py assembles them
   lab = ops.assemble_labels(ids, model.dims['H'], model.dims['W'], model.dims['T'], args.dataset, want=('inst_id', 's_gt'),
                             names=_image_names(data)[b0:b1])
   fg = torch.as_tensor(np.ascontiguousarray(np.asarray(data['fg'][b0:b1]).astype(np.uint8))).to(dev) if 'fg' in data else None
-  count = lambda yc, ths: ops.instance_eval_counts(yc, ids, lab['inst_id'], ths, fg=fg, morph=fg is not None and not args.no_morph,
-                                                   check_fg=False)
-  _analyze_counts(args, count, lab, fg, y_dev, s_dev, thresholds, names, acc)
+  count = lambda yc, ths, want_map=False: ops.instance_eval_counts(
+      yc, ids, lab['inst_id'], ths, fg=fg, morph=fg is not None and not args.no_morph, check_fg=False, want_map=want_map)
+  paint = {'instances': lambda wmap, ths, keep: ops.paint_instances(wmap, ths, keep=keep),
+           'gt': lambda colours: ops.paint_groundtruth(ids, lab['inst_id'], colours),
+           'views': lambda pic: pic}
+  _analyze_counts(args, count, lab, fg, y_dev, s_dev, thresholds, names, acc, paint, render)
 
 
-def _analyze_counts(args, count, lab, fg, y_dev, s_dev, thresholds, names, acc):
-  """apply_confidence, count(yc, thresholds) -> (inter, area_b) in groups of INS_EVAL_MAX_K thresholds, and the analyzers."""
+def _analyze_counts(args, count, lab, fg, y_dev, s_dev, thresholds, names, acc, paint=None, render=None):
+  """apply_confidence, count(yc, thresholds) -> (inter, area_b) in groups of INS_EVAL_MAX_K thresholds, and the analyzers.  With
+  render['img'] the counting pass also returns its winner map, once per group, and the group's pictures are painted from it
+  behind eval_metrics_from_counts, whose areas say which predictions remove_tiny took: picture and metrics cannot disagree.
+  render['gt']: the ground truth painted from the id image in groundtruth_colours of the LAST threshold's iou_pairwise
+  (:139-140).  Nothing of size T * Hf * Wf exists on this route."""
   import analysis
   import ra_ops as ops
   from utils import postprocess as pp
+  import torch
   s2 = s_dev[:, :, 0].contiguous() if s_dev.dim() == 3 else s_dev   # multi-class: :108-110
   yc, s_conf = pp.apply_confidence(y_dev, s2)
+  pictures_wanted = bool(render and render['img'])
+  met = None
   for k0 in range(0, len(thresholds), ops.INS_EVAL_MAX_K):
     ths = thresholds[k0:k0 + ops.INS_EVAL_MAX_K]
-    inter, area_b = count(yc.contiguous(), ths)
+    if pictures_wanted:
+      inter, area_b, wmap = count(yc.contiguous(), ths, True)
+    else:
+      inter, area_b = count(yc.contiguous(), ths)
     # remove_tiny only where a foreground is given, as in the chain (:121-124)
     per = ops.eval_metrics_from_counts(inter, area_b, lab['s_gt'], remove_tiny=args.remove_tiny if fg is not None else 0, conf=s_conf)
-    for th, met in zip(ths, per):
+    pictures = paint['instances'](wmap, ths, ops.paint_keep(per)) if pictures_wanted else None
+    for k, (th, met) in enumerate(zip(ths, per)):
       results = {'_metrics': met, 'iou_pairwise': met['iou_pairwise'], 's_out': met['conf'], 's_gt': lab['s_gt']}
       for n in names:
         acc[th][n].append(analysis.create_analyzer(n)(results).cpu().numpy())
+      if pictures_wanted:  # :71-79: the instance image and the count file of this threshold
+        results['indices'], results['picture'] = render['indices'], paint['views'](pictures[k])
+        render['img'][th].stage(results)
+        render['count'][th].stage(results)
+  if render and render['gt'] is not None:
+    rgb = analysis.groundtruth_colours(met['iou_pairwise'])
+    bgr = torch.as_tensor(np.ascontiguousarray(rgb[:, :, ::-1])).to(y_dev.device)  # the picture's memory order
+    render['gt'].stage({'picture': paint['views'](paint['gt'](bgr)), 'indices': render['indices']})
 
 
 def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, analyze, acc, ys, ss, t0, fg=None, world=1):
@@ -284,17 +341,21 @@ def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, anal
   out_dir = os.path.join(args.output or restore, 'output_' + args.split.split(',')[0])
   img_render, counters, gt_render = {}, {}, None
   dpng, png_code = bool(getattr(args, 'device_png', False)), cap.device_png_code(args)
-  if getattr(args, 'render', False) or getattr(args, 'render_gt_instances', False):
+  # --render_from_ids / --render_gt_from_ids: the same analyzers and the same files, fed by the id path (main has checked that
+  # the input takes it)
+  ids_img, ids_gt = bool(getattr(args, 'render_from_ids', False)), bool(getattr(args, 'render_gt_from_ids', False))
+  if getattr(args, 'render', False) or getattr(args, 'render_gt_instances', False) or ids_img or ids_gt:
     import analysis
     img_names = [str(n) for n in data['names']] if 'names' in data else ['image_%06d' % i for i in range(data['x'].shape[0])]
-    if args.render:
+    if args.render or ids_img:
       for th in thresholds:
         folder = os.path.join(out_dir, '{:02d}'.format(int(th * 100)))  # full_model_eval.py:65
         img_render[th] = analysis.RenderInstanceAnalyzer(folder, img_names, device_png=dpng, device_png_code=png_code)
         counters[th] = analysis.CountAnalyzer(os.path.join(folder, 'count.csv' if world == 1 else 'count_rank%d.csv' % rank))
-    if args.render_gt_instances:
+    if args.render_gt_instances or ids_gt:
       gt_render = analysis.RenderGroundtruthInstanceAnalyzer(os.path.join(out_dir, 'gt'), img_names, device_png=dpng,
                                                                    device_png_code=png_code)
+  ids_render = {'img': img_render, 'count': counters, 'gt': gt_render} if ids_img or ids_gt else None
   cs_dir, sems, render = getattr(args, 'cityscapes_output', None), {}, None
   if cs_dir:
     import analysis
@@ -314,7 +375,7 @@ def _run_shard(args, model, data, lo, hi, rank, restore, thresholds, names, anal
         res['indices'] = list(range(b0, b1))
         render.stage(res)
     if analyze and _id_path(data):
-      _analyze_ids(args, model, data, b0, b1, y_dev, s_dev, thresholds, names, acc)
+      _analyze_ids(args, model, data, b0, b1, y_dev, s_dev, thresholds, names, acc, render=ids_render)
     elif analyze:
       import analysis
       from utils import postprocess as pp

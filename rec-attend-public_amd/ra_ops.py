@@ -1965,7 +1965,28 @@ def _ins_eval_thresholds(thresholds):
   return thr
 
 
-def instance_eval_counts(yc, gt_ids, inst_id, thresholds, fg=None, morph=False, check_fg=True):
+def ins_eval_threshold_pos(thresholds):
+  """pos int32 [K] on the host: pos[k] = how many of the thresholds lie strictly below thresholds[k] (float32 compares,
+  ra_instance_eval_threshold_pos: the order the counting pass itself uses).  A pixel whose winner-map word holds n passes
+  threshold k as given iff n > pos[k]."""
+  thr = _ins_eval_thresholds(thresholds)
+  pos = np.zeros((thr.size,), dtype=np.int32)
+  check(rn.lib().ra_instance_eval_threshold_pos(ptr(thr), int(thr.size), ptr(pos)), 'ra_instance_eval_threshold_pos')
+  return pos
+
+
+def _ins_eval_map(who, map_out, shape, device):
+  """The winner map's tensor: map_out as it is after a check, or a new uint16 tensor of `shape`."""
+  if map_out is None:
+    return torch.empty(shape, dtype=torch.uint16, device=device)
+  if not isinstance(map_out, torch.Tensor) or not map_out.is_cuda:
+    raise rn.RecAttendError('%s needs CUDA (HIP) tensors; got a CPU tensor. There is no CPU fallback.' % who)
+  if map_out.dtype != torch.uint16 or tuple(map_out.shape) != tuple(shape) or not map_out.is_contiguous():
+    raise rn.RecAttendError('%s: map_out must be contiguous uint16 %s, got %s %s' % (who, tuple(shape), map_out.dtype, tuple(map_out.shape)))
+  return map_out
+
+
+def instance_eval_counts(yc, gt_ids, inst_id, thresholds, fg=None, morph=False, check_fg=True, want_map=False, map_out=None):
   """ra_instance_eval_counts_f32: the chain of full_model_eval.py:112-124 behind apply_confidence — upsample [-> morph] ->
   apply_one_label -> per threshold apply_threshold [-> mask_foreground] — as exact counts, for all thresholds in one pass.
   yc float32 [B,T,Hs,Ws] (y_out * s_out at network size), gt_ids int32 [B,Hf,Wf], inst_id int32 [B,T] (the id of ground-truth
@@ -1973,7 +1994,10 @@ def instance_eval_counts(yc, gt_ids, inst_id, thresholds, fg=None, morph=False, 
   order, fg uint8 [B,Hf,Wf] 0 / 1 or None, morph: dilate 5 x 5 behind the filter -> (inter int32 [B,K,T,T + 1], area_b int32
   [B,T]) on the device: inter[b,k,t,j] = the pixels of prediction t on ground-truth slot j at threshold k (column T: on no
   listed instance; a prediction's area is its row sum), area_b[b,j] = the pixels of slot j.  check_fg: look at fg's largest
-  value (one device-to-host copy) and refuse anything but 0 / 1, which is where the chain's mask_foreground is a mask."""
+  value (one device-to-host copy) and refuse anything but 0 / 1, which is where the chain's mask_foreground is a mask.
+  want_map: also return the winner map, uint16 [B,Hf,Wf] (ra_instance_eval_counts_map_f32; into map_out when given) — the word
+  of a pixel is n << 8 | t*, t* the prediction that holds it and n the number of thresholds, in ascending order, it passes (0:
+  none, and then the whole word is 0); paint_instances turns it into pictures.  inter and area_b are the same bits either way."""
   thr = _ins_eval_thresholds(thresholds)
   ts = (yc, gt_ids, inst_id) + (() if fg is None else (fg,))
   if not all(isinstance(t, torch.Tensor) for t in ts) or not all(t.is_cuda for t in ts):
@@ -1998,6 +2022,12 @@ def instance_eval_counts(yc, gt_ids, inst_id, thresholds, fg=None, morph=False, 
   K = int(thr.size)
   inter = torch.empty((B, K, T, T + 1), dtype=torch.int32, device=yc.device)
   area_b = torch.empty((B, T), dtype=torch.int32, device=yc.device)
+  if want_map or map_out is not None:
+    wmap = _ins_eval_map('instance_eval_counts', map_out, (B, Hf, Wf), yc.device)
+    check(rn.lib().ra_instance_eval_counts_map_f32(ptr(yc), ptr(gt_ids), ptr(inst_id), ptr(fg), B, T, Hs, Ws, Hf, Wf,
+                                                   int(bool(morph)), ptr(thr), K, ptr(inter), ptr(area_b), ptr(wmap),
+                                                   rn.stream_ptr()), 'ra_instance_eval_counts_map_f32')
+    return inter, area_b, wmap
   check(rn.lib().ra_instance_eval_counts_f32(ptr(yc), ptr(gt_ids), ptr(inst_id), ptr(fg), B, T, Hs, Ws, Hf, Wf, int(bool(morph)),
                                              ptr(thr), K, ptr(inter), ptr(area_b), rn.stream_ptr()), 'ra_instance_eval_counts_f32')
   return inter, area_b
@@ -2500,10 +2530,13 @@ def assemble_labels_ragged(gt_flat, geo, H, W, T, dataset, want=('y_gt', 's_gt')
   return out
 
 
-def instance_eval_counts_ragged(yc, gt_flat, geo, inst_id, thresholds, fg_flat=None, morph=False, check_fg=True):
+def instance_eval_counts_ragged(yc, gt_flat, geo, inst_id, thresholds, fg_flat=None, morph=False, check_fg=True, want_map=False,
+                                map_out=None):
   """instance_eval_counts for a ragged batch: yc float32 [B,T,Hs,Ws] and inst_id int32 [B,T] dense, gt_flat int32 [P] and
   fg_flat uint8 [P] (or None) flat with one geometry [B,3] -> (inter int32 [B,K,T,T + 1], area_b int32 [B,T]) as there; every
-  image is resized, filtered and walked at its own h x w, h * w <= 2^24 (ra_instance_eval_counts_ragged_f32)."""
+  image is resized, filtered and walked at its own h x w, h * w <= 2^24 (ra_instance_eval_counts_ragged_f32).  want_map: and
+  the winner map uint16 [P], flat at gt_flat's offsets (ra_instance_eval_counts_map_ragged_f32); the elements between the
+  images are zero in a map made here and left as they are in map_out."""
   who = 'instance_eval_counts_ragged'
   thr = _ins_eval_thresholds(thresholds)
   ts = (yc, gt_flat, inst_id) + (() if fg_flat is None else (fg_flat,))
@@ -2526,6 +2559,13 @@ def instance_eval_counts_ragged(yc, gt_flat, geo, inst_id, thresholds, fg_flat=N
   K = int(thr.size)
   inter = torch.empty((B, K, T, T + 1), dtype=torch.int32, device=yc.device)
   area_b = torch.empty((B, T), dtype=torch.int32, device=yc.device)
+  if want_map or map_out is not None:
+    # the kernel never writes between the images: a new map starts as zeros, so that what it holds there is no stale memory
+    wmap = torch.zeros((total,), dtype=torch.uint16, device=yc.device) if map_out is None else _ins_eval_map(who, map_out, (total,), yc.device)
+    check(rn.lib().ra_instance_eval_counts_map_ragged_f32(ptr(yc), ptr(gt_flat), ptr(inst_id), ptr(fg_flat), total, tab, ptr(gdev),
+                                                          B, T, Hs, Ws, int(bool(morph)), ptr(thr), K, ptr(inter), ptr(area_b),
+                                                          ptr(wmap), rn.stream_ptr()), 'ra_instance_eval_counts_map_ragged_f32')
+    return inter, area_b, wmap
   check(rn.lib().ra_instance_eval_counts_ragged_f32(ptr(yc), ptr(gt_flat), ptr(inst_id), ptr(fg_flat), total, tab, ptr(gdev), B, T,
                                                     Hs, Ws, int(bool(morph)), ptr(thr), K, ptr(inter), ptr(area_b),
                                                     rn.stream_ptr()), 'ra_instance_eval_counts_ragged_f32')
@@ -2565,3 +2605,110 @@ def fg_sweep_counts_ragged(src, gt_flat, geo, thresholds):
   g = np.asarray(geo, dtype=np.int64)
   return {'count_a': c[:, :K].copy(), 'sum_ab': c[:, FG_SWEEP_MAX_K:FG_SWEEP_MAX_K + K].copy(), 'sum_b': c[:, 2 * FG_SWEEP_MAX_K].copy(),
           'pixels': (g[:, 1] * g[:, 2]).copy(), 'thresholds': [float(t) for t in _sweep_thresholds(thresholds)]}
+
+
+# ------------------------------------------ pictures on the id path: paint from the winner map (csrc/ra_instance_paint.hip)
+def _paint_geometry(who, t, dtype, what, geo):
+  """(table, device table, B, total, shape of one picture) of a uniform [B,Hf,Wf] or, with geo, a flat [P] device tensor."""
+  if not isinstance(t, torch.Tensor) or not t.is_cuda:
+    raise rn.RecAttendError('%s needs CUDA (HIP) tensors; got a CPU tensor. There is no CPU fallback.' % who)
+  if t.dtype != dtype or not t.is_contiguous():
+    raise rn.RecAttendError('%s: %s must be contiguous %s, got %s' % (who, what, dtype, t.dtype))
+  if geo is None:
+    if t.dim() != 3 or min(t.shape) < 1:
+      raise rn.RecAttendError('%s: %s must be [B,Hf,Wf] (or flat [P] with its geometry), got %s' % (who, what, tuple(t.shape)))
+    B, Hf, Wf = (int(n) for n in t.shape)
+    if Hf * Wf > INS_EVAL_MAX_PIXELS or B > OVERLAP_MAX_B:
+      raise rn.RecAttendError('%s: B=%d, %d x %d (B <= %d, Hf * Wf <= 2^24)' % (who, B, Hf, Wf, OVERLAP_MAX_B))
+    return None, None, B, B * Hf * Wf, (B, Hf, Wf)
+  if t.dim() != 1:
+    raise rn.RecAttendError('%s: with a geometry %s must be flat [P], got %s' % (who, what, tuple(t.shape)))
+  tab, gdev, B, total = _geo_table(who, geo, (t,), t.device)
+  return tab, gdev, B, total, (total,)
+
+
+def _paint_colours(who, colours, lead, T, device):
+  """colours uint8 [T,3] or lead + [T,3] (or a suffix of lead in front of [T,3]) -> contiguous lead + [T,3] on the device."""
+  _need_dev(colours, torch.uint8, 'colours')
+  shape = tuple(colours.shape)
+  if colours.dim() < 2 or colours.dim() > len(lead) + 2 or shape[-2:] != (T, 3) or \
+      (colours.dim() > 2 and shape[:-2] != tuple(lead)[:colours.dim() - 2]):
+    raise rn.RecAttendError('%s: colours must be [T,3] or %s = %s, got %s' % (
+        who, ' / '.join('[%s,T,3]' % ','.join('BK'[:n]) for n in range(1, len(lead) + 1)), list(lead) + [T, 3], shape))
+  while colours.dim() < len(lead) + 2:  # [T,3] -> [1,T,3]; [B,T,3] -> [B,1,T,3]
+    colours = colours.unsqueeze(0 if colours.dim() == 2 else colours.dim() - 2)
+  return colours.expand(*lead, T, 3).contiguous()
+
+
+def paint_keep(per_threshold):
+  """keep bool [B,K,T] for paint_instances from the list eval_metrics_from_counts returns: a prediction is painted at
+  threshold k iff the metrics of that threshold count it (its 'sizes' entry is not zero: remove_tiny zeroes it there)."""
+  return torch.stack([d['sizes'] > 0 for d in per_threshold], dim=1)
+
+
+def paint_instances(wmap, thresholds, colours=None, keep=None, geo=None, out=None):
+  """analysis.py:137-147 on the id path (ra_instance_paint_u8 / ra_instance_paint_ragged_u8): the winner map of
+  instance_eval_counts(..., want_map=True) — uint16 [B,Hf,Wf], or flat [P] with its geometry `geo` — and `thresholds`, THE list of
+  that call (the map counts ranks among them) -> uint8 [Kp,B,Hf,Wf,3] (flat: [Kp,P,3], image b of picture k at
+  out[k, offset_b : offset_b + h * w]), one picture per threshold, in the order given, in the memory order
+  utils/png.write_colour8 takes (B, G, R): colour[t*] where the pixel passes the threshold, black elsewhere.  colours: uint8 [T,3], [B,T,3] or [B,Kp,T,3]; None = analysis.INSTANCE_CMAP[t % 22] for 32 predictions.
+  keep: bool [B,Kp,T] (paint_keep), False = that prediction is not painted in that picture (remove_tiny).  Elements between the
+  images of a flat batch are zero in a result made here and left as they are in `out`."""
+  who = 'paint_instances'
+  pos = ins_eval_threshold_pos(thresholds)
+  Kp = int(pos.size)
+  tab, gdev, B, total, shape = _paint_geometry(who, wmap, torch.uint16, 'map', geo)
+  dev = wmap.device
+  if colours is not None:
+    T = int(colours.shape[-2]) if isinstance(colours, torch.Tensor) and colours.dim() >= 2 else 0
+  elif keep is not None:
+    T = int(keep.shape[-1]) if isinstance(keep, torch.Tensor) and keep.dim() == 3 else 0
+  else:
+    T = LABELS_MAX_T
+  if not 1 <= T <= LABELS_MAX_T:
+    raise rn.RecAttendError('%s: T=%d (1 <= T <= %d)' % (who, T, LABELS_MAX_T))
+  if colours is None:
+    colours = _render_table('instances', T, dev)
+  colours = _paint_colours(who, colours, (B, Kp), T, dev)
+  if keep is not None:
+    if not isinstance(keep, torch.Tensor) or not keep.is_cuda or keep.dtype != torch.bool or tuple(keep.shape) != (B, Kp, T):
+      raise rn.RecAttendError('%s: keep must be a bool device tensor [B,Kp,T] = [%d,%d,%d]' % (who, B, Kp, T))
+    colours = (colours * keep[..., None].to(torch.uint8)).contiguous()
+  want = (Kp,) + shape + (3,)
+  if out is None:
+    out = torch.empty(want, dtype=torch.uint8, device=dev) if geo is None else torch.zeros(want, dtype=torch.uint8, device=dev)
+  elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != want or not out.is_contiguous():
+    raise rn.RecAttendError('%s: out must be a contiguous uint8 device tensor %s' % (who, want))
+  if geo is None:
+    check(rn.lib().ra_instance_paint_u8(ptr(wmap), B, shape[1], shape[2], ptr(pos), Kp, T, ptr(colours), ptr(out), rn.stream_ptr()),
+          'ra_instance_paint_u8')
+  else:
+    check(rn.lib().ra_instance_paint_ragged_u8(ptr(wmap), total, tab, ptr(gdev), B, ptr(pos), Kp, T, ptr(colours), ptr(out),
+                                               rn.stream_ptr()), 'ra_instance_paint_ragged_u8')
+  return out
+
+
+def paint_groundtruth(gt_ids, inst_id, colours, geo=None, out=None):
+  """analysis.py:166-187 on the id path (ra_gt_paint_u8 / ra_gt_paint_ragged_u8): gt_ids int32 [B,Hf,Wf], or flat [P] with its
+  geometry; inst_id int32 [B,T] (the id of ground-truth slot j, negative = empty); colours uint8 [T,3] or [B,T,3] in the
+  picture's channel order (B, G, R) -> uint8 [B,Hf,Wf,3] ([P,3]): the colour of the first slot that lists the pixel's id,
+  black where none does — render_instances(gt planes, colours, first=True) without the planes."""
+  who = 'paint_groundtruth'
+  tab, gdev, B, total, shape = _paint_geometry(who, gt_ids, torch.int32, 'gt_ids', geo)
+  _need_cuda_i32(inst_id, 'inst_id')
+  if inst_id.dim() != 2 or inst_id.shape[0] != B or not 1 <= inst_id.shape[1] <= LABELS_MAX_T:
+    raise rn.RecAttendError('%s: inst_id must be [B,T] = [%d, 1 .. %d], got %s' % (who, B, LABELS_MAX_T, tuple(inst_id.shape)))
+  T = int(inst_id.shape[1])
+  colours = _paint_colours(who, colours, (B,), T, gt_ids.device)
+  want = shape + (3,)
+  if out is None:
+    out = torch.empty(want, dtype=torch.uint8, device=gt_ids.device) if geo is None else torch.zeros(want, dtype=torch.uint8, device=gt_ids.device)
+  elif not isinstance(out, torch.Tensor) or not out.is_cuda or out.dtype != torch.uint8 or tuple(out.shape) != want or not out.is_contiguous():
+    raise rn.RecAttendError('%s: out must be a contiguous uint8 device tensor %s' % (who, want))
+  if geo is None:
+    check(rn.lib().ra_gt_paint_u8(ptr(gt_ids), ptr(inst_id), B, T, shape[1], shape[2], ptr(colours), ptr(out), rn.stream_ptr()),
+          'ra_gt_paint_u8')
+  else:
+    check(rn.lib().ra_gt_paint_ragged_u8(ptr(gt_ids), total, tab, ptr(gdev), ptr(inst_id), B, T, ptr(colours), ptr(out),
+                                         rn.stream_ptr()), 'ra_gt_paint_ragged_u8')
+  return out
