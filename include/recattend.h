@@ -1355,6 +1355,58 @@ int ra_gt_paint_ragged_u8(const int *gt_ids, size_t total, const ra_image_geo *g
                           int B, int T, const unsigned char *colour, unsigned char *out, void *stream);
 
 /* ------------------------------------------------------------------------------------
+ * The device PNG encoder for a batch of MIXED sizes (KITTI): both stream formats above, unchanged — a stream is a function of
+ * one image's scanlines alone, so every image gets the bytes a uniform call on it alone gives — in one launch chain for the
+ * whole batch.  The kernels are the uniform entries' own, instantiated over the geometry source (csrc/ra_png_parts.h,
+ * csrc/ra_ragged.h).  P is ra_png_deflate (fixed format) or ra_png_deflate_dyn (dynamic format).
+ *
+ * LAYOUT   src holds M planes of `total` elements each, all laid out by ONE table of B images (ra_image_geo, above: geo in
+ *   HOST memory, checked before anything is launched, cleared or written; geo_dev a caller-provided DEVICE buffer of B entries,
+ *   filled on the stream ahead of the kernels).  Image b of plane m is h_b rows of pitch w_b from element m * total + offset_b
+ *   on.  An element is 1 byte (RA_PNG_GRAY8), 3 bytes in B, G, R order (RA_PNG_BGR8: what ra_instance_paint_ragged_u8 writes,
+ *   [Kp,total,3]) or 4 bytes (RA_PNG_F32).
+ * STREAMS  the call encodes N = Np * B streams; stream i = k * B + b is image b of plane plane[k], or of plane k when plane is
+ *   NULL (then Np <= M).  The plane list has the semantics of the uniform entries: Np int32 in device memory, clamped in the
+ *   kernel; the host entry refuses an index outside [0, M).  out, sizes [N], offsets [N], adler [N]: as in the uniform entries.
+ * BOUNDS   P_ragged_bound — bpp 1 or 3.  *out_bytes = Np * the sum over b of the uniform entry's stream bound for h_b x w_b:
+ *   what `out` must hold.  *workspace_bytes: the uniform entry's workspace for N images of Hmax = max h_b rows and scanlines of
+ *   n_max = 1 + bpp * max w_b bytes.  Records, slots and bit places keep a uniform stride of Hmax (Hmax + 1) rows per stream,
+ *   so no row-prefix table exists; the price is workspace sized by the tallest and the widest image of the batch (KITTI's four
+ *   sizes, 370 x 1224 .. 376 x 1242: below 2 % more than the images need).
+ * LAUNCHES the uniform chain's, three (fixed) or a clear and five (dynamic), whatever the mix of sizes.  The row grids are
+ *   (Hmax, N); workgroup (r, i) reads table entry i % B — one scalar load — derives n and its threads' chunk from w_b and
+ *   leaves before its first barrier when r >= h_b; the per-image loops of scan, compact and place are bounded by h_b.  LDS
+ *   offsets are sized by n_max.  16-byte loads are decided per workgroup from the row's real address and width: the image's
+ *   first byte 16-byte aligned and w_b * (source bytes per pixel) % 16 == 0; an image that misses takes element loads and its
+ *   neighbours are unaffected (KITTI's widths miss: 1224 % 16 = 8).  No allocation, no synchronisation, no atomics beyond the
+ *   histogram's, no workgroup waits for another.
+ * P_ragged_host — HOST code, no GPU call: the same arguments in host memory without geo_dev and stream (ws may be NULL), the
+ *   sequential rule image by image.  The same bytes as the device entry.
+ * Refusals, before anything is read, written or launched; out, sizes, offsets and adler stay untouched: a NULL src, geo,
+ *   geo_dev, out, sizes, offsets or adler, or another kind: RA_E_INVALID.  M < 1, N < 1 or N > RA_PNG_MAX_IMAGES, Np > M without a
+ *   plane list: RA_E_SHAPE.  A table that breaks the rules of every ragged entry (h, w >= 1, ascending, no overlap, inside
+ *   `total`), or an image whose scanline exceeds RA_PNG_MAX_ROW_BYTES, whose source holds 2^31 bytes or whose stream bound
+ *   reaches 2^31: RA_E_SHAPE, the message names the image.  out_bytes below the bound, a NULL, short or not 16-byte aligned ws
+ *   (device entry): RA_E_WORKSPACE.
+ * ---------------------------------------------------------------------------------- */
+int ra_png_deflate_ragged_bound(const ra_image_geo *geo, int B, int Np, int bpp, unsigned long long *out_bytes,
+                                unsigned long long *workspace_bytes);
+int ra_png_deflate_ragged_u8(const void *src, int kind, int M, size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev, int B,
+                             const int *plane, int Np, unsigned char *out, size_t out_bytes, int *sizes,
+                             unsigned long long *offsets, unsigned int *adler, void *ws, size_t ws_bytes, void *stream);
+int ra_png_deflate_ragged_host(const void *src, int kind, int M, size_t total, const ra_image_geo *geo, int B, const int *plane,
+                               int Np, unsigned char *out, size_t out_bytes, int *sizes, unsigned long long *offsets,
+                               unsigned int *adler, void *ws, size_t ws_bytes);
+int ra_png_deflate_dyn_ragged_bound(const ra_image_geo *geo, int B, int Np, int bpp, unsigned long long *out_bytes,
+                                    unsigned long long *workspace_bytes);
+int ra_png_deflate_dyn_ragged_u8(const void *src, int kind, int M, size_t total, const ra_image_geo *geo, ra_image_geo *geo_dev,
+                                 int B, const int *plane, int Np, unsigned char *out, size_t out_bytes, int *sizes,
+                                 unsigned long long *offsets, unsigned int *adler, void *ws, size_t ws_bytes, void *stream);
+int ra_png_deflate_dyn_ragged_host(const void *src, int kind, int M, size_t total, const ra_image_geo *geo, int B, const int *plane,
+                                   int Np, unsigned char *out, size_t out_bytes, int *sizes, unsigned long long *offsets,
+                                   unsigned int *adler, void *ws, size_t ws_bytes);
+
+/* ------------------------------------------------------------------------------------
  * Training the pre-stage fg_model (csrc/ra_fg_loss.hip).
  *
  * ra_fg_loss_bwd_f32 — the gradient of the loss head of fg_model.py:196-248 with respect to the logits [npix, nsc + no]; the

@@ -314,11 +314,38 @@ class CountAnalyzer(object):
     pass
 
 
+class RaggedPicture(object):
+  """One picture per image of a batch of MIXED sizes as it lies on the device: flat uint8 [P,3] (one plane of what
+  ops.paint_instances(..., geo=...) or ops.paint_groundtruth(..., geo=...) writes) and its geometry [B,3] of (offset, h, w).
+  It has len(), iterates and indexes as the list of [h,w,3] views into `flat` that it replaces, so whoever takes such a list
+  takes this; the render analyzers' device_png route reads .flat and .geo and encodes the batch in one call."""
+
+  def __init__(self, flat, geo):
+    import numpy as np
+    geo = np.asarray(geo)
+    if flat.dim() != 2 or flat.shape[1] != 3 or geo.ndim != 2 or geo.shape[1] != 3:
+      raise ops.rn.RecAttendError('RaggedPicture: flat must be [P,3] and geo [B,3] of (offset, h, w), got %s and %s' % (
+          tuple(flat.shape), geo.shape))
+    self.flat, self.geo = flat, geo
+
+  def __len__(self):
+    return int(self.geo.shape[0])
+
+  def __getitem__(self, ii):
+    if isinstance(ii, slice):
+      return [self[k] for k in range(*ii.indices(len(self)))]
+    o, h, w = (int(v) for v in self.geo[ii])
+    return self.flat[o:o + h * w].view(h, w, 3)
+
+  def __iter__(self):
+    return (self[ii] for ii in range(len(self)))
+
+
 class _RenderBase(object):
   """names: the file name of every image, indexed by results['indices']; an image goes to <folder>/<name without .png>.png.
-  device_png: the batch is compressed on the device (utils/png.write_colour8_dev, one ops.png_deflate call) and only the
-  streams are copied; the files decode to the same pixels, their bytes differ.  device_png_code: the device encoder's stream
-  format, 'fixed' or 'dynamic'."""
+  device_png: the batch is compressed on the device (utils/png.write_colour8_dev, one ops.png_deflate call; a batch of mixed
+  sizes: write_colour8_ragged_dev, one ops.png_deflate_ragged call) and only the streams are copied; the files decode to the
+  same pixels, their bytes differ.  device_png_code: the device encoder's stream format, 'fixed' or 'dynamic'."""
 
   def __init__(self, folder, names, device_png=False, device_png_code='fixed'):
     if folder is None:
@@ -344,12 +371,18 @@ class _RenderBase(object):
 
   def _write_pictures(self, picture, indices):
     """results['picture'] of the id path, painted already (ops.paint_instances / ops.paint_groundtruth): a uint8 [B,H,W,3]
-    batch, or — a batch of mixed sizes — a list of [h,w,3] views.  With device_png the images of a list are encoded one
-    write_colour8_dev call per group of equal size."""
-    if not isinstance(picture, (list, tuple)):
+    batch, or — a batch of mixed sizes — a RaggedPicture or a list of [h,w,3] views.  With device_png a RaggedPicture is
+    encoded where it lies, ONE write_colour8_ragged_dev call (one launch chain) for the batch whatever the mix of sizes; the
+    images of a plain list are encoded one write_colour8_dev call per group of equal size."""
+    if not isinstance(picture, (list, tuple, RaggedPicture)):
       return self._write(picture, indices)
     if len(picture) != len(indices):
       raise ops.rn.RecAttendError('%s: %d pictures for %d indices' % (type(self).__name__, len(picture), len(indices)))
+    if self.device_png and isinstance(picture, RaggedPicture):
+      from utils import png
+      paths = [os.path.join(self.folder, _stem(str(self.names[int(ii)])) + '.png') for ii in indices]
+      self.written += png.write_colour8_ragged_dev(paths, picture.flat, picture.geo, code=self.device_png_code)
+      return
     groups = {}
     for ii, p in enumerate(picture):
       groups.setdefault(tuple(p.shape) if self.device_png else ii, []).append(ii)

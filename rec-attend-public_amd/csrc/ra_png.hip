@@ -24,6 +24,10 @@
 //             shift from the 16-byte-aligned slot); the workgroup of an image's first rows also writes 78 01, the final block
 //             03 00, the Adler-32 and offsets[image] = the sum of the sizes of the images before it.
 // Three plain launches on the caller's stream; no workgroup waits for another, every loop is bounded by n, H or N.
+// The kernels are templates over where the images lie (ra_png_parts.h: Uniform, one size per call, or Ragged, a batch of mixed
+// sizes behind one ra_image_geo table — ra_png_deflate_ragged_u8): a ragged launch keeps a uniform stride of the tallest
+// image's rows per stream, a workgroup beyond its own image's rows leaves before its first barrier, and n, K and the load width
+// are the image's own.  The streams do not depend on the form.
 //
 // Size bound.  A literal takes 8 or 9 bits, so at most 9 per byte.  A match of L >= 3 bytes takes at most 8 (length code) + 5
 // (extra) + 5 (distance code, d = 1 and d = 3 have no extra bits) = 18 <= 9 L bits.  So the tokens of n bytes take <= 9 n bits,
@@ -39,19 +43,23 @@ namespace png {
 // a segment's slot in the workspace: the bound, 4 bytes the compaction's funnel shift may read beyond it, whole 16-byte stores
 inline size_t slot_bytes(size_t n) { return (segment_bound(n) + 4 + 15) / 16 * 16; }
 
-// Workgroup (row, image).  Dynamic LDS: [0, row_bytes) the staged segment, then out_words dwords of bits, then 4 scan words.
-template <int KIND, bool VEC>
-__global__ __launch_bounds__(kThreads) void encode_kernel(const void *src, int M, int H, int W, const int *plane, int n, int K,
-                                                           unsigned row_bytes, unsigned out_words, unsigned char *slots,
-                                                           size_t slot, Record *rec) {
+// Workgroup (row, stream).  Dynamic LDS: [0, row_bytes) the staged segment, then out_words dwords of bits, then 4 scan words.
+// GEO: Uniform or Ragged (ra_png_parts.h).  Ragged: the grid's x extent is the tallest image's rows and a workgroup beyond its
+// own image's leaves before the first barrier; n and K are the image's own, the LDS offsets the launch's (the widest image's).
+template <int KIND, bool VEC, class GEO>
+__global__ __launch_bounds__(kThreads) void encode_kernel(const void *src, GEO geom, const int *plane, unsigned row_bytes,
+                                                           unsigned out_words, unsigned char *slots, size_t slot, Record *rec) {
   extern __shared__ u32x4 dyn[];
   unsigned char *sh_raw = reinterpret_cast<unsigned char *>(dyn);
   unsigned *sh_out = reinterpret_cast<unsigned *>(sh_raw + row_bytes);
   unsigned *sh_scan = sh_out + out_words;
   const int tid = threadIdx.x, r = blockIdx.x, img = blockIdx.y;
   constexpr int d = KIND == RA_PNG_BGR8 ? 3 : 1;
+  const Image im = geom.at(img, plane);
+  if (GEO::kRagged && r >= im.h) return;
+  const int n = im.n, K = im.K;
 
-  stage_segment<KIND, VEC>(src, M, H, W, plane, img, r, sh_raw);
+  stage_segment<KIND, VEC, GEO::kRagged>(src, im, r, sh_raw);
   for (unsigned w = tid; w < out_words; w += kThreads) sh_out[w] = 0u;  // bits are OR-ed in: LDS holds anything at entry
   __syncthreads();
 
@@ -78,26 +86,30 @@ __global__ __launch_bounds__(kThreads) void encode_kernel(const void *src, int M
   __syncthreads();
   // end-of-block (7 zero bits), the stored block's header (3 zero bits), zero bits to the byte boundary, 00 00 FF FF
   const unsigned body = (3u + tok_bits + 10u + 7u) >> 3, bytes = body + 4u;
+  const size_t at_rec = (size_t)img * geom.rows() + r;
   if (tid == 0) {
     unsigned char *o = reinterpret_cast<unsigned char *>(sh_out);
     o[body + 2] = 0xff;
     o[body + 3] = 0xff;
     Record q;
     q.bytes = bytes, q.a = (1u + sum1) % kAdler, q.b = ((unsigned)n + sum2) % kAdler, q.offset = 0u;
-    rec[(size_t)img * H + r] = q;
+    rec[at_rec] = q;
   }
   __syncthreads();
-  u32x4 *dst = reinterpret_cast<u32x4 *>(slots + ((size_t)img * H + r) * slot);
+  u32x4 *dst = reinterpret_cast<u32x4 *>(slots + at_rec * slot);
   for (unsigned v = tid; v < (bytes + 15u) / 16u; v += kThreads) dst[v] = reinterpret_cast<const u32x4 *>(sh_out)[v];
 }
 
-// Workgroup (group of kCompactRows rows, image); a wave copies one segment at a time.
-__global__ __launch_bounds__(kThreads) void compact_kernel(const unsigned char *slots, size_t slot, const Record *rec, int H,
+// Workgroup (group of kCompactRows rows, stream); a wave copies one segment at a time.
+template <class GEO>
+__global__ __launch_bounds__(kThreads) void compact_kernel(const unsigned char *slots, size_t slot, const Record *rec, GEO geom,
                                                             const int *sizes, const unsigned *adler, unsigned char *out,
                                                             unsigned long long *offsets) {
   __shared__ unsigned sh_scan[4];
   __shared__ unsigned long long sh_hi;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, img = blockIdx.y;
+  const int H = geom.dims(img).h, S = geom.rows();
+  if (GEO::kRagged && blockIdx.x * kCompactRows >= H) return;  // nothing of this image here: before the first barrier
   const unsigned long long base = stream_base(sizes, img, sh_scan, &sh_hi);
   unsigned char *o = out + base;
   if (blockIdx.x == 0 && tid == 0) {
@@ -111,8 +123,8 @@ __global__ __launch_bounds__(kThreads) void compact_kernel(const unsigned char *
   for (int k = 0; k < kRowsPerWave; ++k) {
     const int r = blockIdx.x * kCompactRows + wave * kRowsPerWave + k;
     if (r >= H) break;
-    const Record q = rec[(size_t)img * H + r];
-    const unsigned char *s = slots + ((size_t)img * H + r) * slot;
+    const Record q = rec[(size_t)img * S + r];
+    const unsigned char *s = slots + ((size_t)img * S + r) * slot;
     unsigned char *dst = o + 2 + q.offset;
     unsigned head = (unsigned)(4u - (unsigned)(reinterpret_cast<uintptr_t>(dst) & 3u)) & 3u;
     head = head < q.bytes ? head : q.bytes;
@@ -129,15 +141,79 @@ __global__ __launch_bounds__(kThreads) void compact_kernel(const unsigned char *
   }
 }
 
-template <int KIND>
-void launch_encode(bool vec, dim3 grid, size_t lds, hipStream_t st, const void *src, int M, int H, int W, const int *plane, int n,
-                   int K, unsigned row_bytes, unsigned out_words, unsigned char *slots, size_t slot, Record *rec) {
+// The three launches of a call of N streams: `rows` scanlines per stream in the grid, segments of up to n_max bytes.
+template <int KIND, class GEO>
+int launch_chain(const char *who, bool vec, hipStream_t st, const void *src, const GEO &geom, int N, int rows, size_t n_max,
+                 const int *plane, unsigned char *ws, unsigned char *out, int *sizes, unsigned long long *offsets, unsigned *adler) {
+  const size_t slot = slot_bytes(n_max);
+  Record *rec = reinterpret_cast<Record *>(ws);
+  unsigned char *slots = ws + records_bytes(N, rows);
+  const unsigned row_bytes = (unsigned)round_up(kRowPad + (int)n_max, 16);
+  const unsigned out_words = (unsigned)(slot / 4) + 4u;
+  const size_t lds = row_bytes + (size_t)out_words * 4 + 16;  // at most 16 + 24576 + 27680 + 16 + 16 bytes: below 64 KiB
+  constexpr bool kWide = !GEO::kRagged;  // a ragged workgroup decides the load width itself: one instantiation
+  const dim3 grid(rows, N), block(kThreads);
   if (vec)
-    hipLaunchKernelGGL((encode_kernel<KIND, true>), grid, dim3(kThreads), lds, st, src, M, H, W, plane, n, K, row_bytes, out_words,
-                       slots, slot, rec);
+    hipLaunchKernelGGL((encode_kernel<KIND, kWide, GEO>), grid, block, lds, st, src, geom, plane, row_bytes, out_words, slots, slot, rec);
   else
-    hipLaunchKernelGGL((encode_kernel<KIND, false>), grid, dim3(kThreads), lds, st, src, M, H, W, plane, n, K, row_bytes, out_words,
-                       slots, slot, rec);
+    hipLaunchKernelGGL((encode_kernel<KIND, false, GEO>), grid, block, lds, st, src, geom, plane, row_bytes, out_words, slots, slot, rec);
+  if (const int rc = launch_status(who)) return rc;
+  hipLaunchKernelGGL((scan_kernel<false, GEO>), dim3(N), block, 0, st, rec, geom, sizes, adler, static_cast<const Table *>(nullptr),
+                     static_cast<unsigned long long *>(nullptr));
+  if (const int rc = launch_status(who)) return rc;
+  hipLaunchKernelGGL(compact_kernel<GEO>, dim3(ceil_div(rows, kCompactRows), N), block, 0, st, slots, slot, rec, geom, sizes, adler,
+                     out, offsets);
+  return launch_status(who);
+}
+
+template <class GEO>
+int launch_kind(const char *who, int kind, bool vec, hipStream_t st, const void *src, const GEO &geom, int N, int rows, size_t n_max,
+                const int *plane, unsigned char *ws, unsigned char *out, int *sizes, unsigned long long *offsets, unsigned *adler) {
+  if (kind == RA_PNG_GRAY8)
+    return launch_chain<RA_PNG_GRAY8>(who, vec, st, src, geom, N, rows, n_max, plane, ws, out, sizes, offsets, adler);
+  if (kind == RA_PNG_BGR8)
+    return launch_chain<RA_PNG_BGR8>(who, vec, st, src, geom, N, rows, n_max, plane, ws, out, sizes, offsets, adler);
+  return launch_chain<RA_PNG_F32>(who, vec, st, src, geom, N, rows, n_max, plane, ws, out, sizes, offsets, adler);
+}
+
+// HOST code: the stream of the image of H x W whose first element is `base`, written at o; its bytes, *adler = its Adler-32
+inline size_t host_stream(const void *src, int kind, size_t base, int H, int W, int d, unsigned char *seg, unsigned char *o,
+                          unsigned *adler) {
+  const int n = 1 + W * d;
+  BitWriter bw{o};
+  bw.byte(0x78), bw.byte(0x01);
+  unsigned A = 1u, B = 0u;
+  for (int r = 0; r < H; ++r) {
+    host_scanline(src, kind, base, W, r, seg);
+    for (int k = 0; k < n; ++k) {  // a segment is below zlib's 5552 bytes only by luck: reduce every byte
+      A = (A + seg[k]) % kAdler;
+      B = (B + A) % kAdler;
+    }
+    bw.put(2u, 3);  // BFINAL = 0, BTYPE = 01
+    int nb;
+    for (int k = 0; k < n;) {
+      int L = 0;
+      if (k >= d)
+        while (L < 258 && k + L < n && seg[k + L] == seg[k + L - d]) ++L;
+      if (L >= 3) {
+        const unsigned t = match_token(L, d, &nb);
+        bw.put(t, nb);
+        k += L;
+      } else {
+        const unsigned t = literal_token(seg[k], &nb);
+        bw.put(t, nb);
+        ++k;
+      }
+    }
+    bw.put(0u, 7);  // end-of-block
+    bw.put(0u, 3);  // an empty stored block: BFINAL = 0, BTYPE = 00
+    bw.align();
+    bw.byte(0x00), bw.byte(0x00), bw.byte(0xff), bw.byte(0xff);
+  }
+  bw.byte(0x03), bw.byte(0x00);
+  bw.byte(B >> 8), bw.byte(B & 255u), bw.byte(A >> 8), bw.byte(A & 255u);
+  *adler = B << 16 | A;
+  return bw.bit >> 3;
 }
 
 }  // namespace png
@@ -163,31 +239,43 @@ extern "C" int ra_png_deflate_u8(const void *src, int kind, int M, int N, int H,
   png::Geometry g;
   if (const int rc = png::check("ra_png_deflate_u8", false, src, kind, M, N, H, W, out, out_bytes, sizes, offsets, adler, &g)) return rc;
   if (!plane && N > M) return fail(RA_E_SHAPE, "ra_png_deflate_u8: N=%d images of a source of M=%d without a plane list", N, M);
-  const size_t slot = png::slot_bytes(g.n), need = png::records_bytes(N, H) + (size_t)N * H * slot;
+  const size_t need = png::records_bytes(N, H) + (size_t)N * H * png::slot_bytes(g.n);
   if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 15))
     return fail(RA_E_WORKSPACE, "ra_png_deflate_u8: ws=%p ws_bytes=%zu, %zu bytes at a 16-byte boundary are needed", ws, ws_bytes, need);
-  png::Record *rec = static_cast<png::Record *>(ws);
-  unsigned char *slots = static_cast<unsigned char *>(ws) + png::records_bytes(N, H);
-  const int n = (int)g.n, K = png::chunk_bytes(n);
-  const unsigned row_bytes = (unsigned)round_up(png::kRowPad + n, 16);
-  const unsigned out_words = (unsigned)(slot / 4) + 4u;
-  const size_t lds = row_bytes + (size_t)out_words * 4 + 16;  // at most 16 + 24576 + 27680 + 16 + 16 bytes: below 64 KiB
-  const bool vec = png::vector_rows(src, kind, W);
-  const dim3 grid(H, N);
+  const int n = (int)g.n;
+  return png::launch_kind("ra_png_deflate_u8", kind, png::vector_rows(src, kind, W), as_stream(stream), src,
+                          png::Uniform{M, H, W, n, png::chunk_bytes(n)}, N, H, g.n, plane, static_cast<unsigned char *>(ws), out, sizes,
+                          offsets, adler);
+}
+
+extern "C" int ra_png_deflate_ragged_bound(const ra_image_geo *geo, int B, int Np, int bpp, unsigned long long *out_bytes,
+                                           unsigned long long *workspace_bytes) {
+  const char *who = "ra_png_deflate_ragged_bound";
+  if (!geo || !out_bytes || !workspace_bytes) return fail(RA_E_INVALID, "%s: geo, out_bytes or workspace_bytes is NULL", who);
+  if (bpp != 1 && bpp != 3) return fail(RA_E_SHAPE, "%s: bpp=%d (1 = grey, 3 = RGB)", who, bpp);
+  png::RaggedShape s;
+  if (const int rc = png::ragged_shape(who, false, geo, B, Np, bpp, bpp, &s)) return rc;
+  *out_bytes = s.out;
+  *workspace_bytes = png::records_bytes(s.N, s.Hmax) + (size_t)s.N * s.Hmax * png::slot_bytes(s.n_max);
+  return 0;
+}
+
+extern "C" int ra_png_deflate_ragged_u8(const void *src, int kind, int M, size_t total, const ra_image_geo *geo,
+                                        ra_image_geo *geo_dev, int B, const int *plane, int Np, unsigned char *out, size_t out_bytes,
+                                        int *sizes, unsigned long long *offsets, unsigned int *adler, void *ws, size_t ws_bytes,
+                                        void *stream) {
+  const char *who = "ra_png_deflate_ragged_u8";
+  if (!geo_dev) return fail(RA_E_INVALID, "%s: geo_dev is NULL", who);
+  png::RaggedShape s;
+  if (const int rc = png::check_ragged(who, false, src, kind, M, total, geo, B, plane, Np, out, out_bytes, sizes, offsets, adler, &s))
+    return rc;
+  const size_t need = png::records_bytes(s.N, s.Hmax) + (size_t)s.N * s.Hmax * png::slot_bytes(s.n_max);
+  if (!ws || ws_bytes < need || (reinterpret_cast<uintptr_t>(ws) & 15))
+    return fail(RA_E_WORKSPACE, "%s: ws=%p ws_bytes=%zu, %zu bytes at a 16-byte boundary are needed", who, ws, ws_bytes, need);
   hipStream_t st = as_stream(stream);
-  if (kind == RA_PNG_GRAY8)
-    png::launch_encode<RA_PNG_GRAY8>(vec, grid, lds, st, src, M, H, W, plane, n, K, row_bytes, out_words, slots, slot, rec);
-  else if (kind == RA_PNG_BGR8)
-    png::launch_encode<RA_PNG_BGR8>(vec, grid, lds, st, src, M, H, W, plane, n, K, row_bytes, out_words, slots, slot, rec);
-  else
-    png::launch_encode<RA_PNG_F32>(vec, grid, lds, st, src, M, H, W, plane, n, K, row_bytes, out_words, slots, slot, rec);
-  if (const int rc = launch_status("ra_png_deflate_u8 (encode)")) return rc;
-  hipLaunchKernelGGL(png::scan_kernel<false>, dim3(N), dim3(png::kThreads), 0, st, rec, H, n, sizes, adler,
-                     static_cast<const png::Table *>(nullptr), static_cast<unsigned long long *>(nullptr));
-  if (const int rc = launch_status("ra_png_deflate_u8 (scan)")) return rc;
-  hipLaunchKernelGGL(png::compact_kernel, dim3(ceil_div(H, png::kCompactRows), N), dim3(png::kThreads), 0, st, slots, slot, rec, H,
-                     sizes, adler, out, offsets);
-  return launch_status("ra_png_deflate_u8 (compact)");
+  if (const int rc = geo::upload(who, geo, geo_dev, B, st)) return rc;
+  return png::launch_kind(who, kind, false, st, src, png::Ragged{geo_dev, B, M, s.Hmax, kind == RA_PNG_BGR8 ? 3 : 1, total}, s.N, s.Hmax,
+                          s.n_max, plane, static_cast<unsigned char *>(ws), out, sizes, offsets, adler);
 }
 
 // HOST code, no GPU call: the rule as it is stated, one byte after the other.
@@ -200,48 +288,37 @@ extern "C" int ra_png_deflate_host(const void *src, int kind, int M, int N, int 
   if (!plane && N > M) return fail(RA_E_SHAPE, "ra_png_deflate_host: N=%d images of a source of M=%d without a plane list", N, M);
   for (int i = 0; plane && i < N; ++i)
     if (plane[i] < 0 || plane[i] >= M) return fail(RA_E_SHAPE, "ra_png_deflate_host: plane[%d]=%d (0 <= index < M=%d)", i, plane[i], M);
-  const int n = (int)g.n, d = g.d;
   std::vector<unsigned char> seg(g.n);
   size_t at = 0;
   for (int i = 0; i < N; ++i) {
     const size_t m = plane ? plane[i] : i;
-    png::BitWriter bw{out + at};
-    bw.byte(0x78), bw.byte(0x01);
-    unsigned A = 1u, B = 0u;
-    for (int r = 0; r < H; ++r) {
-      png::host_scanline(src, kind, m, H, W, r, seg.data());
-      for (int k = 0; k < n; ++k) {  // a segment is below zlib's 5552 bytes only by luck: reduce every byte
-        A = (A + seg[k]) % png::kAdler;
-        B = (B + A) % png::kAdler;
-      }
-      bw.put(2u, 3);  // BFINAL = 0, BTYPE = 01
-      int nb;
-      for (int k = 0; k < n;) {
-        int L = 0;
-        if (k >= d)
-          while (L < 258 && k + L < n && seg[k + L] == seg[k + L - d]) ++L;
-        if (L >= 3) {
-          const unsigned t = png::match_token(L, d, &nb);
-          bw.put(t, nb);
-          k += L;
-        } else {
-          const unsigned t = png::literal_token(seg[k], &nb);
-          bw.put(t, nb);
-          ++k;
-        }
-      }
-      bw.put(0u, 7);  // end-of-block
-      bw.put(0u, 3);  // an empty stored block: BFINAL = 0, BTYPE = 00
-      bw.align();
-      bw.byte(0x00), bw.byte(0x00), bw.byte(0xff), bw.byte(0xff);
-    }
-    bw.byte(0x03), bw.byte(0x00);
-    bw.byte(B >> 8), bw.byte(B & 255u), bw.byte(A >> 8), bw.byte(A & 255u);
-    const size_t bytes = bw.bit >> 3;
-    sizes[i] = (int)bytes;
+    sizes[i] = (int)png::host_stream(src, kind, m * H * W, H, W, g.d, seg.data(), out + at, &adler[i]);
     offsets[i] = at;
-    adler[i] = B << 16 | A;
-    at += bytes;
+    at += (size_t)sizes[i];
+  }
+  return 0;
+}
+
+// HOST code, no GPU call: the sequential rule per image of the table
+extern "C" int ra_png_deflate_ragged_host(const void *src, int kind, int M, size_t total, const ra_image_geo *geo, int B,
+                                          const int *plane, int Np, unsigned char *out, size_t out_bytes, int *sizes,
+                                          unsigned long long *offsets, unsigned int *adler, void *ws, size_t ws_bytes) {
+  (void)ws, (void)ws_bytes;  // the sequential form needs none
+  const char *who = "ra_png_deflate_ragged_host";
+  png::RaggedShape s;
+  if (const int rc = png::check_ragged(who, false, src, kind, M, total, geo, B, plane, Np, out, out_bytes, sizes, offsets, adler, &s))
+    return rc;
+  for (int k = 0; plane && k < Np; ++k)
+    if (plane[k] < 0 || plane[k] >= M) return fail(RA_E_SHAPE, "%s: plane[%d]=%d (0 <= index < M=%d)", who, k, plane[k], M);
+  std::vector<unsigned char> seg(s.n_max);
+  size_t at = 0;
+  for (int i = 0; i < s.N; ++i) {
+    const int k = i / B, b = i - k * B;
+    const size_t m = plane ? plane[k] : k;
+    sizes[i] = (int)png::host_stream(src, kind, m * total + (size_t)geo[b].offset, geo[b].h, geo[b].w, kind == RA_PNG_BGR8 ? 3 : 1,
+                                     seg.data(), out + at, &adler[i]);
+    offsets[i] = at;
+    at += (size_t)sizes[i];
   }
   return 0;
 }

@@ -174,18 +174,22 @@ __host__ __device__ inline void build_table(int d, Table *t, HuffScratch *s) {
 }
 
 // ---- the kernels -----------------------------------------------------------------------------------------------------------------
-// Workgroup (row, image).  Dynamic LDS: [0, row_bytes) the staged segment, then kTableSymbols histogram words, then 4 scan words.
-template <int KIND, bool VEC>
-__global__ __launch_bounds__(kThreads) void histogram_kernel(const void *src, int M, int H, int W, const int *plane, int n, int K,
-                                                              unsigned row_bytes, unsigned *hist) {
+// Workgroup (row, stream).  Dynamic LDS: [0, row_bytes) the staged segment, then kTableSymbols histogram words, then 4 scan words.
+// GEO: Uniform or Ragged (ra_png_parts.h); a ragged workgroup beyond its image's rows leaves before the first barrier.
+template <int KIND, bool VEC, class GEO>
+__global__ __launch_bounds__(kThreads) void histogram_kernel(const void *src, GEO geom, const int *plane, unsigned row_bytes,
+                                                              unsigned *hist) {
   extern __shared__ u32x4 dyn[];
   unsigned char *sh_raw = reinterpret_cast<unsigned char *>(dyn);
   unsigned *sh_hist = reinterpret_cast<unsigned *>(sh_raw + row_bytes);
   unsigned *sh_scan = sh_hist + kTableSymbols;
   const int tid = threadIdx.x, r = blockIdx.x, img = blockIdx.y;
   constexpr int d = KIND == RA_PNG_BGR8 ? 3 : 1;
+  const Image im = geom.at(img, plane);
+  if (GEO::kRagged && r >= im.h) return;
+  const int n = im.n, K = im.K;
 
-  stage_segment<KIND, VEC>(src, M, H, W, plane, img, r, sh_raw);
+  stage_segment<KIND, VEC, GEO::kRagged>(src, im, r, sh_raw);
   for (int k = tid; k < kTableSymbols; k += kThreads) sh_hist[k] = 0u;  // LDS holds anything at entry
   __syncthreads();
 
@@ -227,12 +231,12 @@ __global__ __launch_bounds__(kWave) void code_kernel(const unsigned *hist, int d
 // a row's slot in the workspace: 15 bits per byte, 4 bytes the placement's funnel shift may read beyond them, whole 16-byte stores
 constexpr size_t dynamic_slot_bytes(size_t n) { return ((15 * n + 7) / 8 + 4 + 15) / 16 * 16; }
 
-// Workgroup (row, image).  Dynamic LDS: [0, row_bytes) the staged segment, out_words dwords of bits, kTableSymbols code words, 4
-// scan words.
-template <int KIND, bool VEC>
-__global__ __launch_bounds__(kThreads) void encode_dynamic_kernel(const void *src, int M, int H, int W, const int *plane, int n,
-                                                                   int K, unsigned row_bytes, unsigned out_words, const Table *tab,
-                                                                   unsigned char *slots, size_t slot, Record *rec) {
+// Workgroup (row, stream).  Dynamic LDS: [0, row_bytes) the staged segment, out_words dwords of bits, kTableSymbols code words, 4
+// scan words.  GEO as in the histogram kernel; the LDS offsets are the launch's (ragged: the widest image's).
+template <int KIND, bool VEC, class GEO>
+__global__ __launch_bounds__(kThreads) void encode_dynamic_kernel(const void *src, GEO geom, const int *plane, unsigned row_bytes,
+                                                                   unsigned out_words, const Table *tab, unsigned char *slots,
+                                                                   size_t slot, Record *rec) {
   extern __shared__ u32x4 dyn[];
   unsigned char *sh_raw = reinterpret_cast<unsigned char *>(dyn);
   unsigned *sh_out = reinterpret_cast<unsigned *>(sh_raw + row_bytes);
@@ -240,8 +244,11 @@ __global__ __launch_bounds__(kThreads) void encode_dynamic_kernel(const void *sr
   unsigned *sh_scan = sh_tab + kTableSymbols;
   const int tid = threadIdx.x, r = blockIdx.x, img = blockIdx.y;
   constexpr int d = KIND == RA_PNG_BGR8 ? 3 : 1;
+  const Image im = geom.at(img, plane);
+  if (GEO::kRagged && r >= im.h) return;
+  const int n = im.n, K = im.K;
 
-  stage_segment<KIND, VEC>(src, M, H, W, plane, img, r, sh_raw);
+  stage_segment<KIND, VEC, GEO::kRagged>(src, im, r, sh_raw);
   for (unsigned w = tid; w < out_words; w += kThreads) sh_out[w] = 0u;  // bits are OR-ed in: LDS holds anything at entry
   for (int k = tid; k < kTableSymbols; k += kThreads) sh_tab[k] = tab[img].sym[k];
   __syncthreads();
@@ -262,12 +269,13 @@ __global__ __launch_bounds__(kThreads) void encode_dynamic_kernel(const void *sr
   const unsigned at = block_scan_excl<OpAdd, false>(bits, sh_scan, &row_bits);
   emit_chunk(code, b, lo, hi, d, s_in, e_in, at, sh_out);
   __syncthreads();
+  const size_t at_rec = (size_t)img * geom.rows() + r;
   if (tid == 0) {
     Record q;
     q.bytes = row_bits, q.a = (1u + sum1) % kAdler, q.b = ((unsigned)n + sum2) % kAdler, q.offset = 0u;
-    rec[(size_t)img * H + r] = q;
+    rec[at_rec] = q;
   }
-  u32x4 *dst = reinterpret_cast<u32x4 *>(slots + ((size_t)img * H + r) * slot);
+  u32x4 *dst = reinterpret_cast<u32x4 *>(slots + at_rec * slot);
   for (unsigned v = tid; v < (row_bits + 127u) / 128u; v += kThreads) dst[v] = reinterpret_cast<const u32x4 *>(sh_out)[v];
 }
 
@@ -286,14 +294,18 @@ __device__ __forceinline__ unsigned piece_bits(const unsigned *w, unsigned nbits
   return v;
 }
 
-// Workgroup (group of kCompactRows pieces, image); a wave places one piece at a time.  Bit places are counted from the dword
-// boundary at or before the stream's first byte (`lead` bits before it), so that a dword index is an aligned address.
+// Workgroup (group of kCompactRows pieces, stream); a wave places one piece at a time.  Bit places are counted from the dword
+// boundary at or before the stream's first byte (`lead` bits before it), so that a dword index is an aligned address.  H is the
+// image's own, S the stride of a stream's records (GEO: ra_png_parts.h).
+template <class GEO>
 __global__ __launch_bounds__(kThreads) void place_kernel(const unsigned char *slots, size_t slot, const Record *rec,
-                                                          const unsigned long long *start, const Table *tab, int H, const int *sizes,
+                                                          const unsigned long long *start, const Table *tab, GEO geom, const int *sizes,
                                                           const unsigned *adler, unsigned char *out, unsigned long long *offsets) {
   __shared__ unsigned sh_scan[4];
   __shared__ unsigned long long sh_hi;
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, img = blockIdx.y;
+  const int H = geom.dims(img).h, S = geom.rows();
+  if (GEO::kRagged && blockIdx.x * kCompactRows > H + 1) return;  // no piece of this image here: before the first barrier
   const unsigned long long base = stream_base(sizes, img, sh_scan, &sh_hi);
   unsigned char *o = out + base;
   const unsigned size = (unsigned)sizes[img];
@@ -304,8 +316,8 @@ __global__ __launch_bounds__(kThreads) void place_kernel(const unsigned char *sl
     t[0] = (unsigned char)(ad >> 24), t[1] = (unsigned char)(ad >> 16), t[2] = (unsigned char)(ad >> 8), t[3] = (unsigned char)ad;
   }
   const Table *t = tab + img;
-  const unsigned long long *st = start + (size_t)img * (H + 1);
-  const Record *q = rec + (size_t)img * H;
+  const unsigned long long *st = start + (size_t)img * (S + 1);
+  const Record *q = rec + (size_t)img * S;
   const unsigned lead = 8u * (unsigned)(reinterpret_cast<uintptr_t>(o) & 3u);
   unsigned char *o4 = o - lead / 8u;                                     // 4-byte aligned; bytes before o are never touched
   const unsigned long long end = lead + 8ull * (size - 4u);              // the Adler-32 starts here
@@ -314,7 +326,7 @@ __global__ __launch_bounds__(kThreads) void place_kernel(const unsigned char *sl
     if (p == 0) {
       *w = t->hdr, *s = lead, *nbits = t->hdr_bits;
     } else if (p <= H) {
-      *w = reinterpret_cast<const unsigned *>(slots + ((size_t)img * H + (p - 1)) * slot), *s = lead + st[p - 1], *nbits = q[p - 1].bytes;
+      *w = reinterpret_cast<const unsigned *>(slots + ((size_t)img * S + (p - 1)) * slot), *s = lead + st[p - 1], *nbits = q[p - 1].bytes;
     } else {
       *w = &t->eob, *s = lead + st[H], *nbits = t->eob_bits;
     }
@@ -372,48 +384,113 @@ constexpr size_t encode_lds(size_t n) {
   return (kRowPad + n + 15) / 16 * 16 + (dynamic_slot_bytes(n) + 16) + (size_t)kTableSymbols * 4 + 16;
 }
 
-template <int KIND>
-int launch_chain(bool vec, hipStream_t st, const void *src, int M, int N, int H, int W, const int *plane, int n, int d,
-                 const Workspace &wsp, unsigned char *ws, unsigned char *out, int *sizes, unsigned long long *offsets,
+// The clear and the five launches of a call of N streams: `rows` scanlines per stream in the grid (wsp is laid out for them),
+// segments of up to n_max bytes.
+template <int KIND, class GEO>
+int launch_chain(const char *who, bool vec, hipStream_t st, const void *src, const GEO &geom, int N, int rows, size_t n_max,
+                 const int *plane, const Workspace &wsp, unsigned char *ws, unsigned char *out, int *sizes, unsigned long long *offsets,
                  unsigned *adler) {
+  constexpr int d = KIND == RA_PNG_BGR8 ? 3 : 1;
   unsigned *hist = reinterpret_cast<unsigned *>(ws + wsp.hist);
   Table *tab = reinterpret_cast<Table *>(ws + wsp.tab);
   Record *rec = reinterpret_cast<Record *>(ws + wsp.rec);
   unsigned long long *start = reinterpret_cast<unsigned long long *>(ws + wsp.start);
   unsigned char *slots = ws + wsp.slots;
-  const int K = chunk_bytes(n);
-  const unsigned row_bytes = (unsigned)round_up(kRowPad + n, 16);
+  const unsigned row_bytes = (unsigned)round_up(kRowPad + (int)n_max, 16);
   const unsigned out_words = (unsigned)(wsp.slot / 4) + 4u;
   const size_t lds_hist = row_bytes + (size_t)kTableSymbols * 4 + 16;
-  const size_t lds_enc = encode_lds((size_t)n);
+  const size_t lds_enc = encode_lds(n_max);
   // the longest row takes 24592 + 46112 + 1152 + 16 bytes of LDS: above the default limit of 64 KiB, below the CU's 160 KiB
   constexpr size_t kMaxEnc = encode_lds(RA_PNG_MAX_ROW_BYTES);
-  const dim3 grid(H, N), block(kThreads);
+  constexpr bool kWide = !GEO::kRagged;  // a ragged workgroup decides the load width itself: one instantiation
+  const dim3 grid(rows, N), block(kThreads);
   if (const hipError_t e = hipMemsetAsync(hist, 0, (size_t)N * kTableSymbols * sizeof(unsigned), st))
-    return fail((int)e, "ra_png_deflate_dyn_u8 (clearing the histograms): %s", hipGetErrorString(e));
+    return fail((int)e, "%s (clearing the histograms): %s", who, hipGetErrorString(e));
   if (vec) {
-    hipLaunchKernelGGL((histogram_kernel<KIND, true>), grid, block, lds_hist, st, src, M, H, W, plane, n, K, row_bytes, hist);
+    hipLaunchKernelGGL((histogram_kernel<KIND, kWide, GEO>), grid, block, lds_hist, st, src, geom, plane, row_bytes, hist);
   } else {
-    hipLaunchKernelGGL((histogram_kernel<KIND, false>), grid, block, lds_hist, st, src, M, H, W, plane, n, K, row_bytes, hist);
+    hipLaunchKernelGGL((histogram_kernel<KIND, false, GEO>), grid, block, lds_hist, st, src, geom, plane, row_bytes, hist);
   }
-  if (const int rc = launch_status("ra_png_deflate_dyn_u8 (histogram)")) return rc;
+  if (const int rc = launch_status(who)) return rc;
   hipLaunchKernelGGL(code_kernel, dim3(N), dim3(kWave), 0, st, hist, d, tab);
-  if (const int rc = launch_status("ra_png_deflate_dyn_u8 (code)")) return rc;
+  if (const int rc = launch_status(who)) return rc;
   if (vec) {
-    static MaxDynamicLds once(encode_dynamic_kernel<KIND, true>, kMaxEnc);
-    hipLaunchKernelGGL((encode_dynamic_kernel<KIND, true>), grid, block, lds_enc, st, src, M, H, W, plane, n, K, row_bytes, out_words,
-                       tab, slots, wsp.slot, rec);
+    static MaxDynamicLds once(encode_dynamic_kernel<KIND, kWide, GEO>, kMaxEnc);
+    hipLaunchKernelGGL((encode_dynamic_kernel<KIND, kWide, GEO>), grid, block, lds_enc, st, src, geom, plane, row_bytes, out_words, tab,
+                       slots, wsp.slot, rec);
   } else {
-    static MaxDynamicLds once(encode_dynamic_kernel<KIND, false>, kMaxEnc);
-    hipLaunchKernelGGL((encode_dynamic_kernel<KIND, false>), grid, block, lds_enc, st, src, M, H, W, plane, n, K, row_bytes, out_words,
-                       tab, slots, wsp.slot, rec);
+    static MaxDynamicLds once(encode_dynamic_kernel<KIND, false, GEO>, kMaxEnc);
+    hipLaunchKernelGGL((encode_dynamic_kernel<KIND, false, GEO>), grid, block, lds_enc, st, src, geom, plane, row_bytes, out_words, tab,
+                       slots, wsp.slot, rec);
   }
-  if (const int rc = launch_status("ra_png_deflate_dyn_u8 (encode)")) return rc;
-  hipLaunchKernelGGL(scan_kernel<true>, dim3(N), block, 0, st, rec, H, n, sizes, adler, tab, start);
-  if (const int rc = launch_status("ra_png_deflate_dyn_u8 (scan)")) return rc;
-  hipLaunchKernelGGL(place_kernel, dim3(ceil_div(H + 2, kCompactRows), N), block, 0, st, slots, wsp.slot, rec, start, tab, H, sizes,
-                     adler, out, offsets);
-  return launch_status("ra_png_deflate_dyn_u8 (place)");
+  if (const int rc = launch_status(who)) return rc;
+  hipLaunchKernelGGL((scan_kernel<true, GEO>), dim3(N), block, 0, st, rec, geom, sizes, adler, tab, start);
+  if (const int rc = launch_status(who)) return rc;
+  hipLaunchKernelGGL(place_kernel<GEO>, dim3(ceil_div(rows + 2, kCompactRows), N), block, 0, st, slots, wsp.slot, rec, start, tab, geom,
+                     sizes, adler, out, offsets);
+  return launch_status(who);
+}
+
+template <class GEO>
+int launch_kind(const char *who, int kind, bool vec, hipStream_t st, const void *src, const GEO &geom, int N, int rows, size_t n_max,
+                const int *plane, const Workspace &wsp, unsigned char *ws, unsigned char *out, int *sizes, unsigned long long *offsets,
+                unsigned *adler) {
+  if (kind == RA_PNG_GRAY8)
+    return launch_chain<RA_PNG_GRAY8>(who, vec, st, src, geom, N, rows, n_max, plane, wsp, ws, out, sizes, offsets, adler);
+  if (kind == RA_PNG_BGR8)
+    return launch_chain<RA_PNG_BGR8>(who, vec, st, src, geom, N, rows, n_max, plane, wsp, ws, out, sizes, offsets, adler);
+  return launch_chain<RA_PNG_F32>(who, vec, st, src, geom, N, rows, n_max, plane, wsp, ws, out, sizes, offsets, adler);
+}
+
+// HOST code: the stream of the image of H x W whose first element is `base`, written at o — the histogram of the greedy tokens,
+// the table (the function the code kernel runs), then the tokens again, one bit after the other; its bytes, *adler = its Adler-32
+inline size_t host_stream(const void *src, int kind, size_t base, int H, int W, int d, unsigned char *seg, HuffScratch *s, Table *t,
+                          unsigned char *o, unsigned *adler) {
+  const int n = 1 + W * d;
+  // the greedy tokens of the scanline in seg: tok(literal / length symbol, extra value, extra bits, is a match)
+  auto tokens = [&](auto &&tok) {
+    for (int k = 0; k < n;) {
+      int L = 0;
+      if (k >= d)
+        while (L < 258 && k + L < n && seg[k + L] == seg[k + L - d]) ++L;
+      if (L >= 3) {
+        int xb, extra;
+        const int sym = length_symbol(L, &xb, &extra);
+        tok(sym, extra, xb, true);
+        k += L;
+      } else {
+        tok((int)seg[k], 0, 0, false);
+        ++k;
+      }
+    }
+  };
+  for (int k = 0; k < kTableSymbols; ++k) s->hist[k] = 0u;
+  unsigned A = 1u, B = 0u;
+  for (int r = 0; r < H; ++r) {
+    host_scanline(src, kind, base, W, r, seg);
+    for (int k = 0; k < n; ++k) {
+      A = (A + seg[k]) % kAdler;
+      B = (B + A) % kAdler;
+    }
+    tokens([&](int sym, int, int, bool) { ++s->hist[sym]; });
+  }
+  s->hist[256] += 1u;  // end-of-block
+  build_table(d, t, s);
+  BitWriter bw{o};
+  for (unsigned k = 0; k < t->hdr_bits; k += 16u) bw.put(t->hdr[k >> 5] >> (k & 31u), (int)(t->hdr_bits - k < 16u ? t->hdr_bits - k : 16u));
+  for (int r = 0; r < H; ++r) {
+    host_scanline(src, kind, base, W, r, seg);
+    tokens([&](int sym, int extra, int xb, bool is_match) {
+      bw.put(t->sym[sym] & 0xffffu, (int)(t->sym[sym] >> 16));
+      if (xb) bw.put((unsigned)extra, xb);
+      if (is_match) bw.put(0u, 1);  // the one distance code
+    });
+  }
+  bw.put(t->eob, (int)t->eob_bits);
+  bw.align();
+  bw.byte(B >> 8), bw.byte(B & 255u), bw.byte(A >> 8), bw.byte(A & 255u);
+  *adler = B << 16 | A;
+  return bw.bit >> 3;
 }
 
 }  // namespace png
@@ -453,14 +530,39 @@ extern "C" int ra_png_deflate_dyn_u8(const void *src, int kind, int M, int N, in
   if (!ws || ws_bytes < wsp.total || (reinterpret_cast<uintptr_t>(ws) & 15))
     return fail(RA_E_WORKSPACE, "ra_png_deflate_dyn_u8: ws=%p ws_bytes=%zu, %zu bytes at a 16-byte boundary are needed", ws, ws_bytes,
                 wsp.total);
-  const bool vec = png::vector_rows(src, kind, W);
+  return png::launch_kind("ra_png_deflate_dyn_u8", kind, png::vector_rows(src, kind, W), as_stream(stream), src,
+                          png::Uniform{M, H, W, (int)g.n, png::chunk_bytes((int)g.n)}, N, H, g.n, plane, wsp,
+                          static_cast<unsigned char *>(ws), out, sizes, offsets, adler);
+}
+
+extern "C" int ra_png_deflate_dyn_ragged_bound(const ra_image_geo *geo, int B, int Np, int bpp, unsigned long long *out_bytes,
+                                               unsigned long long *workspace_bytes) {
+  const char *who = "ra_png_deflate_dyn_ragged_bound";
+  if (!geo || !out_bytes || !workspace_bytes) return fail(RA_E_INVALID, "%s: geo, out_bytes or workspace_bytes is NULL", who);
+  if (bpp != 1 && bpp != 3) return fail(RA_E_SHAPE, "%s: bpp=%d (1 = grey, 3 = RGB)", who, bpp);
+  png::RaggedShape s;
+  if (const int rc = png::ragged_shape(who, true, geo, B, Np, bpp, bpp, &s)) return rc;
+  *out_bytes = s.out;
+  *workspace_bytes = png::Workspace(s.N, s.Hmax, s.n_max).total;
+  return 0;
+}
+
+extern "C" int ra_png_deflate_dyn_ragged_u8(const void *src, int kind, int M, size_t total, const ra_image_geo *geo,
+                                            ra_image_geo *geo_dev, int B, const int *plane, int Np, unsigned char *out,
+                                            size_t out_bytes, int *sizes, unsigned long long *offsets, unsigned int *adler, void *ws,
+                                            size_t ws_bytes, void *stream) {
+  const char *who = "ra_png_deflate_dyn_ragged_u8";
+  if (!geo_dev) return fail(RA_E_INVALID, "%s: geo_dev is NULL", who);
+  png::RaggedShape s;
+  if (const int rc = png::check_ragged(who, true, src, kind, M, total, geo, B, plane, Np, out, out_bytes, sizes, offsets, adler, &s))
+    return rc;
+  const png::Workspace wsp(s.N, s.Hmax, s.n_max);
+  if (!ws || ws_bytes < wsp.total || (reinterpret_cast<uintptr_t>(ws) & 15))
+    return fail(RA_E_WORKSPACE, "%s: ws=%p ws_bytes=%zu, %zu bytes at a 16-byte boundary are needed", who, ws, ws_bytes, wsp.total);
   hipStream_t st = as_stream(stream);
-  unsigned char *w = static_cast<unsigned char *>(ws);
-  if (kind == RA_PNG_GRAY8)
-    return png::launch_chain<RA_PNG_GRAY8>(vec, st, src, M, N, H, W, plane, (int)g.n, g.d, wsp, w, out, sizes, offsets, adler);
-  if (kind == RA_PNG_BGR8)
-    return png::launch_chain<RA_PNG_BGR8>(vec, st, src, M, N, H, W, plane, (int)g.n, g.d, wsp, w, out, sizes, offsets, adler);
-  return png::launch_chain<RA_PNG_F32>(vec, st, src, M, N, H, W, plane, (int)g.n, g.d, wsp, w, out, sizes, offsets, adler);
+  if (const int rc = geo::upload(who, geo, geo_dev, B, st)) return rc;
+  return png::launch_kind(who, kind, false, st, src, png::Ragged{geo_dev, B, M, s.Hmax, kind == RA_PNG_BGR8 ? 3 : 1, total}, s.N, s.Hmax,
+                          s.n_max, plane, wsp, static_cast<unsigned char *>(ws), out, sizes, offsets, adler);
 }
 
 // HOST code, no GPU call: the rule as it is stated, one image after the other: the histogram of the greedy tokens, the table
@@ -474,62 +576,41 @@ extern "C" int ra_png_deflate_dyn_host(const void *src, int kind, int M, int N, 
   if (!plane && N > M) return fail(RA_E_SHAPE, "ra_png_deflate_dyn_host: N=%d images of a source of M=%d without a plane list", N, M);
   for (int i = 0; plane && i < N; ++i)
     if (plane[i] < 0 || plane[i] >= M) return fail(RA_E_SHAPE, "ra_png_deflate_dyn_host: plane[%d]=%d (0 <= index < M=%d)", i, plane[i], M);
-  const int n = (int)g.n, d = g.d;
   std::vector<unsigned char> seg(g.n);
   std::vector<png::HuffScratch> scratch(1);
   std::vector<png::Table> table(1);
-  png::HuffScratch *s = scratch.data();
-  png::Table *t = table.data();
-  // the greedy tokens of the scanline in seg: tok(literal / length symbol, extra value, extra bits, is a match)
-  auto tokens = [&](auto &&tok) {
-    for (int k = 0; k < n;) {
-      int L = 0;
-      if (k >= d)
-        while (L < 258 && k + L < n && seg[k + L] == seg[k + L - d]) ++L;
-      if (L >= 3) {
-        int xb, extra;
-        const int sym = png::length_symbol(L, &xb, &extra);
-        tok(sym, extra, xb, true);
-        k += L;
-      } else {
-        tok((int)seg[k], 0, 0, false);
-        ++k;
-      }
-    }
-  };
   size_t at = 0;
   for (int i = 0; i < N; ++i) {
     const size_t m = plane ? plane[i] : i;
-    for (int k = 0; k < png::kTableSymbols; ++k) s->hist[k] = 0u;
-    unsigned A = 1u, B = 0u;
-    for (int r = 0; r < H; ++r) {
-      png::host_scanline(src, kind, m, H, W, r, seg.data());
-      for (int k = 0; k < n; ++k) {
-        A = (A + seg[k]) % png::kAdler;
-        B = (B + A) % png::kAdler;
-      }
-      tokens([&](int sym, int, int, bool) { ++s->hist[sym]; });
-    }
-    s->hist[256] += 1u;  // end-of-block
-    png::build_table(d, t, s);
-    png::BitWriter bw{out + at};
-    for (unsigned k = 0; k < t->hdr_bits; k += 16u) bw.put(t->hdr[k >> 5] >> (k & 31u), (int)(t->hdr_bits - k < 16u ? t->hdr_bits - k : 16u));
-    for (int r = 0; r < H; ++r) {
-      png::host_scanline(src, kind, m, H, W, r, seg.data());
-      tokens([&](int sym, int extra, int xb, bool is_match) {
-        bw.put(t->sym[sym] & 0xffffu, (int)(t->sym[sym] >> 16));
-        if (xb) bw.put((unsigned)extra, xb);
-        if (is_match) bw.put(0u, 1);  // the one distance code
-      });
-    }
-    bw.put(t->eob, (int)t->eob_bits);
-    bw.align();
-    bw.byte(B >> 8), bw.byte(B & 255u), bw.byte(A >> 8), bw.byte(A & 255u);
-    const size_t bytes = bw.bit >> 3;
-    sizes[i] = (int)bytes;
+    sizes[i] = (int)png::host_stream(src, kind, m * H * W, H, W, g.d, seg.data(), scratch.data(), table.data(), out + at, &adler[i]);
     offsets[i] = at;
-    adler[i] = B << 16 | A;
-    at += bytes;
+    at += (size_t)sizes[i];
+  }
+  return 0;
+}
+
+// HOST code, no GPU call: the sequential rule per image of the table
+extern "C" int ra_png_deflate_dyn_ragged_host(const void *src, int kind, int M, size_t total, const ra_image_geo *geo, int B,
+                                              const int *plane, int Np, unsigned char *out, size_t out_bytes, int *sizes,
+                                              unsigned long long *offsets, unsigned int *adler, void *ws, size_t ws_bytes) {
+  (void)ws, (void)ws_bytes;  // the sequential form needs none
+  const char *who = "ra_png_deflate_dyn_ragged_host";
+  png::RaggedShape s;
+  if (const int rc = png::check_ragged(who, true, src, kind, M, total, geo, B, plane, Np, out, out_bytes, sizes, offsets, adler, &s))
+    return rc;
+  for (int k = 0; plane && k < Np; ++k)
+    if (plane[k] < 0 || plane[k] >= M) return fail(RA_E_SHAPE, "%s: plane[%d]=%d (0 <= index < M=%d)", who, k, plane[k], M);
+  std::vector<unsigned char> seg(s.n_max);
+  std::vector<png::HuffScratch> scratch(1);
+  std::vector<png::Table> table(1);
+  size_t at = 0;
+  for (int i = 0; i < s.N; ++i) {
+    const int k = i / B, b = i - k * B;
+    const size_t m = plane ? plane[k] : k;
+    sizes[i] = (int)png::host_stream(src, kind, m * total + (size_t)geo[b].offset, geo[b].h, geo[b].w, kind == RA_PNG_BGR8 ? 3 : 1,
+                                     seg.data(), scratch.data(), table.data(), out + at, &adler[i]);
+    offsets[i] = at;
+    at += (size_t)sizes[i];
   }
   return 0;
 }

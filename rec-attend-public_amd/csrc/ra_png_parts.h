@@ -7,6 +7,7 @@
 #include <cstring>
 
 #include "ra_common.h"
+#include "ra_ragged.h"
 
 namespace ra {
 namespace png {
@@ -147,6 +148,59 @@ __device__ __forceinline__ unsigned block_scan_excl(unsigned v, unsigned *sh, un
   return Op::f(before, exc);
 }
 
+// a thread's chunk of a segment of n bytes: K bytes, K a multiple of 4 with K / 4 odd, 256 K >= n
+__host__ __device__ inline int chunk_bytes(int n) {
+  int k4 = ceil_div(ceil_div(n, kThreads), 4);
+  k4 |= 1;
+  return 4 * k4;
+}
+
+// ---- where the images of a call lie: the two sources the kernels are templated over (as ra_ragged.h's, with this encoder's
+// plane list and per-image segment sizes) ----------------------------------------------------------------------------------------
+//   Uniform   src holds M images of ONE size back to back; image i of the call is source image plane[i] (or i).  h, w, the
+//             segment's bytes n and a thread's chunk K are kernel arguments.
+//   Ragged    src holds M planes of `total` elements, all laid out by one table of B images; stream i = k * B + b is image b of
+//             plane plane[k] (or k).  tab is indexed by blockIdx alone: ONE scalar load per workgroup; n and K are derived from
+//             the image's w.  Records, slots and bit places keep a uniform stride of Hmax (Hmax + 1) rows per stream.
+// A plane index outside the source is clamped: wrong pixels, never an access outside src.
+struct Image {
+  size_t first;  // the image's first element in src
+  int h, w, n, K;
+};
+
+struct Uniform {
+  static constexpr bool kRagged = false;
+  int M, H, W, n, K;
+  __device__ __forceinline__ int rows() const { return H; }  // the stride of a stream's records
+  __device__ __forceinline__ Image dims(int) const { return Image{0, H, W, n, K}; }
+  __device__ __forceinline__ Image at(int i, const int *plane) const {
+    int m = plane ? plane[i] : i;
+    m = m < 0 ? 0 : (m >= M ? M - 1 : m);
+    return Image{(size_t)m * H * W, H, W, n, K};
+  }
+};
+
+struct Ragged {
+  static constexpr bool kRagged = true;
+  const ra_image_geo *tab;
+  int B, M, Hmax, bpp;
+  size_t total;
+  __device__ __forceinline__ int rows() const { return Hmax; }
+  __device__ __forceinline__ Image dims(int i) const {
+    const ra_image_geo g = tab[i % B];  // i = a blockIdx: a scalar load
+    const int n = 1 + g.w * bpp;
+    return Image{0, g.h, g.w, n, chunk_bytes(n)};
+  }
+  __device__ __forceinline__ Image at(int i, const int *plane) const {
+    const int k = i / B;
+    const ra_image_geo g = tab[i - k * B];
+    int m = plane ? plane[k] : k;
+    m = m < 0 ? 0 : (m >= M ? M - 1 : m);
+    const int n = 1 + g.w * bpp;
+    return Image{(size_t)m * total + (size_t)g.offset, g.h, g.w, n, chunk_bytes(n)};
+  }
+};
+
 // ---- staging a row: file byte j of the row -> sh[j] (sh 16-byte aligned) ----------------------------------------------------
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
@@ -202,16 +256,23 @@ __device__ __forceinline__ void stage_row(const void *row, int W, unsigned char 
   }
 }
 
-// Row r of image img of the call, staged behind its filter-type byte: sh_raw[kRowPad - 1 ..) holds the segment.  No barrier.
-template <int KIND, bool VEC>
-__device__ __forceinline__ void stage_segment(const void *src, int M, int H, int W, const int *plane, int img, int r,
-                                              unsigned char *sh_raw) {
+// Row r of image im, staged behind its filter-type byte: sh_raw[kRowPad - 1 ..) holds the segment.  No barrier.  RAGGED: the
+// wide loads are this workgroup's decision, from the image's real address and width (its first byte 16-byte aligned and whole
+// 16-byte groups per row, so every row is aligned); VEC is the launch's decision otherwise.
+template <int KIND, bool VEC, bool RAGGED>
+__device__ __forceinline__ void stage_segment(const void *src, const Image &im, int r, unsigned char *sh_raw) {
   constexpr size_t px = KIND == RA_PNG_F32 ? 4 : (KIND == RA_PNG_BGR8 ? 3 : 1);  // source bytes per pixel
-  int m = plane ? plane[img] : img;
-  m = m < 0 ? 0 : (m >= M ? M - 1 : m);  // an index outside the source gives wrong pixels, never an access outside it
-  const unsigned char *row = static_cast<const unsigned char *>(src) + ((size_t)m * H + r) * (size_t)W * px;
+  const unsigned char *first = static_cast<const unsigned char *>(src) + im.first * px;
+  const unsigned char *row = first + (size_t)r * (size_t)im.w * px;
   if (threadIdx.x == 0) sh_raw[kRowPad - 1] = 0;  // the filter-type byte
-  stage_row<KIND, VEC>(row, W, sh_raw + kRowPad);
+  if (RAGGED) {
+    if ((reinterpret_cast<uintptr_t>(first) & 15) == 0 && (size_t)im.w * px % 16 == 0)
+      stage_row<KIND, true>(row, im.w, sh_raw + kRowPad);
+    else
+      stage_row<KIND, false>(row, im.w, sh_raw + kRowPad);
+  } else {
+    stage_row<KIND, VEC>(row, im.w, sh_raw + kRowPad);
+  }
 }
 
 // Walk 1 over a thread's chunk [lo, hi) of the segment b[0 .. n) and the two scans behind it: *s_in = the start of the stretch
@@ -297,14 +358,17 @@ __device__ __forceinline__ void emit_chunk(const Coder &code, const unsigned cha
 
 // Workgroup = image: every row's place in its stream, the stream's size and Adler-32.  Fixed format: byte places behind 78 01
 // into rec[].offset.  DYN: rec[].bytes are BITS; 64-bit bit places from the stream's first byte on, behind the header's
-// tab[img].hdr_bits, into start[img * (H + 1) + r], the end-of-block code's place into start[img * (H + 1) + H].
-template <bool DYN>
-__global__ __launch_bounds__(kThreads) void scan_kernel(Record *rec, int H, int n, int *sizes, unsigned *adler, const Table *tab,
+// tab[img].hdr_bits, into start[img * (S + 1) + r], the end-of-block code's place into start[img * (S + 1) + H]; S = the
+// stride of a stream's records (H; ragged: the tallest image's), H and n the image's own.
+template <bool DYN, class GEO>
+__global__ __launch_bounds__(kThreads) void scan_kernel(Record *rec, GEO geom, int *sizes, unsigned *adler, const Table *tab,
                                                          unsigned long long *start) {
   __shared__ unsigned sh_scan[4];
   const int tid = threadIdx.x, img = blockIdx.x;
-  Record *q = rec + (size_t)img * H;
-  unsigned long long *st = DYN ? start + (size_t)img * (H + 1) : nullptr;
+  const Image im = geom.dims(img);
+  const int H = im.h, n = im.n, S = geom.rows();
+  Record *q = rec + (size_t)img * S;
+  unsigned long long *st = DYN ? start + (size_t)img * (S + 1) : nullptr;
   // bytes (bits) before this trip: a trip adds below 2^8 * 2^19; the sum of (A_k - 1) mod 65521 before it; this thread's part of B
   unsigned long long at = DYN ? tab[img].hdr_bits : 0ull;
   unsigned apre = 0u, bsum = 0u;
@@ -405,23 +469,71 @@ inline int check_bound(const char *who, int N, int H, int W, int bpp, const void
   return 0;
 }
 
+// ---- a ragged call (ra_png_deflate*_ragged_*): what the table gives the host side --------------------------------------------
+struct RaggedShape {
+  int N, Hmax;   // streams of the call; the tallest image's rows: the row stride of every stream's records, slots and places
+  size_t n_max;  // the widest image's scanline bytes: what slots and LDS are sized by
+  size_t out;    // Np * the sum of the images' stream bounds
+};
+
+// The per-image limits of the uniform entries, image by image; 0 (and *s filled) or RA_E_SHAPE with a message that names the
+// image or the count.  px: source bytes per pixel (the bound queries know only bpp).
+inline int ragged_shape(const char *who, bool dynamic, const ra_image_geo *geo, int B, int Np, int bpp, size_t px, RaggedShape *s) {
+  if (B < 1 || Np < 1 || (long long)B * Np > RA_PNG_MAX_IMAGES)
+    return fail(RA_E_SHAPE, "%s: B=%d images times Np=%d planes (1 <= N = Np * B <= %d)", who, B, Np, RA_PNG_MAX_IMAGES);
+  s->N = B * Np, s->Hmax = 0, s->n_max = 0;
+  size_t sum = 0;
+  for (int b = 0; b < B; ++b) {
+    const int h = geo[b].h, w = geo[b].w;
+    if (h < 1 || w < 1) return fail(RA_E_SHAPE, "%s: image %d is %d x %d (h, w >= 1)", who, b, h, w);
+    const size_t n = 1 + (size_t)w * bpp;
+    if (n > RA_PNG_MAX_ROW_BYTES)
+      return fail(RA_E_SHAPE, "%s: image %d: w=%d gives scanlines of %zu bytes (at most %d)", who, b, w, n, RA_PNG_MAX_ROW_BYTES);
+    const size_t stream = dynamic ? dynamic_stream_bound(n, h) : 8 + (size_t)h * segment_bound(n);
+    if (stream >= (1ull << 31) || (size_t)h * w * px >= (1ull << 31))
+      return fail(RA_E_SHAPE, "%s: image %d is %d x %d: %zu source bytes, a stream of up to %zu (both below 2^31)", who, b, h, w,
+                  (size_t)h * w * px, stream);
+    s->Hmax = h > s->Hmax ? h : s->Hmax;
+    s->n_max = n > s->n_max ? n : s->n_max;
+    sum += stream;
+  }
+  s->out = (size_t)Np * sum;
+  return 0;
+}
+
+// every check of a ragged entry that does not depend on where the data lives, in the order the header states; 0 or the refusal
+inline int check_ragged(const char *who, bool dynamic, const void *src, int kind, int M, size_t total, const ra_image_geo *geo, int B,
+                        const int *plane, int Np, const void *out, size_t out_bytes, const void *sizes, const void *offsets,
+                        const void *adler, RaggedShape *s) {
+  if (!src || !geo || !out || !sizes || !offsets || !adler)
+    return fail(RA_E_INVALID, "%s: src, geo, out, sizes, offsets or adler is NULL", who);
+  if (kind != RA_PNG_GRAY8 && kind != RA_PNG_BGR8 && kind != RA_PNG_F32)
+    return fail(RA_E_INVALID, "%s: kind %d (RA_PNG_GRAY8, RA_PNG_BGR8 or RA_PNG_F32)", who, kind);
+  if (M < 1) return fail(RA_E_SHAPE, "%s: M=%d (the source holds at least one plane)", who, M);
+  const int bpp = kind == RA_PNG_BGR8 ? 3 : 1;
+  if (B < 1 || Np < 1 || (long long)B * Np > RA_PNG_MAX_IMAGES)
+    return fail(RA_E_SHAPE, "%s: B=%d images times Np=%d planes (1 <= N = Np * B <= %d)", who, B, Np, RA_PNG_MAX_IMAGES);
+  if (!plane && Np > M) return fail(RA_E_SHAPE, "%s: Np=%d planes of a source of M=%d without a plane list", who, Np, M);
+  if (const int rc = geo::check(who, geo, B, total, (1ll << 31) - 1, "h * w < 2^31")) return rc;
+  if (const int rc = ragged_shape(who, dynamic, geo, B, Np, bpp, kind == RA_PNG_F32 ? 4 : bpp, s)) return rc;
+  if (out_bytes < s->out)
+    return fail(RA_E_WORKSPACE, "%s: out_bytes=%zu, %d streams need up to %zu (Np * the sum of the images' bounds)", who, out_bytes,
+                s->N, s->out);
+  return 0;
+}
+
 inline size_t records_bytes(int N, int H) { return ((size_t)N * H * sizeof(Record) + 15) / 16 * 16; }
 
-// a thread's chunk of a segment of n bytes: K bytes, K a multiple of 4 with K / 4 odd, 256 K >= n
-inline int chunk_bytes(int n) {
-  int k4 = ceil_div(ceil_div(n, kThreads), 4);
-  k4 |= 1;
-  return 4 * k4;
-}
 // 16-byte loads: the source 16-byte aligned and whole 16-byte groups per row
 inline bool vector_rows(const void *src, int kind, int W) {
   return (reinterpret_cast<uintptr_t>(src) & 15) == 0 && (kind == RA_PNG_F32 ? W % 4 == 0 : W % 16 == 0);
 }
 
-// scanline r of source image m as the file holds it: the filter-type byte 0 and the row (host entries)
-inline void host_scanline(const void *src, int kind, size_t m, int H, int W, int r, unsigned char *seg) {
+// scanline r of the image of width W whose first element is `base`, as the file holds it: the filter-type byte 0 and the row
+// (host entries)
+inline void host_scanline(const void *src, int kind, size_t base, int W, int r, unsigned char *seg) {
   seg[0] = 0;
-  const size_t first = (m * H + r) * (size_t)W;
+  const size_t first = base + (size_t)r * (size_t)W;
   if (kind == RA_PNG_GRAY8) {
     memcpy(&seg[1], static_cast<const unsigned char *>(src) + first, W);
   } else if (kind == RA_PNG_BGR8) {

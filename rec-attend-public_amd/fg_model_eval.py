@@ -35,6 +35,9 @@ the colour-wheel image of data_api/orientation.py:13-28 from the model's d_out â
 one kernel (analysis.RenderOrientationAnalyzer) â€” with fg_gt_full > 0 as the mask; a model without add_orientation is refused.
 --device_png (not a reference flag) compresses the thresholded planes, gt/ and ori/ on the device (utils/png.write_*_dev): the same
 pixels in files of other bytes.  soft/ is continuous-valued, a run code would enlarge it: it stays with the host's zlib, unchanged.
+On a mixed archive the thresholded planes of a batch are gathered into one flat uint8 [K,P] buffer at the geometry's offsets and
+leave through ONE ragged encoder call (utils/png.write_gray8_ragged_dev: one launch chain for all thresholds and sizes), gt/
+through one more on the flat labels; every file holds the bytes a call on that image alone gives.
 
 Pixel-level class scores: when --input also holds gt_instance_ids [N,H,W] (the *_gtFine_instanceIds.png values; optionally
 gt_label_ids uint8 [N,H,W], the *_gtFine_labelIds.png values, else a pixel's label is derived from its id) and the model has
@@ -107,6 +110,16 @@ def _write_planes_dev(folder, names, planes, code='fixed'):
   os.makedirs(folder, exist_ok=True)
   png.write_gray8_dev([os.path.join(folder, os.path.splitext(os.path.basename(name))[0] + '.png') for name in names], planes,
                       code=code)
+
+
+def _write_ragged_dev(folders, names, flat, geo, code='fixed'):
+  """_write_planes_dev for a batch of MIXED sizes: flat uint8 [K,P] (or [P], K = 1) on the device, every plane laid out by the
+  geometry geo [B,3] -> <folders[k]>/<name>.png for every plane k and image, ONE png_deflate_ragged call."""
+  from utils import png
+  for folder in folders:
+    os.makedirs(folder, exist_ok=True)
+  png.write_gray8_ragged_dev([os.path.join(folder, os.path.splitext(os.path.basename(name))[0] + '.png') for folder in folders
+                              for name in names], flat, geo, code=code)
 
 
 def foreground_plane(y_out):
@@ -267,10 +280,9 @@ def _main_mixed(args, opt, data, model, out_dir, thresholds):
   os.makedirs(out_dir, exist_ok=True)
   dev = torch.device('cuda', torch.cuda.current_device())
   up = lambda a: torch.as_tensor(np.ascontiguousarray(a, dtype=np.float32)).to(dev)
-  to8 = lambda t: (t * 255.0).clamp(0, 255).to(torch.uint8).cpu().numpy()
-  # --device_png: the same quantisation, the plane left on the device and compressed there
-  write_hard = (lambda f, n, t: _write_planes_dev(f, n, (t * 255.0).clamp(0, 255).to(torch.uint8), args.device_png_code)) if args.device_png else (
-      lambda f, n, t: _write_planes(f, n, to8(t)))
+  quant = lambda t: (t * 255.0).clamp(0, 255).to(torch.uint8)  # --device_png: the same quantisation, left on the device
+  to8 = lambda t: quant(t).cpu().numpy()
+  write_hard = lambda f, n, t: _write_planes(f, n, to8(t))
   bs = max(1, opt['batch_size'])
   for b0 in range(0, N, bs):
     b1 = min(N, b0 + bs)
@@ -288,14 +300,25 @@ def _main_mixed(args, opt, data, model, out_dir, thresholds):
       totals[k]['sum_ab'] += int(counts['sum_ab'][:, k].sum())
       totals[k]['sum_b'] += int(counts['sum_b'].sum())
       totals[k]['pixels'] += int(counts['pixels'].sum())
+    # --device_png: the thresholded planes of the whole batch in ONE flat uint8 [K,P_batch] buffer, image i at the geometry's
+    # offset, encoded by one ragged call (one launch chain, whatever the sizes); gt/ is one more call on the flat gt
+    hard = torch.zeros((len(thresholds), p1 - p0), dtype=torch.uint8, device=dev) if args.device_png else None
     for i, (o, h, w) in enumerate(geo.tolist()):  # the rendering path only (:146, :166-173), image by image at its own size
       full = pp.upsample(soft[i:i + 1].contiguous(), (h, w))
-      for t in thresholds:
-        write_hard(os.path.join(out_dir, '{:02d}'.format(int(t * 100))), names[b0 + i:b0 + i + 1], (full > float(t)).to(torch.float32))
+      for k, t in enumerate(thresholds):
+        if hard is not None:
+          hard[k, o:o + h * w] = quant((full > float(t)).to(torch.float32)).view(-1)
+        else:
+          write_hard(os.path.join(out_dir, '{:02d}'.format(int(t * 100))), names[b0 + i:b0 + i + 1], (full > float(t)).to(torch.float32))
       if opt['render_soft']:
         _write_planes(os.path.join(out_dir, 'soft'), names[b0 + i:b0 + i + 1], to8(full))
-      if opt['render_gt']:
+      if opt['render_gt'] and hard is None:
         write_hard(os.path.join(out_dir, 'gt'), names[b0 + i:b0 + i + 1], gt[o:o + h * w].view(1, h, w).to(torch.float32))
+    if hard is not None:
+      _write_ragged_dev([os.path.join(out_dir, '{:02d}'.format(int(t * 100))) for t in thresholds], names[b0:b1], hard, geo,
+                        args.device_png_code)
+      if opt['render_gt']:
+        _write_ragged_dev([os.path.join(out_dir, 'gt')], names[b0:b1], quant(gt.to(torch.float32)), geo, args.device_png_code)
     if have_stats:
       stats.append(model.statistics(x, up(y_gt_all[b0:b1]), None if d_gt_all is None else up(d_gt_all[b0:b1])))
   summary = {}

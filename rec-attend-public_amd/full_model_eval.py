@@ -52,8 +52,9 @@ it and how many of the thresholds it passes: every thresholded mask of every thr
 up to 16 thresholds, and ops.paint_instances looks the pictures up from it behind ops.eval_metrics_from_counts, whose areas
 say which predictions --remove_tiny took; the ground truth is painted from the id image (ops.paint_groundtruth) in
 analysis.groundtruth_colours of the last threshold's iou_pairwise.  Both honour --device_png / --device_png_code (a batch of
-mixed sizes is encoded one call per group of equal size).  Off the id path each is refused by name and points to --render /
---render_gt_instances, whose refusals on id and mixed-size archives stay as they are."""
+mixed sizes is encoded where it lies, in one launch chain: analysis.RaggedPicture, ops.png_deflate_ragged).  Off the id path
+each is refused by name and points to --render / --render_gt_instances, whose refusals on id and mixed-size archives stay as
+they are."""
 import argparse
 import os
 import time
@@ -272,6 +273,7 @@ def _analyze_ids(args, model, data, b0, b1, y_dev, s_dev, thresholds, names, acc
   if render is not None:
     render = dict(render, indices=list(range(b0, b1)))
   if _flat_path(data):  # mixed full sizes: the same chain through the ragged entry points, one launch chain per batch
+    import analysis
     import setup_labels
     off, size = data['pixel_offset'], data['orig_size']
     p0, p1 = int(off[b0]), int(off[b1])
@@ -284,7 +286,7 @@ def _analyze_ids(args, model, data, b0, b1, y_dev, s_dev, thresholds, names, acc
         yc, ids, geo, lab['inst_id'], ths, fg_flat=fg, morph=fg is not None and not args.no_morph, check_fg=False, want_map=want_map)
     paint = {'instances': lambda wmap, ths, keep: ops.paint_instances(wmap, ths, keep=keep, geo=geo),
              'gt': lambda colours: ops.paint_groundtruth(ids, lab['inst_id'], colours, geo=geo),
-             'views': lambda pic: [pic[o:o + h * w].view(h, w, 3) for o, h, w in geo.tolist()]}
+             'views': lambda pic: analysis.RaggedPicture(pic, geo)}
     return _analyze_counts(args, count, lab, fg, y_dev, s_dev, thresholds, names, acc, paint, render)
   ids = torch.as_tensor(np.ascontiguousarray(np.asarray(data['gt_instance_ids'][b0:b1]).astype(np.int32))).to(dev)
   # the slots in the reference's order — by area at NETWORK size — under the --dataset rule, as setup_labels.py assembles them

@@ -2712,3 +2712,90 @@ def paint_groundtruth(gt_ids, inst_id, colours, geo=None, out=None):
     check(rn.lib().ra_gt_paint_ragged_u8(ptr(gt_ids), total, tab, ptr(gdev), ptr(inst_id), B, T, ptr(colours), ptr(out),
                                          rn.stream_ptr()), 'ra_gt_paint_ragged_u8')
   return out
+
+
+# ------------------------------------- PNG output of a ragged batch: one launch chain for mixed sizes (csrc/ra_png.hip, ra_png_dyn.hip)
+def _png_ragged_source(who, src):
+  """(kind, M, P, bpp) of a source of png_deflate_ragged: uint8 [M,P], uint8 [M,P,3] (B, G, R) or float32 [M,P]; a one-plane
+  uint8 [P,3] or, of either type, [P] is M = 1."""
+  if not isinstance(src, torch.Tensor) or not src.is_contiguous():
+    raise rn.RecAttendError('%s: src must be a contiguous tensor' % who)
+  shape = tuple(int(n) for n in src.shape)
+  if src.dtype == torch.uint8 and len(shape) in (2, 3) and shape[-1] == 3:  # a two-dimensional [n,3] is ONE colour plane
+    kind, bpp, lead = rn.RA_PNG_BGR8, 3, shape[:-1]
+  elif src.dtype == torch.uint8 and len(shape) in (1, 2):
+    kind, bpp, lead = rn.RA_PNG_GRAY8, 1, shape
+  elif src.dtype == torch.float32 and len(shape) in (1, 2):
+    kind, bpp, lead = rn.RA_PNG_F32, 1, shape
+  else:
+    raise rn.RecAttendError('%s: src must be uint8 [M,P], uint8 [M,P,3] (B, G, R) or float32 [M,P] (one plane: [P], [P,3]), '
+                            'got %s %s' % (who, src.dtype, shape))
+  M, P = (1, lead[0]) if len(lead) == 1 else lead
+  if M < 1 or P < 1:
+    raise rn.RecAttendError('%s: src has an empty dimension: %s' % (who, shape))
+  return kind, M, P, bpp
+
+
+def png_deflate_ragged_bound(geo, Np, bpp, code='fixed'):
+  """(bytes of all Np * B streams at most — Np times the sum of the images' own bounds —, bytes of workspace) of
+  ra_png_deflate_ragged_bound, or of ra_png_deflate_dyn_ragged_bound with code='dynamic'; geo: the geometry [B,3], bpp 1 or 3."""
+  fn, name = _png_entry('png_deflate_ragged_bound', code, '_ragged_bound')
+  tab, _, B, _ = _geo_table('png_deflate_ragged_bound', geo, (torch.empty((0,)),), 'cpu')
+  out, ws = C.c_ulonglong(0), C.c_ulonglong(0)
+  check(fn(tab, B, int(Np), int(bpp), C.addressof(out), C.addressof(ws)), name)
+  return int(out.value), int(ws.value)
+
+
+def png_deflate_ragged(src, geo, plane_index=None, with_meta=False, code='fixed'):
+  """png_deflate for a batch of MIXED sizes in one launch chain (ra_png_deflate_ragged_u8 / ra_png_deflate_dyn_ragged_u8): src is
+  M planes of P elements on the device — uint8 [M,P], uint8 [M,P,3] in B, G, R order (what paint_instances(..., geo=...) writes)
+  or float32 [M,P]; [P] / [P,3] is one plane — all laid out by the geometry `geo` [B,3].  -> a list of Np * B streams, stream
+  k * B + b = image b of plane plane_index[k] (None: of plane k, all M planes); every stream holds the bytes png_deflate gives
+  for that image alone.  One copy of the metadata, one copy of exactly the bytes used.  with_meta: as png_deflate."""
+  who = 'png_deflate_ragged'
+  fn, name = _png_entry(who, code, '_ragged_u8')
+  kind, M, P, bpp = _png_ragged_source(who, src)
+  if not src.is_cuda:
+    raise rn.RecAttendError('%s: src must be on the device (png_deflate_ragged_host takes host arrays)' % who)
+  tab, gdev, B, total = _geo_table(who, geo, (src.view(-1)[:P],), src.device)
+  idx = None if plane_index is None else _png_planes(who, plane_index, M)
+  Np = M if idx is None else int(idx.size)
+  N = Np * B
+  out_bytes, ws_bytes = png_deflate_ragged_bound(geo, Np, bpp, code)
+  bufs = _PNG_BUFFERS.setdefault(str(src.device), [None, None])
+  for k, need in enumerate((ws_bytes, out_bytes)):
+    if bufs[k] is None or bufs[k].numel() < need:
+      bufs[k] = None
+      bufs[k] = torch.empty((need,), dtype=torch.uint8, device=src.device)
+  ws, out = bufs
+  planes = None if idx is None else torch.from_numpy(idx).to(src.device)
+  # sizes int32 [N], adler uint32 [N], offsets uint64 [N] in ONE tensor of 4 N words, so that one copy brings them back
+  meta = torch.empty((4 * N,), dtype=torch.int32, device=src.device)
+  check(fn(ptr(src), kind, M, total, tab, ptr(gdev), B, ptr(planes), Np, ptr(out), out.numel(), ptr(meta[:N]), ptr(meta[2 * N:]),
+           ptr(meta[N:2 * N]), ptr(ws), ws.numel(), rn.stream_ptr()), name)
+  host = meta.cpu().numpy()
+  sizes, offsets = host[:N].astype(np.int64), host[2 * N:].view(np.int64)
+  used = int(offsets[-1] + sizes[-1])
+  data = out[:used].cpu().numpy().tobytes()
+  streams = [data[int(o):int(o) + int(n)] for n, o in zip(sizes, offsets)]
+  return (streams, sizes, offsets.copy(), host[N:2 * N].view(np.uint32).copy()) if with_meta else streams
+
+
+def png_deflate_ragged_host(src, geo, plane_index=None, code='fixed'):
+  """png_deflate_ragged on host arrays through ra_png_deflate_ragged_host / ra_png_deflate_dyn_ragged_host (plain sequential C++,
+  no GPU call): src a NumPy array of one of png_deflate_ragged's kinds -> (list of streams, sizes int32 [N], offsets uint64 [N],
+  adler uint32 [N])."""
+  who = 'png_deflate_ragged_host'
+  fn, name = _png_entry(who, code, '_ragged_host')
+  src = np.ascontiguousarray(src)
+  t = torch.from_numpy(src)
+  kind, M, P, bpp = _png_ragged_source(who, t)
+  tab, _, B, total = _geo_table(who, geo, (t.view(-1)[:P],), 'cpu')
+  idx = None if plane_index is None else _png_planes(who, plane_index, M)
+  Np = M if idx is None else int(idx.size)
+  N = Np * B
+  out_bytes, _ = png_deflate_ragged_bound(geo, Np, bpp, code)
+  out = np.zeros((out_bytes,), dtype=np.uint8)
+  sizes, offsets, adler = np.zeros((N,), np.int32), np.zeros((N,), np.uint64), np.zeros((N,), np.uint32)
+  check(fn(ptr(src), kind, M, total, tab, B, ptr(idx), Np, ptr(out), out.size, ptr(sizes), ptr(offsets), ptr(adler), None, 0), name)
+  return [out[int(o):int(o) + int(n)].tobytes() for n, o in zip(sizes, offsets)], sizes, offsets, adler

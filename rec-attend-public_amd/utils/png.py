@@ -323,3 +323,39 @@ def write_gray8_dev(paths, t, plane_index=None, code='fixed'):
 def write_colour8_dev(paths, t, code='fixed'):
   """One file per image of encode_colour8_dev(t, code), in the order of paths."""
   return _write_files(paths, encode_colour8_dev(t, code))
+
+
+def _wrap_ragged(streams, geo, colour_type):
+  """One file per stream of a ragged call: stream k * B + b is wrapped with image b's own h, w."""
+  sizes = [(int(h), int(w)) for _, h, w in np.asarray(geo).tolist()]
+  return [wrap(sizes[i % len(sizes)][0], sizes[i % len(sizes)][1], colour_type, z) for i, z in enumerate(streams)]
+
+
+def encode_gray8_ragged_dev(flat, geo, plane_index=None, code='fixed'):
+  """encode_gray8_dev for a batch of MIXED sizes in one launch chain (ra_ops.png_deflate_ragged): flat is a DEVICE tensor of M
+  planes, uint8 or float32 [M,P] ([P]: one plane), all laid out by the geometry geo [B,3] of (offset, h, w) -> the bytes of
+  Np * B PNG files, file k * B + b = image b of plane plane_index[k] (None: plane k).  Every file holds the bytes
+  encode_gray8_dev gives for that image alone."""
+  import ra_ops
+  if flat.dim() not in (1, 2):
+    raise ValueError('encode_gray8_ragged_dev needs a uint8 or float32 [M,P] or [P] tensor, got %s' % (tuple(flat.shape),))
+  return _wrap_ragged(ra_ops.png_deflate_ragged(flat.contiguous(), geo, plane_index, code=code), geo, 0)
+
+
+def encode_colour8_ragged_dev(flat, geo, plane_index=None, code='fixed'):
+  """encode_colour8_dev for a batch of MIXED sizes in one launch chain: flat is a DEVICE tensor uint8 [M,P,3] ([P,3]: one plane)
+  in cv2's B, G, R order, what ra_ops.paint_instances(..., geo=...) writes (see encode_gray8_ragged_dev)."""
+  import ra_ops
+  if flat.dim() not in (2, 3) or flat.shape[-1] != 3:
+    raise ValueError('encode_colour8_ragged_dev needs a uint8 [M,P,3] or [P,3] tensor, got %s' % (tuple(flat.shape),))
+  return _wrap_ragged(ra_ops.png_deflate_ragged(flat.contiguous(), geo, plane_index, code=code), geo, 2)
+
+
+def write_gray8_ragged_dev(paths, flat, geo, plane_index=None, code='fixed'):
+  """One file per image of encode_gray8_ragged_dev(flat, geo, plane_index, code); paths in stream order (plane-major)."""
+  return _write_files(paths, encode_gray8_ragged_dev(flat, geo, plane_index, code))
+
+
+def write_colour8_ragged_dev(paths, flat, geo, plane_index=None, code='fixed'):
+  """One file per image of encode_colour8_ragged_dev(flat, geo, plane_index, code); paths in stream order (plane-major)."""
+  return _write_files(paths, encode_colour8_ragged_dev(flat, geo, plane_index, code))
